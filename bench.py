@@ -2,17 +2,25 @@
 """bench.py -- ThinkTwice per-frame forward path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload forward|voxel_pool|train_step] [--batch B]
+                    [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of B synthetic frames per GPU
 (4 cams x 2 sweeps x 448x896 + LiDAR).  Prints ONE JSON line (rank 0).  For N>1 the driver
 launches one process per GPU through torch.distributed.run; frames shard data-parallel with
 no data-path collective (inference: replicas only), `value` = all ranks' frames / max time.
+
+A plain run only sets up, warms up, times the K steps and prints the headline line.  `--full` adds
+everything else the line used to carry: the serialised roofline pass, the side legs (other precisions,
+tick latency, voxel-pool op, train step, ...) and the CPU baseline.  `--dump-outputs DIR` writes what
+the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all; larger
+tensors as a fixed seeded sample) plus DIR/index.json, so that two builds can be compared output for output.
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 import torch
 
@@ -22,6 +30,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_F32_PEAK_TF = 157.3       # f32-in MFMA
 MFMA_BF16_PEAK_TF = 2500.0     # dense bf16
+DUMP_BYTES = 64 * 2 ** 20      # --dump-outputs: budget over all written arrays
 
 
 # --------------------------------------------------------------------------- workloads
@@ -166,6 +175,55 @@ def make_workload(name, batch, device):
     raise SystemExit(f"unknown workload {name}")
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+def _flatten_outputs(obj, name, out):
+    """Tensors of a step's return value (nested dicts / lists / tuples) -> {dotted name: tensor}, in a fixed order."""
+    if torch.is_tensor(obj):
+        out[name or "out"] = obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            _flatten_outputs(v, f"{name}.{k}" if name else str(k), out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _flatten_outputs(v, f"{name}.{i}" if name else str(i), out)
+
+
+def dump_outputs(result, out_dir):
+    """Write every tensor of `result` as out_dir/<name>.npy: float64 for f64 and integer tensors, float32 for the rest.
+    Each tensor gets an equal share of DUMP_BYTES; one larger than its share is written as a sample of its flattened
+    elements at indices drawn from a generator seeded by the tensor's name (the same indices in every run).
+    out_dir/index.json records shape, source dtype and sampling of each array."""
+    import numpy as np
+    tensors = {}
+    _flatten_outputs(result, "", tensors)
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(len(tensors), 1)
+    index = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        esz = 8 if wide else 4
+        flat = t.reshape(-1)
+        n = flat.numel()
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "sampled": False}
+        if n * esz > share:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.unique(rng.integers(0, n, share // esz, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            entry.update(sampled=True, elements=int(idx.size), index_seed=zlib.crc32(name.encode()),
+                         index_rule="numpy.unique(numpy.random.default_rng(index_seed).integers(0, numel, share))")
+        arr = flat.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        if not entry["sampled"]:
+            arr = arr.reshape(tuple(t.shape))
+        fname = name.replace(os.sep, "_") + ".npy"
+        np.save(os.path.join(out_dir, fname), arr)
+        entry["file"] = fname
+        index[name] = entry
+    with open(os.path.join(out_dir, "index.json"), "w") as f:
+        json.dump(index, f, indent=1)
+    return index
+
+
 # --------------------------------------------------------------------------- main
 def main():
     ap = argparse.ArgumentParser()
@@ -174,7 +232,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8, help="frames per GPU per step")
     ap.add_argument("--workload", default=os.environ.get("TT_BENCH_WORKLOAD", "auto"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline pass, the side legs and the CPU baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -212,10 +274,24 @@ def main():
             else "voxel_pool"
     wl = make_workload(name, args.batch, device)
 
+    last = {}
+    if args.dump_outputs:
+        step = wl.step
+
+        def recording_step():
+            last["out"] = step()
+            return last["out"]
+        wl.step = recording_step
+
     from thinktwice_amd.bench_harness import run_timed
     res = run_timed(wl, args.steps, args.warmup, dist=dist, sync=torch.cuda.synchronize, device=device)
     dt = res["seconds"]
-    if hasattr(wl, "collect"):      # report data that takes collectives to produce: on every rank
+    if args.dump_outputs:
+        del wl.step
+        if rank == 0:
+            dump_outputs(last.pop("out"), args.dump_outputs)
+        last.clear()
+    if args.full and hasattr(wl, "collect"):      # report data that takes collectives to produce: on every rank
         wl.collect()
 
     if rank == 0:
@@ -239,13 +315,14 @@ def main():
                        "parallelism": f"replicas x{world} (no data-path collective)",
                        "launch": getattr(wl, "launch_note", "eager launches"),
                        "batches_in_flight": getattr(wl, "pipeline", 1)},
-            "roofline": wl.roofline(),
         }
-        extra = getattr(wl, "extra", None)
-        if extra:
-            line.update(extra())
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = wl.cpu_baseline()
+        if args.full:
+            line["roofline"] = wl.roofline()
+            extra = getattr(wl, "extra", None)
+            if extra:
+                line.update(extra())
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = wl.cpu_baseline()
         if name == "train_step":
             line["unit"] = "samples/s"
             line["config"]["parallelism"] = f"data parallel x{world}: one all-reduce of the flat gradient buffer per iteration"

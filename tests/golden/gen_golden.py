@@ -646,8 +646,32 @@ def gen_f17():
           ida_mats=ida, cam_intrinsic=meta0["cam_intrinsic"].numpy(), lidar2img=meta0["lidar2img"].numpy(),
           lidar2cam=meta0["lidar2cam"].numpy())
 
+def _json_config(v):
+    """Config values -> JSON; tuples keep their type as {"__tuple__": [...]} (the model builder sees what the file wrote)."""
+    if isinstance(v, dict):
+        return {k: _json_config(x) for k, x in v.items()}
+    if isinstance(v, tuple):
+        return {"__tuple__": [_json_config(x) for x in v]}
+    if isinstance(v, list):
+        return [_json_config(x) for x in v]
+    return v
+
+
+def gen_cfg():
+    """configs/thinktwice.py (with its _base_ files) as parsed by thinktwice_amd.cfgfile.Config.fromfile: the `model` and
+    `optimizer` entries, stored as data for tests/test_host_logic.py."""
+    import json
+    from thinktwice_amd.cfgfile import Config
+    cfg = Config.fromfile(os.path.join(ref_stubs.REF_ROOT, "open_loop_training", "configs", "thinktwice.py"))
+    path = os.path.join(HERE, "reference_config.json")
+    with open(path, "w") as f:
+        json.dump({"model": _json_config(cfg.model), "optimizer": _json_config(cfg.optimizer)}, f, indent=1)
+        f.write("\n")
+    print(f"wrote {path} ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 FIXTURES = {"F17": gen_f17, "F3": gen_f3, "F12": gen_f12, "F7": gen_f7, "F8": gen_f8, "F9": gen_f9, "F10": gen_f10, "F11": gen_f11,
-            "F13": gen_f13, "F13b": gen_f13b, "F14": gen_f14, "F15": gen_f15, "F16": gen_f16}
+            "F13": gen_f13, "F13b": gen_f13b, "F14": gen_f14, "F15": gen_f15, "F16": gen_f16, "CFG": gen_cfg}
 
 
 def main():

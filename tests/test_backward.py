@@ -10,41 +10,88 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("x3,train", [(False, False), (True, False), (False, True)])
 def test_camera_trunk_backward_matches_oracle_autograd(x3, train):
-    """`train`: model.train() semantics -- batch-statistics BatchNorm in the ResNet (oracle inside train_ref.train_mode())."""
+    """`train`: model.train() semantics -- batch-statistics BatchNorm in the ResNet (oracle inside train_ref.train_mode()).
+    In train mode the oracle's ReLUs take their masks from the HIP forward (each ReLU there is the activation of one
+    ops.batchnorm_train call, in the oracle's order): a pre-activation within rounding of zero may land on either side in
+    two float32 computations, and on 4 x 8 maps with batch-statistics BatchNorm one such tie moves whole channels of
+    gradients (the float32 CPU oracle's own ties change with the host's thread count).  Every mask that differs from the
+    oracle's own sign must be such a tie (|x| <= 1e-4 of the layer's largest pre-activation), so a wrong mask still fails."""
     from oracle import model_ref as M, train_ref as TR
-    from thinktwice_amd import autodiff, config, layers, params, weights
+    from thinktwice_amd import autodiff, config, layers, ops, params, weights
     import contextlib
+    import inspect
     hw, NI = (64, 128), 4 if train else 2
     mode = TR.train_mode if train else contextlib.nullcontext
     cfg = config.model_config(final_dim=hw)
     sd = params.init_params(cfg, seed=3, parts=("img_encoder",))
+    g = torch.Generator().manual_seed(7)
+    img = torch.randn(NI, 3, *hw, generator=g)
+    # ---- HIP: taped forward of the trunk (recording the ReLU masks), seeded with R, backward kernels
+    from thinktwice_amd.lss import LSS
+    enc_cfg = {k: v for k, v in cfg["img_encoder"].items() if k != "type"}
+    enc = LSS(**enc_cfg, dtype="f32x3" if x3 else torch.float32).load_state_dict(sd)
+    x = weights.to_channel_last(img, torch.float32).cuda()
+    masks = []
+    bn_train = ops.batchnorm_train
+
+    def recording_bn_train(z, spec, act=0, *args, **kw):
+        out = bn_train(z, spec, act, *args, **kw)
+        if act:
+            assert act == layers.ACT["relu"], act
+            coff = inspect.signature(bn_train).bind(z, spec, act, *args, **kw).arguments.get("out_coff", 0)
+            c = z.shape[-1]
+            masks.append((out[..., coff:coff + c] > 0).permute(0, 3, 1, 2).cpu())
+        return out
+    saved, layers.BN_TRAIN = layers.BN_TRAIN, train
+    ops.batchnorm_train = recording_bn_train
+    try:
+        with autodiff.Tape(x3=x3) as tape:
+            bufs = enc._trunk(x)
+            views = enc._fpn_views(bufs)
+            R = [torch.randn((t.shape[0], c, t.shape[1], t.shape[2]), generator=g) for t, off, c in views]
+            for (t, off, c), r in zip(views, R):
+                tape.seed(t[..., off:off + c], r.permute(0, 2, 3, 1))
+            tape.backward()
+    finally:
+        layers.BN_TRAIN = saved
+        ops.batchnorm_train = bn_train
     # ---- oracle: autograd over the trunk's parameters
     leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items()
               if (k.startswith("img_encoder.img_backbone") or k.startswith("img_encoder.img_neck"))
               and v.is_floating_point() and not k.endswith(("running_mean", "running_var"))}
     sdr = dict(sd)
     sdr.update(leaves)
-    g = torch.Generator().manual_seed(7)
-    img = torch.randn(NI, 3, *hw, generator=g)
-    with mode():
-        outs = M.pafpn(sdr, "img_encoder.img_neck", M.resnet50(sdr, "img_encoder.img_backbone", img))
-        R = [torch.randn(o.shape, generator=g) for o in outs]
-        loss = sum((o * r).sum() for o, r in zip(outs, R))
-        loss.backward()
-    # ---- HIP: taped forward of the same trunk, seeded with R, backward kernels
-    from thinktwice_amd.lss import LSS
-    enc_cfg = {k: v for k, v in cfg["img_encoder"].items() if k != "type"}
-    enc = LSS(**enc_cfg, dtype="f32x3" if x3 else torch.float32).load_state_dict(sd)
-    x = weights.to_channel_last(img, torch.float32).cuda()
-    saved, layers.BN_TRAIN = layers.BN_TRAIN, train
+    ties = []
+
+    class MaskedReLU:              # torch.nn.functional, except that relu applies the next recorded HIP mask
+        def __init__(self):
+            self.next = iter(masks)
+
+        def __getattr__(self, name):
+            return getattr(torch.nn.functional, name)
+
+        def relu(self, v):
+            m = next(self.next)
+            assert m.shape == v.shape, (m.shape, v.shape)
+            d = v.detach()
+            differ = m != (d > 0)
+            if differ.any():
+                ties.append((int(differ.sum()), float(d[differ].abs().max() / d.abs().max())))
+            return v * m.to(v.dtype)
+    saved_f, masked = M.F, MaskedReLU()
+    if train:
+        M.F = masked
     try:
-        with autodiff.Tape(x3=x3) as tape:
-            bufs = enc._trunk(x)
-            for (t, off, c), r in zip(enc._fpn_views(bufs), R):
-                tape.seed(t[..., off:off + c], r.permute(0, 2, 3, 1))
-            tape.backward()
+        with mode():
+            outs = M.pafpn(sdr, "img_encoder.img_neck", M.resnet50(sdr, "img_encoder.img_backbone", img))
+            loss = sum((o * r).sum() for o, r in zip(outs, R))
+            loss.backward()
     finally:
-        layers.BN_TRAIN = saved
+        M.F = saved_f
+    if train:
+        assert len(masks) == 49 and next(masked.next, None) is None      # stem + 16 bottlenecks x 3, each used once
+        print("trunk backward: ReLU ties (elements, |x| / layer max)", ties)
+        assert all(rel <= 1e-4 for _, rel in ties), ties
     torch.cuda.synchronize()
     # forward sanity (same maps), then every parameter's gradient
     for (t, off, c), o in zip(enc._fpn_views(bufs), outs):
@@ -65,14 +112,9 @@ def test_camera_trunk_backward_matches_oracle_autograd(x3, train):
     bad = {k: e for k, e in worst.items() if e > tol}
     print("trunk backward: params", len(worst), "worst rel err", max(worst.values()), "top",
           [(k[25:], round(e, 5), float(leaves[k].grad.abs().max())) for k, e in sorted(worst.items(), key=lambda kv: -kv[1])[:12]])
+    assert not bad, sorted(bad.items(), key=lambda kv: -kv[1])[:8]
     if train:
-        # one ReLU mask flips on this input (channel 10 of layer1.0.conv1: tools/debug_trunk_train.py shows the whole excess in
-        # that one output channel; the same bottleneck is exact to 5e-7 in isolation, tools/debug_bn_block.py): its own
-        # weight / bias gradients move by ~1e-2, everything else stays inside 1e-3
-        assert len(bad) <= 3 and max(bad.values(), default=0.0) < 3e-2, sorted(bad.items(), key=lambda kv: -kv[1])[:8]
         assert float(np.median(list(worst.values()))) < 2e-5
-    else:
-        assert not bad, sorted(bad.items(), key=lambda kv: -kv[1])[:8]
 
 
 def test_seg_loss_backward_through_unet_and_trunk_matches_oracle_autograd():

@@ -12,8 +12,8 @@ run() {  # name, extra rocprof args..., -- bench args
   local name=$1; shift
   timeout 300 rocprofv3 "$@" > "$OUT/prof_${TAG}_${name}.log" 2>&1
 }
-V="python $ROOT/bench.py --workload voxel_pool --steps 5 --warmup 2 --no-cpu-baseline"
-F="python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+V="python $ROOT/bench.py --full --workload voxel_pool --steps 5 --warmup 2 --no-cpu-baseline"
+F="python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
 run trace_voxel --kernel-trace --stats -d "$OUT/prof_${TAG}_trace_voxel" -o p --output-format csv -- $V
 run fetch_voxel --kernel-trace --pmc FETCH_SIZE -d "$OUT/prof_${TAG}_fetch_voxel" -o p --output-format csv -- $V
 run write_voxel --kernel-trace --pmc WRITE_SIZE -d "$OUT/prof_${TAG}_write_voxel" -o p --output-format csv -- $V
