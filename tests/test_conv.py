@@ -734,3 +734,48 @@ def test_bf16x3_layer_with_residual_can_store_half_and_an_f32_twin():
     assert half.dtype == torch.float16
     assert torch.equal(twin, want)
     assert torch.equal(half, want.half())
+
+
+def test_launch_state_is_per_device():
+    """The per-device launch state (csrc/common.cpp: the zero page of the LDS-DMA kernels, the dynamic-LDS opt-ins): one small
+    launch of every kernel family that takes either, on cuda:0 and then on cuda:1 in one process.  The second device gets its
+    own zero page and its own opt-ins, so it runs the same kernels and computes the same bits."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible devices (one process driving two)")
+    from thinktwice_amd import config, decoder_fused as DF, ops, params, weights
+    g = torch.Generator().manual_seed(23)
+    x = _mk((1, 129, 256, 128), g)                  # channel-last, M = 33,024 rows: 129 row tiles make the 256-wide tile cheapest
+    dy = _mk((1, 129, 256, 128), g)
+    w1 = _mk((256, 1, 1, 128), g, 128 ** -0.5)
+    w3 = _mk((256, 3, 3, 128), g, 1152 ** -0.5)
+    nbr, rows_in = _grid_rulebook(2, 10, 60, 60, 0.10, 1, g)
+    feats = _mk((rows_in, 32), g)
+    wsp = _mk((32, 1, 27, 32), g, (27 * 32) ** -0.5)
+    maps = _mk((6, 441, 32), g).abs()
+    sd = params.init_params(config.model_config(final_dim=(128, 256)), seed=0, parts=("fusion",))
+
+    def run(dev):
+        outs, labels = [], []
+
+        def conv(out):
+            outs.append(out)
+            labels.append(ops._last_conv_kernel())
+        with torch.cuda.device(dev):
+            xd, w1d, w3d, wspd = x.to(dev), w1.to(dev), w3.to(dev), wsp.to(dev)
+            conv(ops.conv2d(xd, w1d, w_x3=weights.split_pairs_x3(w1d)))                          # K = 128: 160 KiB LDS-DMA tile
+            conv(ops.conv2d(xd, w3d, pad=1, w_x3=weights.split_pairs_x3(w3d)))                   # K = 1152: run-staged x3 kernel
+            conv(ops.conv2d(xd.half(), w3d.half(), pad=1, w_h2=weights.split_pairs_h2(w3d)))     # h2 pipe kernel
+            live = torch.tensor([nbr.shape[0]], dtype=torch.int32, device=dev)
+            conv(ops.gather_conv(feats.to(dev), nbr.to(dev), live, wspd, w_x3=weights.split_pairs_x3(wspd)))
+            outs.append(ops.conv2d_wgrad(xd, dy.to(dev), 3, 3, 1, 1, x3=True))                   # bf16x3 weight gradient
+            outs.append(ops.dec_flatten(DF.prep_flatten(sd, dev), maps.to(dev)))
+            torch.cuda.synchronize()
+        return [o.cpu() for o in outs], labels
+
+    out0, labels0 = run("cuda:0")
+    out1, labels1 = run("cuda:1")
+    assert labels0 == ["conv_igemm_glds_kernel<float, 256, 4, 2, 128, 23, false, true>", "conv_x3_run3_kernel<256>",
+                       "conv_h2_pipe_kernel", "sp_conv_runs_kernel<1, 8, 1>"], labels0
+    assert labels1 == labels0
+    for a, b in zip(out0, out1):
+        assert torch.equal(a, b)

@@ -1,9 +1,12 @@
-// Error reporting + version for libthinktwice_hip.so.
+// Error reporting, per-device launch state and version for libthinktwice_hip.so.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
-#include "../../include/thinktwice_hip.h"
+#include <mutex>
+#include <unordered_map>
+
+#include "tt_common.h"
 
 namespace tt {
 static thread_local char g_err[512] = "";
@@ -12,6 +15,68 @@ void set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+namespace {
+struct LdsGrant {
+    size_t granted = 0;
+    hipError_t refusal = hipSuccess;
+};
+struct LaunchState {
+    void* zero_page = nullptr;
+    std::unordered_map<const void*, LdsGrant> lds;     // per kernel
+};
+std::mutex g_launch_mutex;
+LaunchState g_launch[kMaxDevices];
+
+int current_device(const char* who) {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) {
+        (void)hipGetLastError();
+        if (who) set_error("%s: no current device", who);
+        return -1;
+    }
+    return dev;
+}
+}  // namespace
+
+const void* zero_page(const char* who) {
+    const int dev = current_device(who);
+    if (dev < 0) return nullptr;
+    std::lock_guard<std::mutex> lock(g_launch_mutex);
+    void*& z = g_launch[dev].zero_page;
+    if (!z) {
+        void* p = nullptr;
+        hipError_t e = hipMalloc(&p, 256);
+        if (e == hipSuccess && (e = hipMemset(p, 0, 256)) != hipSuccess) (void)hipFree(p);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: cannot allocate the zero page on device %d: %s", who, dev, hipGetErrorString(e));
+            return nullptr;
+        }
+        z = p;
+    }
+    return z;
+}
+
+int lds_opt_in(const void* kernel, size_t bytes, const char* name) {
+    const int dev = current_device(name);
+    if (dev < 0) return -1;
+    std::lock_guard<std::mutex> lock(g_launch_mutex);
+    LdsGrant& g = g_launch[dev].lds[kernel];
+    if (bytes <= g.granted) return 0;
+    if (g.refusal == hipSuccess) {
+        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e == hipSuccess) {
+            g.granted = bytes;
+            return 0;
+        }
+        (void)hipGetLastError();     // a refusal must not surface later as a stale launch error
+        g.refusal = e;
+    }
+    if (name)
+        set_error("%s: device %d refuses %zu bytes of dynamic LDS: %s", name, dev, bytes, hipGetErrorString(g.refusal));
+    return -1;
 }
 }  // namespace tt
 

@@ -834,15 +834,6 @@ static int wgrad_splits(int N, int OH, int Cout, int Cin, int taps) {
     return (int)s;
 }
 
-static const float* wgrad_zero_page() {      // source of the LDS-DMA pieces that lie outside the image / the channel window
-    static void* z = nullptr;
-    if (!z) {
-        if (hipMalloc(&z, 256) != hipSuccess) return nullptr;
-        (void)hipMemset(z, 0, 256);
-    }
-    return (const float*)z;
-}
-
 // partial-sum slices in the workspace: one per split, x 4 in the wide kernel (one per wave)
 static int wgrad_slices(int N, int OH, int Cout, int Cin, int taps) {
     int bi, bj;
@@ -879,7 +870,6 @@ static int wgrad_run(const float* x, int N, int H, int W, int Cin, int x_cstride
     // >= 64 channels on both sides: the LDS-staged bf16x3 kernel (iteration 962 -> 820 ms against the f32-MFMA wave-tile form)
     if (x3 && Cout >= 64 && Cin >= 64 && Cout % 4 == 0 && Cin % 4 == 0 && x_cstride % 4 == 0 && x_coff % 4 == 0 &&
         dy_cstride % 4 == 0 && dy_coff % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0) {
-        const float* zp = wgrad_zero_page();
         // the kernel walks image rows in 32-pixel segments: a 1x1 / stride-1 / unpadded layer (linear layers over rows: OW = 1)
         // is the same sum over ANY regrouping of its pixels, so short rows are merged into pseudo-rows of >= 128 pixels;
         // other layers with rows shorter than 16 pixels (the 1 x 9 grouped deformable-conv GEMM) keep the f32 kernels
@@ -895,7 +885,9 @@ static int wgrad_run(const float* x, int N, int H, int W, int Cin, int x_cstride
             }
         }
         const int cap = wgrad_slices(N, OH, Cout, Cin, taps);         // partial-sum slices the caller's workspace holds
-        if (zp && al.OW >= 16) {
+        if (al.OW >= 16) {
+            const float* zp = static_cast<const float*>(zero_page("conv_wgrad_lds_kernel"));
+            if (!zp) return -1;
             WgradArgs& a = al;      // (shadows the caller's view for this launch)
             const int N = a.N, OH = a.OH;
             const int BI = Cout >= 256 ? 4 : (Cout >= 128 ? 2 : 1), BJ = Cin >= 256 ? 4 : (Cin >= 128 ? 2 : 1);
@@ -912,28 +904,20 @@ static int wgrad_run(const float* x, int N, int H, int W, int Cin, int x_cstride
             a.xcd_tiles = 0;
             const dim3 grid((unsigned)tiles, (unsigned)nsplit);
             const size_t smem = (size_t)2 * 32 * (64 * BI + 64 * BJ) * 4;
-#define TT_WGL(BI_, BJ_)                                                                                                  \
-    do {                                                                                                                  \
-        static bool attr = false;                                                                                         \
-        if (!attr) {                                                                                                      \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_lds_kernel<BI_, BJ_>),                     \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                             \
-            attr = true;                                                                                                  \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((conv_wgrad_lds_kernel<BI_, BJ_>), grid, dim3(256), smem, st, a, zp);                          \
-    } while (0)
+            void (*kern)(const WgradArgs, const float*);
             switch (BI * 8 + BJ) {
-                case 4 * 8 + 4: TT_WGL(4, 4); break;
-                case 4 * 8 + 2: TT_WGL(4, 2); break;
-                case 4 * 8 + 1: TT_WGL(4, 1); break;
-                case 2 * 8 + 4: TT_WGL(2, 4); break;
-                case 2 * 8 + 2: TT_WGL(2, 2); break;
-                case 2 * 8 + 1: TT_WGL(2, 1); break;
-                case 1 * 8 + 4: TT_WGL(1, 4); break;
-                case 1 * 8 + 2: TT_WGL(1, 2); break;
-                default: TT_WGL(1, 1); break;
+                case 4 * 8 + 4: kern = conv_wgrad_lds_kernel<4, 4>; break;
+                case 4 * 8 + 2: kern = conv_wgrad_lds_kernel<4, 2>; break;
+                case 4 * 8 + 1: kern = conv_wgrad_lds_kernel<4, 1>; break;
+                case 2 * 8 + 4: kern = conv_wgrad_lds_kernel<2, 4>; break;
+                case 2 * 8 + 2: kern = conv_wgrad_lds_kernel<2, 2>; break;
+                case 2 * 8 + 1: kern = conv_wgrad_lds_kernel<2, 1>; break;
+                case 1 * 8 + 4: kern = conv_wgrad_lds_kernel<1, 4>; break;
+                case 1 * 8 + 2: kern = conv_wgrad_lds_kernel<1, 2>; break;
+                default: kern = conv_wgrad_lds_kernel<1, 1>; break;
             }
-#undef TT_WGL
+            if (lds_opt_in(reinterpret_cast<const void*>(kern), smem, "conv_wgrad_lds_kernel")) return -1;
+            hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, a, zp);
             const long long n = (long long)Cout * taps * cin_pad;
             hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)div_up(n, 32)), dim3(256), 0, st, (const float*)workspace,
                                n, nsplit, accumulate, dw);

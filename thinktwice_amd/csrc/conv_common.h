@@ -487,7 +487,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[T
     }
 }
 
-// glds (LDS-DMA, 3-stage) variant: returns 1 if it took the launch, 0 if the shape is not covered.
+// glds (LDS-DMA, 3-stage) variant: returns 1 if it took the launch, 0 if the shape is not covered, < 0 (error text set) if the
+// launch failed -- the caller returns that and tries no other kernel.
 int try_launch_conv_glds(ConvArgs& a, int dtype, hipStream_t st);
 // bf16x3 variant of the same kernel (f32 storage, pre-split weights in a.weight): same contract.
 int try_launch_conv_glds_x3(ConvArgs& a, hipStream_t st);
@@ -499,7 +500,7 @@ int try_launch_conv_x3_pipe(ConvArgs& a, hipStream_t st, int m_tiles_limit, int 
 // run-staged sparse 3x3x3 conv (csrc/sp_conv_runs.hip; bf16x3, a.weight = pre-split weights): same contract.
 int try_launch_sp_conv_runs(ConvArgs& a, hipStream_t st);
 // "h2" arithmetic (csrc/conv_h2.hip): IEEE-half activations x f16 (hi, lo) weight pairs in a.weight, two MFMAs per product.
-// Returns 1 if it took the launch, 0 if the shape is outside its contract (dense, Cin % 64 == 0, KH*KW <= 31).
+// Returns 1 if it took the launch, 0 if the shape is outside its contract (dense, Cin % 64 == 0, KH*KW <= 31), < 0 on failure.
 int try_launch_conv_h2(ConvArgs& a, hipStream_t st);
 // latency-bound small-M variant (32x32 tile, intra-block split-K): same contract.
 int try_launch_conv_small(ConvArgs& a, int dtype, hipStream_t st);

@@ -575,21 +575,10 @@ __global__ __launch_bounds__(256, 1) void conv_h2_pipe_kernel(const ConvArgs p, 
 #endif
 }
 
-static const void* h2_zero_page() {
-    static void* z = nullptr;
-    if (!z) {
-        if (hipMalloc(&z, 256) != hipSuccess) return nullptr;
-        (void)hipMemset(z, 0, 256);
-    }
-    return z;
-}
-
 template <int BN, int WAVES_M, int WAVES_N, int SA, int SB>
 static int launch_h2(ConvArgs& a, hipStream_t st) {
     constexpr int BM = 256, A_BYTES = BM * 128, B_BYTES = BN * 256;
     constexpr int NW = WAVES_M * WAVES_N, WTN = BN / WAVES_N;
-    const void* zp = h2_zero_page();
-    if (!zp) return 0;
     const int tiles_m = div_up(a.M - a.m_begin, BM), tiles_n = div_up(a.Cout, BN);
     const int nk = a.K / 64;
     const int sa_used = nk < SA ? nk : SA, sb_used = nk < SB ? nk : SB;
@@ -597,13 +586,10 @@ static int launch_h2(ConvArgs& a, hipStream_t st) {
     const size_t epi = (size_t)NW * 32 * (WTN + 4) * 4;
     if (smem < epi) smem = epi;
     auto kern = conv_h2_kernel<BN, WAVES_M, WAVES_N, SA, SB>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        size_t full = (size_t)SA * A_BYTES + (size_t)SB * B_BYTES;
-        if (full < epi) full = epi;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)full);
-        attr_set = true;
-    }
+    size_t full = (size_t)SA * A_BYTES + (size_t)SB * B_BYTES;      // all stages in use: the largest request
+    if (full < epi) full = epi;
+    const void* zp = zero_page("conv_h2_kernel");
+    if (!zp || lds_opt_in(reinterpret_cast<const void*>(kern), full, "conv_h2_kernel")) return -1;
     a.tiles_n = tiles_n;
     a.splits = 1;
     a.ws = nullptr;
@@ -613,15 +599,10 @@ static int launch_h2(ConvArgs& a, hipStream_t st) {
 }
 
 static int launch_h2_pipe(ConvArgs& a, hipStream_t st) {
-    const void* zp = h2_zero_page();
-    if (!zp) return 0;
     const int tiles_m = div_up(a.M - a.m_begin, 256), tiles_n = a.Cout / 128;
     const size_t smem = (size_t)5 * 32 * 1024;                       // 3 + 2 stages (the epilogue's 4 x 32 x 132 floats fit inside)
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_h2_pipe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr_set = true;
-    }
+    const void* zp = zero_page("conv_h2_pipe_kernel");
+    if (!zp || lds_opt_in(reinterpret_cast<const void*>(conv_h2_pipe_kernel), smem, "conv_h2_pipe_kernel")) return -1;
     a.tiles_n = tiles_n;
     a.splits = 1;
     a.ws = nullptr;

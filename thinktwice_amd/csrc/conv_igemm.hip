@@ -266,15 +266,6 @@ static int launch_conv(ConvArgs& a, hipStream_t st) {
     const size_t epi = (size_t)4 * 32 * (WTN_ + 4) * 4;            // LDS-staged epilogue
     if (smem < epi) smem = epi;
     auto kern = conv_igemm_kernel<T, BM, BN, WAVES_M, WAVES_N, GATHER, KX>;
-    static bool attr_set = false;
-    if (!attr_set) {   // once per instantiation, sized for the largest (double-buffered) request
-        size_t mx = (size_t)2 * (BM + BN) * ROWB;
-        if (mx < epi) mx = epi;
-        if (mx > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)mx);
-        attr_set = true;
-    }
     const int tiles = tiles_m * a.tiles_n;
     const int nk = div_up(a.K, BK);
     a.splits = 1;
@@ -293,6 +284,9 @@ static int launch_conv(ConvArgs& a, hipStream_t st) {
         TT_REQUIRE(a.ws_slices >= eff, "tt_conv2d_fwd: split-K workspace holds %d slices, %d needed", a.ws_slices, eff);
         a.ws_slices = eff;
     }
+    size_t mx = (size_t)2 * (BM + BN) * ROWB;      // the largest (double-buffered) request
+    if (mx < epi) mx = epi;
+    if (mx > 48 * 1024 && lds_opt_in(reinterpret_cast<const void*>(kern), mx, "conv_igemm_kernel")) return -1;
     snprintf(g_conv_kernel, sizeof(g_conv_kernel), "conv_igemm_kernel<%s, %d, %d>%s", sizeof(T) == 4 ? "float" : "16-bit",
              BM, BN, a.ws ? " split-K" : "");
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.splits), dim3(256), smem, st, a);
@@ -439,8 +433,9 @@ static int conv2d_run(const tt_conv_desc* d, void* stream, bool query) {
         TT_REQUIRE((reinterpret_cast<uintptr_t>(d->weight_h2) & 15) == 0, "tt_conv2d_fwd: weight_h2 must be 16-byte aligned");
         ConvArgs ah = a;
         ah.weight = d->weight_h2;
-        TT_REQUIRE(try_launch_conv_h2(ah, st), "tt_conv2d_fwd: weight_h2 layer outside the h2 kernel's contract (Cin=%d KH*KW=%d)",
-                   d->Cin, d->KH * d->KW);
+        const int r = try_launch_conv_h2(ah, st);
+        if (r < 0) return r;
+        TT_REQUIRE(r, "tt_conv2d_fwd: weight_h2 layer outside the h2 kernel's contract (Cin=%d KH*KW=%d)", d->Cin, d->KH * d->KW);
         return check_launch("tt_conv2d_fwd(h2)");
     }
     TT_REQUIRE(!d->out2 || a.vec_epi, "tt_conv2d_fwd: out2 needs the vector epilogue (aligned channel counts)");
@@ -453,8 +448,10 @@ static int conv2d_run(const tt_conv_desc* d, void* stream, bool query) {
                    "tt_conv2d_fwd: in_pair / out_pair need the vector epilogue and a 16-byte aligned weight_x3");
         ConvArgs ax = a;
         ax.weight = d->weight_x3;
-        TT_REQUIRE(try_launch_conv_glds_x3(ax, st), "tt_conv2d_fwd: pair-format layer outside the LDS-DMA bf16x3 kernel's contract "
-                   "(M=%d Cin=%d Cout=%d)", a.M, d->Cin, d->Cout);
+        const int r = try_launch_conv_glds_x3(ax, st);
+        if (r < 0) return r;
+        TT_REQUIRE(r, "tt_conv2d_fwd: pair-format layer outside the LDS-DMA bf16x3 kernel's contract (M=%d Cin=%d Cout=%d)", a.M,
+                   d->Cin, d->Cout);
         return check_launch("tt_conv2d_fwd(glds x3, pair)");
     }
     if (!d->splitk_ws && !d->out2 && d->res1_up_w <= 0 && !d->res1_f32 && try_launch_conv_small(a, d->dtype, st)) {
@@ -465,7 +462,8 @@ static int conv2d_run(const tt_conv_desc* d, void* stream, bool query) {
         (reinterpret_cast<uintptr_t>(d->weight_x3) & 15) == 0) {
         ConvArgs ax = a;
         ax.weight = d->weight_x3;
-        if (launch_conv_glds_x3_splitk(ax, st)) {
+        if (const int r = launch_conv_glds_x3_splitk(ax, st)) {
+            if (r < 0) return r;
             const long long tot = (long long)ax.M * ax.Cout;
             hipLaunchKernelGGL(splitk_finalize_kernel<float>, dim3((unsigned)div_up(tot, 256)), dim3(256), 0, st, ax);
             return check_launch("tt_conv2d_fwd(glds x3 split-K)");
@@ -476,9 +474,9 @@ static int conv2d_run(const tt_conv_desc* d, void* stream, bool query) {
                    "tt_conv2d_fwd: weight_x3 needs 16-byte alignment and K %% 16 == 0 (K = %d)", a.K);
         ConvArgs ax = a;
         ax.weight = d->weight_x3;
-        if (try_launch_conv_glds_x3(ax, st)) return check_launch("tt_conv2d_fwd(glds x3)");
+        if (const int r = try_launch_conv_glds_x3(ax, st)) return r < 0 ? r : check_launch("tt_conv2d_fwd(glds x3)");
     }
-    if (!d->splitk_ws && try_launch_conv_glds(a, d->dtype, st)) return check_launch("tt_conv2d_fwd(glds)");
+    if (const int r = d->splitk_ws ? 0 : try_launch_conv_glds(a, d->dtype, st)) return r < 0 ? r : check_launch("tt_conv2d_fwd(glds)");
     a.row_perm = nullptr;      // the tile plan is an LDS-DMA-kernel feature: the other kernels walk rows and taps in
     a.row_mask = nullptr;      // natural order (same result)
     if (d->dtype == TT_F32) return dispatch_conv<float>(a, st);

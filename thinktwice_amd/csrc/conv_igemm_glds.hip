@@ -658,21 +658,10 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
 #endif
 }
 
-static const void* zero_page() {
-    static void* z = nullptr;
-    if (!z) {
-        if (hipMalloc(&z, 256) != hipSuccess) return nullptr;
-        (void)hipMemset(z, 0, 256);
-    }
-    return z;
-}
-
 template <typename T, int BN, int WAVES_M, int WAVES_N, int BKB, int STAGES = 3, bool GATHER = false, bool X3 = false, bool APAIR = false>
 static int launch_glds(ConvArgs& a, hipStream_t st, int m_tiles_limit = 0, int splits = 1, int slices = 1) {
     constexpr int BM = 256;
     constexpr int WTN = BN / WAVES_N;
-    const void* zp = zero_page();
-    if (!zp) return 0;
     // rows [m_begin, M) by default; `m_tiles_limit` > 0 restricts the launch to that many row tiles from m_begin
     int tiles_m = div_up(a.M - a.m_begin, BM);
     if (m_tiles_limit > 0 && m_tiles_limit < tiles_m) tiles_m = m_tiles_limit;
@@ -681,12 +670,8 @@ static int launch_glds(ConvArgs& a, hipStream_t st, int m_tiles_limit = 0, int s
     const size_t epi = (size_t)(WAVES_M * WAVES_N) * 32 * (WTN + 4) * 4;
     if (smem < epi) smem = epi;
     auto kern = conv_igemm_glds_kernel<T, BN, WAVES_M, WAVES_N, BKB, STAGES, GATHER, X3, APAIR>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)smem);
-        attr_set = true;
-    }
+    const void* zp = zero_page("conv_igemm_glds_kernel");
+    if (!zp || lds_opt_in(reinterpret_cast<const void*>(kern), smem, "conv_igemm_glds_kernel")) return -1;
     a.tiles_n = tiles_n;
     a.splits = splits;
     if (splits <= 1) a.ws = nullptr;       // split-K: a.ws / a.ws_slices are the caller's (ordered slices, `slices` non-empty ranges)
@@ -748,10 +733,10 @@ int launch_conv_glds_x3_splitk(ConvArgs& a, hipStream_t st) {
 
 // bf16x3 arithmetic on f32 storage (see the kernel's template comment).  `a.weight` must already point at the
 // pre-split weights.  Returns 0 when the shape is outside the DMA kernel's contract (the caller then runs the exact
-// f32 path on the plain weights).
+// f32 path on the plain weights), < 0 when a launch failed.
 int try_launch_conv_glds_x3(ConvArgs& a, hipStream_t st) {
     if (a.gather) {
-        if (try_launch_sp_conv_runs(a, st)) return 1;      // 3x3x3 rulebooks with 32+ channels: run-staged kernel
+        if (const int r = try_launch_sp_conv_runs(a, st)) return r;      // 3x3x3 rulebooks with 32+ channels: run-staged kernel
         const bool cin_ok = a.Cin >= 16 && (a.Cin & (a.Cin - 1)) == 0;
         if (!cin_ok || a.M < 2048 || a.Cout < 16 || a.Cout > 128) return 0;
         if (a.Cout <= 32) return launch_glds<float, 32, 8, 1, 128, 2, true, true>(a, st);
@@ -804,21 +789,19 @@ int try_launch_conv_glds_x3(ConvArgs& a, hipStream_t st) {
     const bool hand = pipe && a.K >= 1152;
     if (bn == 256) {                                                                                           // 8 x (64 x 128)
         const int main_rows = tail_split_rows(a);
-        if (hand && try_launch_conv_x3_pipe(a, st, main_rows)) { /* taken */ }
-        else if (apair) launch_glds<float, 256, 4, 2, 128, 23, false, true, true>(a, st, main_rows);
-        else launch_glds<float, 256, 4, 2, 128, 23, false, true>(a, st, main_rows);      // 3 activation + 2 weight stages = 160 KiB
-        if (main_rows) {
-            ConvArgs t = a;
-            t.m_begin = main_rows * 256;
-            return apair ? launch_glds<float, 64, 8, 1, 128, 2, false, true, true>(t, st)
-                         : launch_glds<float, 64, 8, 1, 128, 2, false, true>(t, st);
-        }
-        return 1;
+        int r = hand ? try_launch_conv_x3_pipe(a, st, main_rows) : 0;
+        if (!r) r = apair ? launch_glds<float, 256, 4, 2, 128, 23, false, true, true>(a, st, main_rows)
+                          : launch_glds<float, 256, 4, 2, 128, 23, false, true>(a, st, main_rows);     // 3 + 2 stages = 160 KiB
+        if (r < 0 || !main_rows) return r;
+        ConvArgs t = a;
+        t.m_begin = main_rows * 256;
+        return apair ? launch_glds<float, 64, 8, 1, 128, 2, false, true, true>(t, st)
+                     : launch_glds<float, 64, 8, 1, 128, 2, false, true>(t, st);
     }
     // Narrow tiles: two LDS stages (a third costs the 64-wide tile its second workgroup per CU: N=64 K=576 2.13 -> 2.66 ms), eight
     // waves (four waves of 64 x 64 on the 64-wide tile: 3-15 % slower, profiles/r05_x3_64wide_waves_ab.txt)
     if (bn == 128) {                                                                                           // 8 x (32 x 128)
-        if (hand && a.Cout % 128 == 0 && try_launch_conv_x3_pipe(a, st, 0, 128)) return 1;
+        if (const int r = hand && a.Cout % 128 == 0 ? try_launch_conv_x3_pipe(a, st, 0, 128) : 0) return r;
         return apair ? launch_glds<float, 128, 8, 1, 128, 2, false, true, true>(a, st)
                      : launch_glds<float, 128, 8, 1, 128, 2, false, true>(a, st);
     }
@@ -877,7 +860,7 @@ static int launch_glds16(ConvArgs& a, int dtype, hipStream_t st, int min_tiles) 
         }
         if (v == 6 && a.Cout % 256 == 0 && a.Cin % 64 == 0) {
             if (const int main_rows = tail_split_rows(a)) {
-                launch_glds<T16, 256, 2, 4, 128, 2>(a, st, main_rows);
+                if (launch_glds<T16, 256, 2, 4, 128, 2>(a, st, main_rows) < 0) return -1;
                 ConvArgs t = a;
                 t.m_begin = main_rows * 256;
                 return launch_glds<T16, 64, 8, 1, 128, 2>(t, st);

@@ -839,21 +839,13 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
 #endif
 }
 
-static const void* pipe_zero_page() {
-    static void* z = nullptr;
-    if (!z) {
-        if (hipMalloc(&z, 256) != hipSuccess) return nullptr;
-        (void)hipMemset(z, 0, 256);
-    }
-    return z;
-}
-
-// Returns 1 if the launch was taken.  `m_tiles_limit` > 0: only that many row tiles from a.m_begin (tail split).
+// Returns 1 if the launch was taken, 0 if the shape is not covered, < 0 if the launch failed.  `m_tiles_limit` > 0: only that many
+// row tiles from a.m_begin (tail split).
 int try_launch_conv_x3_pipe(ConvArgs& a, hipStream_t st, int m_tiles_limit, int bn) {
     const bool apair = (a.flags & 32) != 0;          // pre-split activations (tt_conv_desc.in_pair)
     if (a.gather || a.m_dev || (bn != 256 && bn != 128) || a.Cout % bn != 0 || a.Cin % 32 != 0 || a.KH * a.KW > 31 || a.K < 64) return 0;
-    const void* zp = pipe_zero_page();
-    if (!zp) return 0;
+    const void* zp = zero_page("conv_x3_pipe_kernel");
+    if (!zp) return -1;
     int tiles_m = div_up(a.M - a.m_begin, 256);
     if (m_tiles_limit > 0 && m_tiles_limit < tiles_m) tiles_m = m_tiles_limit;
     const int tiles_n = a.Cout / bn;
@@ -865,15 +857,7 @@ int try_launch_conv_x3_pipe(ConvArgs& a, hipStream_t st, int m_tiles_limit, int 
         const size_t smem_r = (size_t)2 * 288 * 128 + (size_t)2 * bn * 128 + 256;
         auto kr = bn == 128 ? (apair ? conv_x3_run3_kernel<128, true> : conv_x3_run3_kernel<128>)
                             : (apair ? conv_x3_run3_kernel<256, true> : conv_x3_run3_kernel<256>);
-        static bool attr_r = false;
-        if (!attr_r) {
-            const int s128 = 2 * 288 * 128 + 2 * 128 * 128 + 256, s256 = 2 * 288 * 128 + 2 * 256 * 128 + 256;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_run3_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, s128);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_run3_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, s256);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_run3_kernel<128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, s128);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_run3_kernel<256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, s256);
-            attr_r = true;
-        }
+        if (lds_opt_in(reinterpret_cast<const void*>(kr), smem_r, "conv_x3_run3_kernel")) return -1;
         a.tiles_n = tiles_n;
         a.splits = 1;
         a.ws = nullptr;
@@ -891,15 +875,7 @@ int try_launch_conv_x3_pipe(ConvArgs& a, hipStream_t st, int m_tiles_limit, int 
     // 2 x 2 grid of 128 x 128 waves measured slower, profiles/r04_pipe_ab_grids.txt)
     auto kern = bn == 128 ? (apair ? conv_x3_pipe_kernel<4, 1, 128, true> : conv_x3_pipe_kernel<4, 1, 128>)
                           : (apair ? conv_x3_pipe_kernel<4, 1, 256, true> : conv_x3_pipe_kernel<4, 1>);
-    static bool attr_set = false;
-    if (!attr_set) {
-        const int full = (3 * 256 + 2 * 256) * 128;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_pipe_kernel<4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, full);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_pipe_kernel<4, 1, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, full);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_pipe_kernel<4, 1, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, full);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_pipe_kernel<4, 1, 128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, full);
-        attr_set = true;
-    }
+    if (lds_opt_in(reinterpret_cast<const void*>(kern), smem, "conv_x3_pipe_kernel")) return -1;
     a.tiles_n = tiles_n;
     a.splits = 1;
     a.ws = nullptr;

@@ -583,12 +583,7 @@ extern "C" int tt_mlp_chain(const float* x, long long R, int x_stride, int nstag
             TT_REQUIRE(a.st[a.st[s].in_sel].lds_stride == a.st[s].Kp * 4 + 16, "tt_mlp_chain: stage %d Kp mismatch", s);
     TT_REQUIRE(total <= 160 * 1024, "tt_mlp_chain: intermediates need %zu B of LDS (> 160 KiB)", total);
     if (total < 16) total = 16;
-    static size_t attr = 0;
-    if (total > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr = 160 * 1024;
-    }
+    if (lds_opt_in(reinterpret_cast<const void*>(mlp_chain_kernel), 160 * 1024, "mlp_chain_kernel")) return -1;
     const unsigned blocks = (unsigned)((R + 31) / 32);
     hipLaunchKernelGGL(mlp_chain_kernel, dim3(blocks, (unsigned)n_split), dim3(kChainWaves * 64), total,
                        (hipStream_t)stream, a);
@@ -612,7 +607,6 @@ extern "C" int tt_mlp_chain(const float* x, long long R, int x_stride, int nstag
 namespace {
 constexpr int kEagerSlots = 4096;        // 64 B each; a launch claims one per row group
 constexpr int kCapturedSlots = 12288;
-constexpr int kMaxDevices = 64;
 constexpr int kWideConcurrent = 2;
 struct WidePool {
     unsigned* tickets = nullptr;         // kEagerSlots + kCapturedSlots counters, 64 B apart, device memory

@@ -940,12 +940,7 @@ extern "C" int tt_dec_gru(int B, const float* inp6, const float* state, float* f
     TT_REQUIRE(hipMemsetAsync(a.flags, 0, (size_t)B * 2 * sizeof(unsigned), (hipStream_t)stream) == hipSuccess,
                "tt_dec_gru: hipMemsetAsync failed");
     const size_t smem = (size_t)2 * kMapPixPad * kPS32 + 64 + 3 * 16 * 32 * 4;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_gru_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)smem);
-        attr = true;
-    }
+    if (lds_opt_in(reinterpret_cast<const void*>(dec_gru_kernel), smem, "dec_gru_kernel")) return -1;
     hipLaunchKernelGGL(dec_gru_kernel, dim3(2u, (unsigned)B), dim3(kGruWaves * 64), smem, (hipStream_t)stream, a);
     return check_launch("tt_dec_gru");
 }
@@ -978,16 +973,10 @@ extern "C" int tt_dec_flatten(int maps, const float* in, float* out, float* mids
     a.x4 = x4;
     const size_t smem = (size_t)((kMapPix * kPS32 + 15) / 16 * 16) + 2 * 100 * (64 * 4 + 16) + 64 +
                         2 * (64 * 4 + 16) + 64 * 4 + kFlatWaves * 64 * 2 * 4 + 64;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_flatten_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_tail_conv_kernel<1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_tail_conv_kernel<2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    if (lds_opt_in(reinterpret_cast<const void*>(dec_flatten_kernel), smem, "dec_flatten_kernel") ||
+        lds_opt_in(reinterpret_cast<const void*>(dec_tail_conv_kernel<1>), 160 * 1024, "dec_tail_conv_kernel<1>") ||
+        lds_opt_in(reinterpret_cast<const void*>(dec_tail_conv_kernel<2>), 160 * 1024, "dec_tail_conv_kernel<2>"))
+        return -1;
     hipLaunchKernelGGL(dec_flatten_kernel, dim3((unsigned)maps), dim3(kFlatWaves * 64), smem, (hipStream_t)stream, a);
     // one column-split stage: `set` = weight set; input map HW x HW x C, KH x KW / pad -> OHW x OHW x N
     auto stage = [&](int set, int mode, const float* src, const float* gate, const float* res, float* stage_out,
@@ -1043,12 +1032,7 @@ extern "C" int tt_dec_bev_update(int B, const float* bev, const float* G, float*
     TT_REQUIRE(hipMemsetAsync(a.tickets, 0, (size_t)B * sizeof(unsigned), (hipStream_t)stream) == hipSuccess,
                "tt_dec_bev_update: hipMemsetAsync failed");
     const size_t smem = (size_t)2 * kMapPixPad * kPS32 + 64 + 16 * 32 * 4;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_bev_update_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr = true;
-    }
+    if (lds_opt_in(reinterpret_cast<const void*>(dec_bev_update_kernel), smem, "dec_bev_update_kernel")) return -1;
     hipLaunchKernelGGL(dec_bev_update_kernel, dim3(4u, (unsigned)B), dim3(kBevWaves * 64), smem, (hipStream_t)stream, a);
     return check_launch("tt_dec_bev_update");
 }

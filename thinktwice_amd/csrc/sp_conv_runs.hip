@@ -407,11 +407,7 @@ static int launch_sp_runs(ConvArgs& a, hipStream_t st) {
     const size_t epi = (size_t)NW * 32 * (NCB * 32 + 4) * 4;
     if (smem < epi) smem = epi;
     auto kern = sp_conv_runs_kernel<NCB, WR, WC>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr_set = true;
-    }
+    if (lds_opt_in(reinterpret_cast<const void*>(kern), smem, "sp_conv_runs_kernel")) return -1;
     const int tiles_m = div_up(a.M, TM);
     a.tiles_n = 1;
     a.splits = 1;
@@ -423,7 +419,7 @@ static int launch_sp_runs(ConvArgs& a, hipStream_t st) {
 }
 
 // bf16x3 gathered conv with 27 taps in [kz][ky][kx] order (3x3x3 SubM / strided sparse conv), Cin a multiple of 32,
-// Cout 32 / 64 / 128.  `a.weight` = pre-split pair-format weights.  Returns 0 when the shape is not covered.
+// Cout 32 / 64 / 128.  `a.weight` = pre-split pair-format weights.  Returns 0 when the shape is not covered, < 0 on failure.
 int try_launch_sp_conv_runs(ConvArgs& a, hipStream_t st) {
     if (!a.gather || a.row_perm || a.KH != 1 || a.KW != kG * kNG) return 0;
     // strided sparse convs (the caller states stride 2): the inputs of a (dz, dy) group sit on every other line, the

@@ -18,6 +18,18 @@ int refuse_after_fault(const char* what);
 int* device_fault_word();
 int pair_wait_max_spin();
 
+constexpr int kMaxDevices = 64;    // size of every per-device host table
+
+// Per-device launch state (common.cpp), for the current device and safe from several host threads.  After a kernel's first
+// launch on a device neither makes a HIP call other than hipGetDevice (graph captures after a warm-up stay clean).
+//  * zero_page: 256 zeroed bytes, the source of the LDS-DMA pieces outside the image / the channel window.  Null on failure, with
+//    the error text naming `who` and the device.
+//  * lds_opt_in: makes sure `kernel` may take `bytes` of dynamic LDS; hipFuncSetAttribute only when more is needed than the
+//    device granted before, and a refusal is remembered.  0 on success; -1 on failure, with the error text naming `name` and the
+//    device -- unless `name` is null (a caller with a fallback), which leaves the error text alone.
+const void* zero_page(const char* who);
+int lds_opt_in(const void* kernel, size_t bytes, const char* name);
+
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -1411,21 +1411,6 @@ static bool v3_ok(long long total, int num_points, int C, int X, int Y) {
            total >= 4 * kCsChunk && total < (1ll << 31);
 }
 
-// > 64 KiB of dynamic LDS needs the opt-in (441 cells: 70 KiB, 1024: 160 KiB = the whole CU).  Decided once PER DEVICE; a device
-// that refuses the attribute, or whose limit is below what this launch needs, takes the two-phase kernel below instead
-static bool v3_lds_ready(size_t lds_needed) {
-    static int state[64] = {0};                 // 0 unknown, > 0: the granted limit in bytes, -1 refused
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    if (state[dev] == 0) {
-        const int want = 160 * 1024;            // the whole CU's LDS: 1024 cells need all of it
-        state[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(vp_cs_count_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         want) == hipSuccess ? want : -1;
-        (void)hipGetLastError();
-    }
-    return state[dev] > 0 && lds_needed <= (size_t)state[dev];
-}
-
 struct V3Layout {
     size_t keyrank, table, order, cell_start, seg_off, partial, bytes;
     int cps, segcap;
@@ -1481,8 +1466,11 @@ extern "C" int tt_voxel_pool_fwd_ws(int batch_size, int num_points, int num_chan
     const long long total = (long long)batch_size * num_points;
     const bool aligned = !(reinterpret_cast<uintptr_t>(input_features) & 15) && !(reinterpret_cast<uintptr_t>(output_features) & 15) &&
                          !(reinterpret_cast<uintptr_t>(workspace) & 15);
+    // > 64 KiB of dynamic LDS needs the opt-in (441 cells: 70 KiB, 1024: 160 KiB = the whole CU, which the opt-in asks for).  A
+    // device that refuses it takes the two-phase kernel below instead -- the one launcher with a fallback, so no error text
+    static_assert(kCsWaves * kCsMaxCells * (sizeof(unsigned short) + sizeof(unsigned long long)) <= 160 * 1024, "v3 LDS");
     if (workspace && aligned && v3_ok(total, num_points, num_channels, num_voxel_x, num_voxel_y) &&
-        v3_lds_ready((size_t)kCsWaves * ((num_voxel_x * num_voxel_y + 63) & ~63) * (sizeof(unsigned short) + sizeof(unsigned long long)))) {
+        lds_opt_in(reinterpret_cast<const void*>(vp_cs_count_kernel), 160 * 1024, nullptr) == 0) {
         const int cells = num_voxel_x * num_voxel_y;
         const V3Layout L = v3_layout(batch_size, num_points, num_channels, cells);
         if (workspace_bytes >= (long long)L.bytes) {
@@ -1591,21 +1579,16 @@ extern "C" long long tt_lift_splat_workspace_bytes(int batch_size, int num_cams,
 }
 
 template <typename T>
-static void launch_lift_splat(int batch_size, int num_cams, int D, int fH, int fW, int C, int X, int Y, int Z,
-                              const void* depth_logits, const void* context, const int32_t* geom_xyz, float* out,
-                              int out_cstride, int out_coff, int rot_flip, float* ws_rows, unsigned char* slot_of,
-                              hipStream_t st) {
+static int launch_lift_splat(int batch_size, int num_cams, int D, int fH, int fW, int C, int X, int Y, int Z,
+                             const void* depth_logits, const void* context, const int32_t* geom_xyz, float* out,
+                             int out_cstride, int out_coff, int rot_flip, float* ws_rows, unsigned char* slot_of,
+                             hipStream_t st) {
     if (lift_splat_strip_ok(D, fH, X, Y)) {
         const int strips = div_up(fW, kStripW);
         const unsigned sblocks = (unsigned)(batch_size * num_cams * strips);
         const size_t lds = lift_splat_strip_lds(D, C, X * Y);
-        static bool attr_set = false;
-        if (!attr_set) {    // once per instantiation: the largest request the limits allow
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lift_splat_strip_kernel<T>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lift_splat_strip_lds(kMaxD, kStageC, kMaxCells));
-            attr_set = true;
-        }
+        const size_t lds_max = lift_splat_strip_lds(kMaxD, kStageC, kMaxCells);     // the largest request the limits allow
+        if (lds_opt_in(reinterpret_cast<const void*>(lift_splat_strip_kernel<T>), lds_max, "lift_splat_strip_kernel")) return -1;
         hipLaunchKernelGGL(lift_splat_strip_kernel<T>, dim3(sblocks), dim3(256), lds, st, batch_size, num_cams, D, fH, fW, C,
                            X, Y, Z, (const T*)depth_logits, (const T*)context, geom_xyz, out, out_cstride, out_coff,
                            rot_flip, ws_rows, slot_of);
@@ -1614,12 +1597,13 @@ static void launch_lift_splat(int batch_size, int num_cams, int D, int fH, int f
             hipLaunchKernelGGL(lift_splat_cells_kernel, dim3((unsigned)div_up(waves, 4)), dim3(256), 0, st, batch_size,
                                num_cams * strips, C, X, Y, ws_rows, slot_of, out, out_cstride, out_coff, rot_flip);
         }
-        return;
+        return 0;
     }
     const long long npix = (long long)batch_size * num_cams * fH * fW;
     hipLaunchKernelGGL(lift_splat_kernel<T>, dim3((unsigned)div_up(npix, 4)), dim3(256), 0, st, batch_size, num_cams, D,
                        fH, fW, C, X, Y, Z, (const T*)depth_logits, (const T*)context, geom_xyz, out, out_cstride,
                        out_coff, rot_flip);
+    return 0;
 }
 
 // `ws` (tt_lift_splat_workspace_bytes, contents don't matter) selects the atomics-free, bit-reproducible form; without
@@ -1645,18 +1629,19 @@ extern "C" int tt_lift_splat_fwd_ws(int batch_size, int num_cams, int D, int fH,
         slot_of = (unsigned char*)ws + vp_align((size_t)blocks * kMaxSlots * C * sizeof(float));
     }
     hipStream_t st = (hipStream_t)stream;
+    int rc;
     if (dtype == TT_F32)
-        launch_lift_splat<float>(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
-                                 context, geom_xyz, out, out_cstride, out_coff, rot_flip, ws_rows, slot_of, st);
+        rc = launch_lift_splat<float>(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
+                                      context, geom_xyz, out, out_cstride, out_coff, rot_flip, ws_rows, slot_of, st);
     else if (dtype == TT_BF16)
-        launch_lift_splat<uint16_t>(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
-                                    context, geom_xyz, out, out_cstride, out_coff, rot_flip, ws_rows, slot_of, st);
+        rc = launch_lift_splat<uint16_t>(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
+                                         context, geom_xyz, out, out_cstride, out_coff, rot_flip, ws_rows, slot_of, st);
     else if (dtype == TT_F16)
-        launch_lift_splat<f16_t>(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
-                                 context, geom_xyz, out, out_cstride, out_coff, rot_flip, ws_rows, slot_of, st);
+        rc = launch_lift_splat<f16_t>(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
+                                      context, geom_xyz, out, out_cstride, out_coff, rot_flip, ws_rows, slot_of, st);
     else
         TT_REQUIRE(false, "tt_lift_splat_fwd: bad dtype %d", dtype);
-    return check_launch("tt_lift_splat_fwd");
+    return rc ? rc : check_launch("tt_lift_splat_fwd");
 }
 
 extern "C" int tt_lift_splat_fwd(int batch_size, int num_cams, int D, int fH, int fW, int C,
