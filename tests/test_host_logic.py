@@ -255,8 +255,6 @@ def test_plan_load_rejects_malformed_files(tmp_path):
     import ctypes
     from thinktwice_amd import _lib
     L = _lib.lib()
-    L.tt_plan_load.restype = ctypes.c_void_p
-    L.tt_last_error.restype = ctypes.c_char_p
 
     def load(data):
         f = tmp_path / "p.plan"
@@ -303,9 +301,6 @@ def test_plan_arena_compaction_reuses_memory_by_liveness_and_stream():
     import ctypes
     from thinktwice_amd import _lib
     L = _lib.lib()
-    L.tt_plan_create.restype = ctypes.c_void_p
-    L.tt_plan_compact_arena.restype = ctypes.c_longlong
-    L.tt_plan_add_blob.restype = ctypes.c_longlong
     ll, ci = ctypes.c_longlong, ctypes.c_int
 
     def build(allocs, calls, outputs=(), bad_ptr=None):
@@ -379,7 +374,6 @@ def test_wide_chain_workspace_and_argument_checks_are_host_side():
     import ctypes
     from thinktwice_amd import _lib, ops
     L = _lib.lib()
-    L.tt_mlp_chain_wide_workspace_bytes.restype = ctypes.c_longlong
 
     def stages(dims, srcs):
         arr = (ops._ChainStage * (len(dims) - 1))()
@@ -450,10 +444,8 @@ def test_round5_host_side_contracts():
         warmup_cosine_lr(1e-4, 10, 1000)
     assert warmup_cosine_lr(1e-4, 10, 1000, by_epoch=False) > 0
     L = _lib.lib()
-    L.tt_plan_create.restype = ctypes.c_void_p
     plan = ctypes.c_void_p(L.tt_plan_create())
     try:
-        L.tt_plan_add_blob.restype = ctypes.c_longlong
         blob = (ctypes.c_char * 64)()
         off = L.tt_plan_add_blob(plan, blob, ctypes.c_longlong(64))
         assert off >= 0
@@ -512,8 +504,6 @@ def test_decoder_scratch_queries_and_null_scratch_refusals():
     import ctypes
     from thinktwice_amd import _lib
     L = _lib.lib()
-    for f in (L.tt_dec_flatten_scratch_floats, L.tt_dec_gru_scratch_floats, L.tt_dec_bev_update_scratch_floats):
-        f.restype = ctypes.c_longlong
     # grid2feat tail: x4, MLP4's two hidden maps, pooled fc1 output, gate, block output; the 2x2 level likewise; fc0's output
     per_map = 2048 + 4096 + 2048 + 128 + 128 + 2048 + 1024 + 2048 + 1024 + 256 + 256 + 1024 + 512
     assert L.tt_dec_flatten_scratch_floats(4) == 4 * per_map and L.tt_dec_flatten_scratch_floats(35) == 35 * per_map

@@ -18,7 +18,6 @@ KEYS = ("pred_wp", "mu_branches", "sigma_branches", "future_mu", "future_sigma",
 def test_plan_api_is_exported_and_records_only_stream_taking_entries():
     from thinktwice_amd import _lib
     L = _lib.lib()
-    L.tt_plan_create.restype = ctypes.c_void_p
     p = ctypes.c_void_p(L.tt_plan_create())
     one = (ctypes.c_int * 1)()
     ll, dd = (ctypes.c_longlong * 1)(), (ctypes.c_double * 1)()
@@ -84,7 +83,6 @@ def test_forward_plan_runs_from_c_matches_eager_and_relocates(tmp_path):
         assert e < max(5e-5, 4 * noise), (k, e)
     # save / load: a fresh plan object from the file, bound to the same buffers, gives the same outputs
     d = fp.save(str(tmp_path / "plan"))
-    L.tt_plan_load.restype = ctypes.c_void_p
     p2 = ctypes.c_void_p(L.tt_plan_load(os.path.join(d, "plan.bin").encode()))
     assert p2.value and L.tt_plan_num_calls(p2) == fp.calls
     assert os.path.getsize(os.path.join(d, "weights.bin")) == fp.weights_blob.numel()

@@ -59,13 +59,17 @@ def test_oracle_geometry_matches_reference_golden(golden_dir):
 
 
 def test_c_abi_library_exports_every_declared_symbol():
+    """Every declaration of the header is parsed (no `tt_x(` outside a comment is missed), exported by the library and bound with
+    the header's argument and result types."""
     from thinktwice_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "thinktwice_hip.h")).read()
-    names = set(re.findall(r"\b(tt_[a-z0-9_]+)\s*\(", hdr))
-    assert "tt_voxel_pool_fwd" in names
+    protos = _lib.prototypes()
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "thinktwice_hip.h")).read(), flags=re.S)
+    assert set(re.findall(r"\b(tt_\w+)\s*\(", hdr)) == set(protos) and "tt_voxel_pool_fwd" in protos
     L = _lib.lib()
-    for n in sorted(names):
+    for n, p in protos.items():
         assert hasattr(L, n), f"libthinktwice_hip.so does not export {n}"
+        f = getattr(L, n)
+        assert (f.argtypes, f.restype) == (p.argtypes, p.restype), n
     assert L.tt_version() >= 100
 
 

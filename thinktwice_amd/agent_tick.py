@@ -58,8 +58,8 @@ class LidarSweepMerger:
             rel, n_prev = np.eye(4), 0
         out = torch.empty(n_prev + n_now, 4, dtype=torch.float32, device=self.device)
         m = (ctypes.c_float * 12)(*[float(v) for v in rel[:3].reshape(-1)])
-        check(lib().tt_lidar_merge_half_sweeps(ptr(self.prev), ctypes.c_int(n_prev), ptr(now), ctypes.c_int(n_now), m,
-                                               ctypes.c_float(self.Z_SHIFT), ptr(out), ops.cur_stream(self.device)),
+        check(lib().tt_lidar_merge_half_sweeps(ptr(self.prev), n_prev, ptr(now), n_now, m,
+                                               self.Z_SHIFT, ptr(out), ops.cur_stream(self.device)),
               "tt_lidar_merge_half_sweeps")
         self.prev = now
         self.prev_matrix = ego_pose_matrix(*self._pose_args(pos, compass))

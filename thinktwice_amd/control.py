@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 import torch
 
-from ._lib import check, cur_stream, lib, raise_on_device_fault
+from ._lib import check, cur_stream, lib, ptr, raise_on_device_fault
 
 PID_WINDOW_MAX = 64
 (ACT_STEER, ACT_THROTTLE, ACT_BRAKE, ACT_STEER_CTRL, ACT_THROTTLE_CTRL, ACT_BRAKE_CTRL, ACT_STEER_TRAJ, ACT_THROTTLE_TRAJ,
@@ -88,9 +88,8 @@ class ActionPost:
     def tick_host(self, mu_last, sigma_last, wp_last, speed, target, stuck_desired_speed=-1.0):
         mu, sg, wp, tg = _f32(mu_last, 2), _f32(sigma_last, 2), _f32(wp_last, 8), _f32(target, 2)
         out = (ctypes.c_double * ACTION_OUT)()
-        check(lib().tt_action_post_host(_fp(mu), _fp(sg), _fp(wp), ctypes.c_float(float(speed)), ctypes.c_float(tg[0]),
-                                        ctypes.c_float(tg[1]), ctypes.c_float(stuck_desired_speed), ctypes.byref(self.cfg),
-                                        ctypes.byref(self.state), out), "tt_action_post_host")
+        check(lib().tt_action_post_host(_fp(mu), _fp(sg), _fp(wp), float(speed), tg[0], tg[1], stuck_desired_speed,
+                                        ctypes.byref(self.cfg), ctypes.byref(self.state), out), "tt_action_post_host")
         o = list(out)
         return o[ACT_STEER], o[ACT_THROTTLE], o[ACT_BRAKE], _info(o)
 
@@ -108,13 +107,11 @@ class ActionPost:
             assert r.numel() == n and r.is_contiguous(), "the last stage's row of a head must be dense"
             rows.append(r)
         assert tuple(pred["pred_wp"].shape[-2:]) == (4, 2)
-        last = lambda r, n: ctypes.c_void_p(r.data_ptr())                # noqa: E731
         mu, sg, wp = rows
         tg = _f32(target, 2)
-        check(lib().tt_action_post(last(mu, 2), last(sg, 2), last(wp, 8), ctypes.c_float(float(speed)), ctypes.c_float(tg[0]),
-                                   ctypes.c_float(tg[1]), ctypes.c_float(stuck_desired_speed), ctypes.byref(self.cfg),
-                                   ctypes.c_void_p(self.state.data_ptr()), ctypes.c_void_p(self.out_dev.data_ptr()),
-                                   cur_stream(self.device)), "tt_action_post")
+        check(lib().tt_action_post(ptr(mu), ptr(sg), ptr(wp), float(speed), tg[0], tg[1], stuck_desired_speed,
+                                   ctypes.byref(self.cfg), ptr(self.state), ptr(self.out_dev), cur_stream(self.device)),
+              "tt_action_post")
         self.out_host.copy_(self.out_dev, non_blocking=True)          # the tick's one device -> host copy
         torch.cuda.current_stream(self.device).synchronize()
         # the forward that produced `pred` is complete here: a wide-chain barrier time-out (NaN outputs) is an error, not a
@@ -169,8 +166,8 @@ def control_pid(cfg, turn_controller, speed_controller, waypoints, velocity, tar
     tg = _f32(target, 2)
     speed = float(torch.as_tensor(velocity).reshape(-1)[0])
     out = (ctypes.c_double * ACTION_OUT)()
-    check(lib().tt_action_pid_host(_fp(wp), ctypes.c_float(speed), ctypes.c_float(tg[0]), ctypes.c_float(tg[1]),
-                                   ctypes.c_float(stuck_desired_speed), ctypes.byref(pair.cfg), ctypes.byref(pair.state), out),
+    check(lib().tt_action_pid_host(_fp(wp), speed, tg[0], tg[1],
+                                   stuck_desired_speed, ctypes.byref(pair.cfg), ctypes.byref(pair.state), out),
           "tt_action_pid_host")
     o = list(out)
     w = wp.reshape(4, 2).astype(np.float64)
@@ -185,10 +182,8 @@ def control_pid(cfg, turn_controller, speed_controller, waypoints, velocity, tar
 def arbitrate(cfg_struct, state, steer_ctrl, throttle_ctrl, brake_ctrl, throttle_traj, brake_traj, speed):
     """The agent's arbitration stage alone (AGENT:463-509) on a host state struct -> (steer, throttle, brake, info)."""
     out = (ctypes.c_double * ACTION_OUT)()
-    check(lib().tt_action_arbitrate_host(ctypes.c_double(steer_ctrl), ctypes.c_double(throttle_ctrl), ctypes.c_double(brake_ctrl),
-                                         ctypes.c_double(throttle_traj), ctypes.c_double(float(brake_traj)),
-                                         ctypes.c_float(float(speed)), ctypes.byref(cfg_struct), ctypes.byref(state), out),
-          "tt_action_arbitrate_host")
+    check(lib().tt_action_arbitrate_host(steer_ctrl, throttle_ctrl, brake_ctrl, throttle_traj, float(brake_traj), float(speed),
+                                         ctypes.byref(cfg_struct), ctypes.byref(state), out), "tt_action_arbitrate_host")
     o = list(out)
     return o[ACT_STEER], o[ACT_THROTTLE], o[ACT_BRAKE], {"is_turn": bool(o[ACT_IS_TURN]), "is_stuck": bool(o[ACT_IS_STUCK]),
                                                          "stuck_detector": int(o[ACT_STUCK_DETECTOR])}

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib, ops, weights
 from .layers import conv_from_sd, deconv2x2_from_sd
-from .ops import _c, _ll, check, lib, ptr
+from .ops import check, lib, ptr
 from .registry import BACKBONES, MIDDLE_ENCODERS
 
 F32 = torch.float32
@@ -46,7 +46,7 @@ class _Level:
         if self.vol is None:
             D, H, W = self.dims
             self.vol = torch.empty(self.batch * D * H * W, dtype=torch.int32, device=self.coords.device)
-            check(lib().tt_sp_volume_build(ptr(self.coords), ptr(self.rows), _ll(self.max_rows), _c(self.batch),
+            check(lib().tt_sp_volume_build(ptr(self.coords), ptr(self.rows), self.max_rows, self.batch,
                                            self.dims_c, ptr(self.vol), ops.cur_stream(self.coords.device)),
                   "tt_sp_volume_build")
         return self.vol
@@ -55,7 +55,7 @@ class _Level:
         if self._subm is None:
             g = (ctypes.c_int * 9)(3, 3, 3, 1, 1, 1, 1, 1, 1)
             nbr = torch.empty(self.max_rows, 27, dtype=torch.int32, device=self.coords.device)
-            check(lib().tt_sp_rulebook(ptr(self.coords), ptr(self.rows), _ll(self.max_rows), g, self.dims_c,
+            check(lib().tt_sp_rulebook(ptr(self.coords), ptr(self.rows), self.max_rows, g, self.dims_c,
                                        ptr(self.volume()), ptr(nbr), ops.cur_stream(nbr.device)), "tt_sp_rulebook")
             self._subm = nbr
             self._subm_plan = ops.sp_tile_plan(nbr, self.rows) if _TILE_PLAN else None
@@ -163,15 +163,15 @@ class SparseEncoder_fp32:
         g = (ctypes.c_int * 9)(*kernel, *stride, *pad)
         odc = (ctypes.c_int * 3)(*od)
         st = ops.cur_stream(dev)
-        ws_bytes = int(lib().tt_sp_strided_outputs_workspace_bytes(_ll(cells)))
+        ws_bytes = int(lib().tt_sp_strided_outputs_workspace_bytes(cells))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        check(lib().tt_sp_strided_outputs(ptr(lvl.coords), ptr(lvl.rows), _ll(lvl.max_rows), _c(batch), g, odc,
-                                          ptr(ws), _ll(ws_bytes), ptr(vol), ptr(coords), ptr(rows), _ll(max_out), st),
+        check(lib().tt_sp_strided_outputs(ptr(lvl.coords), ptr(lvl.rows), lvl.max_rows, batch, g, odc,
+                                          ptr(ws), ws_bytes, ptr(vol), ptr(coords), ptr(rows), max_out, st),
               "tt_sp_strided_outputs")
         new = _Level(coords, rows, max_out, od, batch, dev, vol=vol)
         KV = kernel[0] * kernel[1] * kernel[2]
         nbr = torch.empty(max_out, KV, dtype=torch.int32, device=dev)
-        check(lib().tt_sp_rulebook(ptr(coords), ptr(rows), _ll(max_out), g, lvl.dims_c, ptr(lvl.volume()), ptr(nbr), st),
+        check(lib().tt_sp_rulebook(ptr(coords), ptr(rows), max_out, g, lvl.dims_c, ptr(lvl.volume()), ptr(nbr), st),
               "tt_sp_rulebook")
         plan = ops.sp_tile_plan(nbr, rows) if _TILE_PLAN else None
         return _sp_conv(feats, nbr, new, w, bn, plan=plan, in_level=lvl, stride=max(stride)), new
@@ -245,10 +245,9 @@ class LidarNet:
         L = lib()
         capped = Np > max_voxels
         if capped:
-            L.tt_lidar_voxelize_capped_workspace_bytes.restype = ctypes.c_longlong
-            ws_bytes = int(L.tt_lidar_voxelize_capped_workspace_bytes(_ll(n)))
+            ws_bytes = int(L.tt_lidar_voxelize_capped_workspace_bytes(n))
         else:
-            ws_bytes = int(L.tt_lidar_voxelize_workspace_bytes(_ll(n)))
+            ws_bytes = int(L.tt_lidar_voxelize_workspace_bytes(n))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device)
         feats = torch.empty(n, nf, dtype=F32, device=pts.device)
         coords = torch.empty(n, 4, dtype=torch.int32, device=pts.device)
@@ -257,12 +256,12 @@ class LidarNet:
         vsz = (ctypes.c_float * 3)(*vs)
         g = (ctypes.c_int * 3)(*grid)
         if capped:
-            check(L.tt_lidar_voxelize_capped(ptr(pts), _c(B), _c(Np), _c(nf), lo, vsz, g, _c(self.middle.sparse_shape[0]),
-                                             _c(vl["max_num_points"]), _c(int(max_voxels)), ptr(ws), _ll(ws_bytes), ptr(feats),
+            check(L.tt_lidar_voxelize_capped(ptr(pts), B, Np, nf, lo, vsz, g, self.middle.sparse_shape[0],
+                                             vl["max_num_points"], int(max_voxels), ptr(ws), ws_bytes, ptr(feats),
                                              ptr(coords), ptr(num), ops.cur_stream(pts.device)), "tt_lidar_voxelize_capped")
         else:
-            check(L.tt_lidar_voxelize(ptr(pts), _c(B), _c(Np), _c(nf), lo, vsz, g, _c(self.middle.sparse_shape[0]),
-                                      _c(vl["max_num_points"]), ptr(ws), _ll(ws_bytes), ptr(feats), ptr(coords),
+            check(L.tt_lidar_voxelize(ptr(pts), B, Np, nf, lo, vsz, g, self.middle.sparse_shape[0],
+                                      vl["max_num_points"], ptr(ws), ws_bytes, ptr(feats), ptr(coords),
                                       ptr(num), ops.cur_stream(pts.device)), "tt_lidar_voxelize")
         return feats, coords, num, n
 

@@ -6,7 +6,6 @@ order; `seg_loss` / `depth_loss` mirror encoder_decoder_framework.py:172-190 (+ 
 tt_loss_* reduction writing a device float; nothing here synchronises with the host except `parse_losses`' `.item()`
 calls, which the reference makes too.
 """
-import ctypes
 from collections import OrderedDict
 
 import torch
@@ -19,15 +18,12 @@ DISTIL_INDEX = (2, 3, 4, 5)                                            # DEC:284
 DISTIL_W = {2: 0.25, 3: 1.0 / 3.0, 4: 1.0 / 4.0, 5: 1.0 / 11.0}       # DEC:285
 WP_W = ACTION_W = 15.0                                                 # DEC:286-287
 
-_ll, _c, _f = ctypes.c_longlong, ctypes.c_int, ctypes.c_float
-
 
 class LossReducer:
     """Owns the (zeroed once) reduction workspace and the output scalars of one device."""
 
     def __init__(self, device):
         L = lib()
-        L.tt_loss_workspace_bytes.restype = ctypes.c_longlong
         self.device = torch.device(device)
         self.ws = torch.zeros(int(L.tt_loss_workspace_bytes()), dtype=torch.uint8, device=self.device)
 
@@ -52,16 +48,15 @@ class LossReducer:
             rep = pred.numel() // (N * inner)
             assert target.shape[0] == N and rep * inner * N == pred.numel(), (pred.shape, target.shape)
         out = self._out(1) if reduce else torch.empty_like(pred)
-        check(lib().tt_loss_smooth_l1(ptr(pred), ptr(target), _ll(N), _c(rep), _ll(inner), _f(clamp_max), _f(scale),
-                                      _c(1 if reduce else 0), ptr(out), ptr(self.ws), cur_stream(self.device)),
-              "tt_loss_smooth_l1")
+        check(lib().tt_loss_smooth_l1(ptr(pred), ptr(target), N, rep, inner, clamp_max, scale,
+                                      1 if reduce else 0, ptr(out), ptr(self.ws), cur_stream(self.device)), "tt_loss_smooth_l1")
         tape = autodiff.TAPE
         if tape is not None:
             # the term enters the total as its MEAN with weight 1 (parse_losses; an unreduced term is averaged there)
             def bwd():
                 d = torch.empty_like(pred)
-                check(lib().tt_loss_smooth_l1_bwd(ptr(pred), ptr(target), _ll(N), _c(rep), _ll(inner), _f(clamp_max),
-                                                  _f(scale), ptr(d), cur_stream(self.device)), "tt_loss_smooth_l1_bwd")
+                check(lib().tt_loss_smooth_l1_bwd(ptr(pred), ptr(target), N, rep, inner, clamp_max,
+                                                  scale, ptr(d), cur_stream(self.device)), "tt_loss_smooth_l1_bwd")
                 tape.grad(pred_in).add_(d.view(pred_in.shape))
             tape.nodes.append(bwd)
         return out[0] if reduce else out
@@ -75,15 +70,14 @@ class LossReducer:
         rep = p_alpha.numel() // (N * inner)
         assert rep * inner * N == p_alpha.numel() and p_beta.shape == p_alpha.shape and t_beta.shape == t_alpha.shape
         out = self._out()
-        check(lib().tt_loss_beta_kl(ptr(t_alpha), ptr(t_beta), ptr(p_alpha), ptr(p_beta), _ll(N), _c(rep), _ll(inner),
-                                    _f(scale), ptr(out), ptr(self.ws), cur_stream(self.device)), "tt_loss_beta_kl")
+        check(lib().tt_loss_beta_kl(ptr(t_alpha), ptr(t_beta), ptr(p_alpha), ptr(p_beta), N, rep, inner,
+                                    scale, ptr(out), ptr(self.ws), cur_stream(self.device)), "tt_loss_beta_kl")
         tape = autodiff.TAPE
         if tape is not None:
             def bwd():
                 da, db = torch.empty_like(p_alpha), torch.empty_like(p_beta)
-                check(lib().tt_loss_beta_kl_bwd(ptr(t_alpha), ptr(t_beta), ptr(p_alpha), ptr(p_beta), _ll(N), _c(rep),
-                                                _ll(inner), _f(scale), ptr(da), ptr(db), cur_stream(self.device)),
-                      "tt_loss_beta_kl_bwd")
+                check(lib().tt_loss_beta_kl_bwd(ptr(t_alpha), ptr(t_beta), ptr(p_alpha), ptr(p_beta), N, rep,
+                                                inner, scale, ptr(da), ptr(db), cur_stream(self.device)), "tt_loss_beta_kl_bwd")
                 tape.grad(pa_in).add_(da.view(pa_in.shape))
                 tape.grad(pb_in).add_(db.view(pb_in.shape))
             tape.nodes.append(bwd)
@@ -98,7 +92,7 @@ class LossReducer:
         pb = None if pred_beta is None else self._f(pred_beta)
         tb = None if target_beta is None else self._f(target_beta)
         out = self._out(cols)
-        check(lib().tt_loss_l1_cols(ptr(pred), ptr(pb), _ll(cols), ptr(target), ptr(tb), _ll(rows), _c(cols), ptr(out),
+        check(lib().tt_loss_l1_cols(ptr(pred), ptr(pb), cols, ptr(target), ptr(tb), rows, cols, ptr(out),
                                     ptr(self.ws), cur_stream(self.device)), "tt_loss_l1_cols")
         return out
 
@@ -109,9 +103,8 @@ class LossReducer:
         assert logits_cl.dtype == F32 and logits_cl.is_contiguous()
         assert tuple(logits_cl.shape[:3]) == (B * N, H // factor, W // factor), (logits_cl.shape, labels.shape)
         out = self._out(3)              # loss, mean cross entropy, contributing pixels (the last two feed the backward)
-        check(lib().tt_loss_seg_focal(ptr(logits_cl), _c(logits_cl.shape[-1]), _c(num_classes), ptr(labels), _c(B * N),
-                                      _c(H), _c(W), _c(factor), ptr(out), ptr(self.ws), cur_stream(self.device)),
-              "tt_loss_seg_focal")
+        check(lib().tt_loss_seg_focal(ptr(logits_cl), logits_cl.shape[-1], num_classes, ptr(labels), B * N,
+                                      H, W, factor, ptr(out), ptr(self.ws), cur_stream(self.device)), "tt_loss_seg_focal")
         self.seg_aux = out[1:]
         return out[0]
 
@@ -121,8 +114,8 @@ class LossReducer:
         labels = self._f(labels)
         B, N, H, W = labels.shape
         d = torch.empty_like(logits_cl)
-        check(lib().tt_loss_seg_focal_bwd(ptr(logits_cl), _c(logits_cl.shape[-1]), _c(num_classes), ptr(labels), _c(B * N),
-                                          _c(H), _c(W), _c(factor), ptr(self.seg_aux), ptr(upstream), ptr(d),
+        check(lib().tt_loss_seg_focal_bwd(ptr(logits_cl), logits_cl.shape[-1], num_classes, ptr(labels), B * N,
+                                          H, W, factor, ptr(self.seg_aux), ptr(upstream), ptr(d),
                                           cur_stream(self.device)), "tt_loss_seg_focal_bwd")
         return d
 
@@ -134,9 +127,8 @@ class LossReducer:
         assert logits_cl.dtype == F32 and logits_cl.is_contiguous()
         assert tuple(logits_cl.shape[:3]) == (B * N, H // factor, W // factor) and logits_cl.shape[-1] >= D
         out = self._out(2)              # loss, divisor max(1, #foreground cells) (feeds the backward)
-        check(lib().tt_loss_depth_bce(ptr(logits_cl), _c(logits_cl.shape[-1]), _c(D), ptr(gt_depth), _c(B * N), _c(H),
-                                      _c(W), _c(factor), _f(d_bound[0]), _f(d_bound[2]), ptr(out), ptr(self.ws),
-                                      cur_stream(self.device)), "tt_loss_depth_bce")
+        check(lib().tt_loss_depth_bce(ptr(logits_cl), logits_cl.shape[-1], D, ptr(gt_depth), B * N, H, W, factor, d_bound[0],
+                                      d_bound[2], ptr(out), ptr(self.ws), cur_stream(self.device)), "tt_loss_depth_bce")
         self.depth_aux = out[1:]
         return out[0]
 
@@ -146,8 +138,8 @@ class LossReducer:
         B, N, H, W = gt_depth.shape
         D = int((d_bound[1] - d_bound[0]) / d_bound[2])
         d = torch.empty_like(logits_cl)
-        check(lib().tt_loss_depth_bce_bwd(ptr(logits_cl), _c(logits_cl.shape[-1]), _c(D), ptr(gt_depth), _c(B * N), _c(H),
-                                          _c(W), _c(factor), _f(d_bound[0]), _f(d_bound[2]), ptr(self.depth_aux),
+        check(lib().tt_loss_depth_bce_bwd(ptr(logits_cl), logits_cl.shape[-1], D, ptr(gt_depth), B * N, H,
+                                          W, factor, d_bound[0], d_bound[2], ptr(self.depth_aux),
                                           ptr(upstream), ptr(d), cur_stream(self.device)), "tt_loss_depth_bce_bwd")
         return d
 

@@ -12,8 +12,6 @@ from . import _lib
 from ._lib import (TT_BF16, TT_F16, TT_F32, TTError, check, clear_device_faults, cur_stream, device_faults, lib, ptr,  # noqa: F401
                    raise_on_device_fault, require_cuda)
 
-_c = ctypes.c_int
-
 
 def dtype_code(t):
     if t.dtype == torch.float32:
@@ -35,8 +33,7 @@ def frustum_voxel_index(frustum, mats, voxel_lo, voxel_size, batch_size, num_cam
     gf = torch.empty(geom.shape, dtype=torch.float32, device=frustum.device) if want_f32 else None
     lo = (ctypes.c_float * 3)(*[float(v) for v in voxel_lo])
     sz = (ctypes.c_float * 3)(*[float(v) for v in voxel_size])
-    rc = lib().tt_frustum_voxel_index(_c(batch_size), _c(num_cams), _c(D), _c(fH), _c(fW),
-                                      ptr(frustum), ptr(mats), lo, sz, ptr(geom), ptr(gf),
+    rc = lib().tt_frustum_voxel_index(batch_size, num_cams, D, fH, fW, ptr(frustum), ptr(mats), lo, sz, ptr(geom), ptr(gf),
                                       cur_stream(frustum.device))
     check(rc, "tt_frustum_voxel_index")
     return (geom, gf) if want_f32 else geom
@@ -61,16 +58,12 @@ def lift_splat(depth_logits, context, geom_xyz, voxel_num, batch_size, num_cams,
     # TT_LIFT_SPLAT_ATOMIC=1 selects the single-kernel atomic form for A/B
     ws, ws_bytes = None, 0
     if not _LIFT_SPLAT_ATOMIC:
-        ws_bytes = int(lib().tt_lift_splat_workspace_bytes(_c(batch_size), _c(num_cams), _c(D), _c(fH), _c(fW), _c(C),
-                                                           _c(vx), _c(vy)))
+        ws_bytes = int(lib().tt_lift_splat_workspace_bytes(batch_size, num_cams, D, fH, fW, C, vx, vy))
         if ws_bytes > 0:
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=context.device)
-    rc = lib().tt_lift_splat_fwd_ws(_c(batch_size), _c(num_cams), _c(D), _c(fH), _c(fW), _c(C), _c(vx),
-                                    _c(vy), _c(vz), ptr(depth_logits), ptr(context),
-                                    _c(dtype_code(context)), ptr(geom_xyz), ptr(out),
-                                    _c(out.shape[-1]), _c(out_coff), _c(1 if rot_flip else 0),
-                                    ptr(ws) if ws is not None else None, ctypes.c_longlong(ws_bytes),
-                                    cur_stream(context.device))
+    rc = lib().tt_lift_splat_fwd_ws(batch_size, num_cams, D, fH, fW, C, vx, vy, vz, ptr(depth_logits), ptr(context),
+                                    dtype_code(context), ptr(geom_xyz), ptr(out), out.shape[-1], out_coff, 1 if rot_flip else 0,
+                                    ptr(ws), ws_bytes, cur_stream(context.device))
     check(rc, "tt_lift_splat_fwd_ws")
     if record:
         from . import autodiff
@@ -87,9 +80,9 @@ def lift_splat_bwd(depth_logits, context, geom_xyz, voxel_num, batch_size, num_c
     C = context.shape[-1]
     vx, vy, vz = voxel_num
     assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (depth_logits, context, gout, gdepth, gctx))
-    check(lib().tt_lift_splat_bwd(_c(batch_size), _c(num_cams), _c(D), _c(fH), _c(fW), _c(C), _c(vx), _c(vy), _c(vz),
-                                  ptr(depth_logits), ptr(context), ptr(geom_xyz), ptr(gout), _c(gout.shape[-1]),
-                                  _c(out_coff), ptr(gdepth), ptr(gctx), cur_stream(context.device)), "tt_lift_splat_bwd")
+    check(lib().tt_lift_splat_bwd(batch_size, num_cams, D, fH, fW, C, vx, vy, vz,
+                                  ptr(depth_logits), ptr(context), ptr(geom_xyz), ptr(gout), gout.shape[-1],
+                                  out_coff, ptr(gdepth), ptr(gctx), cur_stream(context.device)), "tt_lift_splat_bwd")
 
 
 # ----------------------------------------------------------------------------- conv / linear
@@ -101,33 +94,28 @@ CONV_BYTES = None     # same order as CONV_PROFILE: compulsory HBM bytes of the 
 
 class _ConvDesc(ctypes.Structure):
     _fields_ = [
-        ("in_", ctypes.c_void_p), ("N", _c), ("H", _c), ("W", _c), ("Cin", _c), ("in_cstride", _c),
-        ("in_coff", _c), ("in_nstride", ctypes.c_longlong),
-        ("weight", ctypes.c_void_p), ("Cout", _c), ("KH", _c), ("KW", _c), ("stride", _c),
-        ("pad", _c), ("dil", _c),
-        ("out", ctypes.c_void_p), ("OH", _c), ("OW", _c), ("out_cstride", _c), ("out_coff", _c),
-        ("out_nstride", ctypes.c_longlong),
-        ("pixel_shuffle2", _c),
+        ("in_", ctypes.c_void_p), ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("Cin", ctypes.c_int),
+        ("in_cstride", ctypes.c_int), ("in_coff", ctypes.c_int), ("in_nstride", ctypes.c_longlong),
+        ("weight", ctypes.c_void_p), ("Cout", ctypes.c_int), ("KH", ctypes.c_int), ("KW", ctypes.c_int),
+        ("stride", ctypes.c_int), ("pad", ctypes.c_int), ("dil", ctypes.c_int),
+        ("out", ctypes.c_void_p), ("OH", ctypes.c_int), ("OW", ctypes.c_int), ("out_cstride", ctypes.c_int),
+        ("out_coff", ctypes.c_int), ("out_nstride", ctypes.c_longlong),
+        ("pixel_shuffle2", ctypes.c_int),
         ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p),
-        ("shift_n", ctypes.c_void_p), ("shift_n_mod", _c),
-        ("res1", ctypes.c_void_p), ("res1_cstride", _c), ("res1_coff", _c),
-        ("res2", ctypes.c_void_p), ("res2_cstride", _c), ("res2_coff", _c),
-        ("act", _c), ("dtype", _c), ("out_dtype", _c),
+        ("shift_n", ctypes.c_void_p), ("shift_n_mod", ctypes.c_int),
+        ("res1", ctypes.c_void_p), ("res1_cstride", ctypes.c_int), ("res1_coff", ctypes.c_int),
+        ("res2", ctypes.c_void_p), ("res2_cstride", ctypes.c_int), ("res2_coff", ctypes.c_int),
+        ("act", ctypes.c_int), ("dtype", ctypes.c_int), ("out_dtype", ctypes.c_int),
         ("gather_idx", ctypes.c_void_p), ("m_dev", ctypes.c_void_p), ("splitk_ws", ctypes.c_void_p),
         ("weight_x3", ctypes.c_void_p), ("row_perm", ctypes.c_void_p), ("row_mask", ctypes.c_void_p),
-        ("splitk_slices", _c), ("in_pair", _c), ("out_pair", _c),
-        ("weight_h2", ctypes.c_void_p), ("out2", ctypes.c_void_p), ("out2_cstride", _c), ("out2_coff", _c),
-        ("res1_up_h", _c), ("res1_up_w", _c), ("res1_f32", _c),
+        ("splitk_slices", ctypes.c_int), ("in_pair", ctypes.c_int), ("out_pair", ctypes.c_int),
+        ("weight_h2", ctypes.c_void_p), ("out2", ctypes.c_void_p), ("out2_cstride", ctypes.c_int), ("out2_coff", ctypes.c_int),
+        ("res1_up_h", ctypes.c_int), ("res1_up_w", ctypes.c_int), ("res1_f32", ctypes.c_int),
     ]
-
-
-def _dp(t):
-    return None if t is None else t.data_ptr()
 
 
 def _last_conv_kernel():
     L = lib()
-    L.tt_conv_last_kernel.restype = ctypes.c_char_p
     return L.tt_conv_last_kernel().decode()
 
 
@@ -139,11 +127,11 @@ def sp_tile_plan(nbr, m_dev):
     rows sorted by tap-occupancy mask, so that a 256-row tile of the gathered GEMM only visits the union of its taps."""
     require_cuda(nbr, m_dev)
     M, KV = nbr.shape
-    ws_bytes = int(lib().tt_sp_tile_plan_workspace_bytes(_ll(M)))
+    ws_bytes = int(lib().tt_sp_tile_plan_workspace_bytes(M))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=nbr.device)
     perm = torch.empty(M, dtype=torch.int32, device=nbr.device)
     mask = torch.empty(M, dtype=torch.int32, device=nbr.device)
-    check(lib().tt_sp_tile_plan(ptr(nbr), ptr(m_dev), _ll(M), _c(KV), ptr(ws), _ll(ws_bytes), ptr(perm), ptr(mask),
+    check(lib().tt_sp_tile_plan(ptr(nbr), ptr(m_dev), M, KV, ptr(ws), ws_bytes, ptr(perm), ptr(mask),
                                 ptr(SPARSE_PAIRS), cur_stream(nbr.device)), "tt_sp_tile_plan")
     return perm, mask
 
@@ -166,11 +154,11 @@ def gather_conv(feats, nbr, m_dev, w, *, scale=None, shift=None, act=0, res=None
     d.in_nstride = 0
     d.weight = w.data_ptr(); d.Cout = Cout; d.KH = 1; d.KW = KW; d.stride = stride; d.pad = 0; d.dil = 1
     d.out = out.data_ptr(); d.OH = 1; d.OW = 1; d.out_cstride = Cout; d.out_coff = 0; d.out_nstride = 0
-    d.scale = _dp(scale); d.shift = _dp(shift)
-    d.res1 = _dp(res); d.res1_cstride = 0 if res is None else res.shape[-1]
+    d.scale = ptr(scale); d.shift = ptr(shift)
+    d.res1 = ptr(res); d.res1_cstride = 0 if res is None else res.shape[-1]
     d.act = act; d.dtype = dtype_code(feats); d.out_dtype = dtype_code(out)
-    d.gather_idx = nbr.data_ptr(); d.m_dev = _dp(m_dev)
-    d.weight_x3 = _dp(w_x3)
+    d.gather_idx = nbr.data_ptr(); d.m_dev = ptr(m_dev)
+    d.weight_x3 = ptr(w_x3)
     if plan is not None:
         d.row_perm, d.row_mask = plan[0].data_ptr(), plan[1].data_ptr()
     if CONV_PROFILE is not None:
@@ -203,12 +191,11 @@ def gather_conv_wgrad(feats, nbr, m_dev, dy, taps, cin_pad=None):
     cin_pad = cin_pad or Cin
     out = torch.empty(Cout, 1, taps, cin_pad, dtype=torch.float32, device=dy.device)
     L = lib()
-    L.tt_gather_conv_wgrad_workspace_bytes.restype = ctypes.c_longlong
-    nb = int(L.tt_gather_conv_wgrad_workspace_bytes(_ll(M), _c(Cout), _c(Cin), _c(cin_pad), _c(taps)))
+    nb = int(L.tt_gather_conv_wgrad_workspace_bytes(M, Cout, Cin, cin_pad, taps))
     ws = torch.empty(nb, dtype=torch.uint8, device=dy.device)
     assert feats.is_contiguous() and dy.is_contiguous() and nbr.is_contiguous() and feats.dtype == torch.float32
-    check(L.tt_gather_conv_wgrad(ptr(feats), _c(Cin), _c(Cin), ptr(nbr), ptr(m_dev), _ll(M), _c(taps), ptr(dy), _c(Cout),
-                                 _c(Cout), _c(cin_pad), _c(0), ptr(out), ptr(ws), _ll(nb), _st(dy)), "tt_gather_conv_wgrad")
+    check(L.tt_gather_conv_wgrad(ptr(feats), Cin, Cin, ptr(nbr), ptr(m_dev), M, taps, ptr(dy), Cout,
+                                 Cout, cin_pad, 0, ptr(out), ptr(ws), nb, _st(dy)), "tt_gather_conv_wgrad")
     return out
 
 
@@ -216,7 +203,7 @@ def sp_inverse_rulebook(nbr, m_dev, rows_in):
     """inv int32 [rows_in, taps]: inv[j][t] = m with nbr[m][t] == j, else -1 (transposed rulebook of a strided sparse conv)."""
     M, taps = nbr.shape
     inv = torch.full((rows_in, taps), -1, dtype=torch.int32, device=nbr.device)
-    check(lib().tt_sp_inverse_rulebook(ptr(nbr), ptr(m_dev), _ll(M), _c(taps), ptr(inv), _st(nbr)), "tt_sp_inverse_rulebook")
+    check(lib().tt_sp_inverse_rulebook(ptr(nbr), ptr(m_dev), M, taps, ptr(inv), _st(nbr)), "tt_sp_inverse_rulebook")
     return inv
 
 
@@ -226,7 +213,7 @@ def sp_to_dense(x, coords, rows, max_rows, dims, batch_size):
     C = x.shape[1]
     dense = torch.zeros(batch_size, H, W, C * D, dtype=x.dtype, device=x.device)
     dc = (ctypes.c_int * 3)(*dims)
-    check(lib().tt_sp_to_dense(ptr(x), ptr(coords), ptr(rows), _ll(max_rows), _c(C), dc, ptr(dense), _c(dtype_code(x)),
+    check(lib().tt_sp_to_dense(ptr(x), ptr(coords), ptr(rows), max_rows, C, dc, ptr(dense), dtype_code(x),
                                cur_stream(x.device)), "tt_sp_to_dense")
     from . import autodiff
     if autodiff.TAPE is not None:
@@ -238,7 +225,7 @@ def sp_from_dense(gdense, coords, rows, max_rows, dims, grows):
     """grows += the dense gradient gathered back to the rows (backward of sp_to_dense)."""
     D, H, W = dims
     C = grows.shape[1]
-    check(lib().tt_sp_from_dense(ptr(gdense), ptr(coords), ptr(rows), _ll(max_rows), _c(C), _c(D), _c(H), _c(W),
+    check(lib().tt_sp_from_dense(ptr(gdense), ptr(coords), ptr(rows), max_rows, C, D, H, W,
                                  ptr(grows), cur_stream(grows.device)), "tt_sp_from_dense")
 
 
@@ -288,14 +275,14 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
     d.out_cstride = out.shape[-1]; d.out_coff = out_coff
     d.out_nstride = out_nstride or (out.stride(0) if (out.dim() == 4 and N > 1) else 0)
     d.pixel_shuffle2 = 1 if pixel_shuffle2 else 0
-    d.scale = _dp(scale); d.shift = _dp(shift); d.shift_n = _dp(shift_n); d.shift_n_mod = shift_n_mod
-    d.res1 = _dp(res1); d.res1_cstride = 0 if res1 is None else res1.shape[-1]; d.res1_coff = res1_coff
+    d.scale = ptr(scale); d.shift = ptr(shift); d.shift_n = ptr(shift_n); d.shift_n_mod = shift_n_mod
+    d.res1 = ptr(res1); d.res1_cstride = 0 if res1 is None else res1.shape[-1]; d.res1_coff = res1_coff
     if res1 is not None and res1.dtype == torch.float32 and x.dtype != torch.float32:
         d.res1_f32 = 1                  # an f32 sum chain beside half conv inputs (mixed mode's PAFPN)
     if res1_up:
         assert res1 is not None and res1.dim() == 4 and res1.is_contiguous() and res1.shape[0] == N and splitk_ws is None
         d.res1_up_h, d.res1_up_w = res1.shape[1], res1.shape[2]
-    d.res2 = _dp(res2); d.res2_cstride = 0 if res2 is None else res2.shape[-1]; d.res2_coff = res2_coff
+    d.res2 = ptr(res2); d.res2_cstride = 0 if res2 is None else res2.shape[-1]; d.res2_coff = res2_coff
     d.act = act; d.dtype = dtype_code(x); d.out_dtype = dtype_code(out)
     from . import autodiff
     if w_h2 is not None:
@@ -367,10 +354,6 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
 
 
 # ----------------------------------------------------------------------------- glue kernels
-_ll = ctypes.c_longlong
-_f = ctypes.c_float
-
-
 def _st(t):
     return cur_stream(t.device)
 
@@ -406,8 +389,7 @@ class BNSpec:
 
 def _bn_ws(C, groups, dev):
     L = lib()
-    L.tt_bn_workspace_bytes.restype = ctypes.c_longlong
-    nb = int(L.tt_bn_workspace_bytes(_c(C), _c(groups)))
+    nb = int(L.tt_bn_workspace_bytes(C, groups))
     return torch.empty(nb, dtype=torch.uint8, device=dev), nb
 
 
@@ -430,20 +412,18 @@ def batchnorm_train(z, spec, act=0, res1=None, res1_coff=0, res2=None, res2_coff
     ws, nb = _bn_ws(C, groups, dev)
     st = _st(z)
     L = lib()
-    check(L.tt_bn_stats(ptr(z), _ll(M), _c(C), _c(C), _c(0), ptr(m_dev), _c(groups), ptr(stats), ptr(ws), _ll(nb), st),
-          "tt_bn_stats")
+    check(L.tt_bn_stats(ptr(z), M, C, C, 0, ptr(m_dev), groups, ptr(stats), ptr(ws), nb, st), "tt_bn_stats")
     _all_reduce_sum_(stats)
     scale, shift, mean, invstd = (torch.empty(groups, C, dtype=torch.float32, device=dev) for _ in range(4))
-    check(L.tt_bn_finalize(ptr(stats), _c(C), _c(groups), ptr(spec.gamma), ptr(spec.beta), _f(spec.eps), _f(spec.momentum),
+    check(L.tt_bn_finalize(ptr(stats), C, groups, ptr(spec.gamma), ptr(spec.beta), spec.eps, spec.momentum,
                            ptr(spec.running_mean if update_running else None),
                            ptr(spec.running_var if update_running else None), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
                            st), "tt_bn_finalize")
 
     def cs(t):
         return 0 if t is None else t.shape[-1]
-    check(L.tt_bn_apply(ptr(z), _ll(M), _c(C), _c(C), _c(0), ptr(m_dev), _c(groups), ptr(scale), ptr(shift), ptr(mean), ptr(res1),
-                        _c(cs(res1)), _c(res1_coff), ptr(res2), _c(cs(res2)), _c(res2_coff), _c(act), ptr(out),
-                        _c(out.shape[-1]), _c(out_coff), st), "tt_bn_apply")
+    check(L.tt_bn_apply(ptr(z), M, C, C, 0, ptr(m_dev), groups, ptr(scale), ptr(shift), ptr(mean), ptr(res1), cs(res1),
+                        res1_coff, ptr(res2), cs(res2), res2_coff, act, ptr(out), out.shape[-1], out_coff, st), "tt_bn_apply")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.bn_train(z, out, out_coff, spec, act, res1, res1_coff, res2, res2_coff, m_dev, groups, stats, scale,
@@ -465,14 +445,13 @@ def batchnorm_train_bwd(dy, dy_coff, y, y_coff, z, mean, invstd, scale, stats, a
 
     def cs(t):
         return 0 if t is None else t.shape[-1]
-    check(L.tt_bn_bwd_reduce(ptr(dy), _c(dy.shape[-1]), _c(dy_coff), ptr(y), _c(y.shape[-1]), _c(y_coff), ptr(z), _c(C), _c(0),
-                             _ll(M), _c(C), ptr(m_dev), _c(groups), ptr(mean), ptr(invstd), _c(act), ptr(dres1), _c(cs(dres1)),
-                             _c(dres1_coff), ptr(dres2), _c(cs(dres2)), _c(dres2_coff), ptr(sums), ptr(ws), _ll(nb), st),
-          "tt_bn_bwd_reduce")
+    check(L.tt_bn_bwd_reduce(ptr(dy), dy.shape[-1], dy_coff, ptr(y), y.shape[-1], y_coff, ptr(z), C, 0,
+                             M, C, ptr(m_dev), groups, ptr(mean), ptr(invstd), act, ptr(dres1), cs(dres1),
+                             dres1_coff, ptr(dres2), cs(dres2), dres2_coff, ptr(sums), ptr(ws), nb, st), "tt_bn_bwd_reduce")
     local = sums.sum(0).to(torch.float32)
     _all_reduce_sum_(sums)
-    check(L.tt_bn_bwd_apply(ptr(dy), _c(dy.shape[-1]), _c(dy_coff), ptr(z), _c(C), _c(0), _ll(M), _c(C), ptr(m_dev), _c(groups),
-                            ptr(sums), ptr(stats), ptr(scale), ptr(mean), ptr(invstd), ptr(dz), _c(dz.shape[-1]), _c(0), st),
+    check(L.tt_bn_bwd_apply(ptr(dy), dy.shape[-1], dy_coff, ptr(z), C, 0, M, C, ptr(m_dev), groups,
+                            ptr(sums), ptr(stats), ptr(scale), ptr(mean), ptr(invstd), ptr(dz), dz.shape[-1], 0, st),
           "tt_bn_bwd_apply")
     return local[C:].contiguous(), local[:C].contiguous()
 
@@ -490,8 +469,7 @@ def dropout(x, p=0.5):
         assert mask_in.numel() == x.numel()
     DROPOUT_SEED[1] += 1
     seed = (DROPOUT_SEED[0] * 0x100000001B3 + DROPOUT_SEED[1] * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
-    check(lib().tt_dropout_fwd(ptr(x), ptr(out), _ll(x.numel()), _f(p), ctypes.c_ulonglong(seed), ptr(mask_in), ptr(mask),
-                               _st(x)), "tt_dropout_fwd")
+    check(lib().tt_dropout_fwd(ptr(x), ptr(out), x.numel(), p, seed, ptr(mask_in), ptr(mask), _st(x)), "tt_dropout_fwd")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.dropout(x, out, mask, p)
@@ -500,7 +478,7 @@ def dropout(x, p=0.5):
 
 def dropout_bwd(dout, mask, dx, p):
     assert dout.is_contiguous() and dx.is_contiguous()
-    check(lib().tt_dropout_bwd(ptr(dout), ptr(mask), ptr(dx), _ll(dout.numel()), _f(p), _st(dout)), "tt_dropout_bwd")
+    check(lib().tt_dropout_bwd(ptr(dout), ptr(mask), ptr(dx), dout.numel(), p, _st(dout)), "tt_dropout_bwd")
 
 
 def nchw_to_nhwc_border(x, out, top, left):
@@ -509,8 +487,8 @@ def nchw_to_nhwc_border(x, out, top, left):
     assert x.is_contiguous() and x.dtype == torch.float32 and out.is_contiguous()
     N, C, H, W = x.shape
     _, Hp, Wp, Cp = out.shape
-    check(lib().tt_nchw_to_nhwc_border(ptr(x), ptr(out), _c(N), _c(C), _c(H), _c(W), _c(Cp), _c(Hp), _c(Wp),
-                                       _c(top), _c(left), _c(dtype_code(out)), _st(x)), "tt_nchw_to_nhwc_border")
+    check(lib().tt_nchw_to_nhwc_border(ptr(x), ptr(out), N, C, H, W, Cp, Hp, Wp,
+                                       top, left, dtype_code(out), _st(x)), "tt_nchw_to_nhwc_border")
     return out
 
 
@@ -520,8 +498,7 @@ def nchw_to_nhwc_pad(x, dtype, c_pad):
     assert x.is_contiguous() and x.dtype == torch.float32
     N, C, H, W = x.shape
     out = torch.empty(N, H, W, c_pad, dtype=dtype, device=x.device)
-    check(lib().tt_nchw_to_nhwc_pad(ptr(x), ptr(out), _c(N), _c(C), _c(H), _c(W), _c(c_pad),
-                                    _c(dtype_code(out)), _st(x)), "tt_nchw_to_nhwc_pad")
+    check(lib().tt_nchw_to_nhwc_pad(ptr(x), ptr(out), N, C, H, W, c_pad, dtype_code(out), _st(x)), "tt_nchw_to_nhwc_pad")
     return out
 
 
@@ -531,16 +508,14 @@ def nhwc_to_nchw(x, C=None, coff=0):
     N, H, W, Cs = x.shape
     C = C or Cs
     out = torch.empty(N, C, H, W, dtype=torch.float32, device=x.device)
-    check(lib().tt_nhwc_to_nchw(ptr(x), ptr(out), _c(N), _c(C), _c(H), _c(W), _c(Cs), _c(coff),
-                                _c(dtype_code(x)), _st(x)), "tt_nhwc_to_nchw")
+    check(lib().tt_nhwc_to_nchw(ptr(x), ptr(out), N, C, H, W, Cs, coff, dtype_code(x), _st(x)), "tt_nhwc_to_nchw")
     return out
 
 
 def maxpool3x3s2(x):
     N, H, W, C = x.shape
     out = torch.empty(N, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C, dtype=x.dtype, device=x.device)
-    check(lib().tt_maxpool3x3s2(ptr(x), ptr(out), _c(N), _c(H), _c(W), _c(C), _c(dtype_code(x)), _st(x)),
-          "tt_maxpool3x3s2")
+    check(lib().tt_maxpool3x3s2(ptr(x), ptr(out), N, H, W, C, dtype_code(x), _st(x)), "tt_maxpool3x3s2")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.maxpool3x3s2(x, out)
@@ -549,9 +524,8 @@ def maxpool3x3s2(x):
 
 def upsample_nearest_add_(dst, src):
     N, H, W, C = dst.shape
-    check(lib().tt_upsample_nearest_add(ptr(dst), ptr(src), _c(N), _c(H), _c(W), _c(C), _c(src.shape[1]),
-                                        _c(src.shape[2]), _c(dtype_code(dst)), _st(dst)),
-          "tt_upsample_nearest_add")
+    check(lib().tt_upsample_nearest_add(ptr(dst), ptr(src), N, H, W, C, src.shape[1],
+                                        src.shape[2], dtype_code(dst), _st(dst)), "tt_upsample_nearest_add")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.upsample_nearest_add_(dst, src)
@@ -574,10 +548,9 @@ def bilinear_up2(x, out_pair=False):
     out = torch.empty(N, 2 * H, 2 * W, C, dtype=x.dtype, device=x.device)
     if out_pair:      # f32 -> bf16x3 pair format for a consumer that is a bf16x3 convolution (conv2d(in_pair=True))
         assert x.dtype == torch.float32 and x.is_contiguous() and C % 16 == 0
-        check(lib().tt_bilinear_up2_pair(ptr(x), ptr(out), _c(N), _c(H), _c(W), _c(C), _st(x)), "tt_bilinear_up2_pair")
+        check(lib().tt_bilinear_up2_pair(ptr(x), ptr(out), N, H, W, C, _st(x)), "tt_bilinear_up2_pair")
         return out
-    check(lib().tt_bilinear_up2(ptr(x), ptr(out), _c(N), _c(H), _c(W), _c(C), _c(dtype_code(x)), _st(x)),
-          "tt_bilinear_up2")
+    check(lib().tt_bilinear_up2(ptr(x), ptr(out), N, H, W, C, dtype_code(x), _st(x)), "tt_bilinear_up2")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.bilinear_up2(x, out)
@@ -589,8 +562,7 @@ def spatial_pool(x, mode, C=None, coff=0):
     N, H, W, Cs = x.shape
     C = C or Cs
     out = torch.empty(N, C, dtype=torch.float32, device=x.device)
-    check(lib().tt_spatial_pool(ptr(x), ptr(out), _c(N), _c(H * W), _c(C), _c(Cs), _c(coff), _c(mode),
-                                _c(dtype_code(x)), _st(x)), "tt_spatial_pool")
+    check(lib().tt_spatial_pool(ptr(x), ptr(out), N, H * W, C, Cs, coff, mode, dtype_code(x), _st(x)), "tt_spatial_pool")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.spatial_pool(x, out, mode, C, coff)
@@ -601,8 +573,8 @@ def channel_gate(x, gate, res=None, gate_act=_lib.ACT_SIGMOID, out_act=_lib.ACT_
     N, H, W, C = x.shape
     assert gate.dtype == torch.float32 and gate.shape == (N, C) and gate.is_contiguous()
     out = torch.empty_like(x) if out is None else out
-    check(lib().tt_channel_gate(ptr(x), ptr(gate), ptr(res), ptr(out), _c(N), _c(H * W), _c(C), _c(gate_act),
-                                _c(out_act), _c(dtype_code(x)), _st(x)), "tt_channel_gate")
+    check(lib().tt_channel_gate(ptr(x), ptr(gate), ptr(res), ptr(out), N, H * W, C, gate_act,
+                                out_act, dtype_code(x), _st(x)), "tt_channel_gate")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.channel_gate(x, gate, res, out, gate_act, out_act)
@@ -613,8 +585,8 @@ def affine_rows(x, scale, shift, act=0, out=None):
     """x (R, C) possibly a row-strided 2-D view."""
     R, C = x.shape
     out = torch.empty(R, C, dtype=x.dtype, device=x.device) if out is None else out
-    check(lib().tt_affine_rows(ptr(x), ptr(scale), ptr(shift), ptr(out), _ll(R), _c(C), _c(x.stride(0)),
-                               _c(out.stride(0)), _c(act), _c(dtype_code(x)), _st(x)), "tt_affine_rows")
+    check(lib().tt_affine_rows(ptr(x), ptr(scale), ptr(shift), ptr(out), R, C, x.stride(0),
+                               out.stride(0), act, dtype_code(x), _st(x)), "tt_affine_rows")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.affine_rows(x, scale, shift, act, out)
@@ -626,8 +598,8 @@ def layernorm_rows(x, gamma, beta, eps=1e-5, out=None, D=None):
     R = x.shape[0]
     D = D or x.shape[1]
     out = torch.zeros(R, x.shape[1], dtype=x.dtype, device=x.device) if out is None else out
-    check(lib().tt_layernorm_rows(ptr(x), ptr(gamma), ptr(beta), ptr(out), _ll(R), _c(D), _c(x.stride(0)),
-                                  _c(out.stride(0)), _f(eps), _c(dtype_code(x)), _st(x)), "tt_layernorm_rows")
+    check(lib().tt_layernorm_rows(ptr(x), ptr(gamma), ptr(beta), ptr(out), R, D, x.stride(0),
+                                  out.stride(0), eps, dtype_code(x), _st(x)), "tt_layernorm_rows")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.layernorm_rows(x, gamma, beta, out, D, eps)
@@ -638,27 +610,24 @@ def layernorm_rows_bwd(x, gamma, dout, dx, dgamma, dbeta, D, eps=1e-5):
     """dx[:, :D] += , dgamma += , dbeta += backward of layernorm_rows (2-D row-strided f32 views)."""
     R = x.shape[0]
     L = lib()
-    L.tt_layernorm_rows_bwd_workspace_bytes.restype = ctypes.c_longlong
-    nb = int(L.tt_layernorm_rows_bwd_workspace_bytes(_ll(R), _c(D)))
+    nb = int(L.tt_layernorm_rows_bwd_workspace_bytes(R, D))
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
-    check(L.tt_layernorm_rows_bwd(ptr(x), ptr(gamma), ptr(dout), ptr(dx), ptr(dgamma), ptr(dbeta), _ll(R), _c(D),
-                                  _c(x.stride(0)), _c(dout.stride(0)), _c(dx.stride(0)), _f(eps), ptr(ws), _ll(nb), _st(x)),
-          "tt_layernorm_rows_bwd")
+    check(L.tt_layernorm_rows_bwd(ptr(x), ptr(gamma), ptr(dout), ptr(dx), ptr(dgamma), ptr(dbeta), R, D,
+                                  x.stride(0), dout.stride(0), dx.stride(0), eps, ptr(ws), nb, _st(x)), "tt_layernorm_rows_bwd")
 
 
 def concat_piece_bwd(dout, coff, C, div, mod, dsrc):
     """dsrc[:, :C] += the gradient of one concat_rows piece (dout / dsrc 2-D row-strided f32 views)."""
     R = dout.shape[0]
-    check(lib().tt_concat_piece_bwd(ptr(dout), _c(dout.stride(0)), _c(coff), _ll(R), _c(C), _c(div), _c(mod), ptr(dsrc),
-                                    _c(dsrc.stride(0)), _c(dsrc.shape[0]), _st(dout)), "tt_concat_piece_bwd")
+    check(lib().tt_concat_piece_bwd(ptr(dout), dout.stride(0), coff, R, C, div, mod, ptr(dsrc),
+                                    dsrc.stride(0), dsrc.shape[0], _st(dout)), "tt_concat_piece_bwd")
 
 
 def copy_nhwc(x, out, C=None, in_coff=0, out_coff=0, rot_flip=False):
     N, H, W, Cs = x.shape
     C = C or Cs
-    check(lib().tt_copy_nhwc(ptr(x), ptr(out), _c(N), _c(H), _c(W), _c(C), _c(Cs), _c(in_coff),
-                             _c(out.shape[-1]), _c(out_coff), _c(1 if rot_flip else 0), _c(dtype_code(x)),
-                             _c(dtype_code(out)), _st(x)), "tt_copy_nhwc")
+    check(lib().tt_copy_nhwc(ptr(x), ptr(out), N, H, W, C, Cs, in_coff, out.shape[-1], out_coff, 1 if rot_flip else 0,
+                             dtype_code(x), dtype_code(out), _st(x)), "tt_copy_nhwc")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.copy_nhwc(x, out, C, in_coff, out_coff, rot_flip)
@@ -669,8 +638,8 @@ def broadcast_rows(v, out, out_coff=0):
     """v (N, C) -> out (N,H,W,Ct)[..., out_coff:out_coff+C] = v[n, :]."""
     N, C = v.shape
     _, H, W, Ct = out.shape
-    check(lib().tt_broadcast_rows(ptr(v), ptr(out), _c(N), _c(H * W), _c(C), _c(v.stride(0)), _c(Ct),
-                                  _c(out_coff), _c(dtype_code(out)), _st(out)), "tt_broadcast_rows")
+    check(lib().tt_broadcast_rows(ptr(v), ptr(out), N, H * W, C, v.stride(0), Ct,
+                                  out_coff, dtype_code(out), _st(out)), "tt_broadcast_rows")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.broadcast_rows(v, out, out_coff)
@@ -688,10 +657,9 @@ def ew(op, a, b=None, g=None, out=None, C=None, a_coff=0, b_coff=0, g_coff=0, ou
     assert o2.data_ptr() == out.data_ptr() and o2.stride(1) == 1, "ew: `out` must be viewable as rows"
     b2 = None if b is None else b.reshape(-1, b.shape[-1])
     g2 = None if g is None else g.reshape(-1, g.shape[-1])
-    check(lib().tt_ew(ptr(a2), ptr(b2), ptr(g2), ptr(o2), _ll(R), _c(C), _c(a2.stride(0)), _c(a_coff),
-                      _c(0 if b2 is None else b2.stride(0)), _c(b_coff), _c(0 if g2 is None else g2.stride(0)),
-                      _c(g_coff), _c(o2.stride(0)), _c(out_coff), _c(op), _c(act), _c(dtype_code(a)), _st(a)),
-          "tt_ew")
+    check(lib().tt_ew(ptr(a2), ptr(b2), ptr(g2), ptr(o2), R, C, a2.stride(0), a_coff,
+                      0 if b2 is None else b2.stride(0), b_coff, 0 if g2 is None else g2.stride(0),
+                      g_coff, o2.stride(0), out_coff, op, act, dtype_code(a), _st(a)), "tt_ew")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.ew(op, act, R, C, a2, a_coff, b2, b_coff, g2, g_coff, o2, out_coff)
@@ -702,10 +670,9 @@ def ew_bwd(op, act, R, C, a2, a_coff, b2, b_coff, g2, g_coff, o2, out_coff, dout
     """Backward of `ew` on the same 2-D row views (d* are the gradient views of a2 / b2 / g2 / o2, or None)."""
     def st(t):
         return 0 if t is None else t.stride(0)
-    check(lib().tt_ew_bwd(_c(op), _c(act), _ll(R), _c(C), ptr(a2), _c(st(a2)), _c(a_coff), ptr(b2), _c(st(b2)), _c(b_coff),
-                          ptr(g2), _c(st(g2)), _c(g_coff), ptr(o2), _c(st(o2)), _c(out_coff), ptr(dout), _c(st(dout)),
-                          _c(out_coff), ptr(da), _c(st(da)), _c(a_coff), ptr(db), _c(st(db)), _c(b_coff), ptr(dg),
-                          _c(st(dg)), _c(g_coff), _st(a2)), "tt_ew_bwd")
+    check(lib().tt_ew_bwd(op, act, R, C, ptr(a2), st(a2), a_coff, ptr(b2), st(b2), b_coff, ptr(g2), st(g2), g_coff, ptr(o2),
+                          st(o2), out_coff, ptr(dout), st(dout), out_coff, ptr(da), st(da), a_coff, ptr(db), st(db), b_coff,
+                          ptr(dg), st(dg), g_coff, _st(a2)), "tt_ew_bwd")
 
 
 def concat_rows(out, pieces, coff=0):
@@ -729,7 +696,7 @@ def concat_rows(out, pieces, coff=0):
             srcs[i], strides[i] = None, 0
         widths[i], coffs[i], divs[i], mods[i] = C, c, div, mod
         c += C
-    check(lib().tt_concat_rows(ptr(o2), _ll(o2.shape[0]), _c(o2.stride(0)), _c(n), srcs, strides, widths, coffs, divs,
+    check(lib().tt_concat_rows(ptr(o2), o2.shape[0], o2.stride(0), n, srcs, strides, widths, coffs, divs,
                                mods, _st(out)), "tt_concat_rows")
     from . import autodiff
     if autodiff.TAPE is not None:
@@ -742,9 +709,8 @@ def deform_im2col3x3(x, offsets, pad=1):
     N, H, W, C = x.shape
     assert offsets.dtype == torch.float32 and offsets.is_contiguous()
     cols = torch.empty(N * H * W, 1, 9, C, dtype=x.dtype, device=x.device)
-    check(lib().tt_deform_im2col3x3(ptr(x), ptr(offsets), ptr(cols), _c(N), _c(H), _c(W), _c(C),
-                                    _c(offsets.shape[-1]), _c(pad), _c(dtype_code(x)), _st(x)),
-          "tt_deform_im2col3x3")
+    check(lib().tt_deform_im2col3x3(ptr(x), ptr(offsets), ptr(cols), N, H, W, C,
+                                    offsets.shape[-1], pad, dtype_code(x), _st(x)), "tt_deform_im2col3x3")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.deform_im2col3x3(x, offsets, cols, pad)
@@ -758,7 +724,7 @@ def repeat_rows(t, times):
     out = torch.empty(times * t.shape[0], t.shape[1], dtype=t.dtype, device=t.device)
     nb = t.numel() * t.element_size()
     for k in range(times):          # `times` contiguous block copies (tt_copy_bytes): no torch kernel in the forward
-        check(lib().tt_copy_bytes(ctypes.c_void_p(out.data_ptr() + k * nb), ptr(t), _ll(nb), _st(t)), "tt_copy_bytes")
+        check(lib().tt_copy_bytes(out.data_ptr() + k * nb, ptr(t), nb, _st(t)), "tt_copy_bytes")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.repeat_rows(t, out, times)
@@ -773,7 +739,7 @@ def look_project_pack(wp, lidar2img, ida_mat, img_hw):
     qos = torch.empty(B, 4, 120, dtype=torch.int32, device=dev)
     count = torch.empty(B, 4, dtype=torch.int32, device=dev)
     max_len = torch.empty(1, dtype=torch.int32, device=dev)
-    check(lib().tt_look_project_pack(_c(B), ptr(wp), ptr(lidar2img), ptr(ida_mat), _f(img_hw[0]), _f(img_hw[1]),
+    check(lib().tt_look_project_pack(B, ptr(wp), ptr(lidar2img), ptr(ida_mat), img_hw[0], img_hw[1],
                                      ptr(ref), ptr(qos), ptr(count), ptr(max_len), _st(wp)), "tt_look_project_pack")
     return ref, qos, count, max_len
 
@@ -788,9 +754,9 @@ def look_gather_query(qos, ref, wp, ctrl_sp, temporal, static, meas, flat, maps,
     B = wp.shape[0]
     out = torch.empty(B * 4 * 120, row_stride, dtype=torch.float32, device=wp.device)
     arr, hw = _level_args(maps)
-    check(lib().tt_look_gather_query(_c(B), ptr(qos), ptr(ref), ptr(wp), ptr(ctrl_sp), ptr(temporal), ptr(static),
-                                     ptr(meas), ptr(flat), arr, hw, _c(dtype_code(maps[0])), ptr(out),
-                                     _c(row_stride), _st(wp)), "tt_look_gather_query")
+    check(lib().tt_look_gather_query(B, ptr(qos), ptr(ref), ptr(wp), ptr(ctrl_sp), ptr(temporal), ptr(static),
+                                     ptr(meas), ptr(flat), arr, hw, dtype_code(maps[0]), ptr(out),
+                                     row_stride, _st(wp)), "tt_look_gather_query")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.look_gather_query(qos, ref, out, temporal, static, meas, flat, maps, row_stride)
@@ -799,28 +765,27 @@ def look_gather_query(qos, ref, wp, ctrl_sp, temporal, static, meas, flat, maps,
 
 def look_gather_query_bwd(B, qos, ref, dout, row_stride, dtemporal, dstatic, dmeas, dflat, dmaps):
     arr, hw = _level_args(dmaps)
-    check(lib().tt_look_gather_query_bwd(_c(B), ptr(qos), ptr(ref), ptr(dout), _c(row_stride), ptr(dtemporal), ptr(dstatic),
+    check(lib().tt_look_gather_query_bwd(B, ptr(qos), ptr(ref), ptr(dout), row_stride, ptr(dtemporal), ptr(dstatic),
                                          ptr(dmeas), ptr(dflat), arr, hw, _st(dout)), "tt_look_gather_query_bwd")
 
 
 def msda_sample_bwd(B, value, coff, offsets, logits, ref, level_hw, dout, dvalue, doffsets, dlogits):
     hw = (ctypes.c_int * 8)(*[v for pair in level_hw for v in pair])
     assert value.dtype == torch.float32
-    check(lib().tt_msda_sample_bwd(_c(B), ptr(value), _c(value.shape[-1]), _c(coff), ptr(offsets), ptr(logits), ptr(ref), hw,
+    check(lib().tt_msda_sample_bwd(B, ptr(value), value.shape[-1], coff, ptr(offsets), ptr(logits), ptr(ref), hw,
                                    ptr(dout), ptr(dvalue), ptr(doffsets), ptr(dlogits), _st(dout)), "tt_msda_sample_bwd")
 
 
 def sca_reduce_bwd(B, dout, max_len, dx):
-    check(lib().tt_sca_reduce_bwd(_c(B), ptr(dout), ptr(max_len), ptr(dx), _st(dout)), "tt_sca_reduce_bwd")
+    check(lib().tt_sca_reduce_bwd(B, ptr(dout), ptr(max_len), ptr(dx), _st(dout)), "tt_sca_reduce_bwd")
 
 
 def msda_sample(value, offsets, logits, ref, level_hw, B, coff=0):
     """value (B*4, S, Cv) with Cv >= 256: samples channels [coff, coff+256)."""
     out = torch.empty(B * 4 * 120, 256, dtype=torch.float32, device=value.device)
     hw = (ctypes.c_int * 8)(*[v for pair in level_hw for v in pair])
-    check(lib().tt_msda_sample_strided(_c(B), ptr(value), _c(dtype_code(value)), _c(value.shape[-1]), _c(coff),
-                                       ptr(offsets), ptr(logits), ptr(ref), hw, ptr(out), _st(value)),
-          "tt_msda_sample")
+    check(lib().tt_msda_sample_strided(B, ptr(value), dtype_code(value), value.shape[-1], coff,
+                                       ptr(offsets), ptr(logits), ptr(ref), hw, ptr(out), _st(value)), "tt_msda_sample_strided")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.msda_sample(value, offsets, logits, ref, level_hw, B, coff, out)
@@ -829,7 +794,7 @@ def msda_sample(value, offsets, logits, ref, level_hw, B, coff=0):
 
 def sca_reduce(x, max_len, B):
     out = torch.empty(B, 1024, dtype=torch.float32, device=x.device)
-    check(lib().tt_sca_reduce(_c(B), ptr(x), ptr(max_len), ptr(out), _st(x)), "tt_sca_reduce")
+    check(lib().tt_sca_reduce(B, ptr(x), ptr(max_len), ptr(out), _st(x)), "tt_sca_reduce")
     from . import autodiff
     if autodiff.TAPE is not None:
         autodiff.TAPE.sca_reduce(x, max_len, B, out)
@@ -840,10 +805,10 @@ def sca_reduce(x, max_len, B):
 class _ChainStage(ctypes.Structure):
     _fields_ = [
         ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-        ("K", _c), ("Kp", _c), ("N", _c), ("act", _c), ("in_sel", _c),
-        ("res", ctypes.c_void_p), ("res_stride", _c), ("res_coff", _c),
-        ("side", ctypes.c_void_p), ("side_w", ctypes.c_void_p), ("side_stride", _c), ("side_k", _c),
-        ("out", ctypes.c_void_p), ("out_stride", _c), ("out_coff", _c),
+        ("K", ctypes.c_int), ("Kp", ctypes.c_int), ("N", ctypes.c_int), ("act", ctypes.c_int), ("in_sel", ctypes.c_int),
+        ("res", ctypes.c_void_p), ("res_stride", ctypes.c_int), ("res_coff", ctypes.c_int),
+        ("side", ctypes.c_void_p), ("side_w", ctypes.c_void_p), ("side_stride", ctypes.c_int), ("side_k", ctypes.c_int),
+        ("out", ctypes.c_void_p), ("out_stride", ctypes.c_int), ("out_coff", ctypes.c_int),
     ]
 
 
@@ -911,7 +876,7 @@ def mlp_chain(x, stages, n_split=1, groups=None, wide=None):
     for i, st in enumerate(stages):
         lin = st["lin"]
         d = arr[i]
-        d.w = lin.w.data_ptr(); d.bias = _dp(lin.bias)
+        d.w = lin.w.data_ptr(); d.bias = ptr(lin.bias)
         d.K, d.Kp, d.N, d.act, d.in_sel = lin.K, lin.Kp, lin.N, lin.act, st.get("src", i - 1)
         res = st.get("res")
         if res is not None:
@@ -942,16 +907,15 @@ def mlp_chain(x, stages, n_split=1, groups=None, wide=None):
         if groups is None:
             groups = min(16, max((st["lin"].N + 31) // 32 for st in stages))
         groups = max(1, min(groups, cap // row_groups, 64))
-        L.tt_mlp_chain_wide_workspace_bytes.restype = ctypes.c_longlong
-        nbytes = int(L.tt_mlp_chain_wide_workspace_bytes(_ll(R), _c(n), arr))
+        nbytes = int(L.tt_mlp_chain_wide_workspace_bytes(R, n, arr))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        rc = L.tt_mlp_chain_wide(ptr(x), _ll(R), _c(x.stride(0)), _c(n), arr, _c(groups), ptr(ws), _ll(nbytes), _st(x))
+        rc = L.tt_mlp_chain_wide(ptr(x), R, x.stride(0), n, arr, groups, ptr(ws), nbytes, _st(x))
         if rc != -4 or wide:
             check(rc, "tt_mlp_chain_wide")
             return
         # -4: the ticket slots of graph-captured launches are used up (a process that re-captures over and over): the
         # one-workgroup-per-row-block chain computes the same stages without a cross-workgroup barrier
-    check(lib().tt_mlp_chain(ptr(x), _ll(R), _c(x.stride(0)), _c(n), arr, _c(n_split), _st(x)), "tt_mlp_chain")
+    check(lib().tt_mlp_chain(ptr(x), R, x.stride(0), n, arr, n_split, _st(x)), "tt_mlp_chain")
 
 
 # ----------------------------------------------------------------------------- convolution backward (training step)
@@ -972,16 +936,14 @@ def conv2d_wgrad(x, dy, kh, kw, stride=1, pad=0, dil=1, cin=None, in_coff=0, cou
         out = torch.empty(cout, kh, kw, cin_pad, dtype=torch.float32, device=x.device)
     assert tuple(out.shape) == (cout, kh, kw, cin_pad) and out.is_contiguous()
     L = lib()
-    L.tt_conv2d_wgrad_workspace_bytes.restype = ctypes.c_longlong
-    nb = int(L.tt_conv2d_wgrad_workspace_bytes(_c(N), _c(OH), _c(cout), _c(cin), _c(cin_pad), _c(kh), _c(kw)))
+    nb = int(L.tt_conv2d_wgrad_workspace_bytes(N, OH, cout, cin, cin_pad, kh, kw))
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
     if CONV_PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    fn = L.tt_conv2d_wgrad_x3 if x3 else L.tt_conv2d_wgrad      # x3: the forward's bf16x3 arithmetic (wide layers: LDS-staged kernel)
-    check(fn(ptr(x), _c(N), _c(H), _c(W), _c(cin), _c(Cs), _c(in_coff), ptr(dy), _c(OH), _c(OW), _c(cout),
-                            _c(Cd), _c(dy_coff), _c(kh), _c(kw), _c(stride), _c(pad), _c(dil), _c(cin_pad),
-                            _c(1 if accumulate else 0), ptr(out), ptr(ws), _ll(nb), _st(x)), "tt_conv2d_wgrad")
+    name = "tt_conv2d_wgrad_x3" if x3 else "tt_conv2d_wgrad"   # x3: the forward's bf16x3 arithmetic (wide layers: LDS-staged kernel)
+    check(getattr(L, name)(ptr(x), N, H, W, cin, Cs, in_coff, ptr(dy), OH, OW, cout, Cd, dy_coff, kh, kw, stride, pad, dil,
+                           cin_pad, 1 if accumulate else 0, ptr(out), ptr(ws), nb, _st(x)), name)
     if CONV_PROFILE is not None:
         e1.record()
         CONV_PROFILE.append((2.0 * N * OH * OW * cout * kh * kw * cin, e0, e1,
@@ -1055,18 +1017,16 @@ def conv_epilogue_bwd(dy, y, scale=None, shift=None, act=0, res1=None, res2=None
         dshift = torch.empty(C, dtype=torch.float32, device=dev)
         accumulate = False
     L = lib()
-    L.tt_conv_epilogue_bwd_workspace_bytes.restype = ctypes.c_longlong
-    nb = int(L.tt_conv_epilogue_bwd_workspace_bytes(_c(C)))
+    nb = int(L.tt_conv_epilogue_bwd_workspace_bytes(C))
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
 
     def cs(t):
         return 0 if t is None else t.shape[-1]
-    check(L.tt_conv_epilogue_bwd(ptr(dy), _c(dy.shape[-1]), _c(dy_coff), ptr(y), _c(y.shape[-1]), _c(y_coff),
-                                 ptr(res1), _c(cs(res1)), _c(res1_coff), ptr(res2), _c(cs(res2)), _c(res2_coff),
-                                 ptr(scale), ptr(shift), _ll(M), _c(C), _c(act), ptr(dconv), _c(C), _c(0),
-                                 ptr(dres1), _c(cs(dres1)), _c(dres1_coff), ptr(dres2), _c(cs(dres2)), _c(dres2_coff),
-                                 _c(1 if dres_accumulate else 0), ptr(dscale if scale is not None else None), ptr(dshift),
-                                 _c(1 if accumulate else 0), ptr(m_dev), ptr(pre), ptr(conv_raw), ptr(ws), _ll(nb), _st(y)),
+    check(L.tt_conv_epilogue_bwd(ptr(dy), dy.shape[-1], dy_coff, ptr(y), y.shape[-1], y_coff, ptr(res1), cs(res1), res1_coff,
+                                 ptr(res2), cs(res2), res2_coff, ptr(scale), ptr(shift), M, C, act, ptr(dconv), C, 0,
+                                 ptr(dres1), cs(dres1), dres1_coff, ptr(dres2), cs(dres2), dres2_coff,
+                                 1 if dres_accumulate else 0, ptr(dscale if scale is not None else None), ptr(dshift),
+                                 1 if accumulate else 0, ptr(m_dev), ptr(pre), ptr(conv_raw), ptr(ws), nb, _st(y)),
           "tt_conv_epilogue_bwd")
     return dconv, dres, (dscale if scale is not None else None), dshift
 
@@ -1076,7 +1036,7 @@ def maxpool3x3s2_bwd(x, dy, dx):
     require_cuda(x, dy, dx)
     N, H, W, C = x.shape
     assert x.is_contiguous() and dy.is_contiguous() and dx.is_contiguous() and dx.shape == x.shape
-    check(lib().tt_maxpool3x3s2_bwd(ptr(x), ptr(dy), ptr(dx), _c(N), _c(H), _c(W), _c(C), _st(x)), "tt_maxpool3x3s2_bwd")
+    check(lib().tt_maxpool3x3s2_bwd(ptr(x), ptr(dy), ptr(dx), N, H, W, C, _st(x)), "tt_maxpool3x3s2_bwd")
     return dx
 
 
@@ -1085,7 +1045,7 @@ def bilinear_up2_bwd(dy, dx):
     require_cuda(dy, dx)
     N, H, W, C = dx.shape
     assert dy.is_contiguous() and dx.is_contiguous() and tuple(dy.shape) == (N, 2 * H, 2 * W, C)
-    check(lib().tt_bilinear_up2_bwd(ptr(dy), ptr(dx), _c(N), _c(H), _c(W), _c(C), _st(dy)), "tt_bilinear_up2_bwd")
+    check(lib().tt_bilinear_up2_bwd(ptr(dy), ptr(dx), N, H, W, C, _st(dy)), "tt_bilinear_up2_bwd")
     return dx
 
 
@@ -1095,7 +1055,7 @@ def channel_gate_bwd(x, gate, dy, dx, dgate, out_relu=None, dres=None):
     require_cuda(x, gate, dy, dx, dgate)
     N, H, W, C = x.shape
     assert x.is_contiguous() and dy.is_contiguous() and dx.is_contiguous() and gate.is_contiguous() and dgate.is_contiguous()
-    check(lib().tt_channel_gate_bwd(ptr(x), ptr(gate), ptr(dy), ptr(dx), ptr(dgate), _c(N), _c(H * W), _c(C),
+    check(lib().tt_channel_gate_bwd(ptr(x), ptr(gate), ptr(dy), ptr(dx), ptr(dgate), N, H * W, C,
                                     ptr(out_relu), ptr(dres), _st(x)), "tt_channel_gate_bwd")
 
 
@@ -1104,8 +1064,7 @@ def spatial_meanmax_bwd(x, dpool, dx):
     require_cuda(x, dpool, dx)
     N, H, W, C = x.shape
     assert x.is_contiguous() and dx.is_contiguous() and dpool.is_contiguous()
-    check(lib().tt_spatial_meanmax_bwd(ptr(x), ptr(dpool), ptr(dx), _c(N), _c(H * W), _c(C), _st(x)),
-          "tt_spatial_meanmax_bwd")
+    check(lib().tt_spatial_meanmax_bwd(ptr(x), ptr(dpool), ptr(dx), N, H * W, C, _st(x)), "tt_spatial_meanmax_bwd")
 
 
 def spatial_mean_bwd(dpool, dx, C, coff=0):
@@ -1113,8 +1072,7 @@ def spatial_mean_bwd(dpool, dx, C, coff=0):
     require_cuda(dpool, dx)
     N, H, W, Cs = dx.shape
     assert dpool.is_contiguous() and dx.is_contiguous() and tuple(dpool.shape) == (N, C)
-    check(lib().tt_spatial_mean_bwd(ptr(dpool), ptr(dx), _c(N), _c(H * W), _c(C), _c(Cs), _c(coff), _st(dx)),
-          "tt_spatial_mean_bwd")
+    check(lib().tt_spatial_mean_bwd(ptr(dpool), ptr(dx), N, H * W, C, Cs, coff, _st(dx)), "tt_spatial_mean_bwd")
 
 
 def deform_im2col3x3_bwd(x, offsets, gcols, gx, goff, pad=1):
@@ -1122,15 +1080,15 @@ def deform_im2col3x3_bwd(x, offsets, gcols, gx, goff, pad=1):
     require_cuda(x, offsets, gcols, gx, goff)
     N, H, W, C = x.shape
     assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (x, offsets, gcols, gx, goff))
-    check(lib().tt_deform_im2col3x3_bwd(ptr(x), ptr(offsets), ptr(gcols), ptr(gx), ptr(goff), _c(N), _c(H), _c(W), _c(C),
-                                        _c(offsets.shape[-1]), _c(pad), _st(x)), "tt_deform_im2col3x3_bwd")
+    check(lib().tt_deform_im2col3x3_bwd(ptr(x), ptr(offsets), ptr(gcols), ptr(gx), ptr(goff), N, H, W, C,
+                                        offsets.shape[-1], pad, _st(x)), "tt_deform_im2col3x3_bwd")
 
 
 def broadcast_rows_bwd(dout, dv, out_coff):
     """dv (N, C) (row-strided) += per-image sums of dout (N,H,W,Ct)[..., out_coff:out_coff+C]."""
     N, C = dv.shape
     _, H, W, Ct = dout.shape
-    check(lib().tt_broadcast_rows_bwd(ptr(dout), ptr(dv), _c(N), _c(H * W), _c(C), _c(Ct), _c(out_coff), _c(dv.stride(0)),
+    check(lib().tt_broadcast_rows_bwd(ptr(dout), ptr(dv), N, H * W, C, Ct, out_coff, dv.stride(0),
                                       _st(dout)), "tt_broadcast_rows_bwd")
 
 
@@ -1140,8 +1098,7 @@ def upsample_nearest_add_bwd(ddst, dsrc):
     N, H, W, C = ddst.shape
     _, h, w, _ = dsrc.shape
     assert ddst.is_contiguous() and dsrc.is_contiguous()
-    check(lib().tt_upsample_nearest_add_bwd(ptr(ddst), ptr(dsrc), _c(N), _c(H), _c(W), _c(C), _c(h), _c(w), _st(ddst)),
-          "tt_upsample_nearest_add_bwd")
+    check(lib().tt_upsample_nearest_add_bwd(ptr(ddst), ptr(dsrc), N, H, W, C, h, w, _st(ddst)), "tt_upsample_nearest_add_bwd")
     return dsrc
 
 
@@ -1158,9 +1115,9 @@ def look_query_ln(qos, ref, wp, ctrl, raw_ctrl, temporal, static, meas, flat, ma
     assert flat.is_contiguous() and meas.is_contiguous() and wp.is_contiguous() and ctrl.is_contiguous()
     out = torch.empty(B * 4 * 120, row_stride, dtype=torch.float32, device=wp.device)
     arr, hw = _level_args(maps)
-    check(lib().tt_look_query_ln(_c(B), ptr(qos), ptr(ref), ptr(wp), ptr(ctrl), _c(1 if raw_ctrl else 0), ptr(temporal),
-                                 ptr(static), ptr(meas), ptr(flat), arr, hw, _c(dtype_code(maps[0])), ptr(gamma),
-                                 ptr(beta), _f(eps), ptr(out), _c(row_stride), _st(wp)), "tt_look_query_ln")
+    check(lib().tt_look_query_ln(B, ptr(qos), ptr(ref), ptr(wp), ptr(ctrl), 1 if raw_ctrl else 0, ptr(temporal),
+                                 ptr(static), ptr(meas), ptr(flat), arr, hw, dtype_code(maps[0]), ptr(gamma),
+                                 ptr(beta), eps, ptr(out), row_stride, _st(wp)), "tt_look_query_ln")
     return out
 
 
@@ -1171,8 +1128,8 @@ def msda_sample_ln(value, offsets, logits, ref, level_hw, B, coff, gamma, beta, 
     out = torch.empty(R, 256, dtype=torch.float32, device=value.device)
     out_ln = torch.empty(R, 256, dtype=torch.float32, device=value.device)
     hw = (ctypes.c_int * 8)(*[v for pair in level_hw for v in pair])
-    check(lib().tt_msda_sample_ln(_c(B), ptr(value), _c(dtype_code(value)), _c(value.shape[-1]), _c(coff), ptr(offsets),
-                                  ptr(logits), ptr(ref), hw, ptr(gamma), ptr(beta), _f(eps), ptr(out), ptr(out_ln),
+    check(lib().tt_msda_sample_ln(B, ptr(value), dtype_code(value), value.shape[-1], coff, ptr(offsets),
+                                  ptr(logits), ptr(ref), hw, ptr(gamma), ptr(beta), eps, ptr(out), ptr(out_ln),
                                   ptr(max_len), _st(value)), "tt_msda_sample_ln")
     return out, out_ln
 
@@ -1188,16 +1145,15 @@ def msda_sample_proj_ln(maps, offsets, logits, ref, B, wvT, bias, vshift, gamma,
     out = torch.empty(R, 256, dtype=torch.float32, device=dev)
     out_ln = torch.empty(R, 256, dtype=torch.float32, device=dev)
     arr, hw = _level_args(maps)
-    check(lib().tt_msda_sample_proj_ln(_c(B), arr, hw, ptr(offsets), ptr(logits), ptr(ref), ptr(wvT), ptr(bias), ptr(vshift),
-                                       ptr(gamma), ptr(beta), _f(eps), ptr(out), ptr(out_ln), ptr(max_len), _st(offsets)),
+    check(lib().tt_msda_sample_proj_ln(B, arr, hw, ptr(offsets), ptr(logits), ptr(ref), ptr(wvT), ptr(bias), ptr(vshift),
+                                       ptr(gamma), ptr(beta), eps, ptr(out), ptr(out_ln), ptr(max_len), _st(offsets)),
           "tt_msda_sample_proj_ln")
     return out, out_ln
 
 
 def sca_reduce_ln(x, max_len, B, gamma, beta, eps=1e-5):
     out = torch.empty(B, 1024, dtype=torch.float32, device=x.device)
-    check(lib().tt_sca_reduce_ln(_c(B), ptr(x), ptr(max_len), ptr(gamma), ptr(beta), _f(eps), ptr(out), _st(x)),
-          "tt_sca_reduce_ln")
+    check(lib().tt_sca_reduce_ln(B, ptr(x), ptr(max_len), ptr(gamma), ptr(beta), eps, ptr(out), _st(x)), "tt_sca_reduce_ln")
     return out
 
 
@@ -1205,7 +1161,7 @@ def dec_merge_in(fflat, look, temporal, meas, gamma, beta, eps=1e-5):
     B = look.shape[0]
     assert fflat.is_contiguous() and look.is_contiguous() and meas.is_contiguous()
     out = torch.empty(B * 4, 1024, dtype=torch.float32, device=look.device)
-    check(lib().tt_dec_merge_in(_c(B), ptr(fflat), ptr(look), ptr(temporal), ptr(meas), ptr(gamma), ptr(beta), _f(eps),
+    check(lib().tt_dec_merge_in(B, ptr(fflat), ptr(look), ptr(temporal), ptr(meas), ptr(gamma), ptr(beta), eps,
                                 ptr(out), _st(look)), "tt_dec_merge_in")
     return out
 
@@ -1215,11 +1171,9 @@ def dec_gru(wts, inp6, state, fut):
     B = state.shape[0]
     assert inp6.is_contiguous() and state.is_contiguous() and fut.is_contiguous()
     L = lib()
-    L.tt_dec_gru_scratch_floats.restype = ctypes.c_longlong
-    scratch = torch.empty(L.tt_dec_gru_scratch_floats(_c(B)), dtype=torch.float32, device=state.device)
-    check(L.tt_dec_gru(_c(B), ptr(inp6), ptr(state), ptr(fut), ptr(scratch), wts["w0"], wts["wx"], wts["b0"],
-                       wts["w2"], wts["b2"], ptr(wts["wd0"]), ptr(wts["bd0"]), ptr(wts["wd2"]), ptr(wts["bd2"]),
-                       _st(state)), "tt_dec_gru")
+    scratch = torch.empty(L.tt_dec_gru_scratch_floats(B), dtype=torch.float32, device=state.device)
+    check(L.tt_dec_gru(B, ptr(inp6), ptr(state), ptr(fut), ptr(scratch), wts["w0"], wts["wx"], wts["b0"], wts["w2"], wts["b2"],
+                       ptr(wts["wd0"]), ptr(wts["bd0"]), ptr(wts["wd2"]), ptr(wts["bd2"]), _st(state)), "tt_dec_gru")
     return fut
 
 
@@ -1230,9 +1184,8 @@ def dec_flatten(wts, maps, want_mids=False):
     out = torch.empty(N, 256, dtype=torch.float32, device=maps.device)
     mids = torch.empty(N, 100 * 64 + 16 * 128 + 4 * 256, dtype=torch.float32, device=maps.device) if want_mids else None
     L = lib()
-    L.tt_dec_flatten_scratch_floats.restype = ctypes.c_longlong
-    scratch = torch.empty(L.tt_dec_flatten_scratch_floats(_c(N)), dtype=torch.float32, device=maps.device)
-    check(L.tt_dec_flatten(_c(N), ptr(maps), ptr(out), ptr(mids), ptr(scratch), wts["w"], wts["b"], ptr(wts["bn_scale"]),
+    scratch = torch.empty(L.tt_dec_flatten_scratch_floats(N), dtype=torch.float32, device=maps.device)
+    check(L.tt_dec_flatten(N, ptr(maps), ptr(out), ptr(mids), ptr(scratch), wts["w"], wts["b"], ptr(wts["bn_scale"]),
                                ptr(wts["bn_shift"]), _st(maps)), "tt_dec_flatten")
     return (out, mids) if want_mids else out
 
@@ -1242,8 +1195,7 @@ def dec_bev_update(wts, bev, G, out):
     B = bev.shape[0]
     assert bev.is_contiguous() and G.is_contiguous() and out.is_contiguous()
     L = lib()
-    L.tt_dec_bev_update_scratch_floats.restype = ctypes.c_longlong
-    scratch = torch.empty(L.tt_dec_bev_update_scratch_floats(_c(B)), dtype=torch.float32, device=bev.device)
-    check(L.tt_dec_bev_update(_c(B), ptr(bev), ptr(G), ptr(out), _ll(441 * 32), None, _ll(0), ptr(scratch), ptr(wts["w0"]),
+    scratch = torch.empty(L.tt_dec_bev_update_scratch_floats(B), dtype=torch.float32, device=bev.device)
+    check(L.tt_dec_bev_update(B, ptr(bev), ptr(G), ptr(out), 441 * 32, None, 0, ptr(scratch), ptr(wts["w0"]),
                               ptr(wts["b0"]), wts["w2"], ptr(wts["b2"]), _st(bev)), "tt_dec_bev_update")
     return out

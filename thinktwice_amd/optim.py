@@ -1,12 +1,8 @@
 """AdamW + global-norm gradient clipping over the flat buffers of `grad_sync.FlatGradBuffer` (the reference's
 `optimizer` / `optimizer_config`, configs/thinktwice.py:282-287), two HIP launches per step, no host sync."""
-import ctypes
-
 import torch
 
 from ._lib import check, cur_stream, lib, ptr, require_cuda
-
-_f = ctypes.c_float
 
 
 class FlatAdamW:
@@ -54,21 +50,19 @@ class FlatAdamW:
         """One optimizer step; returns the (device) tensor [grad norm, clip factor] of this step.  `live_ranges`: [(offset,
         count)] element ranges to update -- torch's AdamW skips parameters whose .grad is None (the reference's 90 dead
         ones: no weight decay, no moment update); the ranges of the others, merged, are what this step touches."""
-        n = ctypes.c_longlong(self.p.numel())
         st = cur_stream(self.p.device)
         scale = None
         if self.max_norm is not None:
-            check(lib().tt_grad_norm_clip(ptr(self.g), n, _f(self.max_norm), ptr(self._ws), ptr(self.norm_scale), st),
+            check(lib().tt_grad_norm_clip(ptr(self.g), self.p.numel(), self.max_norm, ptr(self._ws), ptr(self.norm_scale), st),
                   "tt_grad_norm_clip")
-            scale = ctypes.c_void_p(self.norm_scale.data_ptr() + 4)
+            scale = self.norm_scale.data_ptr() + 4
         self.issued += 1
-        sc = scale if scale is not None else ctypes.c_void_p(0)
         for off, cnt in (live_ranges if live_ranges is not None else [(0, self.p.numel())]):
-            at = lambda t: ctypes.c_void_p(t.data_ptr() + 4 * off)
-            check(lib().tt_adamw_step_dev(at(self.p), at(self.g), at(self.m), at(self.v), ctypes.c_longlong(cnt),
-                                          _f(self.lr if lr is None else lr), _f(self.betas[0]), _f(self.betas[1]),
-                                          _f(self.eps), _f(self.wd), ptr(self.steps_dev), sc, st), "tt_adamw_step_dev")
-        check(lib().tt_adamw_advance(ptr(self.steps_dev), sc, st), "tt_adamw_advance")
+            at = lambda t: t.data_ptr() + 4 * off
+            check(lib().tt_adamw_step_dev(at(self.p), at(self.g), at(self.m), at(self.v), cnt,
+                                          self.lr if lr is None else lr, self.betas[0], self.betas[1],
+                                          self.eps, self.wd, ptr(self.steps_dev), scale, st), "tt_adamw_step_dev")
+        check(lib().tt_adamw_advance(ptr(self.steps_dev), scale, st), "tt_adamw_advance")
         return self.norm_scale
 
 

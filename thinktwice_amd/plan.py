@@ -17,6 +17,7 @@ The result (`ForwardPlan`) binds any set of base addresses and runs with no Pyth
 call per half (`tt_encoder_fwd`, `tt_decoder_fwd`); `plan.save(dir)` writes plan + weights for a non-Python host
 (tools/plan_host.cpp)."""
 import ctypes
+import numbers
 import os
 import sys
 
@@ -41,19 +42,40 @@ _VIEW_OK = {
 }
 
 
+_BYREF = type(ctypes.byref(ctypes.c_int()))
+_INTEGERS = (ctypes.c_int, ctypes.c_uint, ctypes.c_longlong, ctypes.c_ulonglong)
+
+
+def arg_kind(argtype, a):
+    """How a plan stores `a` passed for a parameter of the header's ctypes type `argtype` (the tt_plan_add_call kinds):
+    (0, int) integer, (1, float) float / double -- both the value the parameter receives (a `float` is rounded to f32) --,
+    (2, address) device pointer, (3, ctypes object) host blob (an array, a struct or byref() of one), (4, None) NULL; None
+    when `a` cannot be that parameter."""
+    if argtype in _INTEGERS:
+        if isinstance(a, numbers.Integral):
+            return 0, argtype(a).value
+    elif argtype in (ctypes.c_float, ctypes.c_double):
+        if isinstance(a, numbers.Real):
+            return 1, argtype(a).value
+    elif argtype is ctypes.c_void_p:
+        if isinstance(a, ctypes.c_void_p):
+            a = a.value
+        if a is None or (isinstance(a, int) and a == 0):
+            return 4, None
+        if isinstance(a, int):
+            return 2, a
+        if isinstance(a, (ctypes.Array, ctypes.Structure)):
+            return 3, a
+        if isinstance(a, _BYREF):
+            return 3, a._obj
+    return None
+
+
 class _Fn:
     """Recording wrapper of one C entry."""
 
     def __init__(self, builder, real, name):
-        object.__setattr__(self, "_b", builder)
-        object.__setattr__(self, "_real", real)
-        object.__setattr__(self, "_name", name)
-
-    def __setattr__(self, k, v):                     # .restype / .argtypes go to the real function
-        setattr(self._real, k, v)
-
-    def __getattr__(self, k):
-        return getattr(self._real, k)
+        self._b, self._real, self._name = builder, real, name
 
     def __call__(self, *args):
         self._b.record_call(self._name, args)
@@ -66,7 +88,7 @@ class _LibProxy:
 
     def __getattr__(self, name):
         real = getattr(self._real, name)
-        if name.startswith("tt_") and name in self._b.recordable:
+        if name in self._b.recordable:
             return _Fn(self._b, real, name)
         return real
 
@@ -147,9 +169,9 @@ class PlanBuilder:
     def __init__(self, device, arena_bytes):
         self.device = torch.device(device)
         self.L = _lib.lib()
-        self._declare()
-        self.recordable = set(self._thunk_names())
-        self.plan = ctypes.c_void_p(self.L.tt_plan_create())
+        # entry -> argtypes of every call the plan runtime can replay (the header's stream-taking entries: csrc/plan_thunks.inc)
+        self.recordable = {n: p.argtypes for n, p in _lib.prototypes().items() if _lib.takes_stream(n, p.params)}
+        self.plan = self.L.tt_plan_create()
         self.arena = torch.empty(arena_bytes, dtype=torch.uint8, device=self.device)
         self.arena_top = 0
         self.regions = []            # (start, end, buffer id, offset of `start` inside the buffer)
@@ -160,21 +182,6 @@ class PlanBuilder:
         self.calls = 0
         self.marks = {}
         self.compacted_bytes = None
-
-    # ---------------------------------------------------------------- ctypes signatures of the plan API
-    def _declare(self):
-        L = self.L
-        L.tt_plan_create.restype = ctypes.c_void_p
-        L.tt_plan_load.restype = ctypes.c_void_p
-        L.tt_plan_add_blob.restype = ctypes.c_longlong
-        L.tt_plan_compact_arena.restype = ctypes.c_longlong
-        L.tt_plan_buffer_bytes.restype = ctypes.c_longlong
-        L.tt_plan_buffer_name.restype = ctypes.c_char_p
-
-    def _thunk_names(self):
-        inc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "plan_thunks.inc")
-        import re
-        return re.findall(r'\{"(tt_\w+)", thunk_', open(inc).read())
 
     # ---------------------------------------------------------------- regions
     def add_persistent(self, tensors):
@@ -221,8 +228,7 @@ class PlanBuilder:
             raise PlanBuildError(f"activation arena exhausted ({self.arena.numel()} bytes): pass a larger arena_bytes")
         self.arena_top = off + nbytes
         if nbytes:      # declared to the plan: tt_plan_compact_arena re-places the allocations by liveness after the recording
-            _lib.check(self.L.tt_plan_add_arena_alloc(self.plan, ctypes.c_longlong(off), ctypes.c_longlong(nbytes)),
-                       "tt_plan_add_arena_alloc")
+            _lib.check(self.L.tt_plan_add_arena_alloc(self.plan, off, nbytes), "tt_plan_add_arena_alloc")
         t = self.arena[off:off + nbytes].view(dtype).view(*shape) if nbytes else torch.empty(shape, dtype=dtype, device=self.device)
         if zero:
             self.emit_fill(t, 0)
@@ -267,15 +273,12 @@ class PlanBuilder:
         if nbytes % 4:
             raise PlanBuildError(self.where("fill of a buffer whose size is not a multiple of 4 bytes"))
         if nbytes:
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(_lib.lib().tt_fill_u32(ctypes.c_void_p(t.data_ptr()), ctypes.c_longlong(nbytes // 4), ctypes.c_uint(pat), st),
-                       "tt_fill_u32")
+            _lib.check(_lib.lib().tt_fill_u32(t.data_ptr(), nbytes // 4, pat, _lib.cur_stream(self.device)), "tt_fill_u32")
 
     def emit_copy(self, dst, src):
         nbytes = dst.numel() * dst.element_size()
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(_lib.lib().tt_copy_bytes(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), ctypes.c_longlong(nbytes),
-                                            st), "tt_copy_bytes")
+        _lib.check(_lib.lib().tt_copy_bytes(dst.data_ptr(), src.data_ptr(), nbytes, _lib.cur_stream(self.device)),
+                   "tt_copy_bytes")
 
     def record_sync(self, waiter_handle, signal_handle):
         _lib.check(self.L.tt_plan_add_sync(self.plan, self._stream_slot(waiter_handle), self._stream_slot(signal_handle)),
@@ -292,13 +295,12 @@ class PlanBuilder:
         return f"plan compiler: {msg} [{loc}]"
 
     def _blob(self, raw, relocs):
-        off = int(self.L.tt_plan_add_blob(self.plan, raw, ctypes.c_longlong(len(raw))))
+        off = int(self.L.tt_plan_add_blob(self.plan, raw, len(raw)))
         if off < 0:
             raise PlanBuildError("tt_plan_add_blob failed")
         for rel_off, addr in relocs:
             bid, boff = self.classify(addr, "pointer inside a host argument")
-            _lib.check(self.L.tt_plan_add_reloc(self.plan, ctypes.c_longlong(off + rel_off), ctypes.c_int(bid),
-                                                ctypes.c_longlong(boff)), "tt_plan_add_reloc")
+            _lib.check(self.L.tt_plan_add_reloc(self.plan, off + rel_off, bid, boff), "tt_plan_add_reloc")
         return off
 
     def _struct_relocs(self, obj, base=0):
@@ -327,39 +329,29 @@ class PlanBuilder:
         return out
 
     def record_call(self, name, args):
-        if not args:
-            return
-        stream = args[-1]
-        handle = stream.value if isinstance(stream, ctypes.c_void_p) else stream
-        slot = self._stream_slot(handle or 0)
+        argtypes = self.recordable[name]
+        if len(args) != len(argtypes):
+            raise PlanBuildError(self.where(f"{name}: {len(args)} arguments, the header declares {len(argtypes)}"))
+        stream = args[-1].value if isinstance(args[-1], ctypes.c_void_p) else args[-1]
+        slot = self._stream_slot(stream or 0)
         n = len(args) - 1
         kinds, bufs = (ctypes.c_int * max(n, 1))(), (ctypes.c_int * max(n, 1))()
         ivals, fvals = (ctypes.c_longlong * max(n, 1))(), (ctypes.c_double * max(n, 1))()
-        for i, a in enumerate(args[:-1]):
-            if isinstance(a, ctypes.c_void_p) or a is None:
-                v = None if a is None else a.value
-                if not v:
-                    kinds[i] = 4
-                else:
-                    kinds[i] = 2
-                    bufs[i], ivals[i] = self.classify(v, f"{name} argument {i}")
-            elif isinstance(a, (ctypes.c_float, ctypes.c_double)):
-                kinds[i], fvals[i] = 1, float(a.value)
-            elif isinstance(a, float):
-                kinds[i], fvals[i] = 1, a
-            elif isinstance(a, (ctypes.c_int, ctypes.c_longlong, ctypes.c_uint, ctypes.c_ulonglong, ctypes.c_long, ctypes.c_ulong)):
-                kinds[i], ivals[i] = 0, int(a.value) if a.value < (1 << 63) else int(a.value) - (1 << 64)
-            elif isinstance(a, bool) or isinstance(a, int):
-                kinds[i], ivals[i] = 0, int(a)
-            elif isinstance(a, (ctypes.Array, ctypes.Structure)):
-                kinds[i], ivals[i] = 3, self._blob(bytes(a), self._struct_relocs(a))
-            elif hasattr(a, "_obj"):                                # ctypes.byref(x)
-                kinds[i], ivals[i] = 3, self._blob(bytes(a._obj), self._struct_relocs(a._obj))
-            elif isinstance(a, ctypes._Pointer):
-                raise PlanBuildError(self.where(f"{name} argument {i}: typed ctypes pointer (pass the array / byref)"))
-            else:
-                raise PlanBuildError(self.where(f"{name} argument {i}: unsupported argument {type(a)}"))
-        _lib.check(self.L.tt_plan_add_call(self.plan, name.encode(), ctypes.c_int(n), kinds, bufs, ivals, fvals, ctypes.c_int(slot)),
+        for i, (t, a) in enumerate(zip(argtypes[:-1], args)):
+            k = arg_kind(t, a)
+            if k is None:
+                raise PlanBuildError(self.where(f"{name} argument {i}: {type(a).__name__} for a {t.__name__} parameter"))
+            kind, v = k
+            kinds[i] = kind
+            if kind == 0:
+                ivals[i] = v
+            elif kind == 1:
+                fvals[i] = v
+            elif kind == 2:
+                bufs[i], ivals[i] = self.classify(v, f"{name} argument {i}")
+            elif kind == 3:
+                ivals[i] = self._blob(bytes(v), self._struct_relocs(v))
+        _lib.check(self.L.tt_plan_add_call(self.plan, name.encode(), n, kinds, bufs, ivals, fvals, slot),
                    f"tt_plan_add_call({name})")
         self.calls += 1
 
@@ -445,7 +437,7 @@ class ForwardPlan:
 
     def bind(self):
         arr, nb = self.bases()
-        _lib.check(self.L.tt_plan_bind(self.plan, arr, ctypes.c_int(nb)), "tt_plan_bind")
+        _lib.check(self.L.tt_plan_bind(self.plan, arr, nb), "tt_plan_bind")
 
     def _stream_array(self, main=None):
         main = main or torch.cuda.current_stream(self.device)
@@ -456,10 +448,10 @@ class ForwardPlan:
         """Issue the forward from C on the current stream (+ the plan's side streams): two ctypes calls, or one."""
         arr, n = self._stream_array()
         if halves:
-            _lib.check(self.L.tt_encoder_fwd(self.plan, arr, ctypes.c_int(n)), "tt_encoder_fwd")
-            _lib.check(self.L.tt_decoder_fwd(self.plan, arr, ctypes.c_int(n)), "tt_decoder_fwd")
+            _lib.check(self.L.tt_encoder_fwd(self.plan, arr, n), "tt_encoder_fwd")
+            _lib.check(self.L.tt_decoder_fwd(self.plan, arr, n), "tt_decoder_fwd")
         else:
-            _lib.check(self.L.tt_plan_run(self.plan, arr, ctypes.c_int(n)), "tt_plan_run")
+            _lib.check(self.L.tt_plan_run(self.plan, arr, n), "tt_plan_run")
         return self.outputs
 
     def update(self, batch):
@@ -526,28 +518,24 @@ def compile_forward(model, batch, arena_bytes=None, channel_last_out=False, prev
         model._plan_builder = None
     torch.cuda.synchronize(dev)
     L = b.L
-    _lib.check(L.tt_plan_set_buffer(b.plan, 0, ctypes.c_longlong(max(b.weights_bytes, ALIGN)), b"weights"), "tt_plan_set_buffer")
-    _lib.check(L.tt_plan_set_buffer(b.plan, 1, ctypes.c_longlong((b.arena_top + ALIGN - 1) // ALIGN * ALIGN), b"arena"),
-               "tt_plan_set_buffer")
+    _lib.check(L.tt_plan_set_buffer(b.plan, 0, max(b.weights_bytes, ALIGN), b"weights"), "tt_plan_set_buffer")
+    _lib.check(L.tt_plan_set_buffer(b.plan, 1, (b.arena_top + ALIGN - 1) // ALIGN * ALIGN, b"arena"), "tt_plan_set_buffer")
     for i, (name, t) in enumerate(b.inputs):
-        _lib.check(L.tt_plan_set_buffer(b.plan, 2 + i, ctypes.c_longlong(t.untyped_storage().nbytes()), name.encode()),
-                   "tt_plan_set_buffer")
+        _lib.check(L.tt_plan_set_buffer(b.plan, 2 + i, t.untyped_storage().nbytes(), name.encode()), "tt_plan_set_buffer")
     outputs = {}
     for k, v in out.items():
         if torch.is_tensor(v) and v.is_cuda and not k.startswith("_") and v.dim() <= 8:
             bid, off = b.classify(v.data_ptr(), f"output {k}")
             shape = (ctypes.c_longlong * 8)(*list(v.shape))
             stride = (ctypes.c_longlong * 8)(*list(v.stride()))
-            _lib.check(L.tt_plan_add_output(b.plan, k.encode(), ctypes.c_int(bid), ctypes.c_longlong(off), ctypes.c_int(v.dim()),
-                                            shape, stride), "tt_plan_add_output")
+            _lib.check(L.tt_plan_add_output(b.plan, k.encode(), bid, off, v.dim(), shape, stride), "tt_plan_add_output")
             outputs[k] = v
     first = b.marks.get("decoder", int(L.tt_plan_num_ops(b.plan)))
-    _lib.check(L.tt_plan_add_output(b.plan, b"__decoder_first_op", ctypes.c_int(-1), ctypes.c_longlong(first), ctypes.c_int(0),
-                                    None, None), "tt_plan_add_output")
+    _lib.check(L.tt_plan_add_output(b.plan, b"__decoder_first_op", -1, first, 0, None, None), "tt_plan_add_output")
     # liveness-based re-placement of the arena (TT_PLAN_COMPACT=0: keep the bump layout, A/B knob)
     b.compacted_bytes = None
     if os.environ.get("TT_PLAN_COMPACT", "1") != "0":
-        nb = int(L.tt_plan_compact_arena(b.plan, ctypes.c_int(PlanBuilder.ARENA), ctypes.c_longlong(ALIGN)))
+        nb = int(L.tt_plan_compact_arena(b.plan, PlanBuilder.ARENA, ALIGN))
         if nb > 0:
             b.compacted_bytes = nb
         else:

@@ -6,7 +6,7 @@ import ctypes
 import torch
 
 from . import _lib, calib, ops
-from .ops import _c, check, lib, ptr
+from .ops import check, lib, ptr
 
 
 class ImagePreprocessor:
@@ -48,10 +48,9 @@ class ImagePreprocessor:
             cp = c_pad or (4 if channel_last_dtype == torch.float32 else 8)
             nhwc = torch.empty(NI, fh, fw, cp, dtype=channel_last_dtype, device=raw.device)
             code = ops.dtype_code(nhwc)
-        check(lib().tt_preprocess_images(ptr(raw), _c(NI), _c(H), _c(W), ptr(self.mapx), ptr(self.mapy),
-                                         _c(self.resized[0]), _c(self.resized[1]), _c(self.crop[0]), _c(self.crop[1]),
-                                         _c(fh), _c(fw), self.mean, self.std, ptr(nhwc), _c(cp), _c(code), ptr(nchw),
-                                         ops.cur_stream(raw.device)), "tt_preprocess_images")
+        check(lib().tt_preprocess_images(ptr(raw), NI, H, W, ptr(self.mapx), ptr(self.mapy), self.resized[0], self.resized[1],
+                                         self.crop[0], self.crop[1], fh, fw, self.mean, self.std, ptr(nhwc), cp, code,
+                                         ptr(nchw), ops.cur_stream(raw.device)), "tt_preprocess_images")
         if nchw is not None:
             return nchw.view(*lead, 3, fh, fw)
         return nhwc

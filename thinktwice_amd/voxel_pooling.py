@@ -10,8 +10,6 @@ required).  Differences that do not change results:
   * `voxel_num` entries are read once on the host (the reference converts three
     0-dim tensors through pybind on every call: voxel_pooling.py:45-47).
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 
@@ -22,13 +20,11 @@ def _pool_launch(B, Np, C, vx, vy, vz, geom_xyz, input_features, out, pos_memo):
     """tt_voxel_pool_fwd_ws with a torch-allocated workspace (atomics-free two-phase kernel); the
     library itself falls back to the single-pass atomic kernel for shapes the fast path does not cover."""
     L = _lib.lib()
-    ws_bytes = int(L.tt_voxel_pool_workspace_bytes(ctypes.c_int(B), ctypes.c_int(Np), ctypes.c_int(C),
-                                                   ctypes.c_int(vx), ctypes.c_int(vy)))
+    ws_bytes = int(L.tt_voxel_pool_workspace_bytes(B, Np, C, vx, vy))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input_features.device) if ws_bytes > 0 else None
     rc = L.tt_voxel_pool_fwd_ws(
-        ctypes.c_int(B), ctypes.c_int(Np), ctypes.c_int(C), ctypes.c_int(vx), ctypes.c_int(vy), ctypes.c_int(vz),
-        _lib.ptr(geom_xyz), _lib.ptr(input_features), _lib.ptr(out), _lib.ptr(pos_memo), _lib.ptr(ws),
-        ctypes.c_longlong(ws_bytes), _lib.cur_stream(input_features.device))
+        B, Np, C, vx, vy, vz, _lib.ptr(geom_xyz), _lib.ptr(input_features), _lib.ptr(out), _lib.ptr(pos_memo), _lib.ptr(ws),
+        ws_bytes, _lib.cur_stream(input_features.device))
     _lib.check(rc, "tt_voxel_pool_fwd_ws")
 
 
@@ -75,8 +71,7 @@ class VoxelPooling(Function):
         g = grad_output_features.permute(0, 2, 3, 1).contiguous()  # [B,Y,X,C]
         grad_in = g.new_empty(B, Np, C)
         rc = _lib.lib().tt_voxel_pool_bwd(
-            ctypes.c_int(B), ctypes.c_int(Np), ctypes.c_int(C), ctypes.c_int(vx), ctypes.c_int(vy),
-            _lib.ptr(pos_memo), _lib.ptr(g), _lib.ptr(grad_in), _lib.cur_stream(g.device))
+            B, Np, C, vx, vy, _lib.ptr(pos_memo), _lib.ptr(g), _lib.ptr(grad_in), _lib.cur_stream(g.device))
         _lib.check(rc, "tt_voxel_pool_bwd")
         return None, grad_in.reshape(ctx.in_shape), None
 
@@ -110,17 +105,13 @@ class VoxelPoolPlan:
         g = geom_xyz.reshape(geom_xyz.shape[0], -1, 3)
         self.B, self.Np = g.shape[0], g.shape[1]
         self.vx, self.vy, self.vz = _voxel_num_tuple(voxel_num)
-        L, ci = _lib.lib(), ctypes.c_int
-        L.tt_voxel_pool_plan_bytes.restype = ctypes.c_longlong
-        L.tt_voxel_pool_plan_workspace_bytes.restype = ctypes.c_longlong
-        L.tt_voxel_pool_planned_workspace_bytes.restype = ctypes.c_longlong
-        pb = int(L.tt_voxel_pool_plan_bytes(ci(self.B), ci(self.Np), ci(self.vx), ci(self.vy)))
-        wb = int(L.tt_voxel_pool_plan_workspace_bytes(ci(self.B), ci(self.Np)))
+        L = _lib.lib()
+        pb = int(L.tt_voxel_pool_plan_bytes(self.B, self.Np, self.vx, self.vy))
+        wb = int(L.tt_voxel_pool_plan_workspace_bytes(self.B, self.Np))
         self.plan = torch.empty(pb, dtype=torch.uint8, device=g.device)
         ws = torch.empty(wb, dtype=torch.uint8, device=g.device)
-        _lib.check(L.tt_voxel_pool_plan_build(ci(self.B), ci(self.Np), ci(self.vx), ci(self.vy), ci(self.vz), _lib.ptr(g),
-                                              _lib.ptr(ws), ctypes.c_longlong(wb), _lib.ptr(self.plan),
-                                              ctypes.c_longlong(pb), _lib.cur_stream(g.device)), "tt_voxel_pool_plan_build")
+        _lib.check(L.tt_voxel_pool_plan_build(self.B, self.Np, self.vx, self.vy, self.vz, _lib.ptr(g), _lib.ptr(ws), wb,
+                                              _lib.ptr(self.plan), pb, _lib.cur_stream(g.device)), "tt_voxel_pool_plan_build")
         self._ws = None
 
     def forward_into(self, input_features, out):
@@ -129,12 +120,12 @@ class VoxelPoolPlan:
         f = input_features.reshape(self.B, self.Np, -1)
         assert f.is_contiguous() and f.dtype == torch.float32 and out.is_contiguous()
         C = f.shape[-1]
-        L, ci = _lib.lib(), ctypes.c_int
-        wb = int(L.tt_voxel_pool_planned_workspace_bytes(ci(self.B), ci(self.Np), ci(C), ci(self.vx), ci(self.vy)))
+        L = _lib.lib()
+        wb = int(L.tt_voxel_pool_planned_workspace_bytes(self.B, self.Np, C, self.vx, self.vy))
         if self._ws is None or self._ws.numel() < wb:
             self._ws = torch.empty(wb, dtype=torch.uint8, device=f.device)
-        _lib.check(L.tt_voxel_pool_fwd_planned(ci(self.B), ci(self.Np), ci(C), ci(self.vx), ci(self.vy), _lib.ptr(self.plan),
-                                               _lib.ptr(f), _lib.ptr(out), _lib.ptr(self._ws), ctypes.c_longlong(wb),
+        _lib.check(L.tt_voxel_pool_fwd_planned(self.B, self.Np, C, self.vx, self.vy, _lib.ptr(self.plan),
+                                               _lib.ptr(f), _lib.ptr(out), _lib.ptr(self._ws), wb,
                                                _lib.cur_stream(f.device)), "tt_voxel_pool_fwd_planned")
         return out
 
