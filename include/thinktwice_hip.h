@@ -496,6 +496,25 @@ int tt_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* ex
                       const float* grad_scale_or_null, void* stream);
 int tt_adamw_advance(int* good_steps_dev, const float* grad_scale_or_null, void* stream);
 
+/* ------------------------------------------------------------------------
+ * SURVEY 8f-4, the torch-autograd route of the training step (thinktwice_amd/autograd_route.py): what mmcv's OptimizerHook gets
+ * from `outputs['loss'].backward()` depositing into every parameter's `.grad` (apis/mmdet_train.py:70-97) -- here the reverse
+ * sweep leaves one separately allocated f32 tensor per parameter, and ONE launch gathers `nseg` of them into one flat f32 buffer
+ * (per-parameter views of which go back to autograd), scaled by the device scalar grad_output:
+ *     flat[dst_off[i] .. + count[i])  (=|+=)  scale * src[i][0 .. count[i])
+ * The work is cut by bytes (16 KiB pieces of the covered range, the segment(s) under a piece found by binary search), 16-byte
+ * loads and stores where source and destination are co-aligned.  `scale * src` and the sum are rounded separately.  Elements
+ * of `flat` no segment covers are not written.  nseg == 0: returns 0, launches nothing.
+ * ---------------------------------------------------------------------- */
+typedef struct tt_grad_seg {
+    const void* src;        /* device f32 array of `count` elements, 4-byte aligned (may be a view inside a larger allocation) */
+    long long dst_off;      /* first element of `flat` it lands on, >= 0; the table is sorted by it and the ranges do not overlap */
+    long long count;        /* elements, >= 0 */
+} tt_grad_seg;
+/* segs_dev: the table in DEVICE memory (8-byte aligned); scale_dev_or_null: device scalar (null = 1.0); accumulate: 0 "=", 1 "+=" */
+int tt_grad_gather(const tt_grad_seg* segs_dev, int nseg, float* flat, const float* scale_dev_or_null, int accumulate,
+                   void* stream);
+
 /* ----------------------------------------------------------------------
  * SURVEY 8f-4 / row A24, loss half of the training forward: device reductions for every term of
  * ThinkTwiceDecoder.loss (thinktwice_decoder.py:536-619), the focal segmentation loss (utils.py:31-47 at

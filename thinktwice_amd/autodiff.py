@@ -222,10 +222,14 @@ class _Keep(list):
 class Tape:
     EAGER_RELEASE = os.environ.get("TT_TAPE_EAGER_RELEASE", "1") != "0"     # A/B knob (memory only; same arithmetic)
 
-    def __init__(self, x3=True, release=False):
+    def __init__(self, x3=True, release=False, param_tensors=None):
         """`release`: let backward() drop every activation and its gradient buffer as soon as the node that first referenced
         the storage has run (the training step; only parameter gradients survive the sweep).  Off by default: the sub-network
-        tests read the gradients of graph inputs after backward()."""
+        tests read the gradients of graph inputs after backward().  `param_tensors`: the (tensor, name) pairs of PARAM_TENSORS
+        this tape's forward reads, taken when it is recorded (`PARAM_TENSORS.items(owner)`): a tape whose backward() runs later
+        (the torch autograd route) then survives a re-preparation of the operands in between.  Default: the table as it
+        stands when backward() runs."""
+        self.param_tensors = param_tensors
         self.release = release and self.EAGER_RELEASE
         self.nodes = []
         self.grads = {}             # storage data_ptr -> flat f32 gradient buffer covering the whole storage
@@ -279,7 +283,8 @@ class Tape:
         active, TAPE = TAPE, None          # the backward closures call forward ops too: nothing of that is recorded
         # storages to release after node i: those whose first reference is node i -- except parameter storages, whose gradient
         # buffers are collected below
-        param_keys = {t.untyped_storage().data_ptr() for t, _ in PARAM_TENSORS.items()}
+        param_tensors = PARAM_TENSORS.items() if self.param_tensors is None else self.param_tensors
+        param_keys = {t.untyped_storage().data_ptr() for t, _ in param_tensors}
         release, held = {}, {}
         if self.release:
             for key, idx in self._keep.first.items():
@@ -301,7 +306,7 @@ class Tape:
             TAPE = active
             self._held = None
             held.clear()
-        for t, name in PARAM_TENSORS.items():
+        for t, name in param_tensors:
             if t.is_cuda and t.untyped_storage().data_ptr() in self.grads:
                 self.add_param_grad(name, self.grad(t).clone())
         self.nodes.clear()

@@ -34,22 +34,24 @@ def make_frustum(final_dim, downsample_factor, d_bound):
 
 def stack_img_metas(img_metas, num_cams=4):
     """list[B][T] of dicts -> dict of (B,T,ncam,4,4) tensors (+ lidar2img / ida of the key frame).
-    sensor2ego is the transpose of `currlidar2keycam`, exactly as the reference builds it."""
+    sensor2ego is the transpose of `currlidar2keycam`, exactly as the reference builds it.  Host arithmetic: matrices that
+    arrive on a GPU (torch's DistributedDataParallel moves every tensor of its inputs there; mmcv keeps img_metas in cpu_only
+    DataContainers) are brought back."""
     K, A, S = [], [], []
     for sample in img_metas:
         k_t, a_t, s_t = [], [], []
         for m in sample:
             k = torch.zeros(num_cams, 4, 4)
-            k[:, :3, :3] = torch.as_tensor(m["cam_intrinsic"], dtype=torch.float32)
+            k[:, :3, :3] = torch.as_tensor(m["cam_intrinsic"], dtype=torch.float32, device="cpu")
             k[:, 3, 3] = 1.0
             k_t.append(k)
-            a_t.append(torch.as_tensor(m["ida_mats"], dtype=torch.float32))
-            s_t.append(torch.as_tensor(m["currlidar2keycam"], dtype=torch.float32).transpose(1, 2))
+            a_t.append(torch.as_tensor(m["ida_mats"], dtype=torch.float32, device="cpu"))
+            s_t.append(torch.as_tensor(m["currlidar2keycam"], dtype=torch.float32, device="cpu").transpose(1, 2))
         K.append(torch.stack(k_t))
         A.append(torch.stack(a_t))
         S.append(torch.stack(s_t))
     out = {"intrin_mats": torch.stack(K), "ida_mats": torch.stack(A), "sensor2ego_mats": torch.stack(S)}
-    out["lidar2img"] = torch.stack([torch.as_tensor(s[-1]["lidar2img"], dtype=torch.float32)
+    out["lidar2img"] = torch.stack([torch.as_tensor(s[-1]["lidar2img"], dtype=torch.float32, device="cpu")
                                     for s in img_metas])
     out["ida_mat"] = out["ida_mats"][:, -1].clone()
     return out

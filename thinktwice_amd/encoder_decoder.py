@@ -6,7 +6,7 @@ package's registry.  Every tensor op runs on the gfx950 kernels behind include/t
 """
 import torch
 
-from . import _lib, autodiff, control, ops
+from . import _lib, autodiff, control, masters, ops
 from .fusion import BEVFusion
 from .layers import linear_from_sd, rows, unrows
 from .registry import DETECTORS, build_backbone, build_head
@@ -20,13 +20,31 @@ class EncoderDecoder(torch.nn.Module):
     plain-Python sub-objects), but it has the Module surface the reference's callers rely on -- `eval()`, `to()`,
     `state_dict()`, and `_load_from_state_dict`, the hook through which mmcv's `load_checkpoint(model, path)` /
     `load_state_dict(module, state_dict)` (mmcv/runner/checkpoint.py, used at thinktwice_agent.py:170-171 and
-    train.py:238) hand a checkpoint to a module tree."""
+    train.py:238) hand a checkpoint to a module tree.
+
+    `trainable=True` (opt-in; dtype torch.float32 or "f32x3") makes it the module the reference's TRAINING lines expect
+    (thinktwice_amd/autograd_route.py): after load_state_dict / init_weights the master weights are nn.Parameters -- f32 views of
+    one flat device buffer, in the reference's `model.parameters()` order -- and the BatchNorm statistics, call counters and LSS
+    constants are registered buffers, all under the reference's names; `state_dict()` returns them live; with autograd enabled
+    `train_step(...)["loss"]` back-propagates through the HIP backward kernels (`loss.backward()` leaves `.grad` on the
+    parameters, None on those the loss does not reach); a write to the parameters (optimizer.step(), load_state_dict, an
+    in-place op under no_grad, DDP's initial broadcast) is noticed through the flat buffer's version counter and the kernels'
+    operands are re-prepared before the next forward.  A write through `p.data` bypasses that counter: call
+    `parameters_changed()` after one.  `.to(other_gpu)` rebuilds the model there: the parameters are NEW objects afterwards
+    (build optimizers after placing the model, as the reference does)."""
 
     def __init__(self, img_encoder, decoder, lidar_encoder=None, num_cams=4, use_depth=False, use_seg=False,
                  downsample_factor=16, seg_downsample_factor=2, train_cfg=None, test_cfg=None,
-                 dtype=torch.float32, device="cuda", cfg=None, lidar_dtype=None):
+                 dtype=torch.float32, device="cuda", cfg=None, lidar_dtype=None, trainable=False):
         super().__init__()
         self._ref_sd = None
+        self.trainable = bool(trainable)
+        self._masters = None                     # autograd_route.MasterState once a trainable model holds weights
+        if self.trainable:
+            for what, d in (("dtype", dtype), ("lidar_dtype", lidar_dtype)):
+                if not (d is torch.float32 or (isinstance(d, str) and d == "f32x3") or (what == "lidar_dtype" and d is None)):
+                    raise _lib.TTError(f"EncoderDecoder(trainable=True, {what}={d!r}): training needs f32 activation storage "
+                                       f"-- torch.float32 or 'f32x3'")
         self.config = train_cfg if train_cfg is not None else cfg
         self.num_cams = num_cams
         self.dtype = dtype
@@ -56,6 +74,10 @@ class EncoderDecoder(torch.nn.Module):
         if torch.cuda.is_available() and device.index >= torch.cuda.device_count():
             raise _lib.TTError(f"EncoderDecoder: {device} requested, {torch.cuda.device_count()} GPU(s) visible")
         self.device = device
+        if self._masters is not None:            # (another GPU: the parameters are rebuilt there by the load that follows)
+            from .autograd_route import MasterState
+            MasterState.unregister(self)
+            self._masters = None
         c = self._ctor
         # "f32x3h" (weights.X3H): the camera encoder's PAFPN on half storage / two-MFMA products, everything else -- the rest of the
         # camera encoder, the LiDAR branch, the decoder -- exactly the bf16x3 mode
@@ -128,7 +150,8 @@ class EncoderDecoder(torch.nn.Module):
             device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else self.device.index or 0)
         if device == self.device:
             return self
-        sd, mode = self._ref_sd, self.training
+        mode = self.training
+        sd = self.state_dict() if self._masters is not None else self._ref_sd
         self._build(device)                    # raises for a non-GPU device before anything is torn down
         if sd is not None:
             self.load_state_dict(sd)
@@ -189,16 +212,54 @@ class EncoderDecoder(torch.nn.Module):
         self.load_state_dict(sub)
 
     def state_dict(self, destination=None, prefix="", keep_vars=False):
-        """The reference-format state_dict this model was loaded from (what torch.save(model.state_dict()) stores)."""
+        """The reference-format state_dict this model was loaded from (what torch.save(model.state_dict()) stores).  Trainable
+        mode: torch's own Module.state_dict over the registered parameters and buffers -- the LIVE tensors (updated weights,
+        running statistics, call counters), in the key order of the loaded dict."""
+        if self._masters is not None:
+            return torch.nn.Module.state_dict(self, destination=destination, prefix=prefix, keep_vars=keep_vars)
         out = destination if destination is not None else {}
         for k, v in (self._ref_sd or {}).items():
             out[prefix + k] = v
         return out
 
     def load_state_dict(self, sd, strict=False):
-        """Accepts the reference's checkpoint `state_dict` (optionally with a `module.` prefix)."""
-        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items() if k != "_metadata"}
-        self._ref_sd = sd
+        """Accepts the reference's checkpoint `state_dict` (optionally with a `module.` prefix).  Trainable mode: the first
+        load creates the master parameters and buffers; later loads copy into them (the Parameter objects keep their identity,
+        an optimizer built on them stays valid)."""
+        sd = masters.strip(sd)
+        if not self.trainable:
+            self._ref_sd = sd
+            return self._prepare_operands(sd)
+        if self._masters is None:
+            from .autograd_route import MasterState
+            self._masters = MasterState(self, sd)
+        else:
+            self._masters.copy_from(sd)
+        self._refresh_operands()
+        return self
+
+    def parameters_changed(self):
+        """Trainable mode: declare the parameters (or BatchNorm statistics) written behind the version counter's back
+        (`p.data.mul_()`, a raw-pointer kernel): the next forward re-prepares the operands."""
+        if self._masters is not None:
+            self._masters.seen = None
+
+    def _refresh_operands(self):
+        st = self._masters
+        st.seen = st.versions()
+        st.stats_moved, st.flags_stale = False, True
+        st.preparations += 1
+        masters.prepare_on_device(self, st.operand_tensors(), False, load=self._prepare_operands)
+
+    def _sync_operands(self, bn_train=False):
+        """One compare per forward: re-prepare the operands if somebody wrote the masters since they were prepared (or, for a
+        forward on the running statistics, if a train-mode forward has moved those since)."""
+        st = self._masters
+        if st is not None and (st.seen != st.versions() or (st.stats_moved and not bn_train)):
+            self._refresh_operands()
+
+    def _prepare_operands(self, sd):
+        """Checkpoint tensors (host or device) -> the kernels' operand formats of every sub-object."""
         dev = self.device
         autodiff.clear_metas(self)            # the previous checkpoint's operand registrations of THIS model
         with autodiff.owned_by(self):         # (the training tape's tensor -> parameter-name tables are scoped per model)
@@ -265,6 +326,9 @@ class EncoderDecoder(torch.nn.Module):
             raise _lib.TTError("EncoderDecoder: load_state_dict() first")
         # sticky device fault (a tt_mlp_chain_wide barrier that gave up in an EARLIER forward: its outputs were NaN)
         ops.raise_on_device_fault("EncoderDecoder.forward_inference")
+        if self._masters is not None:
+            from . import layers
+            self._sync_operands(bn_train=layers.BN_TRAIN)
         self.epoch = 10000
         meas = self.measurement_feat(batch)
         cam, cam_bev, lidar = self.extract_sensor_feat(batch["img"], batch["img_metas"], batch.get("points"),
@@ -290,9 +354,29 @@ class EncoderDecoder(torch.nn.Module):
         carry no torch autograd graph: inside `with autodiff.Tape()` the forward ops and the loss terms record their
         backward on the tape (trainer.Trainer.step runs it)."""
         from . import layers
+        st = self._masters
+        taped = st is not None and torch.is_grad_enabled() and autodiff.TAPE is None
         saved, layers.BN_TRAIN = layers.BN_TRAIN, bool(self.training)
         try:
-            return self._forward_train(batch)
+            if not taped:
+                out = self._forward_train(batch)
+            else:
+                # trainable mode under autograd: the forward records on a tape of its own, which `_parse_losses` hands to the
+                # autograd node behind the total `loss` (autograd_route.TapedLoss); the terms stay plain device scalars
+                from .autograd_route import TapedLosses
+                self._sync_operands(bn_train=layers.BN_TRAIN)
+                if st.flags_stale and not layers.BN_TRAIN:
+                    autodiff.refresh_small_scale_flags(owner=self)       # (frozen-BN backward; one host sync per preparation)
+                    st.flags_stale = False
+                tape = autodiff.Tape(x3=self.dtype != torch.float32, release=True,
+                                     param_tensors=autodiff.PARAM_TENSORS.items(self))
+                with tape:
+                    out = TapedLosses(self._forward_train(batch))
+                out.tape = tape
+            if st is not None and layers.BN_TRAIN:
+                st.nbt.add_(st.nbt_inc)                  # nn.BatchNorm's call counters (masters.bn_calls_per_iteration)
+                st.stats_moved = True                    # (the folded eval-mode affines are stale now)
+            return out
         finally:
             layers.BN_TRAIN = saved
 
@@ -331,12 +415,20 @@ class EncoderDecoder(torch.nn.Module):
 
     def _parse_losses(self, losses):
         from . import losses as LS
-        return LS.parse_losses(losses)
+        loss, log_vars = LS.parse_losses(losses)
+        tape = getattr(losses, "tape", None)
+        if tape is not None:
+            from .autograd_route import attach
+            losses.tape = None
+            loss = attach(self, self._masters, tape, loss)
+        return loss, log_vars
 
     def train_step(self, data, optimizer=None):
         """encoder_decoder_framework.py:140-145: dict(loss, log_vars, num_samples).  `optimizer` is unused, as in the
         reference (the mmcv OptimizerHook calls loss.backward() and steps it); the backward + all-reduce + AdamW half of
-        the iteration is trainer.Trainer.step, which calls this inside its tape."""
+        the iteration is trainer.Trainer.step, which calls this inside its tape -- or, on a `trainable=True` model with
+        autograd enabled, torch's own: `loss` then carries the autograd node whose backward sweeps this forward's tape
+        (autograd_route.TapedLoss)."""
         loss, log_vars = self._parse_losses(self.forward_train(data))
         return dict(loss=loss, log_vars=log_vars, num_samples=data["img"].shape[0])
 

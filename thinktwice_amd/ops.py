@@ -1199,3 +1199,61 @@ def dec_bev_update(wts, bev, G, out):
     check(L.tt_dec_bev_update(B, ptr(bev), ptr(G), ptr(out), 441 * 32, None, 0, ptr(scratch), ptr(wts["w0"]),
                               ptr(wts["b0"]), wts["w2"], ptr(wts["b2"]), _st(bev)), "tt_dec_bev_update")
     return out
+
+
+class GradSegTable:
+    """The segment table of tt_grad_gather for one device: `tt_grad_seg` records {src pointer, dst offset, count} (three 64-bit
+    fields) written into a PINNED host buffer and uploaded to its device twin on the current stream.  The buffers grow as
+    needed and are reused; an event guards the host buffer against being rewritten while the previous upload is in flight."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.host = self.dev = self.event = None
+        self.nseg = self.flat_numel = 0
+
+    def upload(self, srcs, dst_offs, flat_numel):
+        """`srcs`: contiguous f32 device tensors (views are fine); `dst_offs`: their first element in the flat buffer.  The
+        records are sorted by destination and checked on the host (inside `flat_numel`, no overlap): the kernel trusts them."""
+        order = sorted(range(len(srcs)), key=lambda i: dst_offs[i])
+        rec, end = [], 0
+        for i in order:
+            s, off = srcs[i], int(dst_offs[i])
+            require_cuda(s)
+            if s.dtype != torch.float32 or not s.is_contiguous() or s.device != self.device:
+                raise TTError("grad_gather: sources are contiguous f32 tensors on the table's device")
+            if off < end or off + s.numel() > flat_numel:
+                raise TTError(f"grad_gather: segment [{off}, {off + s.numel()}) overlaps its neighbour or leaves the flat "
+                              f"buffer of {flat_numel} elements")
+            end = off + s.numel()
+            rec += [s.data_ptr(), off, s.numel()]
+        self.nseg, self.flat_numel = len(order), int(flat_numel)
+        if self.nseg == 0:
+            return self
+        if self.host is None or self.host.numel() < len(rec):
+            cap = max(len(rec), 3 * 1024)
+            self.host = torch.empty(cap, dtype=torch.int64, pin_memory=True)
+            self.dev = torch.empty(cap, dtype=torch.int64, device=self.device)
+            self.event = torch.cuda.Event()
+        else:
+            self.event.synchronize()
+        self.host[:len(rec)] = torch.tensor(rec, dtype=torch.int64)
+        self.dev[:len(rec)].copy_(self.host[:len(rec)], non_blocking=True)
+        self.event.record(torch.cuda.current_stream(self.device))
+        return self
+
+
+def grad_gather(table, flat, scale=None, accumulate=False):
+    """flat[dst_off_i .. + count_i) (=|+=) scale * src_i for every segment of `table` (a GradSegTable uploaded on this
+    stream), ONE launch; `scale`: device f32 scalar or None (1.0).  Elements no segment covers are not written.  The sources
+    must stay allocated until the launch is issued (stream order does the rest)."""
+    require_cuda(flat, scale)
+    if flat.dtype != torch.float32 or not flat.is_contiguous() or flat.device != table.device or flat.numel() < table.flat_numel:
+        raise TTError("grad_gather: the destination is a contiguous f32 buffer on the table's device, of the size the table "
+                      "was checked against")
+    if scale is not None and (scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != flat.device):
+        raise TTError("grad_gather: scale is one f32 value on the destination's device")
+    check(lib().tt_grad_gather(ptr(table.dev), table.nseg, ptr(flat), ptr(scale), 1 if accumulate else 0, _st(flat)),
+          "tt_grad_gather")
+    return flat

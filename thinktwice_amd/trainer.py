@@ -16,17 +16,11 @@ import sys
 
 import torch
 
-from . import autodiff
+from . import autodiff, masters
+from ._lib import TTError
 from .grad_sync import FlatGradBuffer
+from .masters import BUFFERS as _BUFFERS, trainable as _trainable  # noqa: F401  (the layout rule, shared with the autograd route)
 from .optim import FlatAdamW
-
-
-# registered buffers of the reference modules (BatchNorm statistics; the LSS frustum / voxel grid constants, lss.py:470-476)
-_BUFFERS = ("running_mean", "running_var", "num_batches_tracked", "voxel_size", "voxel_coord", "voxel_num", "frustum")
-
-
-def _trainable(name, t):
-    return torch.is_tensor(t) and t.is_floating_point() and t.dim() > 0 and not name.endswith(_BUFFERS)
 
 
 class Trainer:
@@ -38,25 +32,18 @@ class Trainer:
         the ranks, running statistics updated in `self.buffers`, live ASPP dropout; goldens F11 / F16).  `frozen_bn=True`:
         BatchNorm on its running statistics (model.eval() arithmetic, goldens F10 / F13) -- fine-tuning with frozen
         statistics; the BatchNorm affine parameters still train."""
+        if getattr(model, "trainable", False):
+            raise TTError("Trainer: this model was built with trainable=True and owns its master weights (torch autograd "
+                          "route); a Trainer keeps its own -- build the model without trainable=True")
         dev = model.device
         self.model = model
         self.frozen_bn = bool(frozen_bn)
         self.x3 = (model.dtype != torch.float32) if x3 is None else x3
-        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items() if k != "_metadata"}
-        self.names = [k for k, v in sd.items() if _trainable(k, v)]
+        sd = masters.strip(state_dict)
+        self.names, self.flat_param, views = masters.flat_masters(sd, dev)
         self._trainable = set(self.names)
-        total = sum(sd[k].numel() for k in self.names)
-        self.flat_param = torch.empty(total, dtype=torch.float32, device=dev)
-        self.sd = {}
-        off = 0
-        for k, v in sd.items():
-            if k in self._trainable:
-                view = self.flat_param[off:off + v.numel()].view(v.shape)
-                view.copy_(v.to(dev, torch.float32))
-                self.sd[k] = view.requires_grad_(True)          # a leaf whose .grad FlatGradBuffer points into its buffer
-                off += v.numel()
-            else:
-                self.sd[k] = v
+        # (a master view is a leaf whose .grad FlatGradBuffer points into its buffer)
+        self.sd = {k: (views[k].requires_grad_(True) if k in views else v) for k, v in sd.items()}
         self.grads = FlatGradBuffer([self.sd[k] for k in self.names])
         self.opt = FlatAdamW(self.flat_param, self.grads.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                              max_grad_norm=max_grad_norm)
@@ -81,20 +68,17 @@ class Trainer:
         the device once), so nothing crosses PCIe.  TT_TRAIN_PREPARE=host takes the route a checkpoint takes instead (one
         0.5 GB device-to-host copy + host-side preparation per iteration); it is also the fallback if the load code meets
         a host-only operation on a device tensor."""
+        if self._prepare_on_device:
+            try:
+                masters.prepare_on_device(self.model, {k: (v.detach() if k in self._trainable else self._dev_buffers.get(k, v))
+                                                       for k, v in self.sd.items()}, self.frozen_bn)
+                return
+            except (RuntimeError, TypeError) as e:
+                print(f"[trainer] device-side operand preparation failed ({type(e).__name__}: {e}); "
+                      f"using the host path", file=sys.stderr, flush=True)
+                self._prepare_on_device = False
         autodiff.clear_metas(self.model)
         with torch.no_grad():
-            if self._prepare_on_device:
-                try:
-                    self.model.load_state_dict({k: (v.detach() if k in self._trainable else self._dev_buffers.get(k, v))
-                                                for k, v in self.sd.items()})
-                    if self.frozen_bn:
-                        autodiff.refresh_small_scale_flags(owner=self.model)
-                    return
-                except (RuntimeError, TypeError) as e:
-                    print(f"[trainer] device-side operand preparation failed ({type(e).__name__}: {e}); "
-                          f"using the host path", file=sys.stderr, flush=True)
-                    self._prepare_on_device = False
-                    autodiff.clear_metas(self.model)
             self.model.load_state_dict({k: (v.detach().cpu() if k in self._trainable else v) for k, v in self.sd.items()})
 
     def backward(self, batch):
@@ -185,14 +169,10 @@ class Trainer:
 
     # ---- checkpoints (mmcv CheckpointHook / torch.save layout: meta + state_dict + optimizer)
     def _num_batches_tracked(self, key, value):
-        """nn.BatchNorm's call counter under model.train(): every BatchNorm inside the per-sweep camera pass is called once
-        per SWEEP and iteration (lss.py:689-714; older sweeps run under no_grad but in train mode), the others once per
-        iteration."""
+        """nn.BatchNorm's call counter under model.train() (masters.bn_calls_per_iteration) after the applied iterations."""
         if self.frozen_bn or self._bn_steps == 0:
             return value
-        T = int((self.model.config or {}).get("queue_length", 1))
-        per_iter = T if (key.startswith("img_encoder.") and "bev_multiframe_merge" not in key) else 1
-        return value + self._bn_steps * per_iter
+        return value + self._bn_steps * masters.bn_calls_per_iteration(self.model, key)
 
     def state_dict(self):
         """Reference-format weights (own copies: the master tensors are views of one flat buffer), BatchNorm running
