@@ -15,7 +15,7 @@
 // contiguous range of output rows (n, oh); its waves take the rows round-robin and their accumulators are added through LDS.
 // gridDim.y row ranges ("splits") write their partial tiles to a workspace that a second kernel adds in split order:
 // deterministic, no atomics.
-#include "conv_common.h"
+#include "conv_lds_dma.h"
 
 namespace tt {
 
@@ -71,12 +71,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
     const int r_end = min(rows, r_begin + a.rows_per_split);
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
     // channel validity of this lane's two co / ci blocks (zero operands outside the tensor's channels)
     const bool co_ok[2] = {co0 + c < a.Cout, co0 + 32 + c < a.Cout};
@@ -166,12 +161,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_wide_kernel(const WgradArgs a)
     const int r_end = min(rows, r_begin + a.rows_per_split);
 
     f32x16 acc[BI][BJ];
-#pragma unroll
-    for (int i = 0; i < BI; ++i)
-#pragma unroll
-        for (int j = 0; j < BJ; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
     bool co_ok[BI], ci_ok[BJ];
     int cco[BI], cci[BJ];                                    // clamped channels: unconditional loads, masked afterwards
 #pragma unroll
@@ -280,7 +270,6 @@ __device__ __forceinline__ void lds_col8(unsigned addr, float (&v)[8]) {      //
 template <int BI, int BJ>
 __global__ __launch_bounds__(256, 1) void conv_wgrad_lds_kernel(const WgradArgs a, const float* __restrict__ zp) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
     constexpr int TA = 64 * BI, TB = 64 * BJ;             // channels per staged row = the workgroup's tile of dW
     constexpr int PX = 32;                                // output pixels per stage (two 16-pixel MFMA steps)
     constexpr int RA = TA * 4, RB = TB * 4;               // row bytes
@@ -305,12 +294,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_lds_kernel(const WgradArgs 
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)wsm;
 
     f32x16 acc[BI][BJ];
-#pragma unroll
-    for (int i = 0; i < BI; ++i)
-#pragma unroll
-        for (int j = 0; j < BJ; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
     // ---- stage walker: (row r, 32-pixel segment); rows whose tap row falls outside the image are skipped
     struct It {
@@ -350,7 +334,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_lds_kernel(const WgradArgs 
             const int i = wave_s + 4 * j;                                  // piece
             const int ow = ow0 + i * (64 / LPA) + pa_px;
             const float* src = (ow < a.OW && a_ch_ok) ? dyrow + (long long)ow * a.dy_cstride : zp;
-            __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(sa + (unsigned)i * 1024u), 16, 0, 0);
+            dma_piece(src, sa + (unsigned)i * 1024u);
         }
 #pragma unroll
         for (int j = 0; j < NIB; ++j) {
@@ -358,7 +342,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_lds_kernel(const WgradArgs 
             const int ow = ow0 + i * (64 / LPB) + pb_px;
             const int iw = ow * a.stride - a.pad + kw * a.dil;
             const float* src = (ow < a.OW && iw >= 0 && iw < a.W && b_ch_ok) ? xrow + (long long)iw * a.x_cstride : zp;
-            __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(sb + (unsigned)i * 1024u), 16, 0, 0);
+            dma_piece(src, sb + (unsigned)i * 1024u);
         }
     };
     // fragment columns of this lane: row block i of dy / column block j of x, pixel group kg (8 pixels) of a 16-pixel step
@@ -492,12 +476,7 @@ __global__ __launch_bounds__(256) void gather_wgrad_kernel(const GatherWgradArgs
     const long long p_begin = (long long)blockIdx.y * pps;
     const long long p_end = min(npairs, p_begin + pps);
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
     const bool co_ok[2] = {co0 + c < a.Cout, co0 + 32 + c < a.Cout};
     const bool ci_ok[2] = {ci0 + c < a.Cin, ci0 + 32 + c < a.Cin};
     for (long long p0 = p_begin + (long long)wave * kWgUnroll; p0 < p_end; p0 += 4 * kWgUnroll) {
@@ -709,12 +688,7 @@ __global__ __launch_bounds__(256) void gather_wgrad_wide_kernel(const GatherWgra
     const long long p_begin = (long long)blockIdx.y * pps;
     const long long p_end = min(npairs, p_begin + pps);
     f32x16 acc[BI][BJ];
-#pragma unroll
-    for (int i = 0; i < BI; ++i)
-#pragma unroll
-        for (int j = 0; j < BJ; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
     bool co_ok[BI], ci_ok[BJ];
     int cco[BI], cci[BJ];
 #pragma unroll

@@ -1,4 +1,5 @@
-// Shared definitions of the implicit-GEMM convolution kernels (conv_igemm.hip, conv_igemm_glds.hip).
+// Shared definitions of the implicit-GEMM convolution kernels: arguments, MFMA wrappers, the fused epilogue.  (The data movement of the
+// LDS-DMA kernels is in conv_lds_dma.h.)
 #pragma once
 #include <type_traits>
 #include "tt_common.h"
@@ -74,6 +75,20 @@ template <> struct Mfma<f16_t> {
         c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     }
 };
+
+// A wave's accumulator blocks, element by element (compile-time indices: they stay registers)
+template <int TN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TN]) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+}
+template <int TM, int TN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i) zero_acc(acc[i]);
+}
 
 // Stage one 32 x WTN block of a wave's accumulators into its private LDS region with the folded-BN scale/shift
 // already applied.  In the MFMA C/D layout a lane owns ONE output channel per 32-wide column block, so the affine

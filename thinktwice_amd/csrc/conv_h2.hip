@@ -7,7 +7,7 @@
 // -- two thirds of the bf16x3 form's matrix work, no operand split on the VALU, and half the activation / output bytes
 // of f32 storage for the layers that sit at the HBM roof.
 //
-// Data movement is the LDS-DMA pipeline of conv_igemm_glds.hip (global_load_lds_dwordx4, counted vmcnt, raw s_barrier,
+// Data movement is the LDS-DMA pipeline (conv_lds_dma.h: global_load_lds_dwordx4, counted vmcnt, raw s_barrier,
 // XOR swizzle on the DMA source address, zero page for padding, XCD-aware tile order) with operand rows of different width:
 //   * K tile = 64 halves.  Activation rows are 128 B (whole cache lines per DMA lane group), 256 rows per tile = 32 KiB;
 //     weight rows are 256 B (per 16 K elements 64 B = [hi k0-7 | hi k8-15 | lo k0-7 | lo k8-15],
@@ -21,18 +21,13 @@
 // Epilogue: the shared conv_epilogue (folded BN, residual in half, ReLU, half or f32 output, optional second f32 copy).
 // Contract (tt_conv2d_fwd dispatches here whenever tt_conv_desc.weight_h2 is set; anything else is refused there): dense
 // convolution, Cin % 64 == 0, KH*KW <= 31.
-#include <stdlib.h>
-
-#include "conv_common.h"
+#include "conv_lds_dma.h"
 
 namespace tt {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 template <int BN, int WAVES_M, int WAVES_N, int SA, int SB>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 2 : 1)
-void conv_h2_kernel(const ConvArgs p, const void* zero_page, int tiles_m, int tiles_n, int sa_used, int sb_used) {
+void conv_h2_kernel(const ConvArgs p, const void* zero_page, int tiles_m, int tiles_n, int sa_used) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BM = 256, BK = 64;
     constexpr int A_ROWB = 128, B_ROWB = 256;
@@ -50,14 +45,9 @@ void conv_h2_kernel(const ConvArgs p, const void* zero_page, int tiles_m, int ti
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int Mlim = p.M;
 
-    // XCD-aware tile order (bijective for any grid size): hardware places block b on XCD b % 8
     const int nblk = tiles_m * tiles_n;
     if ((int)blockIdx.x >= nblk) return;
-    int L;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = nblk >> 3, r = nblk & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int L = xcd_tile(nblk);
     const int tile_n = L % tiles_n, tile_m = L / tiles_n;
     const int m0 = p.m_begin + tile_m * BM, n0 = tile_n * BN;
     if (m0 >= Mlim) return;
@@ -66,36 +56,11 @@ void conv_h2_kernel(const ConvArgs p, const void* zero_page, int tiles_m, int ti
     const uint16_t* __restrict__ wgt = reinterpret_cast<const uint16_t*>(p.weight);
     const uint16_t* zp = reinterpret_cast<const uint16_t*>(zero_page);
 
-    // ---- DMA slots.  Activation slot j = 1 KiB piece (wave + NW j): 8 rows x 8 chunks; ONE pointer (tap (0,0), channel 0,
-    // possibly outside the image) and ONE tap-validity mask per slot
+    // ---- DMA slots.  Activation slot j = 1 KiB piece (wave + NW j): 8 rows x 8 chunks
     const uint16_t* a_ptr[NIA];
     unsigned a_mask[NIA];
 #pragma unroll
-    for (int j = 0; j < NIA; ++j) {
-        const int g = (wave + NW * j) * 64 + lane;
-        const int row = g >> 3, pos = g & 7;
-        const int c = (pos ^ ((row >> 1) & 7)) * 8;
-        const int m = m0 + row;
-        const bool ok = m < Mlim;
-        const int mm = ok ? m : 0;
-        const int n = mm / (p.OH * p.OW);
-        const int r = mm - n * (p.OH * p.OW);
-        const int oh = r / p.OW, ow = r - oh * p.OW;
-        const int h0 = oh * p.stride - p.pad, w0 = ow * p.stride - p.pad;
-        a_ptr[j] = in + (long long)n * p.in_nstride + p.in_coff + ((long long)h0 * p.W + w0) * p.in_cstride + c;
-        unsigned mk = 0;
-        if (ok) {
-            int tbit = 0;
-            for (int kh = 0; kh < p.KH; ++kh) {
-                const int ih = h0 + kh * p.dil;
-                for (int kw = 0; kw < p.KW; ++kw, ++tbit) {
-                    const int iw = w0 + kw * p.dil;
-                    if (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W) mk |= 1u << tbit;
-                }
-            }
-        }
-        a_mask[j] = mk;
-    }
+    for (int j = 0; j < NIA; ++j) dense_slot<A_ROWB>(p, in, (wave + NW * j) * 64 + lane, m0, Mlim, a_ptr[j], a_mask[j]);
     // Weight slot j = piece (wave + NW j): 4 rows x 16 chunks of the [BN][256 B] tile; rows of 2 K halves in memory
     const uint16_t* b_ptr[NIB];
     bool b_ok[NIB];
@@ -104,59 +69,19 @@ void conv_h2_kernel(const ConvArgs p, const void* zero_page, int tiles_m, int ti
         const int g = (wave + NW * j) * 64 + lane;
         const int row = g >> 4, pos = g & 15;
         b_ok[j] = (n0 + row) < p.Cout;
-        b_ptr[j] = wgt + (long long)(b_ok[j] ? n0 + row : 0) * (2ll * p.K) + (pos ^ (row & 15)) * 8;
+        b_ptr[j] = wgt + (long long)(b_ok[j] ? n0 + row : 0) * (2ll * p.K) + (pos ^ swz<B_ROWB>(row)) * 8;
     }
 
     const int nk = p.K / BK;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const unsigned ldsA = lds_base, ldsB = lds_base + (unsigned)sa_used * A_BYTES;
-    (void)sb_used;
 
-    struct KWalk {
-        int kh, kw, ci;
-    };
     KWalk wa{0, 0, 0}, wb{0, 0, 0};
-    auto advance = [&](KWalk& w) {
-        if (++w.kw == p.KW) {
-            w.kw = 0;
-            if (++w.kh == p.KH) {
-                w.kh = 0;
-                w.ci += BK;
-            }
-        }
-    };
-    struct DmaCtx {
-        unsigned st;
-        int tap;
-        long long off;
-        bool on;
-    };
-    auto a_begin = [&](int kt) {
-        DmaCtx c{0u, 0, 0, kt < nk};
-        if (!c.on) return c;
-        c.st = ldsA + (unsigned)(kt % SA) * A_BYTES;
-        c.tap = wa.kh * p.KW + wa.kw;
-        c.off = ((long long)(wa.kh * p.dil) * p.W + wa.kw * p.dil) * p.in_cstride + wa.ci;
-        advance(wa);
-        return c;
-    };
-    auto a_emit = [&](const DmaCtx& c, int j) {
-        const uint16_t* src = ((a_mask[j] >> c.tap) & 1u) ? a_ptr[j] + c.off : zp;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(c.st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
-    };
-    auto b_begin = [&](int kt) {
-        DmaCtx c{0u, 0, 0, kt < nk};
-        if (!c.on) return c;
-        c.st = ldsB + (unsigned)(kt % SB) * B_BYTES;
-        c.off = 2ll * ((long long)(wb.kh * p.KW + wb.kw) * p.Cin + wb.ci);
-        advance(wb);
-        return c;
-    };
-    auto b_emit = [&](const DmaCtx& c, int j) {
-        const uint16_t* src = b_ok[j] ? b_ptr[j] + c.off : zp;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(c.st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
-    };
+    auto a_begin = [&](int kt) { return dma_begin_a<BK>(p, wa, ldsA + (unsigned)(kt % SA) * A_BYTES, kt < nk); };
+    auto b_begin = [&](int kt) { return dma_begin_b<BK, 2>(p, wb, ldsB + (unsigned)(kt % SB) * B_BYTES, kt < nk); };
+    auto a_emit = [&](const DmaCtx& c, int j) { dma_emit_a(c, a_ptr[j], a_mask[j], zp, wave_s + NW * j); };
+    auto b_emit = [&](const DmaCtx& c, int j) { dma_emit_b(c, b_ptr[j], b_ok[j], zp, wave_s + NW * j); };
     auto issue_a = [&](int kt) {
         const DmaCtx c = a_begin(kt);
         if (!c.on) return;
@@ -171,12 +96,7 @@ void conv_h2_kernel(const ConvArgs p, const void* zero_page, int tiles_m, int ti
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // ---- prologue: issue order = the order of the loop below (weights of a tile before the activations issued with it)
     //   (2,2): A0 B0            (3,2): A0 B0 A1            (3,3): A0 B0 A1 B1
@@ -191,37 +111,16 @@ void conv_h2_kernel(const ConvArgs p, const void* zero_page, int tiles_m, int ti
 #pragma unroll
     for (int kc = 0; kc < NKC; ++kc) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int row = wm * WTM + i * 32 + (lane & 31);
-            fa_pre[kc][i] = row * A_ROWB + (((2u * kc + hi) ^ ((row >> 1) & 7)) << 4);
-        }
+        for (int i = 0; i < TM; ++i) fa_pre[kc][i] = frag_off<A_ROWB>(wm * WTM + i * 32 + (lane & 31), 2u * kc + hi);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int row = wn * WTN + j * 32 + (lane & 31);
-            fb_pre[kc][j] = row * B_ROWB + (((4u * kc + hi) ^ (row & 15)) << 4);     // hi half; the lo half is this ^ 32
-        }
+        for (int j = 0; j < TN; ++j) fb_pre[kc][j] = frag_off<B_ROWB>(wn * WTN + j * 32 + (lane & 31), 4u * kc + hi);     // hi half; the lo half is this ^ 32
     }
-    auto lds_read = [](unsigned addr) {
-        u32x4 v;
-        asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-        return v;
-    };
 
     for (int kt = 0; kt < nk; ++kt) {
         // tile kt has landed for THIS wave once only the loads issued after its last piece are outstanding
-        if (SA == 3 && SB == 2 && kt + 1 < nk) {                       // in flight behind B(kt): A(kt+1)
-            if constexpr (NIA == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if constexpr (NIA == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else if (SA == 3 && SB == 3 && kt + 1 < nk) {                // behind A(kt): B(kt+1) A(kt+1)
-            if constexpr (NIA + NIB == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else if constexpr (NIA + NIB == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-            else if constexpr (NIA + NIB == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if constexpr (NIA + NIB == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        if (SA == 3 && SB == 2 && kt + 1 < nk) wait_vmcnt<NIA>();                 // in flight behind B(kt): A(kt+1)
+        else if (SA == 3 && SB == 3 && kt + 1 < nk) wait_vmcnt<NIA + NIB>();      // behind A(kt): B(kt+1) A(kt+1)
+        else wait_vmcnt<0>();
         asm volatile("s_barrier" ::: "memory");       // publishes tile kt; everyone is done reading tile kt - 1
 
         const unsigned sa = ldsA + (unsigned)(kt % SA) * A_BYTES, sb = ldsB + (unsigned)(kt % SB) * B_BYTES;
@@ -234,7 +133,7 @@ void conv_h2_kernel(const ConvArgs p, const void* zero_page, int tiles_m, int ti
             fbl[0][j] = lds_read(sb + (fb_pre[0][j] ^ 32u));
         }
         // the DMA this iteration owes the ring, one piece group behind each K step's MFMAs (all eight waves issuing a whole
-        // tile at once queues the CU's one texture path: conv_igemm_glds.hip "spread")
+        // tile at once queues the CU's one texture path: conv_lds_dma.h "spread")
         const DmaCtx cb = b_begin(kt + SB - 1);
         const DmaCtx ca = a_begin(kt + SA - 1);
         constexpr int PER = (NIA + NIB + NKC - 1) / NKC;
@@ -313,11 +212,7 @@ __global__ __launch_bounds__(256, 1) void conv_h2_pipe_kernel(const ConvArgs p, 
     const int Mlim = p.M;
     const int nblk = tiles_m * tiles_n;
     if ((int)blockIdx.x >= nblk) return;
-    int L;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = nblk >> 3, r = nblk & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int L = xcd_tile(nblk);
     const int tile_n = L % tiles_n, tile_m = L / tiles_n;
     const int m0 = p.m_begin + tile_m * BM, n0 = tile_n * BN;
     if (m0 >= Mlim) return;
@@ -326,41 +221,17 @@ __global__ __launch_bounds__(256, 1) void conv_h2_pipe_kernel(const ConvArgs p, 
     const uint16_t* __restrict__ wgt = reinterpret_cast<const uint16_t*>(p.weight);
     const uint16_t* zp = reinterpret_cast<const uint16_t*>(zero_page);
 
-    // ---- DMA slots (conv_h2_kernel's): activation slot j = piece (wave + 4 j): 8 rows x 8 chunks; weight slot j = piece
-    // (wave + 4 j): 4 rows x 16 chunks, rows 16 j apart: one pointer + a uniform stride
+    // ---- DMA slots: activation slot j = piece (wave + 4 j): 8 rows x 8 chunks; weight slot j = piece (wave + 4 j): 4 rows x 16
+    // chunks, rows 16 j apart: one pointer + a uniform stride
     const uint16_t* a_ptr[NIA];
     unsigned a_mask[NIA];
 #pragma unroll
-    for (int j = 0; j < NIA; ++j) {
-        const int g = (wave + NW * j) * 64 + lane;
-        const int row = g >> 3, pos = g & 7;
-        const int c = (pos ^ ((row >> 1) & 7)) * 8;
-        const int m = m0 + row;
-        const bool ok = m < Mlim;
-        const int mm = ok ? m : 0;
-        const int n = mm / (p.OH * p.OW);
-        const int r = mm - n * (p.OH * p.OW);
-        const int oh = r / p.OW, ow = r - oh * p.OW;
-        const int h0 = oh * p.stride - p.pad, w0 = ow * p.stride - p.pad;
-        a_ptr[j] = in + (long long)n * p.in_nstride + p.in_coff + ((long long)h0 * p.W + w0) * p.in_cstride + c;
-        unsigned mk = 0;
-        if (ok) {
-            int tbit = 0;
-            for (int kh = 0; kh < p.KH; ++kh) {
-                const int ih = h0 + kh * p.dil;
-                for (int kw = 0; kw < p.KW; ++kw, ++tbit) {
-                    const int iw = w0 + kw * p.dil;
-                    if (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W) mk |= 1u << tbit;
-                }
-            }
-        }
-        a_mask[j] = mk;
-    }
+    for (int j = 0; j < NIA; ++j) dense_slot<A_ROWB>(p, in, (wave + NW * j) * 64 + lane, m0, Mlim, a_ptr[j], a_mask[j]);
     const uint16_t* b_ptr0;
     {
         const int g = wave * 64 + lane;
         const int row = g >> 4, pos = g & 15;
-        b_ptr0 = wgt + (long long)(n0 + row) * (2ll * p.K) + (pos ^ (row & 15)) * 8;
+        b_ptr0 = wgt + (long long)(n0 + row) * (2ll * p.K) + (pos ^ swz<B_ROWB>(row)) * 8;
     }
     const long long b_jstride = (long long)(NW * 4) * (2ll * p.K);      // halves between consecutive slots of a wave
 
@@ -369,7 +240,8 @@ __global__ __launch_bounds__(256, 1) void conv_h2_pipe_kernel(const ConvArgs p, 
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const unsigned ldsA = lds_base, ldsB = lds_base + 3u * A_BYTES;
 
-    // ---- the two DMA walkers (wave-uniform, branch-free: conv_x3_pipe.hip).  K order: channel chunk outer, filter tap inner
+    // ---- the two DMA walkers (wave-uniform, branch-free; the same as conv_x3_pipe_kernel's, which explains them, over rows of
+    // 2 Cin halves -- see there why they stay lambdas of the kernel).  K order: channel chunk outer, filter tap inner
     const int ntaps = p.KH * p.KW;
     const long long a_d1 = (long long)p.dil * p.in_cstride;
     const long long a_d2 = ((long long)p.dil * p.W - (long long)(p.KW - 1) * p.dil) * p.in_cstride;
@@ -414,41 +286,25 @@ __global__ __launch_bounds__(256, 1) void conv_h2_pipe_kernel(const ConvArgs p, 
     auto a_emit = [&](int j) {      // beyond the last tile every activation row reads the zero page (bit 31 is never set)
         const int tapbit = a_rem > 0 ? a_tap : 31;
         const uint16_t* src = ((a_mask[j] >> tapbit) & 1u) ? a_ptr[j] + a_off : zp;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(a_st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
+        dma_piece(src, a_st + (unsigned)(wave_s + NW * j) * 1024u);
     };
     auto b_emit = [&](int j) {
         const uint16_t* src = b_ptr0 + b_off + (long long)j * b_jstride;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(b_st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
+        dma_piece(src, b_st + (unsigned)(wave_s + NW * j) * 1024u);
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const unsigned hi = lane >> 5;
     unsigned fa_pre[NKC][TM], fb_pre[NKC][TN];
 #pragma unroll
     for (int kc = 0; kc < NKC; ++kc) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int row = wm * WTM + i * 32 + (lane & 31);
-            fa_pre[kc][i] = row * A_ROWB + (((2u * kc + hi) ^ ((row >> 1) & 7)) << 4);
-        }
+        for (int i = 0; i < TM; ++i) fa_pre[kc][i] = frag_off<A_ROWB>(wm * WTM + i * 32 + (lane & 31), 2u * kc + hi);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int row = j * 32 + (lane & 31);
-            fb_pre[kc][j] = row * B_ROWB + (((4u * kc + hi) ^ (row & 15)) << 4);     // hi half; the lo half is this ^ 32
-        }
+        for (int j = 0; j < TN; ++j) fb_pre[kc][j] = frag_off<B_ROWB>(j * 32 + (lane & 31), 4u * kc + hi);     // hi half; the lo half is this ^ 32
     }
-    auto lds_read = [](unsigned addr) {
-        u32x4 v;
-        asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-        return v;
-    };
 #define TT_H2_MFMA(c, a, b) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b))
 
     u32x4 fa[2][TM];                  // [K step parity][row block]
@@ -465,7 +321,7 @@ __global__ __launch_bounds__(256, 1) void conv_h2_pipe_kernel(const ConvArgs p, 
             for (int j = 0; j < NIB; ++j) b_emit(j);
             b_walk1(); b_walk2();
         }
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");       // tile 0 has landed for this wave
+        wait_vmcnt<NIA + NIB>();                                // tile 0 has landed for this wave
         asm volatile("s_barrier" ::: "memory");
 #pragma unroll
         for (int i = 0; i < TM; ++i) fa[0][i] = lds_read(ldsA + fa_pre[0][i]);
@@ -585,30 +441,19 @@ static int launch_h2(ConvArgs& a, hipStream_t st) {
     size_t smem = (size_t)sa_used * A_BYTES + (size_t)sb_used * B_BYTES;
     const size_t epi = (size_t)NW * 32 * (WTN + 4) * 4;
     if (smem < epi) smem = epi;
-    auto kern = conv_h2_kernel<BN, WAVES_M, WAVES_N, SA, SB>;
     size_t full = (size_t)SA * A_BYTES + (size_t)SB * B_BYTES;      // all stages in use: the largest request
     if (full < epi) full = epi;
-    const void* zp = zero_page("conv_h2_kernel");
-    if (!zp || lds_opt_in(reinterpret_cast<const void*>(kern), full, "conv_h2_kernel")) return -1;
-    a.tiles_n = tiles_n;
-    a.splits = 1;
-    a.ws = nullptr;
-    snprintf(g_conv_kernel, sizeof(g_conv_kernel), "conv_h2_kernel<%d, %d, %d, %d, %d>", BN, WAVES_M, WAVES_N, SA, SB);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(NW * 64), smem, st, a, zp, tiles_m, tiles_n, sa_used, sb_used);
-    return 1;
+    char label[96];
+    snprintf(label, sizeof(label), "conv_h2_kernel<%d, %d, %d, %d, %d>", BN, WAVES_M, WAVES_N, SA, SB);
+    return launch_lds_dma(conv_h2_kernel<BN, WAVES_M, WAVES_N, SA, SB>, dim3((unsigned)(tiles_m * tiles_n)), dim3(NW * 64), smem, full,
+                          "conv_h2_kernel", label, a, st, tiles_m, tiles_n, 1, sa_used);
 }
 
 static int launch_h2_pipe(ConvArgs& a, hipStream_t st) {
     const int tiles_m = div_up(a.M - a.m_begin, 256), tiles_n = a.Cout / 128;
     const size_t smem = (size_t)5 * 32 * 1024;                       // 3 + 2 stages (the epilogue's 4 x 32 x 132 floats fit inside)
-    const void* zp = zero_page("conv_h2_pipe_kernel");
-    if (!zp || lds_opt_in(reinterpret_cast<const void*>(conv_h2_pipe_kernel), smem, "conv_h2_pipe_kernel")) return -1;
-    a.tiles_n = tiles_n;
-    a.splits = 1;
-    a.ws = nullptr;
-    snprintf(g_conv_kernel, sizeof(g_conv_kernel), "conv_h2_pipe_kernel");
-    hipLaunchKernelGGL(conv_h2_pipe_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem, st, a, zp, tiles_m, tiles_n);
-    return 1;
+    return launch_lds_dma(conv_h2_pipe_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem, smem, "conv_h2_pipe_kernel",
+                          "conv_h2_pipe_kernel", a, st, tiles_m, tiles_n, 1);
 }
 
 int try_launch_conv_h2(ConvArgs& a, hipStream_t st) {
@@ -616,7 +461,7 @@ int try_launch_conv_h2(ConvArgs& a, hipStream_t st) {
     a.m_begin = 0;
     // long K, 128-wide column tiles: the hand-pipelined one-wave-per-SIMD kernel.  TT_H2_PIPE=0 (test hook: tests/test_conv.py
     // compares the two kernels bit for bit): the compiler-scheduled kernel everywhere
-    static const bool pipe = [] { const char* e = getenv("TT_H2_PIPE"); return e ? atoi(e) != 0 : true; }();
+    static const bool pipe = env_flag("TT_H2_PIPE", true);
     if (pipe && a.Cout % 128 == 0 && a.K >= 1152) return launch_h2_pipe(a, st);
     // 128-wide: 8 waves of 64 x 64 on a 3 + 2 ring (160 KiB); measured against four waves of 128 x 64 (+15 %) and a 2 + 2 ring (-0.5 %:
     // kept out, one variant less): profiles/r06_h2_microbench.txt.  64-wide: 8 waves of 32 x 64, 3 + 3 ring (four waves: +20 %)

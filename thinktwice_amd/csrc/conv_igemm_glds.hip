@@ -11,22 +11,13 @@
 //     whole cache lines per DMA lane group (the faster choice wherever 2 x tile fits the LDS budget).
 //   * K order: channel chunk outer, filter tap inner (dense); natural [tap][channel] order, 1-4 taps per 128 B
 //     row, rulebook entries fetched one tile ahead (gather).
-//   * per DMA slot ONE precomputed pointer (tap (0,0)) and ONE tap-validity bitmask; per K tile a slot costs a
-//     64-bit add of a wave-uniform offset, a bit test and a select.
-//   * LDS rows are unpadded (the DMA writes wave-uniform base + lane*16); bank conflicts are removed
-//     by an XOR swizzle applied to the SOURCE address: 16 B chunk c of row r is stored at chunk slot
-//     c ^ f(r), f(r) = (r>>1)&7 for 128 B rows, (r>>2)&3 for 64 B rows -- every 16-lane
-//     group of ds_read_b128 then touches 16 distinct slots of the 256 B bank row.
-//   * rows that are padding / beyond M / beyond K read from a 16 B zero page instead of branching.
-//   * XCD-aware tile order: workgroups that share an A row-block are consecutive on ONE XCD (its L2).
+//   * the pieces shared with the kernels derived from this one are defined in conv_lds_dma.h: per DMA slot ONE precomputed
+//     pointer (tap (0,0)) and ONE tap-validity bitmask, the XOR swizzle applied to the DMA SOURCE address, the zero page that
+//     rows which are padding / beyond M / beyond K read instead of branching, the XCD-aware tile order.
 // Requires: Cin % BK == 0 (dense: one tap per K tile) or power-of-two Cin >= 16 (gather); KH*KW <= 32; no split-K.
-#include <stdlib.h>
-
-#include "conv_common.h"
+#include "conv_lds_dma.h"
 
 namespace tt {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // Timing experiments only (tools/conv_microbench.py, TT_MB_ACT=97/98 on the 2-stage variants): skip the weight /
 // activation DMA after the first K tile to see how much of the loop time is the L2->LDS stream.  0 in the product.
@@ -97,16 +88,11 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
         const int md = *p.m_dev;
         Mlim = md < Mlim ? md : Mlim;
     }
-    // XCD-aware remap (bijective for any grid size): hardware places block b on XCD b % 8.  Sparse launches cover the
-    // ALLOCATED rows: remap over the live row tiles only, or whole XCDs end up holding nothing but dead tiles
+    // sparse launches cover the ALLOCATED rows: the tile order is dealt over the live row tiles only
     const int live_m = (GATHER && p.m_dev) ? (Mlim - p.m_begin + BM - 1) / BM : tiles_m;
     const int nblk = (live_m < tiles_m ? (live_m > 0 ? live_m : 0) : tiles_m) * tiles_n;
     if ((int)blockIdx.x >= nblk) return;               // block-uniform, before any barrier
-    int L;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = nblk >> 3, r = nblk & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int L = xcd_tile(nblk);
     const int tile_n = L % tiles_n, tile_m = L / tiles_n;
     const int m0 = p.m_begin + tile_m * BM, n0 = tile_n * BN;
     if (m0 >= Mlim) return;            // block-uniform, before any barrier
@@ -117,52 +103,25 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
     const T* __restrict__ wgt = reinterpret_cast<const T*>(p.weight);
     const T* zp = reinterpret_cast<const T*>(zero_page);
 
-    auto swz = [](int row) { return (BKB == 64) ? ((row >> 2) & 3) : ((row >> 1) & 7); };
-
-    // ---- per-thread DMA slots: A slot j covers LDS chunk g = (wave + 8*j)*64 + lane of the A tile
-    int a_h0[NIA], a_w0[NIA], a_c[NIA];
+    // ---- per-thread DMA slots: A slot j covers LDS chunk g = (wave + NW*j)*64 + lane of the A tile.  Dense: one pointer + one
+    // tap mask (dense_slot).  GATHER: the chunk's element offset inside the K tile, the slot's rulebook row and whether it is live
+    int a_c[NIA];
     long long a_base[NIA];
     bool a_ok[NIA];
+    const T* a_ptr[NIA];
+    unsigned a_mask[NIA];
 #pragma unroll
     for (int j = 0; j < NIA; ++j) {
         const int g = (wave + NW * j) * 64 + lane;
-        const int row = g / CPR, pos = g % CPR;
-        a_c[j] = (pos ^ swz(row)) * VEC;               // element offset of the global chunk inside the K tile
-        const int m = m0 + row;
-        a_ok[j] = m < Mlim;
-        const int mm = a_ok[j] ? m : 0;
-        const int n = mm / (p.OH * p.OW);
-        const int r = mm - n * (p.OH * p.OW);
-        const int oh = r / p.OW, ow = r - oh * p.OW;
-        a_h0[j] = oh * p.stride - p.pad;
-        a_w0[j] = ow * p.stride - p.pad;
-        // GATHER: rulebook row; with a tile plan the tile's slot `mm` stands for output row row_perm[mm]
-        a_base[j] = GATHER ? (long long)((p.row_perm && a_ok[j]) ? p.row_perm[mm] : mm) * p.KW
-                           : (long long)n * p.in_nstride + p.in_coff;
-    }
-    // Dense path: everything about a slot that does not change over the K loop is folded into ONE pointer (the
-    // chunk's address for tap (0,0), possibly outside the image) and ONE bitmask (bit t = tap t of this row is
-    // inside the image; KH*KW <= 32, dispatcher).  Per K tile a slot then costs a 64-bit add of a wave-uniform
-    // tap offset, a bit test and a select -- the per-tile im2col arithmetic was ~2/3 of the kernel's VALU issue
-    // (SQ_INSTS_VALU 5.6 per MFMA, profiles/r01_conv_sq_counters.txt).
-    const T* a_ptr[NIA];
-    unsigned a_mask[NIA];
-    if (!GATHER) {
-#pragma unroll
-        for (int j = 0; j < NIA; ++j) {
-            a_ptr[j] = in + a_base[j] + ((long long)a_h0[j] * p.W + a_w0[j]) * p.in_cstride + a_c[j];
-            unsigned mk = 0;
-            if (a_ok[j]) {
-                int tbit = 0;
-                for (int kh = 0; kh < p.KH; ++kh) {
-                    const int ih = a_h0[j] + kh * p.dil;
-                    for (int kw = 0; kw < p.KW; ++kw, ++tbit) {
-                        const int iw = a_w0[j] + kw * p.dil;
-                        if (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W) mk |= 1u << tbit;
-                    }
-                }
-            }
-            a_mask[j] = mk;
+        if constexpr (GATHER) {
+            const int row = g / CPR, pos = g % CPR;
+            a_c[j] = (pos ^ swz<BKB>(row)) * VEC;
+            a_ok[j] = m0 + row < Mlim;
+            const int mm = a_ok[j] ? m0 + row : 0;
+            // with a tile plan the tile's slot `mm` stands for output row row_perm[mm]
+            a_base[j] = (long long)((p.row_perm && a_ok[j]) ? p.row_perm[mm] : mm) * p.KW;
+        } else {
+            dense_slot<BKB>(p, in, g, m0, Mlim, a_ptr[j], a_mask[j]);
         }
     }
     int b_c[NIB];
@@ -173,7 +132,7 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
     for (int j = 0; j < NIB; ++j) {
         const int g = ((wave + NW * j) % NB_INSTR) * 64 + lane;
         const int row = g / CPR, pos = g % CPR;
-        b_c[j] = (pos ^ swz(row)) * VEC;
+        b_c[j] = (pos ^ swz<BKB>(row)) * VEC;
         b_ok[j] = (n0 + row) < p.Cout;
         b_base[j] = (long long)(n0 + row) * p.K;
         b_ptr[j] = wgt + b_base[j] + b_c[j];
@@ -181,13 +140,7 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
 
     int nk = (p.K + BK - 1) / BK;
 
-    // K order: channel chunk OUTER, filter tap INNER (Cin % BK == 0: one tap per K tile).  The KH*KW taps of one
-    // BK-channel chunk re-read the same (tile + halo) pixels back to back, so the re-reads hit the XCD's 4 MiB L2
-    // (64 resident tiles x ~700 px x 128 B lines = ~2 MiB with the XCD-contiguous tile order).  With taps outer the
-    // reuse distance was the whole channel extent (~8 MiB per XCD for Cin = 256) and 8 of 9 reads fell through to
-    // the Infinity Cache.  Summation order differs from (tap, channel) only in f32 rounding.
-    int it_kh = 0, it_kw = 0, it_ci = 0;               // running (kh, kw, ci) of the next tile to issue
-    // GATHER (sparse conv) walks K in natural [tap][channel] order; a K tile covers BK/Cin taps when Cin < BK
+    // Dense: K order of conv_lds_dma.h (KWalk).  GATHER (sparse conv) walks K in natural [tap][channel] order; a K tile covers BK/Cin taps when Cin < BK
     // (each 16 B chunk of a row then comes from its own tap's input row) or a BK-channel slice of one tap.
     // Cin is a power of two there (dispatcher): tap / channel by shift and mask, not integer division.
     int g_cur[NIA];                                    // rulebook entries of the next tile to issue
@@ -262,15 +215,8 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
         }
         ++g_t;
     };
-    // The activation and the weight stream walk the same (channel chunk, tap) sequence; with the asymmetric ring the
-    // activation walker runs one tile ahead of the weight walker, so each keeps its own position.
-    // The LDS destination of a DMA instruction is wave-uniform (it goes to M0): keep it in scalar registers instead of
-    // deriving it from threadIdx through a VALU add + v_readfirstlane per load.
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     const unsigned lds_dma_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    struct KWalk {
-        int kh, kw, ci;
-    };
     KWalk wa{0, 0, 0}, wb{0, 0, 0};
     if (!GATHER && p.splits > 1) {
         // split-K (few rows, long K: gridDim.y K ranges): this workgroup owns K tiles [kt0, kt1) of the (channel chunk outer, tap
@@ -287,15 +233,6 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
         wa.kw = wb.kw = tap - (tap / p.KW) * p.KW;
         nk = kt1 > kt0 ? kt1 - kt0 : 0;
     }
-    auto advance = [&](KWalk& w) {
-        if (++w.kw == p.KW) {
-            w.kw = 0;
-            if (++w.kh == p.KH) {
-                w.kh = 0;
-                w.ci += BK;
-            }
-        }
-    };
     auto issue_a = [&](int kt) {
         const unsigned st = lds_dma_base + (unsigned)off_a(kt);
         const int kh = wa.kh, kw = wa.kw, ci = wa.ci;
@@ -303,7 +240,7 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
         // wave-uniform (SALU): tap index and the element offset of tap (kh, kw), channel ci from tap (0, 0), channel 0
         const int tap = kh * p.KW + kw;
         const long long tap_off = ((long long)(kh * p.dil) * p.W + kw * p.dil) * p.in_cstride + ci;
-        advance(wa);
+        advance<BK>(wa, p);
         const bool dbg_skip_a = TT_GLDS_DEBUG && p.act == 98 && kt > 0;
 #pragma unroll
         for (int j = 0; j < NIA; ++j) {
@@ -318,14 +255,14 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
             } else {
                 src = ((a_mask[j] >> tap) & 1u) ? a_ptr[j] + tap_off : zp;
             }
-            __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
+            dma_piece(src, st + (unsigned)(wave_s + NW * j) * 1024u);
         }
     };
     auto issue_b = [&](int kt) {
         const unsigned st = lds_dma_base + (unsigned)off_b(kt);
         const int k0 = GATHER ? kt * BK                // position of this tile in the [KH][KW][Cin] weight row
                               : (wb.kh * p.KW + wb.kw) * p.Cin + wb.ci;
-        advance(wb);
+        advance<BK>(wb, p);
         const bool dbg_skip_b = TT_GLDS_DEBUG && p.act == 97 && kt > 0;
         int tpi[TPTMAX];
         if (planned) next_taps(wi, tpi);
@@ -340,8 +277,7 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
                 ok = b_ok[j] && t >= 0;
                 src = ok ? b_ptr[j] - b_c[j] + (long long)t * p.Cin + ((k0 + b_c[j]) & cin_mask) : zp;
             }
-            __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(st + (unsigned)((wave_s + NW * j) % NB_INSTR) * 1024u),
-                                             16, 0, 0);
+            dma_piece(src, st + (unsigned)((wave_s + NW * j) % NB_INSTR) * 1024u);
         }
     };
     auto issue_tile = [&](int kt) {
@@ -358,51 +294,15 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
         }
     };
 
-    // The same DMA, one instruction at a time (dense bf16x3 body): when all eight waves issue their 8 pieces of the next tile
-    // together right after the barrier, the CU's one texture path (64 B/clk: 16 clk per 1 KiB piece) queues 64 pieces and every
-    // wave sits ~1000 cycles in instruction issue before its first MFMA.  Spread over the sub-steps of the tile -- one piece
-    // behind each group of MFMAs -- the queue never fills.  Order of issue is unchanged (weights of tile kt+1, then
-    // activations of kt+2), so the counted waits at the top of the next tile still hold.
-    struct DmaCtx {
-        unsigned st;
-        int tap, k0;
-        long long tap_off;
-        bool on;
-    };
-    auto a_begin = [&](int kt, bool on) {
-        DmaCtx c{0u, 0, 0, 0, on};
-        if (!on) return c;
-        c.st = lds_dma_base + (unsigned)off_a(kt);
-        c.tap = wa.kh * p.KW + wa.kw;
-        c.tap_off = ((long long)(wa.kh * p.dil) * p.W + wa.kw * p.dil) * p.in_cstride + wa.ci;
-        advance(wa);
-        return c;
-    };
-    auto a_emit = [&](const DmaCtx& c, int j) {
-        const T* src = ((a_mask[j] >> c.tap) & 1u) ? a_ptr[j] + c.tap_off : zp;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(c.st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
-    };
-    auto b_begin = [&](int kt, bool on) {
-        DmaCtx c{0u, 0, 0, 0, on};
-        if (!on) return c;
-        c.st = lds_dma_base + (unsigned)off_b(kt);
-        c.k0 = (wb.kh * p.KW + wb.kw) * p.Cin + wb.ci;
-        advance(wb);
-        return c;
-    };
-    auto b_emit = [&](const DmaCtx& c, int j) {
-        const T* src = b_ok[j] ? b_ptr[j] + c.k0 : zp;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(c.st + (unsigned)((wave_s + NW * j) % NB_INSTR) * 1024u),
-                                         16, 0, 0);
-    };
+    // The same DMA, one instruction at a time (dense bf16x3 body; conv_lds_dma.h "spread").  Order of issue is unchanged (weights
+    // of tile kt+1, then activations of kt+2), so the counted waits at the top of the next tile still hold.
+    auto a_begin = [&](int kt, bool on) { return dma_begin_a<BK>(p, wa, lds_dma_base + (unsigned)off_a(kt), on); };
+    auto b_begin = [&](int kt, bool on) { return dma_begin_b<BK, 1>(p, wb, lds_dma_base + (unsigned)off_b(kt), on); };
+    auto a_emit = [&](const DmaCtx& c, int j) { dma_emit_a(c, a_ptr[j], a_mask[j], zp, wave_s + NW * j); };
+    auto b_emit = [&](const DmaCtx& c, int j) { dma_emit_b(c, b_ptr[j], b_ok[j], zp, (wave_s + NW * j) % NB_INSTR); };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     if (GATHER && nk > 0) fetch_rulebook();
     if (nk > 0) issue_tile(0);
@@ -410,11 +310,9 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
     if (STAGES == 3 && nk > 1) issue_tile(1);
     if (ASYM && nk > 1) issue_a(1);
 
-    // fragment addressing: row = tile row + (lane&31); 16 B chunk c16 = 2*kc + (lane>>5), swizzled.
-    // The fragment reads are INLINE ASM: hipcc treats every ds_read of this array as aliasing the
-    // in-flight LDS-DMA and would insert `s_waitcnt vmcnt(0)` in front of it (draining the two tiles
-    // of prefetch every iteration); asm reads are invisible to that pass, ordering is by the counted
-    // vmcnt + barrier above (MI355X_MICROARCH.md "Two waves per SIMD" item 7).
+    // fragment addressing: row = tile row + (lane&31); 16 B chunk c16 = 2*kc + (lane>>5), swizzled -- conv_lds_dma.h's frag_off with the
+    // row term and the swizzle term of a row kept apart (written through frag_off, the first tile's block of 20 of these kernels came
+    // out of the compiler with other instruction counts; this form leaves every MFMA block as it was)
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     unsigned fa_off[TM], fb_off[TN], fa_s[TM], fb_s[TN];
     const unsigned hi = lane >> 5;
@@ -422,15 +320,14 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
     for (int i = 0; i < TM; ++i) {
         const int row = wm * WTM + i * 32 + (lane & 31);
         fa_off[i] = row * BKB;
-        fa_s[i] = swz(row);
+        fa_s[i] = swz<BKB>(row);
     }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int row = wn * WTN + j * 32 + (lane & 31);
         fb_off[j] = BM * BKB + row * BKB;
-        fb_s[j] = swz(row);
+        fb_s[j] = swz<BKB>(row);
     }
-    // swizzled fragment offsets inside a stage for every k-step: registers instead of 3 VALU per read per step
     // X3: a k-step is 16 f32 = 64 B.  A: lane half h owns floats 8h..8h+7 = chunks 4kc+2h and 4kc+2h+1 (the second is
     // the first with address bit 4 flipped, the swizzle being an XOR); B: hi chunk 4kc+h, lo chunk 4kc+2+h (bit 5).
     constexpr int NKC_ = X3 ? BKB / 64 : BKB / 32;
@@ -448,38 +345,13 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
 #pragma unroll
         for (int j = 0; j < TN; ++j) fb_pre[kc][j] = fb_off[j] + ((cb ^ fb_s[j]) << 4);
     }
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    auto lds_read = [](unsigned addr) {
-        u32x4 v;
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-#else
-        v = u32x4{addr, 0, 0, 0};   // host pass only parses this kernel
-#endif
-        return v;
-    };
 
     for (int kt = 0; kt < nk; ++kt) {
         // tile kt has landed for THIS wave once at most one younger tile (LPT loads) is outstanding
-#if defined(__HIP_DEVICE_COMPILE__)
-        if (ASYM && kt + 1 < nk) {                     // outstanding in issue order: A(kt) B(kt) A(kt+1)
-            if constexpr (NIA == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if constexpr (NIA == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else if constexpr (NIA == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else if (STAGES == 3 && kt + 1 < nk) {
-            if constexpr (LPT == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if constexpr (LPT == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else if constexpr (LPT == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else if constexpr (LPT == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-            else if constexpr (LPT == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if constexpr (LPT == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        if (ASYM && kt + 1 < nk) wait_vmcnt<NIA>();                 // outstanding in issue order: A(kt) B(kt) A(kt+1)
+        else if (STAGES == 3 && kt + 1 < nk) wait_vmcnt<LPT>();
+        else wait_vmcnt<0>();
         asm volatile("s_barrier" ::: "memory");   // publishes tile kt; everyone is done reading tile kt-1
-#endif
         if (tr && kt == 0) tr[1] = (long long)wall_clock64();
 
         // fragment offsets carry the activation / weight split of a symmetric stage (weights at + A_BYTES): the two bases
@@ -527,7 +399,7 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
             bl[0] = lds_read(sbase_b + (fb_pre[0][0] ^ 32u));
             constexpr bool SPREAD = !GATHER;
             constexpr int PER = (NIA + NIB + NS - 1) / NS;         // DMA pieces per sub-step
-            DmaCtx ca{0u, 0, 0, 0, false}, cb{0u, 0, 0, 0, false};
+            DmaCtx ca{0u, 0, 0, false}, cb{0u, 0, 0, false};
             if constexpr (SPREAD) {
                 if (spread) {
                     // first pieces issued: weights (ASYM: of tile kt+1; else of kt+STAGES-1, after its activations)
@@ -619,7 +491,6 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
         for (int kc = 0; kc < NKC; ++kc) {
             const int cur = kc & 1, nxt = cur ^ 1;
             // wait for the fragments of step kc; tie the wait to the registers the MFMAs read
-#if defined(__HIP_DEVICE_COMPILE__)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // volatile asms stay in order: these empty ones come after the wait, and the MFMAs below
             // consume their outputs, so no MFMA can be scheduled above the wait
@@ -627,7 +498,6 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
             for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(fa[cur][i]));
 #pragma unroll
             for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(fb[cur][j]));
-#endif
             if (kc + 1 < NKC) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i) fa[nxt][i] = lds_read(sbase + fa_pre[kc + 1][i]);
@@ -669,19 +539,14 @@ static int launch_glds(ConvArgs& a, hipStream_t st, int m_tiles_limit = 0, int s
     size_t smem = STAGES == 23 ? (size_t)(3 * BM + 2 * BN) * BKB : (size_t)STAGES * (BM + BN) * BKB;
     const size_t epi = (size_t)(WAVES_M * WAVES_N) * 32 * (WTN + 4) * 4;
     if (smem < epi) smem = epi;
-    auto kern = conv_igemm_glds_kernel<T, BN, WAVES_M, WAVES_N, BKB, STAGES, GATHER, X3, APAIR>;
-    const void* zp = zero_page("conv_igemm_glds_kernel");
-    if (!zp || lds_opt_in(reinterpret_cast<const void*>(kern), smem, "conv_igemm_glds_kernel")) return -1;
-    a.tiles_n = tiles_n;
-    a.splits = splits;
-    if (splits <= 1) a.ws = nullptr;       // split-K: a.ws / a.ws_slices are the caller's (ordered slices, `slices` non-empty ranges)
-    if (a.m_begin == 0)      // (the tail launch of a split keeps the main launch's label)
-        snprintf(g_conv_kernel, sizeof(g_conv_kernel), "conv_igemm_glds_kernel<%s, %d, %d, %d, %d, %d, %s, %s>%s%s",
-                 sizeof(T) == 4 ? "float" : "16-bit", BN, WAVES_M, WAVES_N, BKB, STAGES, GATHER ? "true" : "false",
-                 X3 ? "true" : "false", APAIR ? " pre-split A" : "", splits > 1 ? " split-K" : (m_tiles_limit > 0 ? " + tail" : ""));
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n), (unsigned)(splits > 1 ? slices : 1)),
-                       dim3(WAVES_M * WAVES_N * 64), smem, st, a, zp, tiles_m, tiles_n);
-    return 1;
+    char label[96];      // (the tail launch of a split keeps the main launch's label: launch_lds_dma)
+    snprintf(label, sizeof(label), "conv_igemm_glds_kernel<%s, %d, %d, %d, %d, %d, %s, %s>%s%s", sizeof(T) == 4 ? "float" : "16-bit", BN,
+             WAVES_M, WAVES_N, BKB, STAGES, GATHER ? "true" : "false", X3 ? "true" : "false", APAIR ? " pre-split A" : "",
+             splits > 1 ? " split-K" : (m_tiles_limit > 0 ? " + tail" : ""));
+    // split-K: a.ws / a.ws_slices are the caller's (ordered slices, `slices` non-empty ranges)
+    return launch_lds_dma(conv_igemm_glds_kernel<T, BN, WAVES_M, WAVES_N, BKB, STAGES, GATHER, X3, APAIR>,
+                          dim3((unsigned)(tiles_m * tiles_n), (unsigned)(splits > 1 ? slices : 1)), dim3(WAVES_M * WAVES_N * 64), smem, smem,
+                          "conv_igemm_glds_kernel", label, a, st, tiles_m, tiles_n, splits);
 }
 
 // Tail split of a 256x256-tile launch.  With T tiles on 256 CUs (one workgroup per CU: 128 KiB of LDS) the launch
@@ -785,7 +650,7 @@ int try_launch_conv_glds_x3(ConvArgs& a, hipStream_t st) {
     // 8-wave tile: there the tile's prologue + epilogue dominate and eight waves issue the output stores faster than four
     // (K = 1024: 0.203 vs 0.216 ms, K = 256 N = 1280: 0.52 vs 0.77 ms; profiles/r04_pipe_ab_first.txt).
     // TT_X3_PIPE=0 (test hook: tests/test_conv.py compares the two families bit for bit): the compiler-scheduled tiles everywhere
-    static const bool pipe = [] { const char* e = getenv("TT_X3_PIPE"); return e ? atoi(e) != 0 : true; }();
+    static const bool pipe = env_flag("TT_X3_PIPE", true);
     const bool hand = pipe && a.K >= 1152;
     if (bn == 256) {                                                                                           // 8 x (64 x 128)
         const int main_rows = tail_split_rows(a);

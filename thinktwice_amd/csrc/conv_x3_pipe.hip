@@ -1,6 +1,6 @@
 // bf16x3 implicit-GEMM convolution, 256 x 256 tile, FOUR waves of 128 x 128: one wave per SIMD, hand-pipelined K loop.
 //
-// Same arithmetic, operand formats, LDS image (XOR swizzle on the DMA source address) and epilogue as the X3 body of
+// Same arithmetic, operand formats, LDS image (the pipeline of conv_lds_dma.h) and epilogue as the X3 body of
 // conv_igemm_glds.hip (f32 activations split into bf16 (hi, lo) in registers, pre-split pair-format weights, three
 // v_mfma_f32_32x32x16_bf16 per product: a_lo*b_hi, a_hi*b_lo, a_hi*b_hi, f32 accumulate) -- results are bit-identical
 // to that kernel's.  What differs is who overlaps what.  The 8-wave tile keeps two waves per SIMD that run in lock step:
@@ -21,14 +21,9 @@
 // hazards it would pad are spaced by construction or by explicit s_nop); the split and the address arithmetic are
 // plain C++ pinned into their gap by empty asm statements on their inputs / outputs.
 // Contract (dispatcher in conv_igemm_glds.hip): dense conv, f32 storage, Cin % 32 == 0, Cout % 256 == 0, KH*KW <= 31.
-#include <stdlib.h>
-
-#include "conv_common.h"
+#include "conv_lds_dma.h"
 
 namespace tt {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef TT_PIPE_DEBUG
 #define TT_PIPE_DEBUG 0
@@ -60,14 +55,9 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int Mlim = p.M;
 
-    // XCD-aware tile order (bijective), as in conv_igemm_glds.hip
     const int nblk = tiles_m * tiles_n;
     if ((int)blockIdx.x >= nblk) return;
-    int L;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = nblk >> 3, r = nblk & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int L = xcd_tile(nblk);
     const int tile_n = L % tiles_n, tile_m = L / tiles_n;
     const int m0 = p.m_begin + tile_m * BM, n0 = tile_n * BN;
     if (m0 >= Mlim) return;
@@ -75,43 +65,18 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
     const float* __restrict__ in = reinterpret_cast<const float*>(p.in);
     const float* __restrict__ wgt = reinterpret_cast<const float*>(p.weight);
     const float* zp = reinterpret_cast<const float*>(zero_page);
-    auto swz = [](int row) { return (row >> 1) & 7; };
 
     // ---- DMA slots.  Activation slot j of this wave = 1 KiB piece (wave + 4 j) of the tile: 8 rows x 8 chunks.
     const float* a_ptr[NIA];            // the chunk's address for tap (0, 0), channel 0 (possibly outside the image)
     unsigned a_mask[NIA];               // bit t: tap t of this row lies inside the image (bit 31 never set)
 #pragma unroll
-    for (int j = 0; j < NIA; ++j) {
-        const int g = (wave + NW * j) * 64 + lane;
-        const int row = g >> 3, pos = g & 7;
-        const int c = (pos ^ swz(row)) * 4;
-        const int m = m0 + row;
-        const bool ok = m < Mlim;
-        const int mm = ok ? m : 0;
-        const int n = mm / (p.OH * p.OW);
-        const int r = mm - n * (p.OH * p.OW);
-        const int oh = r / p.OW, ow = r - oh * p.OW;
-        const int h0 = oh * p.stride - p.pad, w0 = ow * p.stride - p.pad;
-        a_ptr[j] = in + (long long)n * p.in_nstride + p.in_coff + ((long long)h0 * p.W + w0) * p.in_cstride + c;
-        unsigned mk = 0;
-        if (ok) {
-            int tbit = 0;
-            for (int kh = 0; kh < p.KH; ++kh) {
-                const int ih = h0 + kh * p.dil;
-                for (int kw = 0; kw < p.KW; ++kw, ++tbit) {
-                    const int iw = w0 + kw * p.dil;
-                    if (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W) mk |= 1u << tbit;
-                }
-            }
-        }
-        a_mask[j] = mk;
-    }
+    for (int j = 0; j < NIA; ++j) dense_slot<BKB>(p, in, (wave + NW * j) * 64 + lane, m0, Mlim, a_ptr[j], a_mask[j]);
     // Weight slot j = piece (wave + 4 j) of the 256-row weight tile: rows 32 j apart, one pointer + a uniform stride.
     const float* b_ptr0;
     {
         const int g = wave * 64 + lane;
         const int row = g >> 3, pos = g & 7;
-        b_ptr0 = wgt + (long long)(n0 + row) * p.K + (pos ^ swz(row)) * 4;
+        b_ptr0 = wgt + (long long)(n0 + row) * p.K + (pos ^ swz<BKB>(row)) * 4;
     }
     const long long b_jstride = (long long)(NW * 8) * p.K;        // elements between consecutive slots of a wave
 
@@ -123,7 +88,10 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
 
     // ---- the two DMA walkers (wave-uniform, SALU).  K order: channel chunk outer, filter tap inner.  Everything a tile
     // needs is kept incrementally -- tap index, element offset from the slot pointer, ring stage -- and advanced by
-    // compare + select (no branches: the loop body stays one basic block, its instruction order is the schedule).
+    // compare + select (no branches: the loop body stays one basic block, its instruction order is the schedule).  They are lambdas
+    // of the kernel, here and in conv_h2_pipe_kernel, not functions of conv_lds_dma.h: as members of a struct, and as free functions
+    // over the same scalars, the compiler made another loop of them (conv_h2_pipe_kernel: one block of 328 instructions instead of
+    // 17 + 296, 81 scalar instructions instead of 65, longest run between two MFMAs 19 instead of 14).
     const int ntaps = p.KH * p.KW;
     const long long a_d1 = (long long)p.dil * p.in_cstride;                                         // kw + 1
     const long long a_d2 = ((long long)p.dil * p.W - (long long)(p.KW - 1) * p.dil) * p.in_cstride;  // kw -> 0, kh + 1
@@ -170,20 +138,15 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
     auto a_emit = [&](int j) {
         const int tapbit = a_rem > 0 ? a_tap : 31;
         const float* src = ((a_mask[j] >> tapbit) & 1u) ? a_ptr[j] + a_off : zp;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(a_st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
+        dma_piece(src, a_st + (unsigned)(wave_s + NW * j) * 1024u);
     };
     auto b_emit = [&](int j) {
         const float* src = b_ptr0 + b_off + (long long)j * b_jstride;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(b_st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
+        dma_piece(src, b_st + (unsigned)(wave_s + NW * j) * 1024u);
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // ---- fragment offsets inside a stage.  A: row = lane & 31 of the row block, lane half h owns floats 8h .. 8h+7 of the
     // 16-wide K step = 16 B chunks 4 kc + 2 h and that + 1 (address ^ 16); B: hi chunk 4 kc + h, lo chunk that + 2 (^ 32).
@@ -192,21 +155,10 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int row = wm * WTM + i * 32 + (lane & 31);
-            fa_pre[kc][i] = row * BKB + (((4u * kc + (APAIR ? hi : 2u * hi)) ^ swz(row)) << 4);
-        }
+        for (int i = 0; i < TM; ++i) fa_pre[kc][i] = frag_off<BKB>(wm * WTM + i * 32 + (lane & 31), 4u * kc + (APAIR ? hi : 2u * hi));
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int row = wn * WTN + j * 32 + (lane & 31);
-            fb_pre[kc][j] = row * BKB + (((4u * kc + hi) ^ swz(row)) << 4);
-        }
+        for (int j = 0; j < TN; ++j) fb_pre[kc][j] = frag_off<BKB>(wn * WTN + j * 32 + (lane & 31), 4u * kc + hi);
     }
-    auto lds_read = [](unsigned addr) {
-        u32x4 v;
-        asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-        return v;
-    };
 // Timing ablations (tools/build_pipe_debug.sh; results are wrong by design): TT_PIPE_DEBUG bit 0 no DMA in the loop, bit 1 no
 // operand split, bit 2 no MFMA, bit 3 no fragment reads in the loop, bit 4 no tile barrier
 #if TT_PIPE_DEBUG & 4
@@ -239,9 +191,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
             b_walk1(); b_walk2();
         }
         // tile 0 has landed for this wave once only tile 1's pieces (NIA + NIB) are outstanding
-        if constexpr (NIA + NIB == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if constexpr (NIA + NIB == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<NIA + NIB>();
         asm volatile("s_barrier" ::: "memory");
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -484,11 +434,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
     const int Mlim = p.M;
     const int nblk = tiles_m * tiles_n;
     if ((int)blockIdx.x >= nblk) return;
-    int L;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = nblk >> 3, r = nblk & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int L = xcd_tile(nblk);
     const int tile_n = L % tiles_n, tile_m = L / tiles_n;
     const int m0 = p.m_begin + tile_m * BM, n0 = tile_n * BN;
     if (m0 >= Mlim) return;
@@ -496,7 +442,6 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
     const float* __restrict__ in = reinterpret_cast<const float*>(p.in);
     const float* __restrict__ wgt = reinterpret_cast<const float*>(p.weight);
     const float* zp = reinterpret_cast<const float*>(zero_page);
-    auto swz = [](int row) { return (row >> 1) & 7; };
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const unsigned ldsB = lds_base + 2u * RUN_BYTES;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
@@ -512,7 +457,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
         const int g = (wave + NW * j) * 64 + lane;
         const int q = g >> 3, pos = g & 7;
         const long long G0 = (long long)m0 - p.W - 1 + q;
-        a_ptr[j] = in + p.in_coff + G0 * p.in_cstride + (pos ^ swz(q)) * 4;
+        a_ptr[j] = in + p.in_coff + G0 * p.in_cstride + (pos ^ swz<BKB>(q)) * 4;
         unsigned mk = 0;
         for (int kh = 0; kh < p.KH; ++kh) {
             const long long G = G0 + (long long)kh * p.W;
@@ -524,7 +469,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
     {
         const int g = wave * 64 + lane;
         const int row = g >> 3, pos = g & 7;
-        b_ptr0 = wgt + (long long)(n0 + row) * p.K + (pos ^ swz(row)) * 4;
+        b_ptr0 = wgt + (long long)(n0 + row) * p.K + (pos ^ swz<BKB>(row)) * 4;
     }
     const long long b_jstride = (long long)(NW * 8) * p.K;
 
@@ -536,7 +481,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
     for (int i = 0; i < TM; ++i) {
         const int row = wm * WTM + i * 32 + (lane & 31);
         const int m = m0 + row;
-        unsigned mk = 0;
+        unsigned mk = 0;          // (its own loop: KW = 3, stride 1, dilation 1, pad 1 are the dispatcher's contract and constants here)
         if (m < Mlim) {
             const int n = m / (p.OH * p.OW);
             const int r = m - n * (p.OH * p.OW);
@@ -552,18 +497,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
-            for (int kc = 0; kc < 2; ++kc) {
-                const int q = row + kw;
-                fa_run[kw][kc][i] = q * BKB + (((4u * kc + (APAIR ? hi : 2u * hi)) ^ swz(q)) << 4);
-            }
+            for (int kc = 0; kc < 2; ++kc) fa_run[kw][kc][i] = frag_off<BKB>(row + kw, 4u * kc + (APAIR ? hi : 2u * hi));
     }
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int row = j * 32 + (lane & 31);
-            fb_pre[kc][j] = row * BKB + (((4u * kc + hi) ^ swz(row)) << 4);
-        }
+        for (int j = 0; j < TN; ++j) fb_pre[kc][j] = frag_off<BKB>(j * 32 + (lane & 31), 4u * kc + hi);
 
     const int nk = p.K / BK, nruns = nk / 3;
     const int ntaps = p.KH * 3;
@@ -583,7 +522,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
     auto run_emit = [&](int j) {
         const int bit = r_rem > 0 ? r_kh : 31;
         const float* src = ((a_mask[j] >> bit) & 1u) ? a_ptr[j] + r_off : zp;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(r_st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
+        dma_piece(src, r_st + (unsigned)(wave_s + NW * j) * 1024u);
     };
     // weight walker: per tile, tap inner
     const long long b_d1 = p.Cin, b_e2 = (BK - (long long)(ntaps - 1) * p.Cin) - b_d1;
@@ -603,22 +542,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
     };
     auto b_emit = [&](int j) {
         const float* src = b_ptr0 + b_off + (long long)j * b_jstride;
-        __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(uintptr_t)(b_st + (unsigned)(wave_s + NW * j) * 1024u), 16, 0, 0);
+        dma_piece(src, b_st + (unsigned)(wave_s + NW * j) * 1024u);
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
-    auto lds_read = [](unsigned addr) {
-        u32x4 v;
-        asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-        return v;
-    };
     auto split_a = [](float x0, float x1, uint32_t& h, float& t0, float& t1) {
         h = pack_bf16x2(x0, x1);
         t0 = __uint_as_float(h << 16);
@@ -641,8 +570,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
             for (int j = 0; j < NIB; ++j) b_emit(j);
             b_walk1(); b_walk2();
         }
-        if constexpr (NIB == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // only weight tile 1 outstanding
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        wait_vmcnt<NIB>();                               // only weight tile 1 outstanding
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -844,28 +772,21 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
 int try_launch_conv_x3_pipe(ConvArgs& a, hipStream_t st, int m_tiles_limit, int bn) {
     const bool apair = (a.flags & 32) != 0;          // pre-split activations (tt_conv_desc.in_pair)
     if (a.gather || a.m_dev || (bn != 256 && bn != 128) || a.Cout % bn != 0 || a.Cin % 32 != 0 || a.KH * a.KW > 31 || a.K < 64) return 0;
-    const void* zp = zero_page("conv_x3_pipe_kernel");
-    if (!zp) return -1;
     int tiles_m = div_up(a.M - a.m_begin, 256);
     if (m_tiles_limit > 0 && m_tiles_limit < tiles_m) tiles_m = m_tiles_limit;
     const int tiles_n = a.Cout / bn;
+    char label[96];
     // 3 x 3 stride-1 "same" convolutions over a dense batch: the run-staged form (one staged pixel run per filter row serves
     // its three taps).  TT_X3_RUN3=0 (test hook: tests/test_conv.py compares the two forms bit for bit): the per-tap form everywhere
-    static const bool run3 = [] { const char* e = getenv("TT_X3_RUN3"); return e ? atoi(e) != 0 : true; }();
+    static const bool run3 = env_flag("TT_X3_RUN3", true);
     if (run3 && a.KW == 3 && a.KH <= 5 && a.stride == 1 && a.dil == 1 && a.pad == 1 && a.OH == a.H && a.OW == a.W &&
         (a.N == 1 || a.in_nstride == (long long)a.H * a.W * a.in_cstride)) {
         const size_t smem_r = (size_t)2 * 288 * 128 + (size_t)2 * bn * 128 + 256;
         auto kr = bn == 128 ? (apair ? conv_x3_run3_kernel<128, true> : conv_x3_run3_kernel<128>)
                             : (apair ? conv_x3_run3_kernel<256, true> : conv_x3_run3_kernel<256>);
-        if (lds_opt_in(reinterpret_cast<const void*>(kr), smem_r, "conv_x3_run3_kernel")) return -1;
-        a.tiles_n = tiles_n;
-        a.splits = 1;
-        a.ws = nullptr;
-        if (a.m_begin == 0)
-            snprintf(g_conv_kernel, sizeof(g_conv_kernel), "conv_x3_run3_kernel<%d>%s%s", bn, apair ? " pre-split A" : "",
-                     m_tiles_limit > 0 ? " + tail" : "");
-        hipLaunchKernelGGL(kr, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem_r, st, a, zp, tiles_m, tiles_n);
-        return 1;
+        snprintf(label, sizeof(label), "conv_x3_run3_kernel<%d>%s%s", bn, apair ? " pre-split A" : "", m_tiles_limit > 0 ? " + tail" : "");
+        return launch_lds_dma(kr, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem_r, smem_r, "conv_x3_run3_kernel", label, a, st,
+                              tiles_m, tiles_n, 1);
     }
     // activation ring 3 x 32 KiB + weight ring 2 x (bn x 128 B); the epilogue stages 4 x 32 x (WTN + 4) floats
     size_t smem = (size_t)(3 * 256 + 2 * bn) * 128;
@@ -875,15 +796,10 @@ int try_launch_conv_x3_pipe(ConvArgs& a, hipStream_t st, int m_tiles_limit, int 
     // 2 x 2 grid of 128 x 128 waves measured slower, profiles/r04_pipe_ab_grids.txt)
     auto kern = bn == 128 ? (apair ? conv_x3_pipe_kernel<4, 1, 128, true> : conv_x3_pipe_kernel<4, 1, 128>)
                           : (apair ? conv_x3_pipe_kernel<4, 1, 256, true> : conv_x3_pipe_kernel<4, 1>);
-    if (lds_opt_in(reinterpret_cast<const void*>(kern), smem, "conv_x3_pipe_kernel")) return -1;
-    a.tiles_n = tiles_n;
-    a.splits = 1;
-    a.ws = nullptr;
-    if (a.m_begin == 0)
-        snprintf(g_conv_kernel, sizeof(g_conv_kernel), "conv_x3_pipe_kernel<%s>%s%s", bn == 128 ? "4, 1, 128" : "4, 1", apair ? " pre-split A" : "",
-                 m_tiles_limit > 0 ? " + tail" : "");
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem, st, a, zp, tiles_m, tiles_n);
-    return 1;
+    snprintf(label, sizeof(label), "conv_x3_pipe_kernel<%s>%s%s", bn == 128 ? "4, 1, 128" : "4, 1", apair ? " pre-split A" : "",
+             m_tiles_limit > 0 ? " + tail" : "");
+    return launch_lds_dma(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem, smem, "conv_x3_pipe_kernel", label, a, st, tiles_m,
+                          tiles_n, 1);
 }
 
 }  // namespace tt

@@ -22,17 +22,14 @@
 // registers, pre-split pair-format weights, a_lo*b_hi + a_hi*b_lo + a_hi*b_hi into an f32 accumulator); epilogue =
 // conv_epilogue (folded BN1d, residual, ReLU).  Summation order: (dz, dy) groups, chunks, 32-channel slices, dx taps.
 #include <limits.h>
-#include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv_lds_dma.h"
 
 #ifndef TT_SP_DEBUG
 #define TT_SP_DEBUG 0
 #endif
 
 namespace tt {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 namespace {
 constexpr int kG = 3;      // taps per group (the dx run)
@@ -68,17 +65,12 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
         const int md = *p.m_dev;
         Mlim = md < Mlim ? md : Mlim;
     }
-    // XCD-aware remap over the LIVE tiles only (the launch covers the allocation; hardware places block b on XCD b % 8):
-    // consecutive tiles, which share their halo rows, land on one XCD's L2, and every XCD gets an equal share of the live
-    // ones.  (Remapping over the allocated tile count left whole XCDs with dead tiles: level 2 of the bench cloud has
-    // 6,585 live of 16,384 allocated tiles -- 3.2 of 8 XCDs were working.)
+    // XCD-aware tile order over the LIVE tiles only (the launch covers the allocation): consecutive tiles, which share their halo
+    // rows, land on one XCD's L2, and every XCD gets an equal share of the live ones.  (Remapping over the allocated tile count left
+    // whole XCDs with dead tiles: level 2 of the bench cloud has 6,585 live of 16,384 allocated tiles -- 3.2 of 8 XCDs were working.)
     const int live_tiles = (Mlim + TM - 1) / TM;
     if ((int)blockIdx.x >= live_tiles) return;
-    int L;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = live_tiles >> 3, r = live_tiles & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int L = xcd_tile(live_tiles);
     (void)tiles_m;
     const int m0 = L * TM;
 
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
             if (i < ENT_INSTR) {
                 long long off = (long long)i * 1024 + lane * 16;
                 off = off < avail ? off : avail;
-                __builtin_amdgcn_global_load_lds(src + off, (lds_ptr_t)(uintptr_t)(se + (unsigned)i * 1024u), 16, 0, 0);
+                dma_piece(src + off, se + (unsigned)i * 1024u);
             }
         }
     }
@@ -220,13 +212,13 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
     for (int j = 0; j < NIA; ++j) {
         const int row = 8 * (wave + NW * j) + d_row;
         a_row[j] = row;
-        a_chunk[j] = (d_pos ^ ((row >> 1) & 7)) << 2;
+        a_chunk[j] = (d_pos ^ swz<kRowB>(row)) << 2;
     }
 #pragma unroll
     for (int j = 0; j < NIB; ++j) {
         const int r = 8 * (wave + NW * j) + d_row;                 // r = t * BN + n
         const int t = r / BN, n = r - t * BN;
-        b_off[j] = n * p.K + t * p.Cin + ((d_pos ^ ((n >> 1) & 7)) << 2);     // < 2^31 elements: Cout * K floats
+        b_off[j] = n * p.K + t * p.Cin + ((d_pos ^ swz<kRowB>(n)) << 2);     // < 2^31 elements: Cout * K floats
     }
     auto issue = [&](const Walk& w, int buf) {
         const bool skip_a = dbg_no_a && !first_issue, skip_b = dbg_no_b && !first_issue;
@@ -241,7 +233,7 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
                 // rows past the range: the last valid line (never read).  row * stride < 2^24 * 2^7 fits 32 bits
                 const int row = a_row[j] < nrows ? a_row[j] : nrows - 1;
                 const float* sp = abase + (unsigned)(__umul24((unsigned)row, (unsigned)p.in_cstride) + (unsigned)a_chunk[j]);
-                __builtin_amdgcn_global_load_lds(sp, (lds_ptr_t)(uintptr_t)(sa + (unsigned)i * 1024u), 16, 0, 0);
+                dma_piece(sp, sa + (unsigned)i * 1024u);
             }
         }
         const float* bbase = wgt + (long long)(w.g * kG) * p.Cin + w.sl * 32;                  // wave-uniform
@@ -249,8 +241,7 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
         for (int j = 0; j < NIB; ++j) {
             const int i = wave_s + NW * j;
             if (i < NB_INSTR && !skip_b)
-                __builtin_amdgcn_global_load_lds(bbase + (unsigned)b_off[j], (lds_ptr_t)(uintptr_t)(sb + (unsigned)i * 1024u),
-                                                 16, 0, 0);
+                dma_piece(bbase + (unsigned)b_off[j], sb + (unsigned)i * 1024u);
         }
     };
     // rulebook entries of this lane's output row for the three taps of group g (asm LDS reads, see `rng`)
@@ -270,24 +261,15 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
     };
 
     f32x16 acc[NCB];
-#pragma unroll
-    for (int j = 0; j < NCB; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    zero_acc(acc);
 
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    auto lds_read = [](unsigned addr) {
-        u32x4 v;
-        asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-        return v;
-    };
     const unsigned kb = lane >> 5;                                   // K half of this lane's MFMA operands
     unsigned fb_row[NCB], fb_swz[NCB];
 #pragma unroll
     for (int j = 0; j < NCB; ++j) {
         const int n = wn * WTN + j * 32 + (lane & 31);
         fb_row[j] = (unsigned)n * kRowB;
-        fb_swz[j] = (n >> 1) & 7;
+        fb_swz[j] = swz<kRowB>(n);
     }
 
     Walk wc{0, 0, 0, 0};
@@ -323,7 +305,7 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
             any = any || ok;
             const unsigned ar = (ok && !dbg_zero_a) ? (unsigned)s : (unsigned)S;   // absent (or in another chunk): the zero row
             a_off[t] = sa + ar * kRowB;
-            a_swz[t] = (ar >> 1) & 7;
+            a_swz[t] = swz<kRowB>((int)ar);
         }
         // no row of this wave has a neighbour of this group in this chunk (chunked ranges, isolated sites): nothing to add
         if (__builtin_amdgcn_ballot_w64(any) != 0ull && !dbg_no_mfma) {
@@ -399,6 +381,7 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
 #endif
 }
 
+// (Not launch_lds_dma: this kernel reads no zero page -- absent neighbours read the zero row of its own LDS stage.)
 template <int NCB, int WR, int WC>
 static int launch_sp_runs(ConvArgs& a, hipStream_t st) {
     constexpr int TM = WR * 32, BN = WC * NCB * 32, S = TM + 32, NW = WR * WC;

@@ -30,6 +30,10 @@ constexpr int kMaxDevices = 64;    // size of every per-device host table
 const void* zero_page(const char* who);
 int lds_opt_in(const void* kernel, size_t bytes, const char* name);
 
+// Test / measurement hook read from the environment: unset -> `dflt`, else whether its integer value is non-zero.  Call sites keep
+// the result in a `static const bool`: read once per process.
+bool env_flag(const char* name, bool dflt);
+
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -1405,7 +1405,7 @@ static bool v2_ok(long long total, int C, int X, int Y) {
 
 // ---- v3: per-launch counting sort + the planned streaming kernels (vp_cs_* above)
 static bool v3_ok(long long total, int num_points, int C, int X, int Y) {
-    static const bool on = [] { const char* e = getenv("TT_VP_SORT"); return e ? atoi(e) != 0 : true; }();   // A/B knob
+    static const bool on = env_flag("TT_VP_SORT", true);   // A/B knob
     const long long cps = ((long long)num_points + kCsChunk - 1) / kCsChunk;
     return on && C % 4 == 0 && C <= 1024 && (long long)X * Y <= kCsMaxCells && cps <= kCsMaxChunksPerSample &&
            total >= 4 * kCsChunk && total < (1ll << 31);
