@@ -206,8 +206,15 @@ typedef struct tt_conv_desc {
 } tt_conv_desc;
 
 int tt_conv2d_fwd(const tt_conv_desc* d, void* stream);
-/* K splits tt_conv2d_fwd would use for this descriptor if it is given a split-K workspace (0: the layer does not split) */
+/* K splits tt_conv2d_fwd would use for this descriptor if it is given a split-K workspace (0: the layer does not split).  Asks the
+ * dispatch function of a launch, so a descriptor whose launch would be refused (tt_conv2d_plan != 0: out2 / res1 without the vector
+ * epilogue, a misaligned weight_x3, ...) answers 0 and leaves that refusal in tt_last_error. */
 int tt_conv2d_splitk_slices(const tt_conv_desc* d);
+/* Host only: which kernel tt_conv2d_fwd would run `d` on.  Runs the validation and the dispatch of a launch (csrc/conv_choose.cpp) and
+ * writes into `label` (label_bytes bytes, NUL-terminated) what tt_conv_last_kernel would report after that launch.  Dereferences no
+ * data pointer of the descriptor (null-ness and alignment are all it looks at) and touches no device; returns the non-zero code, with
+ * the error text, that the launch of `d` would return before launching. */
+int tt_conv2d_plan(const tt_conv_desc* d, char* label, int label_bytes);
 
 /* ------------------------------------------------------------------------
  * A chain of nn.Linear layers over R rows in ONE launch (the decoder's row-batched MLPs:

@@ -736,6 +736,11 @@ def test_bf16x3_layer_with_residual_can_store_half_and_an_f32_twin():
     assert torch.equal(half, want.half())
 
 
+# what test_launch_state_is_per_device's four convolutions run on (tests/test_conv_choice.py replays them through tt_conv2d_plan)
+LAUNCH_STATE_LABELS = ["conv_igemm_glds_kernel<float, 256, 4, 2, 128, 23, false, true>", "conv_x3_run3_kernel<256>",
+                       "conv_h2_pipe_kernel", "sp_conv_runs_kernel<1, 8, 1>"]
+
+
 def test_launch_state_is_per_device():
     """The per-device launch state (csrc/common.cpp: the zero page of the LDS-DMA kernels, the dynamic-LDS opt-ins): one small
     launch of every kernel family that takes either, on cuda:0 and then on cuda:1 in one process.  The second device gets its
@@ -774,8 +779,7 @@ def test_launch_state_is_per_device():
 
     out0, labels0 = run("cuda:0")
     out1, labels1 = run("cuda:1")
-    assert labels0 == ["conv_igemm_glds_kernel<float, 256, 4, 2, 128, 23, false, true>", "conv_x3_run3_kernel<256>",
-                       "conv_h2_pipe_kernel", "sp_conv_runs_kernel<1, 8, 1>"], labels0
+    assert labels0 == LAUNCH_STATE_LABELS, labels0
     assert labels1 == labels0
     for a, b in zip(out0, out1):
         assert torch.equal(a, b)

@@ -1,0 +1,335 @@
+// The dispatch of tt_conv2d_fwd, stated once: from a validated layer to the kernel family, tile variant and split it runs with.
+// Plain host arithmetic (no HIP call), so tt_conv2d_plan / tt_conv2d_splitk_slices answer without a device and the rules are
+// testable on any machine (tests/test_conv_choice.py).  The launchers in the kernel files only map a choice onto its template
+// instantiation; a rule that is not here does not exist.
+#include <stdint.h>
+
+#include "conv_choose.h"
+
+namespace tt {
+namespace {
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+void set_tile(ConvChoice* c, int family, int bn, int waves_m, int waves_n, int bkb, int stages) {
+    c->family = family;
+    c->bn = bn;
+    c->waves_m = waves_m;
+    c->waves_n = waves_n;
+    c->bkb = bkb;
+    c->stages = stages;
+}
+
+// ---- "h2" arithmetic (conv_h2.hip): dense, Cin % 64 == 0, KH*KW <= 31
+bool choose_h2(const ConvArgs& a, ConvChoice* c) {
+    if (a.gather || a.m_dev || a.ws || a.pixel_shuffle2 || a.Cin % 64 != 0 || a.KH * a.KW > 31 || a.K < 64) return false;
+    // long K, 128-wide column tiles: the hand-pipelined one-wave-per-SIMD kernel.  TT_H2_PIPE=0 (test hook: tests/test_conv.py
+    // compares the two kernels bit for bit): the compiler-scheduled kernel everywhere
+    static const bool pipe = env_flag("TT_H2_PIPE", true);
+    if (pipe && a.Cout % 128 == 0 && a.K >= 1152) set_tile(c, CONV_H2_PIPE, 128, 4, 1, 128, 32);
+    // 128-wide: 8 waves of 64 x 64 on a 3 + 2 ring (160 KiB); measured against four waves of 128 x 64 (+15 %) and a 2 + 2 ring (-0.5 %:
+    // kept out, one variant less): profiles/r06_h2_microbench.txt.  64-wide: 8 waves of 32 x 64, 3 + 3 ring (four waves: +20 %)
+    else if (a.Cout > 64) set_tile(c, CONV_H2, 128, 4, 2, 128, 32);
+    else set_tile(c, CONV_H2, 64, 8, 1, 128, 33);
+    return true;
+}
+
+// ---- latency-bound small-M variant (conv_small.hip: 32 x 32 tile, intra-block split-K)
+bool choose_small(const ConvArgs& a, ConvChoice* c) {
+    if (a.gather || a.m_dev || a.M > 4096) return false;
+    if ((long long)div_up(a.M, 32) * div_up(a.Cout, 32) > 4096) return false;
+    set_tile(c, CONV_SMALL, 32, 1, 1, 32, 1);
+    return true;
+}
+
+// Tail split of a 256x256-tile launch.  With T tiles on 256 CUs (one workgroup per CU: 128 KiB of LDS) the launch
+// takes ceil(T / 256) rounds; when the last round is less than a quarter full (the 512 -> 512 DepthNet layers: 784
+// tiles = 3 rounds + 16 tiles, i.e. 23 % of the launch spent on 2 % of the work) the row tiles of that remainder are
+// peeled off into a second launch of 256x64 tiles (4x as many, 1/4 the work each) that fills the chip.
+// Returns the number of row tiles the MAIN launch should cover (0: no split).
+int tail_split_rows(const ConvArgs& a) {
+    if (a.Cout % 256 != 0) return 0;
+    const int tiles_m = div_up(a.M, 256), tiles_n = a.Cout / 256;
+    const long long T = (long long)tiles_m * tiles_n;
+    const int rounds = (int)((T + kNumCU - 1) / kNumCU);
+    const int last = (int)(T - (long long)kNumCU * (rounds - 1));
+    if (rounds < 2 || rounds > 8 || last > kNumCU / 4) return 0;
+    const int peel = div_up(last, tiles_n);            // row tiles moved to the tail launch
+    return peel < tiles_m ? tiles_m - peel : 0;
+}
+
+// Split-K form of the 64-wide bf16x3 tile: few rows, long K (batch-1 ticks: ResNet layer 4 at M = 3,136, K = 2048 / 4608 --
+// 13 row tiles are a twentieth of the chip, so those layers ran the exact-f32 register-staged kernel with a K split, 2.0 ms per
+// tick).  Column blocks of 64 give tiles_m x Cout / 64 workgroups; the K tiles are dealt over up to 16 ranges of >= 8 tiles until
+// ~512 workgroups (two per CU) are in flight.  The workspace must hold one [M][Cout] slice per non-empty K range.
+bool choose_x3_splitk(const ConvArgs& a, bool assume_ws, ConvChoice* c) {
+    if (a.gather || a.m_dev || a.M < 512 || a.M > 8192 || a.Cout < 64 || a.KH * a.KW > 32) return false;
+    if (a.Cin % 32 != 0 || a.K < 1024 || a.pixel_shuffle2) return false;
+    const int tiles = div_up(a.M, 256) * div_up(a.Cout, 64);
+    const int nk = a.K / 32;
+    if (tiles >= 256) return false;
+    int sp = 512 / tiles;
+    if (sp > nk / 8) sp = nk / 8;
+    if (sp > 16) sp = 16;
+    if (sp < 2) return false;
+    const int slices = div_up(nk, div_up(nk, sp));
+    if (slices < 2 || (!assume_ws && a.ws_slices < slices)) return false;
+    set_tile(c, CONV_GLDS, 64, 8, 1, 128, 2);
+    c->x3 = true;
+    c->splits = sp;
+    c->slices = slices;
+    return true;
+}
+
+// ---- run-staged sparse 3x3x3 conv (sp_conv_runs.hip): bf16x3 gathered conv with 27 taps in [kz][ky][kx] order, Cin a multiple
+// of 32, Cout 32 / 64 / 128
+bool choose_sp_runs(const ConvArgs& a, ConvChoice* c) {
+    if (!a.gather || a.row_perm || a.KH != 1 || a.KW != 27) return false;
+    // strided sparse convs (the caller states stride 2): the inputs of a (dz, dy) group sit on every other line, the
+    // contiguous range is ~4x the tile and is walked in mostly-empty chunks (measured 0.74 -> 4.1 ms): gather kernel
+    if (a.stride != 1) return false;
+    if (a.Cin % 32 != 0 || a.Cin > 128 || a.M < 2048 || a.pixel_shuffle2) return false;
+    if ((a.in_cstride & 3) || (a.in_coff & 3)) return false;
+    if (a.Cout == 32) set_tile(c, CONV_SP_RUNS, 32, 8, 1, 128, 2);            // <NCB, WR, WC> = <1, 8, 1>
+    else if (a.Cout == 64) set_tile(c, CONV_SP_RUNS, 64, 8, 1, 128, 2);       //                 <2, 8, 1>
+    else if (a.Cout == 128) set_tile(c, CONV_SP_RUNS, 128, 4, 2, 128, 2);     //                 <2, 4, 2>
+    else return false;
+    c->gather = c->x3 = true;
+    return true;
+}
+
+// the hand-pipelined bf16x3 tiles (conv_x3_pipe.hip) take: dense, Cout a multiple of the tile width, at most 31 taps
+bool x3_pipe_ok(const ConvArgs& a, int bn) {
+    return !(a.gather || a.m_dev || (bn != 256 && bn != 128) || a.Cout % bn != 0 || a.Cin % 32 != 0 || a.KH * a.KW > 31 || a.K < 64);
+}
+
+// ---- bf16x3 arithmetic on f32 storage (conv_igemm_glds.hip's X3 tiles and the kernels derived from them).  false when the shape is
+// outside the LDS-DMA kernels' contract (the layer then runs the exact f32 path on the plain weights).
+bool choose_x3(const ConvArgs& a, ConvChoice* c) {
+    c->x3 = true;
+    if (a.gather) {
+        if (choose_sp_runs(a, c)) return true;      // 3x3x3 rulebooks with 32+ channels: run-staged kernel
+        const bool cin_ok = a.Cin >= 16 && (a.Cin & (a.Cin - 1)) == 0;
+        if (!cin_ok || a.M < 2048 || a.Cout < 16 || a.Cout > 128) return false;
+        set_tile(c, CONV_GLDS, a.Cout <= 32 ? 32 : (a.Cout <= 64 ? 64 : 128), 8, 1, 128, 2);
+        c->gather = true;
+        return true;
+    }
+    if (a.m_dev || a.M < 2048 || a.KH * a.KW > 32) return false;
+    if (a.Cin % 32 != 0 || a.K < 64) return false;       // 128 B rows = 32 f32 of one tap per K tile, >= 2 tiles
+    // pre-split activations (tt_conv_desc.in_pair): 16-channel pair groups must line up with the 32-channel K tiles
+    const bool apair = (a.flags & 32) != 0;
+    if (apair && (a.in_coff % 16 != 0 || a.in_cstride % 16 != 0)) return false;
+    c->apair = apair;
+    // few output channels over many rows (the segmentation head: 3 x 3, 64 -> 12 at 224 x 448 per image; the deformable conv's
+    // offset head: 3 x 3, 512 -> 18; seg_res_to_image_feature's 64 -> 16): a 256 x 32 tile, two workgroups per CU.  Below 2^16
+    // rows the exact-f32 register-staged kernel keeps them
+    if (a.Cout < 64) {
+        if (a.Cout > 32 || a.Cout < 8) return false;
+        if (!apair && a.M < (1 << 16)) return false;
+        set_tile(c, CONV_GLDS, 32, 8, 1, 128, 2);
+        return true;
+    }
+    // Tile width along N.  The widest wave tile the layer allows is the most efficient per tile (the operand split costs
+    // 8/TN VALU per MFMA; measured ~1.0 / 0.85 / 0.63 relative MFMA rate for the 256 / 128 / 64 wide tiles), but a
+    // launch with fewer workgroups than the chip holds (batch-1 ticks: 49 row tiles x 2 on 256 CUs) is bound by its
+    // rounds, not by the per-tile rate: pick the width with the smallest  rounds x (BN / rate).
+    const int tiles_m = div_up(a.M, 256);
+    auto cost = [&](int bn, double rate) {      // the busiest CU runs ceil(tiles / 256) tiles at the tile's measured rate
+        const long long tiles = (long long)tiles_m * div_up(a.Cout, bn);
+        return (double)((tiles + kNumCU - 1) / kNumCU) * bn / rate;
+    };
+    const bool wide = a.Cout % 256 == 0 || a.Cout > 512;
+    const int main_rows = tail_split_rows(a);
+    // 256-wide with a tail split: the main launch's full rounds + the peeled row tiles as 256 x 64 tiles
+    auto cost256 = [&]() {
+        if (!main_rows) return cost(256, 1.0);
+        const long long tn = a.Cout / 256;
+        const long long main_tiles = (long long)main_rows * tn, tail_tiles = (long long)(tiles_m - main_rows) * tn * 4;
+        return (double)((main_tiles + kNumCU - 1) / kNumCU) * 256 / 1.0 + (double)((tail_tiles + kNumCU - 1) / kNumCU) * 64 / 0.63;
+    };
+    const double c256 = wide ? cost256() : 1e30;
+    // (long-K layers run the 128-wide tile on the hand-pipelined kernel: 404 vs 423 TF/s for the 256-wide one, profiles/r04_run3_ab.txt)
+    const double c128 = a.Cout > 64 ? cost(128, (a.K >= 1152 && a.Cout % 128 == 0) ? 0.95 : 0.85) : 1e30;
+    const double c64 = cost(64, 0.63);
+    const int bn = (c256 <= c128 && c256 <= c64) ? 256 : (c128 <= c64 ? 128 : 64);
+    // Long-K layers (K >= 1152: every 3 x 3 of the trunks) on the 256- and 128-wide tiles: four hand-pipelined waves, one per SIMD
+    // (csrc/conv_x3_pipe.hip: MFMA pipe 77 % busy against 58 %, profiles/r04_conv_sq_counters_noepilogue.txt).  Short K keeps the
+    // 8-wave tile: there the tile's prologue + epilogue dominate and eight waves issue the output stores faster than four
+    // (K = 1024: 0.203 vs 0.216 ms, K = 256 N = 1280: 0.52 vs 0.77 ms; profiles/r04_pipe_ab_first.txt).
+    // TT_X3_PIPE=0 (test hook: tests/test_conv.py compares the two families bit for bit): the compiler-scheduled tiles everywhere
+    static const bool pipe = env_flag("TT_X3_PIPE", true);
+    if (pipe && a.K >= 1152 && bn != 64 && x3_pipe_ok(a, bn)) {
+        // 3 x 3 stride-1 "same" convolutions over a dense batch: the run-staged form (one staged pixel run per filter row serves
+        // its three taps).  TT_X3_RUN3=0 (test hook: tests/test_conv.py compares the two forms bit for bit): the per-tap form everywhere
+        static const bool run3 = env_flag("TT_X3_RUN3", true);
+        const bool runs = run3 && a.KW == 3 && a.KH <= 5 && a.stride == 1 && a.dil == 1 && a.pad == 1 && a.OH == a.H && a.OW == a.W &&
+                          (a.N == 1 || a.in_nstride == (long long)a.H * a.W * a.in_cstride);
+        // wave grid 4 x 1: 64 x 256 (64 x 128 on the 128-wide tile) per wave -- every activation fragment is split by ONE wave (the
+        // 2 x 2 grid of 128 x 128 waves measured slower, profiles/r04_pipe_ab_grids.txt)
+        set_tile(c, runs ? CONV_X3_RUN3 : CONV_X3_PIPE, bn, 4, 1, 128, 23);
+    } else if (bn == 256) {
+        set_tile(c, CONV_GLDS, 256, 4, 2, 128, 23);      // 8 x (64 x 128), 3 + 2 stages = 160 KiB
+    } else {
+        // Narrow tiles: two LDS stages (a third costs the 64-wide tile its second workgroup per CU: N=64 K=576 2.13 -> 2.66 ms), eight
+        // waves (four waves of 64 x 64 on the 64-wide tile: 3-15 % slower, profiles/r05_x3_64wide_waves_ab.txt; pre-split activations:
+        // 1-5 % slower there too, profiles/r06_pair_format.txt)
+        set_tile(c, CONV_GLDS, bn, 8, 1, 128, 2);        // 8 x (32 x 128) / 8 x (32 x 64)
+    }
+    if (bn == 256) c->main_rows = main_rows;
+    return true;
+}
+
+// ---- the LDS-DMA kernel on exact-f32 and 16-bit operands (conv_igemm_glds.hip)
+bool choose_glds(const ConvArgs& a, int dtype, ConvChoice* c) {
+    constexpr int min_tiles = 2;      // K = 64 1x1 layers: 0.43 -> 0.27 ms against the register-staged kernel
+    if (a.gather) {
+        // sparse 3D conv as a gathered GEMM (rulebook rows): whole 128 B+ activation rows per DMA lane group
+        const bool cin_ok = a.Cin >= 16 && (a.Cin & (a.Cin - 1)) == 0;   // power of two: taps tile the 128 B rows
+        if (dtype == TT_F32 || !cin_ok || a.M < 2048 || a.Cout < 16 || a.Cout > 128) return false;
+        if (a.Cout <= 32) set_tile(c, CONV_GLDS, 32, 8, 1, 128, 2);
+        else if (a.Cout <= 64) set_tile(c, CONV_GLDS, 64, 8, 1, 128, 2);
+        else set_tile(c, CONV_GLDS, 128, 4, 2, 128, 2);
+        c->gather = true;
+        return true;
+    }
+    if (a.m_dev || a.M < 2048 || a.Cout < 64 || a.KH * a.KW > 32) return false;
+    if (dtype == TT_F32) {
+        if (a.Cin % 16 != 0 || div_up(a.K, 16) < min_tiles) return false;
+        if (a.Cout > 64) set_tile(c, CONV_GLDS, 128, 4, 2, 64, 3);
+        else set_tile(c, CONV_GLDS, 64, 8, 1, 64, 3);
+        return true;
+    }
+    if (a.Cin % 32 != 0 || div_up(a.K, 32) < min_tiles) return false;
+    // Tile selection (profiles/r01_conv_microbench_tiles.txt).  Three things set the rate of these kernels:
+    //  * L2->LDS bytes per FLOP = workgroup tile: 256x128 -> 85 FLOP/B, 256x256 -> 128 FLOP/B;
+    //  * whether a DMA lane group consumes WHOLE 128 B cache lines: with 64 B rows every activation line is
+    //    fetched twice from L2 (the other half is needed one K tile later and the 32 KiB L1 cannot hold a tile);
+    //    128 B rows in 2 stages beat 64 B rows in 3 stages by 10-17 % on every layer whose LDS budget allows it;
+    //  * LDS fragment bytes per MFMA = per-wave register tile (64x64: 1 KiB, 128x64: 0.75 KiB) -- second order.
+    // Auto: Cout % 256 == 0 -> 256x256 tile of eight 128x64 waves (128 B rows if Cin % 64 == 0); short K -> four
+    // 128x64 waves on 256x128; Cout <= 64 -> 256x64 tile with 128 B rows; else eight 64x64 waves on 256x128.
+    // Retired after measurement (same file): 16-wave 256x256, 8x1 wave grid, 128 B rows x 3 stages (1 workgroup/CU),
+    // 128 B x 2 stages on the 256x128 tile.
+    if (a.Cout > 64) {
+        const long long tiles256 = (long long)div_up(a.M, 256) * (a.Cout / 256);
+        if (a.Cout % 256 == 0 && tiles256 >= 200) {
+            if (a.Cin % 64 == 0) {
+                set_tile(c, CONV_GLDS, 256, 2, 4, 128, 2);
+                c->main_rows = tail_split_rows(a);
+            } else {
+                set_tile(c, CONV_GLDS, 256, 2, 4, 64, 3);          // 8 waves x 128x64
+            }
+        } else if (a.K <= 512) {
+            set_tile(c, CONV_GLDS, 128, 2, 2, 64, 3);              // 4 waves x 128x64
+        } else {
+            set_tile(c, CONV_GLDS, 128, 4, 2, 64, 3);              // 8 waves x 64x64
+        }
+        return true;
+    }
+    // Cout <= 64 (the 224x448 UNet / stem-level layers): 128 B rows in 2 stages (80 KiB, 2 workgroups / CU)
+    // measured +17 % over 64 B rows x 3 stages (1.61 vs 1.89 ms on M=6.4M K=1152)
+    if (a.Cin % 64 == 0) set_tile(c, CONV_GLDS, 64, 8, 1, 128, 2);
+    else set_tile(c, CONV_GLDS, 64, 8, 1, 64, 3);
+    return true;
+}
+
+// ---- the register-staged kernel (conv_igemm.hip) takes everything; with a workspace, few tiles and a long K it splits K
+int choose_igemm(const ConvArgs& a, int dtype, bool ws, bool assume_ws, ConvChoice* c) {
+    if (a.Cout > 64) set_tile(c, CONV_IGEMM, 128, 2, 2, 64, 2);
+    else if (a.Cout > 32) set_tile(c, CONV_IGEMM, 64, 2, 2, 64, 2);
+    else set_tile(c, CONV_IGEMM, 32, 4, 1, 64, 2);
+    if (dtype != TT_F32) c->bkb = 128;
+    c->gather = a.gather != nullptr;
+    const int tiles = div_up(a.M, 128) * div_up(a.Cout, c->bn);
+    const int nk = div_up(a.K, c->bkb / (dtype == TT_F32 ? 4 : 2));
+    if (ws && !a.m_dev && tiles < 128 && nk >= 8) {
+        int sp = div_up(512, tiles);
+        if (sp > nk / 2) sp = nk / 2;
+        if (sp > 64) sp = 64;
+        c->splits = sp < 1 ? 1 : sp;
+    }
+    if (c->splits <= 1) return 0;
+    c->slices = c->splits;
+    if (!assume_ws) {
+        c->slices = 0;
+        if (a.ws_slices > 0) {
+            // ordered form: the non-empty splits (the K tiles are dealt in runs of ceil(nk / splits)) store into their own slices
+            const int eff = div_up(nk, div_up(nk, c->splits));
+            TT_REQUIRE(a.ws_slices >= eff, "tt_conv2d_fwd: split-K workspace holds %d slices, %d needed", a.ws_slices, eff);
+            c->slices = eff;
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+int conv_choose(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
+    *c = ConvChoice{};
+    c->splits = 1;
+    const bool ws = a.ws || f.assume_ws;
+    if (f.weight_h2) {
+        // half storage x (hi, lo) weights: the only kernel with this arithmetic -- a shape outside its contract is an error, not a
+        // silent change of precision
+        TT_REQUIRE(aligned16(f.weight_h2), "tt_conv2d_fwd: weight_h2 must be 16-byte aligned");
+        TT_REQUIRE(choose_h2(a, c), "tt_conv2d_fwd: weight_h2 layer outside the h2 kernel's contract (Cin=%d KH*KW=%d)", a.Cin,
+                   a.KH * a.KW);
+        return 0;
+    }
+    TT_REQUIRE(!f.out2 || a.vec_epi, "tt_conv2d_fwd: out2 needs the vector epilogue (aligned channel counts)");
+    TT_REQUIRE(!f.res1_up || a.vec_epi, "tt_conv2d_fwd: an upsampled res1 needs the vector epilogue (aligned channel counts)");
+    TT_REQUIRE(!f.res1_f32 || (a.vec_epi && a.res_vec), "tt_conv2d_fwd: an f32 res1 needs the vector epilogue and aligned residual rows");
+    TT_REQUIRE(!(f.dtype == TT_F32 && a.out_dtype != TT_F32 && a.res1) || (a.vec_epi && a.res_vec),
+               "tt_conv2d_fwd: a 16-bit output of an f32 layer with a residual needs the vector epilogue");
+    if (a.flags & (32 | 64)) {      // in_pair / out_pair: bf16x3 on the LDS-DMA kernels or nothing
+        TT_REQUIRE(a.vec_epi && aligned16(f.weight_x3) && a.K % 16 == 0,
+                   "tt_conv2d_fwd: in_pair / out_pair need the vector epilogue and a 16-byte aligned weight_x3");
+        TT_REQUIRE(choose_x3(a, c), "tt_conv2d_fwd: pair-format layer outside the LDS-DMA bf16x3 kernel's contract (M=%d Cin=%d Cout=%d)",
+                   a.M, a.Cin, a.Cout);
+        return 0;
+    }
+    if (!ws && !f.out2 && !f.res1_up && !f.res1_f32 && choose_small(a, c)) return 0;
+    const bool x3 = f.weight_x3 && f.dtype == TT_F32;
+    // few rows, long K, bf16x3 operand: the 64-wide x3 tile, K split
+    if (ws && x3 && a.K % 16 == 0 && aligned16(f.weight_x3) && choose_x3_splitk(a, f.assume_ws, c)) return 0;
+    if (!ws && x3) {
+        TT_REQUIRE(aligned16(f.weight_x3) && a.K % 16 == 0, "tt_conv2d_fwd: weight_x3 needs 16-byte alignment and K %% 16 == 0 (K = %d)",
+                   a.K);
+        if (choose_x3(a, c)) return 0;
+        *c = ConvChoice{};
+        c->splits = 1;
+    }
+    if (!ws && choose_glds(a, f.dtype, c)) return 0;
+    return choose_igemm(a, f.dtype, ws, f.assume_ws, c);
+}
+
+ConvChoice conv_tail_choice(const ConvChoice& c) {
+    ConvChoice t{};
+    set_tile(&t, CONV_GLDS, 64, 8, 1, 128, 2);
+    t.x3 = c.x3;
+    t.apair = c.apair;
+    t.splits = 1;
+    return t;
+}
+
+void conv_label(const ConvChoice& c, int dtype, char* out, size_t bytes) {
+    const char* tn = dtype == TT_F32 ? "float" : "16-bit";
+    const char* pre = c.apair ? " pre-split A" : "";
+    const char* tail = c.main_rows > 0 ? " + tail" : "";
+    switch (c.family) {
+        case CONV_H2: snprintf(out, bytes, "conv_h2_kernel<%d, %d, %d, %d, %d>", c.bn, c.waves_m, c.waves_n, c.stages / 10, c.stages % 10); break;
+        case CONV_H2_PIPE: snprintf(out, bytes, "conv_h2_pipe_kernel"); break;
+        case CONV_SMALL: snprintf(out, bytes, "conv_small_kernel"); break;
+        case CONV_SP_RUNS: snprintf(out, bytes, "sp_conv_runs_kernel<%d, %d, %d>", c.bn / (32 * c.waves_n), c.waves_m, c.waves_n); break;
+        case CONV_X3_PIPE: snprintf(out, bytes, "conv_x3_pipe_kernel<%s>%s%s", c.bn == 128 ? "4, 1, 128" : "4, 1", pre, tail); break;
+        case CONV_X3_RUN3: snprintf(out, bytes, "conv_x3_run3_kernel<%d>%s%s", c.bn, pre, tail); break;
+        case CONV_GLDS:
+            snprintf(out, bytes, "conv_igemm_glds_kernel<%s, %d, %d, %d, %d, %d, %s, %s>%s%s", tn, c.bn, c.waves_m, c.waves_n, c.bkb,
+                     c.stages, c.gather ? "true" : "false", c.x3 ? "true" : "false", pre, c.splits > 1 ? " split-K" : tail);
+            break;
+        default: snprintf(out, bytes, "conv_igemm_kernel<%s, 128, %d>%s", tn, c.bn, c.splits > 1 ? " split-K" : ""); break;
+    }
+}
+
+}  // namespace tt

@@ -1,56 +1,17 @@
-// Shared definitions of the implicit-GEMM convolution kernels: arguments, MFMA wrappers, the fused epilogue.  (The data movement of the
-// LDS-DMA kernels is in conv_lds_dma.h.)
+// Shared definitions of the implicit-GEMM convolution kernels: MFMA wrappers, the fused epilogue, the launch entries.  (Their arguments
+// and the choice of a layer's kernel are in conv_choose.h, the data movement of the LDS-DMA kernels in conv_lds_dma.h.)
 #pragma once
 #include <type_traits>
-#include "tt_common.h"
+#include "conv_choose.h"
 
 namespace tt {
-extern thread_local char g_conv_kernel[96];   // common.cpp: label of the kernel the last conv launch used
+extern thread_local char g_conv_kernel[96];   // common.cpp: label of the kernel the last conv launch used (conv_label)
 extern long long* g_conv_trace;               // common.cpp: tt_conv_set_trace (measurement aid; null in the product)
 
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-struct ConvArgs {
-    const void* in;
-    const void* weight;
-    void* out;
-    const float* scale;
-    const float* shift;
-    const float* shift_n;
-    const void* res1;
-    const void* res2;
-    const int* gather;   // GATHER mode: [M][KH*KW] input row per (output row, tap), -1 = none
-    const int* m_dev;    // optional device-side row count (rows >= *m_dev are skipped)
-    const int* row_perm;         // GATHER, optional: tile slot -> actual output row (rows sorted by tap mask)
-    const unsigned* row_mask;    //   "       the sorted masks (bit t = tap t present), 0xFFFFFFFF beyond the live rows
-    float* ws;           // split-K: f32 [M][Cout] partial-sum workspace (pre-zeroed), else null
-    long long in_nstride, out_nstride;
-    int N, H, W, Cin, in_cstride, in_coff;
-    int Cout, KH, KW, stride, pad, dil;
-    int OH, OW, out_cstride, out_coff;
-    int pixel_shuffle2, shift_n_mod;
-    int res1_cstride, res1_coff, res2_cstride, res2_coff;
-    int act, out_dtype;
-    int M, K;            // GEMM sizes
-    int cin_fast;        // 1 if Cin % BK == 0 (tap uniform per K tile)
-    int out_fast;        // 1 if plain [M][out_cstride] addressing
-    int vec_epi;         // 1: LDS-staged epilogue with 16 B stores (channel counts / offsets aligned)
-    int res_vec;         // 1: residual chunks are 8/16 B aligned (vector loads)
-    int splits;          // split-K factor (gridDim.y)
-    int tiles_n;
-    int m_begin;         // first output row of this launch (tail-split launches of the LDS-DMA kernel), else 0
-    int ws_slices;       // split-K: > 0 = every split stores into its own [M][Cout] slice of ws (ordered finalize)
-    int flags;           // bit 4: non-temporal f32 output stores (every launch of the product); bit 5: the activations are pre-split bf16 (hi, lo) pairs (tt_conv_desc.in_pair);
-                         // bit 6: write the output in that pair format (tt_conv_desc.out_pair); < 0: split-K query (no launch)
-    int res1_up_h, res1_up_w;   // > 0: res1 is a [N][res1_up_h][res1_up_w][..] map read through nearest upsampling (tt_conv_desc)
-    float* out2;         // optional second, f32, row-linear copy of the output (tt_conv_desc.out2): [M][out2_cstride] at out2_coff
-    int out2_cstride, out2_coff;
-    long long* trace;    // measurement aid (tt_conv_set_trace): 4 wall-clock stamps (10 ns ticks) per workgroup of the LDS-DMA kernel
-                         // -- entry, first K tile landed, K loop done, epilogue done -- at trace[blockIdx.x * 4]; null in the product
-};
 
 template <typename T> struct Mfma;
 template <> struct Mfma<float> {
@@ -502,22 +463,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[T
     }
 }
 
-// glds (LDS-DMA, 3-stage) variant: returns 1 if it took the launch, 0 if the shape is not covered, < 0 (error text set) if the
-// launch failed -- the caller returns that and tries no other kernel.
-int try_launch_conv_glds(ConvArgs& a, int dtype, hipStream_t st);
-// bf16x3 variant of the same kernel (f32 storage, pre-split weights in a.weight): same contract.
-int try_launch_conv_glds_x3(ConvArgs& a, hipStream_t st);
-// split-K form of the 64-wide bf16x3 tile (few rows, long K): workspace slices it would use (0: not eligible) / the tile launch
-int conv_glds_x3_splitk_slices(const ConvArgs& a);
-int launch_conv_glds_x3_splitk(ConvArgs& a, hipStream_t st);
-// bf16x3, 256 x 256 tile as four hand-pipelined 128 x 128 waves (csrc/conv_x3_pipe.hip); `m_tiles_limit` > 0 = tail split
-int try_launch_conv_x3_pipe(ConvArgs& a, hipStream_t st, int m_tiles_limit, int bn = 256);
-// run-staged sparse 3x3x3 conv (csrc/sp_conv_runs.hip; bf16x3, a.weight = pre-split weights): same contract.
-int try_launch_sp_conv_runs(ConvArgs& a, hipStream_t st);
-// "h2" arithmetic (csrc/conv_h2.hip): IEEE-half activations x f16 (hi, lo) weight pairs in a.weight, two MFMAs per product.
-// Returns 1 if it took the launch, 0 if the shape is outside its contract (dense, Cin % 64 == 0, KH*KW <= 31), < 0 on failure.
-int try_launch_conv_h2(ConvArgs& a, hipStream_t st);
-// latency-bound small-M variant (32x32 tile, intra-block split-K): same contract.
-int try_launch_conv_small(ConvArgs& a, int dtype, hipStream_t st);
+// The launch entries of the kernel files: each maps a choice of conv_choose onto its template instantiation and launches it (LDS size
+// and opt-in, zero page, grid, ConvArgs bookkeeping).  1, or < 0 with the error text set -- a variant the file does not instantiate
+// included; never another kernel.  a.weight is the operand the family reads (pre-split weights for bf16x3, the (hi, lo) pairs for h2).
+int launch_conv_h2(const ConvChoice& c, ConvArgs& a, hipStream_t st);                      // conv_h2.hip
+int launch_conv_small(ConvArgs& a, int dtype, hipStream_t st);                             // conv_small.hip
+int launch_sp_conv_runs(const ConvChoice& c, ConvArgs& a, hipStream_t st);                 // sp_conv_runs.hip
+int launch_conv_x3_pipe(const ConvChoice& c, ConvArgs& a, hipStream_t st);                 // conv_x3_pipe.hip
+int launch_conv_glds(const ConvChoice& c, ConvArgs& a, int dtype, hipStream_t st);         // conv_igemm_glds.hip
 
 }  // namespace tt

@@ -443,30 +443,24 @@ static int launch_h2(ConvArgs& a, hipStream_t st) {
     if (smem < epi) smem = epi;
     size_t full = (size_t)SA * A_BYTES + (size_t)SB * B_BYTES;      // all stages in use: the largest request
     if (full < epi) full = epi;
-    char label[96];
-    snprintf(label, sizeof(label), "conv_h2_kernel<%d, %d, %d, %d, %d>", BN, WAVES_M, WAVES_N, SA, SB);
     return launch_lds_dma(conv_h2_kernel<BN, WAVES_M, WAVES_N, SA, SB>, dim3((unsigned)(tiles_m * tiles_n)), dim3(NW * 64), smem, full,
-                          "conv_h2_kernel", label, a, st, tiles_m, tiles_n, 1, sa_used);
+                          "conv_h2_kernel", a, st, tiles_m, tiles_n, 1, sa_used);
 }
 
 static int launch_h2_pipe(ConvArgs& a, hipStream_t st) {
     const int tiles_m = div_up(a.M - a.m_begin, 256), tiles_n = a.Cout / 128;
     const size_t smem = (size_t)5 * 32 * 1024;                       // 3 + 2 stages (the epilogue's 4 x 32 x 132 floats fit inside)
     return launch_lds_dma(conv_h2_pipe_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem, smem, "conv_h2_pipe_kernel",
-                          "conv_h2_pipe_kernel", a, st, tiles_m, tiles_n, 1);
+                          a, st, tiles_m, tiles_n, 1);
 }
 
-int try_launch_conv_h2(ConvArgs& a, hipStream_t st) {
-    if (a.gather || a.m_dev || a.ws || a.pixel_shuffle2 || a.Cin % 64 != 0 || a.KH * a.KW > 31 || a.K < 64) return 0;
+// a.weight = the f16 (hi, lo) weight pairs.  1, or < 0 on failure.
+int launch_conv_h2(const ConvChoice& c, ConvArgs& a, hipStream_t st) {
     a.m_begin = 0;
-    // long K, 128-wide column tiles: the hand-pipelined one-wave-per-SIMD kernel.  TT_H2_PIPE=0 (test hook: tests/test_conv.py
-    // compares the two kernels bit for bit): the compiler-scheduled kernel everywhere
-    static const bool pipe = env_flag("TT_H2_PIPE", true);
-    if (pipe && a.Cout % 128 == 0 && a.K >= 1152) return launch_h2_pipe(a, st);
-    // 128-wide: 8 waves of 64 x 64 on a 3 + 2 ring (160 KiB); measured against four waves of 128 x 64 (+15 %) and a 2 + 2 ring (-0.5 %:
-    // kept out, one variant less): profiles/r06_h2_microbench.txt.  64-wide: 8 waves of 32 x 64, 3 + 3 ring (four waves: +20 %)
-    if (a.Cout > 64) return launch_h2<128, 4, 2, 3, 2>(a, st);
-    return launch_h2<64, 8, 1, 3, 3>(a, st);
+    if (c.family == CONV_H2_PIPE) return launch_h2_pipe(a, st);
+    if (c.bn == 128 && c.waves_m == 4 && c.waves_n == 2 && c.stages == 32) return launch_h2<128, 4, 2, 3, 2>(a, st);
+    if (c.bn == 64 && c.waves_m == 8 && c.waves_n == 1 && c.stages == 33) return launch_h2<64, 8, 1, 3, 3>(a, st);
+    TT_REQUIRE(false, "tt_conv2d_fwd: no conv_h2_kernel for a %d-wide tile of %d x %d waves, ring %d", c.bn, c.waves_m, c.waves_n, c.stages);
 }
 
 }  // namespace tt

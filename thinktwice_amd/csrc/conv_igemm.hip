@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256) void splitk_finalize_kernel(const ConvArgs p) 
 }
 
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N, bool GATHER, int KX = 1>
-static int launch_conv(ConvArgs& a, hipStream_t st) {
+static int launch_conv(const ConvChoice& c, ConvArgs& a, hipStream_t st) {
     constexpr int BKB = ((sizeof(T) == 4) ? 64 : 128) * KX;
     constexpr int BK = BKB / (int)sizeof(T);
     constexpr int ROWB = BKB + 16;
@@ -262,62 +262,46 @@ static int launch_conv(ConvArgs& a, hipStream_t st) {
     if (smem < epi) smem = epi;
     auto kern = conv_igemm_kernel<T, BM, BN, WAVES_M, WAVES_N, GATHER, KX>;
     const int tiles = tiles_m * a.tiles_n;
-    const int nk = div_up(a.K, BK);
-    a.splits = 1;
-    if ((a.ws || a.flags < 0) && !a.m_dev && tiles < 128 && nk >= 8) {
-        int sp = div_up(512, tiles);
-        if (sp > nk / 2) sp = nk / 2;
-        if (sp > 64) sp = 64;
-        a.splits = sp < 1 ? 1 : sp;
-    }
-    if (a.flags < 0) return a.splits > 1 ? a.splits : 0;       // query (tt_conv2d_splitk_slices): no launch
+    a.splits = c.splits;
     if (a.splits <= 1) a.ws = nullptr;
-    if (a.ws && a.ws_slices > 0) {
-        // ordered form: the non-empty splits (the K tiles are dealt in runs of ceil(nk / splits)) store into their own slices
-        const int per = div_up(nk, a.splits);
-        const int eff = div_up(nk, per);
-        TT_REQUIRE(a.ws_slices >= eff, "tt_conv2d_fwd: split-K workspace holds %d slices, %d needed", a.ws_slices, eff);
-        a.ws_slices = eff;
-    }
+    if (a.ws) a.ws_slices = c.slices;              // ordered form: the non-empty splits store into their own slices
     size_t mx = (size_t)2 * (BM + BN) * ROWB;      // the largest (double-buffered) request
     if (mx < epi) mx = epi;
     if (mx > 48 * 1024 && lds_opt_in(reinterpret_cast<const void*>(kern), mx, "conv_igemm_kernel")) return -1;
-    snprintf(g_conv_kernel, sizeof(g_conv_kernel), "conv_igemm_kernel<%s, %d, %d>%s", sizeof(T) == 4 ? "float" : "16-bit",
-             BM, BN, a.ws ? " split-K" : "");
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.splits), dim3(256), smem, st, a);
-    if (a.ws) {
-        const long long tot = (long long)a.M * a.Cout;
-        hipLaunchKernelGGL(splitk_finalize_kernel<T>, dim3((unsigned)div_up(tot, 256)), dim3(256), 0, st, a);
-    }
-    return check_launch("tt_conv2d_fwd");
+    return 1;
 }
 
 template <typename T, bool GATHER>
-static int dispatch_conv2(ConvArgs& a, hipStream_t st) {
-    if (a.Cout > 64) return launch_conv<T, 128, 128, 2, 2, GATHER>(a, st);
-    if (a.Cout > 32) return launch_conv<T, 128, 64, 2, 2, GATHER>(a, st);
-    return launch_conv<T, 128, 32, 4, 1, GATHER>(a, st);
+static int launch_igemm2(const ConvChoice& c, ConvArgs& a, hipStream_t st) {
+    if (c.bn == 128 && c.waves_m == 2 && c.waves_n == 2) return launch_conv<T, 128, 128, 2, 2, GATHER>(c, a, st);
+    if (c.bn == 64 && c.waves_m == 2 && c.waves_n == 2) return launch_conv<T, 128, 64, 2, 2, GATHER>(c, a, st);
+    if (c.bn == 32 && c.waves_m == 4 && c.waves_n == 1) return launch_conv<T, 128, 32, 4, 1, GATHER>(c, a, st);
+    TT_REQUIRE(false, "tt_conv2d_fwd: no conv_igemm_kernel for a %d-wide tile of %d x %d waves", c.bn, c.waves_m, c.waves_n);
 }
 
-template <typename T>
-static int dispatch_conv(ConvArgs& a, hipStream_t st) {
-    return a.gather ? dispatch_conv2<T, true>(a, st) : dispatch_conv2<T, false>(a, st);
+// the register-staged kernel; split-K (c.splits > 1) launches the tiles only
+static int launch_conv_igemm(const ConvChoice& c, ConvArgs& a, int dtype, hipStream_t st) {
+    if (dtype == TT_F32) return a.gather ? launch_igemm2<float, true>(c, a, st) : launch_igemm2<float, false>(c, a, st);
+    if (dtype == TT_F16) return a.gather ? launch_igemm2<f16_t, true>(c, a, st) : launch_igemm2<f16_t, false>(c, a, st);
+    return a.gather ? launch_igemm2<uint16_t, true>(c, a, st) : launch_igemm2<uint16_t, false>(c, a, st);
+}
+
+// the split-K epilogue over the slices / the atomically summed workspace the tiles of `a` wrote
+static void launch_splitk_finalize(const ConvArgs& a, int dtype, hipStream_t st) {
+    const dim3 grid((unsigned)div_up((long long)a.M * a.Cout, 256));
+    if (dtype == TT_F32) hipLaunchKernelGGL(splitk_finalize_kernel<float>, grid, dim3(256), 0, st, a);
+    else if (dtype == TT_F16) hipLaunchKernelGGL(splitk_finalize_kernel<f16_t>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(splitk_finalize_kernel<uint16_t>, grid, dim3(256), 0, st, a);
 }
 
 }  // namespace tt
 
 using namespace tt;
 
-static int conv2d_run(const tt_conv_desc* d, void* stream, bool query);
-
-extern "C" int tt_conv2d_fwd(const tt_conv_desc* d, void* stream) { return conv2d_run(d, stream, false); }
-
-extern "C" int tt_conv2d_splitk_slices(const tt_conv_desc* d) {
-    const int n = conv2d_run(d, nullptr, true);
-    return n > 0 ? n : 0;
-}
-
-static int conv2d_run(const tt_conv_desc* d, void* stream, bool query) {
+// Validation of a descriptor and its translation into the kernels' arguments and the facts conv_choose takes.  Dereferences no data
+// pointer and touches no device: tt_conv2d_fwd, tt_conv2d_plan and tt_conv2d_splitk_slices all start here.
+static int conv2d_prepare(const tt_conv_desc* d, ConvArgs& a, ConvFacts& f) {
     TT_REQUIRE(d && d->in && d->weight && d->out, "tt_conv2d_fwd: null pointer");
     TT_REQUIRE(d->dtype == TT_F32 || d->dtype == TT_BF16 || d->dtype == TT_F16, "tt_conv2d_fwd: bad dtype %d", d->dtype);
     TT_REQUIRE(d->out_dtype == TT_F32 || d->out_dtype == d->dtype ||
@@ -344,7 +328,6 @@ static int conv2d_run(const tt_conv_desc* d, void* stream, bool query) {
                    d->stride > 0 && d->dil > 0 && d->OH > 0 && d->OW > 0,
                "tt_conv2d_fwd: bad geometry");
     TT_REQUIRE(!d->pixel_shuffle2 || d->Cout % 4 == 0, "tt_conv2d_fwd: pixel_shuffle2 needs Cout%%4==0");
-    ConvArgs a;
     a.in = d->in; a.weight = d->weight; a.out = d->out;
     a.scale = d->scale; a.shift = d->shift; a.shift_n = d->shift_n;
     a.res1 = d->res1; a.res2 = d->res2;
@@ -394,7 +377,6 @@ static int conv2d_run(const tt_conv_desc* d, void* stream, bool query) {
         if (d->out_pair) a.flags |= 64;
     }
     if (d->res1_f32) a.flags |= 128;
-    if (query) a.flags = -1;       // launch_conv returns the split count instead of launching
     {
         const int co_vec = (d->out_dtype == TT_F32 && !d->out_pair) ? 4 : 8;
         const int osz = d->out_dtype == TT_F32 ? 4 : 2;
@@ -408,73 +390,88 @@ static int conv2d_run(const tt_conv_desc* d, void* stream, bool query) {
         };
         a.res_vec = (res_ok(d->res1, d->res1_cstride, d->res1_coff) && res_ok(d->res2, d->res2_cstride, d->res2_coff)) ? 1 : 0;
     }
+    f.dtype = d->dtype;
+    f.weight_x3 = d->weight_x3;
+    f.weight_h2 = d->weight_h2;
+    f.out2 = d->out2 != nullptr;
+    f.res1_up = d->res1_up_w > 0;
+    f.res1_f32 = d->res1_f32 != 0;
+    f.assume_ws = false;
+    return 0;
+}
+
+// validate -> choose -> launch
+extern "C" int tt_conv2d_fwd(const tt_conv_desc* d, void* stream) {
+    ConvArgs a;
+    ConvFacts f;
+    ConvChoice c;
+    if (const int r = conv2d_prepare(d, a, f)) return r;
+    if (const int r = conv_choose(a, f, &c)) return r;
     hipStream_t st = (hipStream_t)stream;
-    if (query) {
-        if (d->in_pair || d->out_pair || d->weight_h2 || d->res1_up_w > 0) return 0;
-        a.ws = nullptr;
-        a.row_perm = nullptr;
-        a.row_mask = nullptr;
-        if (d->weight_x3 && d->dtype == TT_F32 && a.K % 16 == 0) {      // few rows, long K, bf16x3 operand: the 64-wide x3 tile, K split
-            const int n = conv_glds_x3_splitk_slices(a);
-            if (n > 0) return n;
-        }
-        if (d->dtype == TT_F32) return dispatch_conv<float>(a, st);
-        if (d->dtype == TT_F16) return dispatch_conv<f16_t>(a, st);
-        return dispatch_conv<uint16_t>(a, st);
+    const bool pair = d->in_pair || d->out_pair;
+    const char* what = "tt_conv2d_fwd";
+    int r;
+    if (c.x3) a.weight = d->weight_x3;
+    switch (c.family) {
+        case CONV_H2:
+        case CONV_H2_PIPE:
+            a.weight = d->weight_h2;
+            what = "tt_conv2d_fwd(h2)";
+            r = launch_conv_h2(c, a, st);
+            break;
+        case CONV_SMALL:
+            what = "tt_conv2d_fwd(small)";
+            r = launch_conv_small(a, d->dtype, st);
+            break;
+        case CONV_SP_RUNS:
+            what = "tt_conv2d_fwd(glds x3)";
+            r = launch_sp_conv_runs(c, a, st);
+            break;
+        case CONV_X3_PIPE:
+        case CONV_X3_RUN3:
+            what = pair ? "tt_conv2d_fwd(glds x3, pair)" : "tt_conv2d_fwd(glds x3)";
+            r = launch_conv_x3_pipe(c, a, st);
+            break;
+        case CONV_GLDS:
+            what = !c.x3 ? "tt_conv2d_fwd(glds)" : c.splits > 1 ? "tt_conv2d_fwd(glds x3 split-K)" : pair ? "tt_conv2d_fwd(glds x3, pair)" : "tt_conv2d_fwd(glds x3)";
+            if (c.splits > 1) a.ws_slices = c.slices;
+            r = launch_conv_glds(c, a, d->dtype, st);
+            break;
+        default:
+            a.row_perm = nullptr;      // the tile plan is an LDS-DMA-kernel feature: the other kernels walk rows and taps in
+            a.row_mask = nullptr;      // natural order (same result)
+            r = launch_conv_igemm(c, a, d->dtype, st);
+            break;
     }
-    if (d->weight_h2) {
-        // half storage x (hi, lo) weights: the only kernel with this arithmetic -- a shape outside its contract is an error, not a
-        // silent change of precision
-        TT_REQUIRE((reinterpret_cast<uintptr_t>(d->weight_h2) & 15) == 0, "tt_conv2d_fwd: weight_h2 must be 16-byte aligned");
-        ConvArgs ah = a;
-        ah.weight = d->weight_h2;
-        const int r = try_launch_conv_h2(ah, st);
-        if (r < 0) return r;
-        TT_REQUIRE(r, "tt_conv2d_fwd: weight_h2 layer outside the h2 kernel's contract (Cin=%d KH*KW=%d)", d->Cin, d->KH * d->KW);
-        return check_launch("tt_conv2d_fwd(h2)");
+    if (r < 0) return r;
+    conv_label(c, d->dtype, g_conv_kernel, sizeof(g_conv_kernel));
+    if (c.main_rows > 0) {             // tail split: the row tiles of the last, nearly empty round as 256 x 64 tiles
+        ConvArgs t = a;
+        t.m_begin = c.main_rows * 256;
+        if (launch_conv_glds(conv_tail_choice(c), t, d->dtype, st) < 0) return -1;
     }
-    TT_REQUIRE(!d->out2 || a.vec_epi, "tt_conv2d_fwd: out2 needs the vector epilogue (aligned channel counts)");
-    TT_REQUIRE(d->res1_up_w <= 0 || a.vec_epi, "tt_conv2d_fwd: an upsampled res1 needs the vector epilogue (aligned channel counts)");
-    TT_REQUIRE(!d->res1_f32 || (a.vec_epi && a.res_vec), "tt_conv2d_fwd: an f32 res1 needs the vector epilogue and aligned residual rows");
-    TT_REQUIRE(!(d->dtype == TT_F32 && d->out_dtype != TT_F32 && d->res1) || (a.vec_epi && a.res_vec),
-               "tt_conv2d_fwd: a 16-bit output of an f32 layer with a residual needs the vector epilogue");
-    if (d->in_pair || d->out_pair) {
-        TT_REQUIRE(a.vec_epi && (reinterpret_cast<uintptr_t>(d->weight_x3) & 15) == 0 && a.K % 16 == 0,
-                   "tt_conv2d_fwd: in_pair / out_pair need the vector epilogue and a 16-byte aligned weight_x3");
-        ConvArgs ax = a;
-        ax.weight = d->weight_x3;
-        const int r = try_launch_conv_glds_x3(ax, st);
-        if (r < 0) return r;
-        TT_REQUIRE(r, "tt_conv2d_fwd: pair-format layer outside the LDS-DMA bf16x3 kernel's contract (M=%d Cin=%d Cout=%d)", a.M,
-                   d->Cin, d->Cout);
-        return check_launch("tt_conv2d_fwd(glds x3, pair)");
-    }
-    if (!d->splitk_ws && !d->out2 && d->res1_up_w <= 0 && !d->res1_f32 && try_launch_conv_small(a, d->dtype, st)) {
-        snprintf(g_conv_kernel, sizeof(g_conv_kernel), "conv_small_kernel");
-        return check_launch("tt_conv2d_fwd(small)");
-    }
-    if (d->splitk_ws && d->weight_x3 && d->dtype == TT_F32 && a.K % 16 == 0 &&
-        (reinterpret_cast<uintptr_t>(d->weight_x3) & 15) == 0) {
-        ConvArgs ax = a;
-        ax.weight = d->weight_x3;
-        if (const int r = launch_conv_glds_x3_splitk(ax, st)) {
-            if (r < 0) return r;
-            const long long tot = (long long)ax.M * ax.Cout;
-            hipLaunchKernelGGL(splitk_finalize_kernel<float>, dim3((unsigned)div_up(tot, 256)), dim3(256), 0, st, ax);
-            return check_launch("tt_conv2d_fwd(glds x3 split-K)");
-        }
-    }
-    if (!d->splitk_ws && d->weight_x3 && d->dtype == TT_F32) {
-        TT_REQUIRE((reinterpret_cast<uintptr_t>(d->weight_x3) & 15) == 0 && a.K % 16 == 0,
-                   "tt_conv2d_fwd: weight_x3 needs 16-byte alignment and K %% 16 == 0 (K = %d)", a.K);
-        ConvArgs ax = a;
-        ax.weight = d->weight_x3;
-        if (const int r = try_launch_conv_glds_x3(ax, st)) return r < 0 ? r : check_launch("tt_conv2d_fwd(glds x3)");
-    }
-    if (const int r = d->splitk_ws ? 0 : try_launch_conv_glds(a, d->dtype, st)) return r < 0 ? r : check_launch("tt_conv2d_fwd(glds)");
-    a.row_perm = nullptr;      // the tile plan is an LDS-DMA-kernel feature: the other kernels walk rows and taps in
-    a.row_mask = nullptr;      // natural order (same result)
-    if (d->dtype == TT_F32) return dispatch_conv<float>(a, st);
-    if (d->dtype == TT_F16) return dispatch_conv<f16_t>(a, st);
-    return dispatch_conv<uint16_t>(a, st);
+    if (c.splits > 1) launch_splitk_finalize(a, d->dtype, st);
+    return check_launch(what);
+}
+
+extern "C" int tt_conv2d_splitk_slices(const tt_conv_desc* d) {
+    ConvArgs a;
+    ConvFacts f;
+    ConvChoice c;
+    if (conv2d_prepare(d, a, f)) return 0;
+    if (d->in_pair || d->out_pair || d->weight_h2 || d->res1_up_w > 0) return 0;       // layers that never take a workspace
+    f.assume_ws = true;
+    if (conv_choose(a, f, &c)) return 0;
+    return c.splits > 1 ? c.slices : 0;
+}
+
+extern "C" int tt_conv2d_plan(const tt_conv_desc* d, char* label, int label_bytes) {
+    ConvArgs a;
+    ConvFacts f;
+    ConvChoice c;
+    if (const int r = conv2d_prepare(d, a, f)) return r;
+    if (const int r = conv_choose(a, f, &c)) return r;
+    TT_REQUIRE(label && label_bytes > 0, "tt_conv2d_plan: no room for the label");
+    conv_label(c, d->dtype, label, (size_t)label_bytes);
+    return 0;
 }

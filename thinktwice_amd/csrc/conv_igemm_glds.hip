@@ -4,7 +4,7 @@
 // camera trunk / SECOND / decoder value projections, the 7x7/2 stem in row-run form, and (GATHER) the sparse 3D
 // convolutions of the LiDAR encoder:
 //   * block tile 256 x {256, 128, 64, 32}, 4 or 8 waves with 64x64 or 128x64 register tiles (template parameters;
-//     the dispatcher at the bottom of this file states which shape gets which and why).
+//     conv_choose.cpp states which shape gets which and why).
 //   * global -> LDS by DMA (no staging VGPRs).  STAGES = 3: tile k+2 is issued right after the barrier that
 //     publishes tile k, with a COUNTED `s_waitcnt vmcnt(N)` (never 0 in the main loop) and a raw `s_barrier`, so
 //     two K tiles of loads overlap the MFMA phase (64 B rows).  STAGES = 2: one tile in flight, 128 B rows =
@@ -529,217 +529,68 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
 }
 
 template <typename T, int BN, int WAVES_M, int WAVES_N, int BKB, int STAGES = 3, bool GATHER = false, bool X3 = false, bool APAIR = false>
-static int launch_glds(ConvArgs& a, hipStream_t st, int m_tiles_limit = 0, int splits = 1, int slices = 1) {
+static int launch_glds(const ConvChoice& c, ConvArgs& a, hipStream_t st) {
     constexpr int BM = 256;
     constexpr int WTN = BN / WAVES_N;
-    // rows [m_begin, M) by default; `m_tiles_limit` > 0 restricts the launch to that many row tiles from m_begin
+    // rows [m_begin, M) by default; c.main_rows > 0 (tail split) restricts the launch to that many row tiles from m_begin
     int tiles_m = div_up(a.M - a.m_begin, BM);
-    if (m_tiles_limit > 0 && m_tiles_limit < tiles_m) tiles_m = m_tiles_limit;
+    if (c.main_rows > 0 && c.main_rows < tiles_m) tiles_m = c.main_rows;
     const int tiles_n = div_up(a.Cout, BN);
     size_t smem = STAGES == 23 ? (size_t)(3 * BM + 2 * BN) * BKB : (size_t)STAGES * (BM + BN) * BKB;
     const size_t epi = (size_t)(WAVES_M * WAVES_N) * 32 * (WTN + 4) * 4;
     if (smem < epi) smem = epi;
-    char label[96];      // (the tail launch of a split keeps the main launch's label: launch_lds_dma)
-    snprintf(label, sizeof(label), "conv_igemm_glds_kernel<%s, %d, %d, %d, %d, %d, %s, %s>%s%s", sizeof(T) == 4 ? "float" : "16-bit", BN,
-             WAVES_M, WAVES_N, BKB, STAGES, GATHER ? "true" : "false", X3 ? "true" : "false", APAIR ? " pre-split A" : "",
-             splits > 1 ? " split-K" : (m_tiles_limit > 0 ? " + tail" : ""));
-    // split-K: a.ws / a.ws_slices are the caller's (ordered slices, `slices` non-empty ranges)
+    // split-K: a.ws / a.ws_slices are the caller's (ordered slices, c.slices non-empty ranges)
     return launch_lds_dma(conv_igemm_glds_kernel<T, BN, WAVES_M, WAVES_N, BKB, STAGES, GATHER, X3, APAIR>,
-                          dim3((unsigned)(tiles_m * tiles_n), (unsigned)(splits > 1 ? slices : 1)), dim3(WAVES_M * WAVES_N * 64), smem, smem,
-                          "conv_igemm_glds_kernel", label, a, st, tiles_m, tiles_n, splits);
+                          dim3((unsigned)(tiles_m * tiles_n), (unsigned)(c.splits > 1 ? c.slices : 1)), dim3(WAVES_M * WAVES_N * 64), smem,
+                          smem, "conv_igemm_glds_kernel", a, st, tiles_m, tiles_n, c.splits);
 }
 
-// Tail split of a 256x256-tile launch.  With T tiles on 256 CUs (one workgroup per CU: 128 KiB of LDS) the launch
-// takes ceil(T / 256) rounds; when the last round is less than a quarter full (the 512 -> 512 DepthNet layers: 784
-// tiles = 3 rounds + 16 tiles, i.e. 23 % of the launch spent on 2 % of the work) the row tiles of that remainder are
-// peeled off into a second launch of 256x64 tiles (4x as many, 1/4 the work each) that fills the chip.
-// Returns the number of row tiles the MAIN launch should cover (0: no split).
-static int tail_split_rows(const ConvArgs& a) {
-    if (a.Cout % 256 != 0) return 0;
-    const int tiles_m = div_up(a.M, 256), tiles_n = a.Cout / 256;
-    const long long T = (long long)tiles_m * tiles_n;
-    const int rounds = (int)((T + kNumCU - 1) / kNumCU);
-    const int last = (int)(T - (long long)kNumCU * (rounds - 1));
-    if (rounds < 2 || rounds > 8 || last > kNumCU / 4) return 0;
-    const int peel = div_up(last, tiles_n);            // row tiles moved to the tail launch
-    return peel < tiles_m ? tiles_m - peel : 0;
-}
-
-// Split-K form of the 64-wide bf16x3 tile: few rows, long K (batch-1 ticks: ResNet layer 4 at M = 3,136, K = 2048 / 4608 --
-// 13 row tiles are a twentieth of the chip, so those layers ran the exact-f32 register-staged kernel with a K split, 2.0 ms per
-// tick).  Column blocks of 64 give tiles_m x Cout / 64 workgroups; the K tiles are dealt over up to 16 ranges of >= 8 tiles until
-// ~512 workgroups (two per CU) are in flight.  Returns the number of non-empty K ranges (= workspace slices), 0 = not this path.
-static int x3_splitk_plan(const ConvArgs& a, int* splits_out) {
-    if (a.gather || a.m_dev || a.M < 512 || a.M > 8192 || a.Cout < 64 || a.KH * a.KW > 32) return 0;
-    if (a.Cin % 32 != 0 || a.K < 1024 || a.pixel_shuffle2) return 0;
-    const int tiles = div_up(a.M, 256) * div_up(a.Cout, 64);
-    const int nk = a.K / 32;
-    if (tiles >= 256) return 0;
-    int sp = 512 / tiles;
-    if (sp > nk / 8) sp = nk / 8;
-    if (sp > 16) sp = 16;
-    if (sp < 2) return 0;
-    const int per = div_up(nk, sp);
-    if (splits_out) *splits_out = sp;
-    return div_up(nk, per);
-}
-
-int conv_glds_x3_splitk_slices(const ConvArgs& a) { return x3_splitk_plan(a, nullptr); }
-
-// a.weight = the pre-split weights, a.ws = the workspace of >= conv_glds_x3_splitk_slices(a) [M][Cout] f32 slices.  Launches the
-// tiles only; the caller runs splitk_finalize_kernel (a.ws_slices is set to the slices written).
-int launch_conv_glds_x3_splitk(ConvArgs& a, hipStream_t st) {
-    int sp = 0;
-    const int slices = x3_splitk_plan(a, &sp);
-    if (slices < 2 || !a.ws || a.ws_slices < slices) return 0;
-    a.ws_slices = slices;
-    return launch_glds<float, 64, 8, 1, 128, 2, false, true>(a, st, 0, sp, slices);
-}
-
-// bf16x3 arithmetic on f32 storage (see the kernel's template comment).  `a.weight` must already point at the
-// pre-split weights.  Returns 0 when the shape is outside the DMA kernel's contract (the caller then runs the exact
-// f32 path on the plain weights), < 0 when a launch failed.
-int try_launch_conv_glds_x3(ConvArgs& a, hipStream_t st) {
-    if (a.gather) {
-        if (const int r = try_launch_sp_conv_runs(a, st)) return r;      // 3x3x3 rulebooks with 32+ channels: run-staged kernel
-        const bool cin_ok = a.Cin >= 16 && (a.Cin & (a.Cin - 1)) == 0;
-        if (!cin_ok || a.M < 2048 || a.Cout < 16 || a.Cout > 128) return 0;
-        if (a.Cout <= 32) return launch_glds<float, 32, 8, 1, 128, 2, true, true>(a, st);
-        if (a.Cout <= 64) return launch_glds<float, 64, 8, 1, 128, 2, true, true>(a, st);
-        return launch_glds<float, 128, 8, 1, 128, 2, true, true>(a, st);
-    }
-    if (a.m_dev || a.M < 2048 || a.KH * a.KW > 32) return 0;
-    if (a.Cin % 32 != 0 || a.K < 64) return 0;       // 128 B rows = 32 f32 of one tap per K tile, >= 2 tiles
-    // pre-split activations (tt_conv_desc.in_pair): 16-channel pair groups must line up with the 32-channel K tiles
-    const bool apair = (a.flags & 32) != 0;
-    if (apair && (a.in_coff % 16 != 0 || a.in_cstride % 16 != 0)) return 0;
-    // few output channels over many rows (the segmentation head: 3 x 3, 64 -> 12 at 224 x 448 per image; the deformable conv's
-    // offset head: 3 x 3, 512 -> 18; seg_res_to_image_feature's 64 -> 16): a 256 x 32 tile, two workgroups per CU.  Below 2^16
-    // rows the exact-f32 register-staged kernel keeps them
-    if (a.Cout < 64) {
-        if (a.Cout > 32 || a.Cout < 8) return 0;
-        if (apair) return launch_glds<float, 32, 8, 1, 128, 2, false, true, true>(a, st);
-        if (a.M < (1 << 16)) return 0;
-        return launch_glds<float, 32, 8, 1, 128, 2, false, true>(a, st);
-    }
-    // Tile width along N.  The widest wave tile the layer allows is the most efficient per tile (the operand split costs
-    // 8/TN VALU per MFMA; measured ~1.0 / 0.85 / 0.63 relative MFMA rate for the 256 / 128 / 64 wide tiles), but a
-    // launch with fewer workgroups than the chip holds (batch-1 ticks: 49 row tiles x 2 on 256 CUs) is bound by its
-    // rounds, not by the per-tile rate: pick the width with the smallest  rounds x (BN / rate).
-    const int tiles_m = div_up(a.M, 256);
-    auto cost = [&](int bn, double rate) {      // the busiest CU runs ceil(tiles / 256) tiles at the tile's measured rate
-        const long long tiles = (long long)tiles_m * div_up(a.Cout, bn);
-        return (double)((tiles + kNumCU - 1) / kNumCU) * bn / rate;
-    };
-    const bool wide = a.Cout % 256 == 0 || a.Cout > 512;
-    // 256-wide with a tail split: the main launch's full rounds + the peeled row tiles as 256 x 64 tiles
-    auto cost256 = [&]() {
-        const int main_rows = tail_split_rows(a);
-        if (!main_rows) return cost(256, 1.0);
-        const long long tn = a.Cout / 256;
-        const long long main_tiles = (long long)main_rows * tn, tail_tiles = (long long)(tiles_m - main_rows) * tn * 4;
-        return (double)((main_tiles + kNumCU - 1) / kNumCU) * 256 / 1.0 + (double)((tail_tiles + kNumCU - 1) / kNumCU) * 64 / 0.63;
-    };
-    const double c256 = wide ? cost256() : 1e30;
-    // (long-K layers run the 128-wide tile on the hand-pipelined kernel: 404 vs 423 TF/s for the 256-wide one, profiles/r04_run3_ab.txt)
-    const double c128 = a.Cout > 64 ? cost(128, (a.K >= 1152 && a.Cout % 128 == 0) ? 0.95 : 0.85) : 1e30;
-    const double c64 = cost(64, 0.63);
-    const int bn = (c256 <= c128 && c256 <= c64) ? 256 : (c128 <= c64 ? 128 : 64);
-    // Long-K layers (K >= 1152: every 3 x 3 of the trunks) on the 256- and 128-wide tiles: four hand-pipelined waves, one per SIMD
-    // (csrc/conv_x3_pipe.hip: MFMA pipe 77 % busy against 58 %, profiles/r04_conv_sq_counters_noepilogue.txt).  Short K keeps the
-    // 8-wave tile: there the tile's prologue + epilogue dominate and eight waves issue the output stores faster than four
-    // (K = 1024: 0.203 vs 0.216 ms, K = 256 N = 1280: 0.52 vs 0.77 ms; profiles/r04_pipe_ab_first.txt).
-    // TT_X3_PIPE=0 (test hook: tests/test_conv.py compares the two families bit for bit): the compiler-scheduled tiles everywhere
-    static const bool pipe = env_flag("TT_X3_PIPE", true);
-    const bool hand = pipe && a.K >= 1152;
-    if (bn == 256) {                                                                                           // 8 x (64 x 128)
-        const int main_rows = tail_split_rows(a);
-        int r = hand ? try_launch_conv_x3_pipe(a, st, main_rows) : 0;
-        if (!r) r = apair ? launch_glds<float, 256, 4, 2, 128, 23, false, true, true>(a, st, main_rows)
-                          : launch_glds<float, 256, 4, 2, 128, 23, false, true>(a, st, main_rows);     // 3 + 2 stages = 160 KiB
-        if (r < 0 || !main_rows) return r;
-        ConvArgs t = a;
-        t.m_begin = main_rows * 256;
-        return apair ? launch_glds<float, 64, 8, 1, 128, 2, false, true, true>(t, st)
-                     : launch_glds<float, 64, 8, 1, 128, 2, false, true>(t, st);
-    }
-    // Narrow tiles: two LDS stages (a third costs the 64-wide tile its second workgroup per CU: N=64 K=576 2.13 -> 2.66 ms), eight
-    // waves (four waves of 64 x 64 on the 64-wide tile: 3-15 % slower, profiles/r05_x3_64wide_waves_ab.txt)
-    if (bn == 128) {                                                                                           // 8 x (32 x 128)
-        if (const int r = hand && a.Cout % 128 == 0 ? try_launch_conv_x3_pipe(a, st, 0, 128) : 0) return r;
-        return apair ? launch_glds<float, 128, 8, 1, 128, 2, false, true, true>(a, st)
-                     : launch_glds<float, 128, 8, 1, 128, 2, false, true>(a, st);
-    }
-    // (pre-split activations: four waves of 64 x 64 measured 1-5 % slower than eight of 32 x 64 here too, profiles/r06_pair_format.txt)
-    return apair ? launch_glds<float, 64, 8, 1, 128, 2, false, true, true>(a, st)                              // 8 x (32 x 64)
-                 : launch_glds<float, 64, 8, 1, 128, 2, false, true>(a, st);
-}
+// the tile variants this file instantiates: a choice naming one of them launches it
+#define TT_GLDS_VARIANT(T, BN, WM, WN, BKB, ST, G, X3, AP)                                                                          \
+    if (c.bn == BN && c.waves_m == WM && c.waves_n == WN && c.bkb == BKB && c.stages == ST && c.gather == G && c.x3 == X3 && c.apair == AP) \
+        return launch_glds<T, BN, WM, WN, BKB, ST, G, X3, AP>(c, a, st);
 
 // T16 = uint16_t (bf16) or f16_t (IEEE half): same tiles, same MFMA rate.
 template <typename T16>
-static int launch_glds16(ConvArgs& a, int dtype, hipStream_t st, int min_tiles);
-
-int try_launch_conv_glds(ConvArgs& a, int dtype, hipStream_t st) {
-    constexpr int min_tiles = 2;      // K = 64 1x1 layers: 0.43 -> 0.27 ms against the register-staged kernel
-    if (a.gather) {
-        // sparse 3D conv as a gathered GEMM (rulebook rows): whole 128 B+ activation rows per DMA lane group
-        const bool cin_ok = a.Cin >= 16 && (a.Cin & (a.Cin - 1)) == 0;   // power of two: taps tile the 128 B rows
-        if (dtype == TT_F32 || !cin_ok || a.M < 2048 || a.Cout < 16 || a.Cout > 128) return 0;
-        return dtype == TT_F16 ? launch_glds16<f16_t>(a, dtype, st, min_tiles) : launch_glds16<uint16_t>(a, dtype, st, min_tiles);
-    }
-    if (a.m_dev || a.M < 2048 || a.Cout < 64 || a.KH * a.KW > 32) return 0;
-    if (dtype == TT_F32) {
-        if (a.Cin % 16 != 0 || div_up(a.K, 16) < min_tiles) return 0;
-        if (a.Cout > 64) return launch_glds<float, 128, 4, 2, 64>(a, st);
-        return launch_glds<float, 64, 8, 1, 64>(a, st);
-    }
-    if (a.Cin % 32 != 0 || div_up(a.K, 32) < min_tiles) return 0;
-    return dtype == TT_F16 ? launch_glds16<f16_t>(a, dtype, st, min_tiles) : launch_glds16<uint16_t>(a, dtype, st, min_tiles);
+static int launch_glds16(const ConvChoice& c, ConvArgs& a, hipStream_t st) {
+    TT_GLDS_VARIANT(T16, 32, 8, 1, 128, 2, true, false, false)
+    TT_GLDS_VARIANT(T16, 64, 8, 1, 128, 2, true, false, false)
+    TT_GLDS_VARIANT(T16, 128, 4, 2, 128, 2, true, false, false)
+    TT_GLDS_VARIANT(T16, 256, 2, 4, 128, 2, false, false, false)
+    TT_GLDS_VARIANT(T16, 256, 2, 4, 64, 3, false, false, false)
+    TT_GLDS_VARIANT(T16, 128, 2, 2, 64, 3, false, false, false)
+    TT_GLDS_VARIANT(T16, 128, 4, 2, 64, 3, false, false, false)
+    TT_GLDS_VARIANT(T16, 64, 8, 1, 128, 2, false, false, false)
+    TT_GLDS_VARIANT(T16, 64, 8, 1, 64, 3, false, false, false)
+    return 0;
 }
 
-template <typename T16>
-static int launch_glds16(ConvArgs& a, int dtype, hipStream_t st, int min_tiles) {
-    (void)dtype; (void)min_tiles;
-    if (a.gather) {
-        if (a.Cout <= 32) return launch_glds<T16, 32, 8, 1, 128, 2, true>(a, st);
-        if (a.Cout <= 64) return launch_glds<T16, 64, 8, 1, 128, 2, true>(a, st);
-        return launch_glds<T16, 128, 4, 2, 128, 2, true>(a, st);
-    }
-    // Tile selection (profiles/r01_conv_microbench_tiles.txt).  Three things set the rate of these kernels:
-    //  * L2->LDS bytes per FLOP = workgroup tile: 256x128 -> 85 FLOP/B, 256x256 -> 128 FLOP/B;
-    //  * whether a DMA lane group consumes WHOLE 128 B cache lines: with 64 B rows every activation line is
-    //    fetched twice from L2 (the other half is needed one K tile later and the 32 KiB L1 cannot hold a tile);
-    //    128 B rows in 2 stages beat 64 B rows in 3 stages by 10-17 % on every layer whose LDS budget allows it;
-    //  * LDS fragment bytes per MFMA = per-wave register tile (64x64: 1 KiB, 128x64: 0.75 KiB) -- second order.
-    // Auto: Cout % 256 == 0 -> 256x256 tile of eight 128x64 waves (128 B rows if Cin % 64 == 0); short K -> four
-    // 128x64 waves on 256x128; Cout <= 64 -> 256x64 tile with 128 B rows; else eight 64x64 waves on 256x128.
-    // Retired after measurement (same file): 16-wave 256x256, 8x1 wave grid, 128 B rows x 3 stages (1 workgroup/CU),
-    // 128 B x 2 stages on the 256x128 tile.
-    if (a.Cout > 64) {
-        int v;
-        {
-            const long long tiles256 = (long long)div_up(a.M, 256) * (a.Cout / 256);
-            if (a.Cout % 256 == 0 && tiles256 >= 200) v = (a.Cin % 64 == 0) ? 6 : 2;
-            else if (a.K <= 512) v = 1;
-            else v = 0;
-        }
-        if (v == 6 && a.Cout % 256 == 0 && a.Cin % 64 == 0) {
-            if (const int main_rows = tail_split_rows(a)) {
-                if (launch_glds<T16, 256, 2, 4, 128, 2>(a, st, main_rows) < 0) return -1;
-                ConvArgs t = a;
-                t.m_begin = main_rows * 256;
-                return launch_glds<T16, 64, 8, 1, 128, 2>(t, st);
-            }
-            return launch_glds<T16, 256, 2, 4, 128, 2>(a, st);
-        }
-        if (v == 1) return launch_glds<T16, 128, 2, 2, 64>(a, st);                         // 4 waves x 128x64
-        if (v == 2 && a.Cout % 256 == 0) return launch_glds<T16, 256, 2, 4, 64>(a, st);    // 8 waves x 128x64
-        return launch_glds<T16, 128, 4, 2, 64>(a, st);                                     // 8 waves x 64x64
-    }
-    // Cout <= 64 (the 224x448 UNet / stem-level layers): 128 B rows in 2 stages (80 KiB, 2 workgroups / CU)
-    // measured +17 % over 64 B rows x 3 stages (1.61 vs 1.89 ms on M=6.4M K=1152)
-    if (a.Cin % 64 == 0) return launch_glds<T16, 64, 8, 1, 128, 2>(a, st);
-    return launch_glds<T16, 64, 8, 1, 64>(a, st);
+static int launch_glds32(const ConvChoice& c, ConvArgs& a, hipStream_t st) {
+    TT_GLDS_VARIANT(float, 128, 4, 2, 64, 3, false, false, false)
+    TT_GLDS_VARIANT(float, 64, 8, 1, 64, 3, false, false, false)
+    // bf16x3 (a.weight = the pre-split weights): gathered, dense, dense with pre-split activations
+    TT_GLDS_VARIANT(float, 32, 8, 1, 128, 2, true, true, false)
+    TT_GLDS_VARIANT(float, 64, 8, 1, 128, 2, true, true, false)
+    TT_GLDS_VARIANT(float, 128, 8, 1, 128, 2, true, true, false)
+    TT_GLDS_VARIANT(float, 32, 8, 1, 128, 2, false, true, false)
+    TT_GLDS_VARIANT(float, 64, 8, 1, 128, 2, false, true, false)
+    TT_GLDS_VARIANT(float, 128, 8, 1, 128, 2, false, true, false)
+    TT_GLDS_VARIANT(float, 256, 4, 2, 128, 23, false, true, false)
+    TT_GLDS_VARIANT(float, 32, 8, 1, 128, 2, false, true, true)
+    TT_GLDS_VARIANT(float, 64, 8, 1, 128, 2, false, true, true)
+    TT_GLDS_VARIANT(float, 128, 8, 1, 128, 2, false, true, true)
+    TT_GLDS_VARIANT(float, 256, 4, 2, 128, 23, false, true, true)
+    return 0;
+}
+#undef TT_GLDS_VARIANT
+
+// One launch of the LDS-DMA kernel (of a tail split: the main launch, or with a.m_begin set the tail).  Split-K (c.splits > 1) launches
+// the tiles only; the caller runs splitk_finalize_kernel.  1, or < 0 on failure.
+int launch_conv_glds(const ConvChoice& c, ConvArgs& a, int dtype, hipStream_t st) {
+    const int r = dtype == TT_F32 ? launch_glds32(c, a, st) : dtype == TT_F16 ? launch_glds16<f16_t>(c, a, st) : launch_glds16<uint16_t>(c, a, st);
+    TT_REQUIRE(r, "tt_conv2d_fwd: no conv_igemm_glds_kernel<%d, %d, %d, %d, %d, %d, %d, %d> for dtype %d", c.bn, c.waves_m, c.waves_n, c.bkb,
+               c.stages, (int)c.gather, (int)c.x3, (int)c.apair, dtype);
+    return r;
 }
 
 }  // namespace tt

@@ -165,18 +165,16 @@ __device__ __forceinline__ void dma_emit_b(const DmaCtx& c, const E* ptr, bool o
 }
 
 // ---- host side: the tail of every launcher of the family.  Zero page and LDS opt-in for the current device (`lds_max` = the
-// largest request any launch of `kern` makes, so the opt-in happens once), the ConvArgs bookkeeping, the label tt_conv_last_kernel
-// reports (the tail launch of a split, m_begin > 0, keeps the main launch's label) and the launch of kern(a, zero page, tiles_m,
-// tiles_n, extra...).  Returns 1, or -1 with the error text set (naming `who` and the device); never another kernel.
+// largest request any launch of `kern` makes, so the opt-in happens once), the ConvArgs bookkeeping and the launch of kern(a, zero
+// page, tiles_m, tiles_n, extra...).  Returns 1, or -1 with the error text set (naming `who` and the device); never another kernel.
 template <typename K, typename... Extra>
-static int launch_lds_dma(K kern, dim3 grid, dim3 block, size_t lds, size_t lds_max, const char* who, const char* label, ConvArgs& a,
-                          hipStream_t st, int tiles_m, int tiles_n, int splits, Extra... extra) {
+static int launch_lds_dma(K kern, dim3 grid, dim3 block, size_t lds, size_t lds_max, const char* who, ConvArgs& a, hipStream_t st,
+                          int tiles_m, int tiles_n, int splits, Extra... extra) {
     const void* zp = zero_page(who);
     if (!zp || lds_opt_in(reinterpret_cast<const void*>(kern), lds_max, who)) return -1;
     a.tiles_n = tiles_n;
     a.splits = splits;
     if (splits <= 1) a.ws = nullptr;       // split-K: a.ws / a.ws_slices are the caller's
-    if (a.m_begin == 0) snprintf(g_conv_kernel, sizeof(g_conv_kernel), "%s", label);
     hipLaunchKernelGGL(kern, grid, block, lds, st, a, zp, tiles_m, tiles_n, extra...);
     return 1;
 }

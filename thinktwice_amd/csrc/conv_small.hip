@@ -129,10 +129,8 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const ConvArgs p, int t
     }
 }
 
-int try_launch_conv_small(ConvArgs& a, int dtype, hipStream_t st) {
-    if (a.gather || a.m_dev || a.M > 4096) return 0;
+int launch_conv_small(ConvArgs& a, int dtype, hipStream_t st) {
     const int tiles_m = div_up(a.M, 32), tiles_n = div_up(a.Cout, 32);
-    if ((long long)tiles_m * tiles_n > 4096) return 0;
     a.ws = nullptr;
     a.splits = 1;
     const size_t smem = (size_t)4 * 32 * 33 * 4;

@@ -767,38 +767,28 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
 #endif
 }
 
-// Returns 1 if the launch was taken, 0 if the shape is not covered, < 0 if the launch failed.  `m_tiles_limit` > 0: only that many
-// row tiles from a.m_begin (tail split).
-int try_launch_conv_x3_pipe(ConvArgs& a, hipStream_t st, int m_tiles_limit, int bn) {
-    const bool apair = (a.flags & 32) != 0;          // pre-split activations (tt_conv_desc.in_pair)
-    if (a.gather || a.m_dev || (bn != 256 && bn != 128) || a.Cout % bn != 0 || a.Cin % 32 != 0 || a.KH * a.KW > 31 || a.K < 64) return 0;
+// c.family = CONV_X3_RUN3 (the run-staged form of a 3 x 3 stride-1 "same" convolution) or CONV_X3_PIPE (per tap); c.main_rows > 0:
+// only that many row tiles from a.m_begin (tail split).  a.weight = the pre-split weights.  1, or < 0 on failure.
+int launch_conv_x3_pipe(const ConvChoice& c, ConvArgs& a, hipStream_t st) {
+    const int bn = c.bn;
+    TT_REQUIRE(bn == 256 || bn == 128, "tt_conv2d_fwd: no hand-pipelined bf16x3 kernel for a %d-wide tile", bn);
     int tiles_m = div_up(a.M - a.m_begin, 256);
-    if (m_tiles_limit > 0 && m_tiles_limit < tiles_m) tiles_m = m_tiles_limit;
+    if (c.main_rows > 0 && c.main_rows < tiles_m) tiles_m = c.main_rows;
     const int tiles_n = a.Cout / bn;
-    char label[96];
-    // 3 x 3 stride-1 "same" convolutions over a dense batch: the run-staged form (one staged pixel run per filter row serves
-    // its three taps).  TT_X3_RUN3=0 (test hook: tests/test_conv.py compares the two forms bit for bit): the per-tap form everywhere
-    static const bool run3 = env_flag("TT_X3_RUN3", true);
-    if (run3 && a.KW == 3 && a.KH <= 5 && a.stride == 1 && a.dil == 1 && a.pad == 1 && a.OH == a.H && a.OW == a.W &&
-        (a.N == 1 || a.in_nstride == (long long)a.H * a.W * a.in_cstride)) {
+    if (c.family == CONV_X3_RUN3) {
         const size_t smem_r = (size_t)2 * 288 * 128 + (size_t)2 * bn * 128 + 256;
-        auto kr = bn == 128 ? (apair ? conv_x3_run3_kernel<128, true> : conv_x3_run3_kernel<128>)
-                            : (apair ? conv_x3_run3_kernel<256, true> : conv_x3_run3_kernel<256>);
-        snprintf(label, sizeof(label), "conv_x3_run3_kernel<%d>%s%s", bn, apair ? " pre-split A" : "", m_tiles_limit > 0 ? " + tail" : "");
-        return launch_lds_dma(kr, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem_r, smem_r, "conv_x3_run3_kernel", label, a, st,
+        auto kr = bn == 128 ? (c.apair ? conv_x3_run3_kernel<128, true> : conv_x3_run3_kernel<128>)
+                            : (c.apair ? conv_x3_run3_kernel<256, true> : conv_x3_run3_kernel<256>);
+        return launch_lds_dma(kr, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem_r, smem_r, "conv_x3_run3_kernel", a, st,
                               tiles_m, tiles_n, 1);
     }
     // activation ring 3 x 32 KiB + weight ring 2 x (bn x 128 B); the epilogue stages 4 x 32 x (WTN + 4) floats
     size_t smem = (size_t)(3 * 256 + 2 * bn) * 128;
     const size_t epi = (size_t)4 * 32 * ((bn == 128 ? 128 : 256) + 4) * 4;
     if (smem < epi) smem = epi;
-    // wave grid 4 x 1: 64 x 256 (64 x 128 on the 128-wide tile) per wave -- every activation fragment is split by ONE wave (the
-    // 2 x 2 grid of 128 x 128 waves measured slower, profiles/r04_pipe_ab_grids.txt)
-    auto kern = bn == 128 ? (apair ? conv_x3_pipe_kernel<4, 1, 128, true> : conv_x3_pipe_kernel<4, 1, 128>)
-                          : (apair ? conv_x3_pipe_kernel<4, 1, 256, true> : conv_x3_pipe_kernel<4, 1>);
-    snprintf(label, sizeof(label), "conv_x3_pipe_kernel<%s>%s%s", bn == 128 ? "4, 1, 128" : "4, 1", apair ? " pre-split A" : "",
-             m_tiles_limit > 0 ? " + tail" : "");
-    return launch_lds_dma(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem, smem, "conv_x3_pipe_kernel", label, a, st, tiles_m,
+    auto kern = bn == 128 ? (c.apair ? conv_x3_pipe_kernel<4, 1, 128, true> : conv_x3_pipe_kernel<4, 1, 128>)
+                          : (c.apair ? conv_x3_pipe_kernel<4, 1, 256, true> : conv_x3_pipe_kernel<4, 1>);
+    return launch_lds_dma(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem, smem, "conv_x3_pipe_kernel", a, st, tiles_m,
                           tiles_n, 1);
 }
 

@@ -396,24 +396,16 @@ static int launch_sp_runs(ConvArgs& a, hipStream_t st) {
     a.splits = 1;
     a.ws = nullptr;
     a.m_begin = 0;
-    snprintf(g_conv_kernel, sizeof(g_conv_kernel), "sp_conv_runs_kernel<%d, %d, %d>", NCB, WR, WC);
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles_m), dim3(NW * 64), smem, st, a, tiles_m);
     return 1;
 }
 
-// bf16x3 gathered conv with 27 taps in [kz][ky][kx] order (3x3x3 SubM / strided sparse conv), Cin a multiple of 32,
-// Cout 32 / 64 / 128.  `a.weight` = pre-split pair-format weights.  Returns 0 when the shape is not covered, < 0 on failure.
-int try_launch_sp_conv_runs(ConvArgs& a, hipStream_t st) {
-    if (!a.gather || a.row_perm || a.KH != 1 || a.KW != kG * kNG) return 0;
-    // strided sparse convs (the caller states stride 2): the inputs of a (dz, dy) group sit on every other line, the
-    // contiguous range is ~4x the tile and is walked in mostly-empty chunks (measured 0.74 -> 4.1 ms): gather kernel
-    if (a.stride != 1) return 0;
-    if (a.Cin % 32 != 0 || a.Cin > 128 || a.M < 2048 || a.pixel_shuffle2) return 0;
-    if ((a.in_cstride & 3) || (a.in_coff & 3)) return 0;
-    if (a.Cout == 32) return launch_sp_runs<1, 8, 1>(a, st);
-    if (a.Cout == 64) return launch_sp_runs<2, 8, 1>(a, st);
-    if (a.Cout == 128) return launch_sp_runs<2, 4, 2>(a, st);
-    return 0;
+// `a.weight` = pre-split pair-format weights.  1, or < 0 on failure.
+int launch_sp_conv_runs(const ConvChoice& c, ConvArgs& a, hipStream_t st) {
+    if (c.bn == 32 && c.waves_m == 8 && c.waves_n == 1) return launch_sp_runs<1, 8, 1>(a, st);
+    if (c.bn == 64 && c.waves_m == 8 && c.waves_n == 1) return launch_sp_runs<2, 8, 1>(a, st);
+    if (c.bn == 128 && c.waves_m == 4 && c.waves_n == 2) return launch_sp_runs<2, 4, 2>(a, st);
+    TT_REQUIRE(false, "tt_conv2d_fwd: no sp_conv_runs_kernel for a %d-wide tile of %d x %d waves", c.bn, c.waves_m, c.waves_n);
 }
 
 }  // namespace tt

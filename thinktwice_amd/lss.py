@@ -403,7 +403,7 @@ class LSS:
             dbg.update(blocks=d)
         mid = d.shape[-1]
         cat = torch.empty(NI, h, w, 4 * mid, dtype=dt, device=dev)
-        pr_cat = x3 and mid % 16 == 0 and ops.pair_ok(NI * h * w, 4 * mid, mid)   # the branch concat: one reader, conv1 of the ASPP
+        pr_cat = x3 and mid % 16 == 0 and ops.pair_ok(NI * h * w, 4 * mid, mid, taps=1)   # the branch concat: one reader, conv1 of the ASPP
         for i, br in enumerate(self.aspp):
             br(d, out=cat, out_coff=i * mid, out_pair=pr_cat)
         x5 = self.aspp_gap(rows(ops.spatial_pool(d, 0)))                 # (NI,1,1,mid) f32

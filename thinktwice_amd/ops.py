@@ -535,12 +535,14 @@ def upsample_nearest_add_(dst, src):
 PAIR = os.environ.get("TT_X3_PAIR", "1") != "0"     # A/B knob: 0 = every activation tensor stays plain f32
 
 
-def pair_ok(rows, cin=32, cout=64):
-    """Whether a bf16x3 convolution with this many output rows / these channel counts accepts a pair-format input
-    (tt_conv_desc.in_pair: the LDS-DMA kernel's contract; up to 4096 rows a layer runs the exact-f32 latency kernel, which a
-    pair-format layer could not take).  Producer and consumer of a tensor ask with the CONSUMER's numbers."""
+def pair_ok(rows, cin=32, cout=64, taps=9):
+    """Whether a bf16x3 convolution with this many output rows / these channel counts / `taps` = KH * KW filter taps accepts a
+    pair-format input (tt_conv_desc.in_pair: the LDS-DMA kernel's contract, K = taps * cin of at least two 32-channel tiles; up to
+    4096 rows a layer runs the exact-f32 latency kernel, which a pair-format layer could not take).  Producer and consumer of a
+    tensor ask with the CONSUMER's numbers.  tests/test_conv_choice.py pins this to the library's rule."""
     from . import autodiff
-    return PAIR and autodiff.TAPE is None and rows > 4096 and cin % 32 == 0 and (8 <= cout <= 32 or cout >= 64)
+    return (PAIR and autodiff.TAPE is None and rows > 4096 and cin % 32 == 0 and taps * cin >= 64 and
+            (8 <= cout <= 32 or cout >= 64))
 
 
 def bilinear_up2(x, out_pair=False):
