@@ -482,6 +482,42 @@ int tt_preprocess_images(const uint8_t* raw_hwc, int num_images, int H, int W, c
                          int out_channels_padded, int out_dtype, float* out_nchw_or_null, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The TRAINING image pipeline: IDAImageTransform(is_train=True) (configs/thinktwice.py:238-240;
+ * datasets/pipelines/transform.py:248-263 the draw, :275-341 its application) + ImageTransformMulti(aug=False)
+ * (:144,163).  Every camera of a sample has its own resize / crop / flip; both sweeps of the camera and its depth and
+ * segmentation label maps share it.
+ *
+ * Parameter table: `sets` is a HOST pointer to B * N tt_ida_set, entry b * N + n for camera n of sample b (image (b, t, n) of
+ * the frames and label map (b, n) both use it).  The entry checks every set and copies the table into the kernel's
+ * arguments (passed by value: no device buffer, no copy, the caller may reuse the memory on return), which bounds it to
+ * TT_IDA_MAX_SETS sets per call.  Returns an error, before any launch, for a non-positive resized size, crop_x < 0,
+ * crop_y < 0, crop_x + out_w > resized_w, crop_y + out_h > resized_h or a flip that is not 0 / 1.
+ *
+ * Per output pixel (oy, ox), tt_preprocess_images' arithmetic: cx = flip ? out_w - 1 - ox : ox; source coordinate
+ * (oy + crop_y + 0.5) * H / resized_h - 0.5 (and likewise along x with cx), clamped at 0, neighbours clamped at the last row /
+ * column, each tap a zero-padded bilinear read of the raw image through the undistortion map.  One launch, no
+ * synchronisation, no allocation.
+ * ---------------------------------------------------------------------- */
+#define TT_IDA_MAX_SETS 64
+typedef struct tt_ida_set {
+    int resized_h, resized_w;   /* resize_dims of sample_ida_augmentation, (int(H * resize), int(W * resize)) */
+    int crop_y, crop_x;         /* crop origin in the resized image (crop[1], crop[0]) */
+    int flip;                   /* 1: horizontal flip after the crop (torch.flip(img, [-1])) */
+} tt_ida_set;
+/* frames: transform.py:280-283 (undistortion), img_transform :346-358 (T.Resize, crop, flip), :163 (/255, Normalize).
+ * raw uint8 [B,T,N,H,W,3]; mapx/mapy f32 [H,W] as for tt_preprocess_images; mean3/std3: HOST floats.  Writes channel-last
+ * out_nhwc [B*T*N,out_h,out_w,Cp] (dtype) and/or NCHW f32 [B*T*N,3,out_h,out_w]. */
+int tt_preprocess_images_ida(const uint8_t* raw_hwc, int B, int T, int N, int H, int W, const float* mapx,
+                             const float* mapy, const tt_ida_set* sets, int out_h, int out_w, const float* mean3,
+                             const float* std3, void* out_nhwc, int out_channels_padded, int out_dtype,
+                             float* out_nchw_or_null, void* stream);
+/* label maps of the key sweep: transform.py:285-292 (undistortion), depth_transform :386-396 (T.Resize -- bilinear, for the
+ * segmentation class ids too, as the reference does --, crop, flip); no normalisation.  maps f32 [B,N,H,W] (depth in metres
+ * or class ids) -> out f32 [B,N,out_h,out_w].  One call per kind. */
+int tt_preprocess_labels_ida(const float* maps, int B, int N, int H, int W, const float* mapx, const float* mapy,
+                             const tt_ida_set* sets, int out_h, int out_w, float* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * SURVEY 8f-4 (training step), optimizer half: the reference's `optimizer_config = dict(grad_clip=dict(max_norm=100,
  * norm_type=2))` and `optimizer = dict(type='AdamW', lr=1e-4, weight_decay=1e-7)` (configs/thinktwice.py:282-287:
  * torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW through mmcv's OptimizerHook) over ONE flat f32 parameter /

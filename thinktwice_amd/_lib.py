@@ -22,6 +22,7 @@ LIB_PATH = os.path.join(_HERE, "libthinktwice_hip.so")
 LIB_PATH = os.environ.get("TT_LIB_PATH", LIB_PATH)
 
 TT_F32, TT_BF16, TT_F16 = 0, 1, 2
+TT_IDA_MAX_SETS = 64     # parameter sets (samples x cameras) of one tt_preprocess_*_ida call
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_GELU, ACT_SOFTPLUS, ACT_SOFTPLUS_CLAMP = 0, 1, 2, 3, 4, 5
 
 _lib = None

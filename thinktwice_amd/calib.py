@@ -31,6 +31,10 @@ UNDISTORT_LIDAR2IMG = {  # transform.py:33-38
 IMG_H, IMG_W = 900, 1600          # raw camera size (configs/thinktwice.py:116-117)
 FINAL_H, FINAL_W = 448, 896       # network input (configs/thinktwice.py:113)
 
+# image-data augmentation of the training pipeline (configs/thinktwice.py:111-119), read by IDAImageTransform
+IDA_AUG_CONF = {"resize_lim": (0.56, 0.6255), "final_dim": (FINAL_H, FINAL_W), "rot_lim": (0, 0), "H": IMG_H, "W": IMG_W,
+                "rand_flip": True, "bot_pct_lim": (0.0, 0.0)}
+
 
 def eval_ida_mat(final_dim=(FINAL_H, FINAL_W)):
     """IDAImageTransform.sample_ida_augmentation, is_train=False branch (transform.py:264-273)

@@ -6,6 +6,8 @@
 // in ONE gather kernel: every output pixel blends 2x2 taps of the (virtual) undistorted image, each of
 // which is a bilinear read of the raw frame through the undistortion map (zero padding), so the
 // 17.3 MB uint8 frame set is read once and the normalised tensor is written once, channel-last.
+#include <limits.h>
+
 #include "tt_common.h"
 
 namespace tt {
@@ -74,6 +76,120 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a, const uint8_
         for (int c = 3; c < a.Cp; ++c) Elem<T>::st(out + t * a.Cp + c, 0.f);
 }
 
+// ---- train-mode pipeline: IDAImageTransform(is_train=True) (transform.py:248-341), one draw per (sample, camera) ----
+// The table of draws travels in the kernel arguments (tt_ida_set of thinktwice_hip.h, TT_IDA_MAX_SETS entries at the most),
+// so the entry can check every set on the host and needs neither a device buffer nor a copy.
+struct IdaTable {
+    tt_ida_set s[TT_IDA_MAX_SETS];
+};
+
+struct IdaArgs {
+    int NI, H, W;            // raw images (frames: B*T*N, labels: B*N)
+    int per_sample, N;       // images per sample (frames: T*N, labels: N) and cameras: set = (n / per_sample) * N + n % N
+    int OH, OW, Cp;          // output size and padded channels
+    int pixel16;             // channel-last pixels are 16 bytes and 16-byte aligned
+    float mean[3], inv_std[3];
+};
+
+// The evaluation kernel's source coordinates for output pixel (oy, ox) of an image under set `p`; a flip mirrors the column.
+struct IdaTaps {
+    int y0, y1, x0, x1;
+    float ly, lx;
+};
+
+__device__ __forceinline__ IdaTaps ida_taps(const tt_ida_set& p, int H, int W, int OW, int oy, int ox) {
+    const int cx = p.flip ? OW - 1 - ox : ox;
+    // F.interpolate(bilinear, align_corners=False): src = (dst + 0.5) * in/out - 0.5, clamped at 0
+    const float sy = fmaxf(((float)(oy + p.crop_y) + 0.5f) * ((float)H / (float)p.resized_h) - 0.5f, 0.f);
+    const float sx = fmaxf(((float)(cx + p.crop_x) + 0.5f) * ((float)W / (float)p.resized_w) - 0.5f, 0.f);
+    IdaTaps t;
+    t.y0 = min((int)sy, H - 1);   // (never binds for a crop inside the resized image, which the entry requires: the map
+    t.x0 = min((int)sx, W - 1);   //  is read unchecked at these coordinates)
+    t.y1 = min(t.y0 + 1, H - 1);
+    t.x1 = min(t.x0 + 1, W - 1);
+    t.ly = sy - (float)t.y0;
+    t.lx = sx - (float)t.x0;
+    return t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void preprocess_ida_kernel(IdaArgs a, IdaTable tab, const uint8_t* __restrict__ raw,
+                                                             const float* __restrict__ mapx,
+                                                             const float* __restrict__ mapy, T* __restrict__ out,
+                                                             float* __restrict__ out_nchw) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long total = (long long)a.NI * a.OH * a.OW;
+    if (t >= total) return;
+    const int ox = (int)(t % a.OW);
+    const int oy = (int)((t / a.OW) % a.OH);
+    const int n = (int)(t / ((long long)a.OW * a.OH));
+    const IdaTaps k = ida_taps(tab.s[(n / a.per_sample) * a.N + n % a.N], a.H, a.W, a.OW, oy, ox);
+    const uint8_t* img = raw + (long long)n * a.H * a.W * 3;
+    float p00[3], p01[3], p10[3], p11[3];
+    undist_px(img, mapx, mapy, a.H, a.W, k.y0, k.x0, p00);
+    undist_px(img, mapx, mapy, a.H, a.W, k.y0, k.x1, p01);
+    undist_px(img, mapx, mapy, a.H, a.W, k.y1, k.x0, p10);
+    undist_px(img, mapx, mapy, a.H, a.W, k.y1, k.x1, p11);
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float top = (1.f - k.lx) * p00[c] + k.lx * p01[c];
+        const float bot = (1.f - k.lx) * p10[c] + k.lx * p11[c];
+        v[c] = (1.f - k.ly) * top + k.ly * bot;
+        v[c] = (v[c] / 255.f - a.mean[c]) * a.inv_std[c];
+        if (out_nchw) out_nchw[(((long long)n * 3 + c) * a.OH + oy) * a.OW + ox] = v[c];
+    }
+    if (!out) return;
+    if (a.pixel16) {   // the trunk's forms (f32 x 4, 16-bit x 8): the padded pixel is one aligned 16-byte store per lane
+        constexpr int kN = 16 / (int)sizeof(T);
+        union { T e[kN]; uint4 q; } px;
+#pragma unroll
+        for (int c = 0; c < kN; ++c) Elem<T>::st(px.e + c, c < 3 ? v[c] : 0.f);
+        *reinterpret_cast<uint4*>(out + t * kN) = px.q;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Elem<T>::st(out + t * a.Cp + c, v[c]);
+        for (int c = 3; c < a.Cp; ++c) Elem<T>::st(out + t * a.Cp + c, 0.f);
+    }
+}
+
+// single-channel f32 label maps (depth in metres, segmentation class ids): the same two bilinear stages, no normalisation
+__device__ __forceinline__ float label_at(const float* __restrict__ img, int H, int W, int y, int x) {
+    return (y >= 0 && y < H && x >= 0 && x < W) ? img[(long long)y * W + x] : 0.f;
+}
+
+__device__ __forceinline__ float undist_label(const float* __restrict__ img, const float* __restrict__ mapx,
+                                              const float* __restrict__ mapy, int H, int W, int Y, int X) {
+    const float px = mapx[(long long)Y * W + X] - 0.5f;
+    const float py = mapy[(long long)Y * W + X] - 0.5f;
+    const float fx = floorf(px), fy = floorf(py);
+    const int x0 = (int)fx, y0 = (int)fy;
+    const float lx = px - fx, ly = py - fy;
+    const float v00 = label_at(img, H, W, y0, x0), v01 = label_at(img, H, W, y0, x0 + 1);
+    const float v10 = label_at(img, H, W, y0 + 1, x0), v11 = label_at(img, H, W, y0 + 1, x0 + 1);
+    return v00 * (1.f - lx) * (1.f - ly) + v01 * lx * (1.f - ly) + v10 * (1.f - lx) * ly + v11 * lx * ly;
+}
+
+__global__ __launch_bounds__(256) void preprocess_labels_ida_kernel(IdaArgs a, IdaTable tab, const float* __restrict__ maps,
+                                                                    const float* __restrict__ mapx,
+                                                                    const float* __restrict__ mapy, float* __restrict__ out) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long total = (long long)a.NI * a.OH * a.OW;
+    if (t >= total) return;
+    const int ox = (int)(t % a.OW);
+    const int oy = (int)((t / a.OW) % a.OH);
+    const int n = (int)(t / ((long long)a.OW * a.OH));
+    const IdaTaps k = ida_taps(tab.s[(n / a.per_sample) * a.N + n % a.N], a.H, a.W, a.OW, oy, ox);
+    const float* img = maps + (long long)n * a.H * a.W;
+    const float p00 = undist_label(img, mapx, mapy, a.H, a.W, k.y0, k.x0);
+    const float p01 = undist_label(img, mapx, mapy, a.H, a.W, k.y0, k.x1);
+    const float p10 = undist_label(img, mapx, mapy, a.H, a.W, k.y1, k.x0);
+    const float p11 = undist_label(img, mapx, mapy, a.H, a.W, k.y1, k.x1);
+    const float top = (1.f - k.lx) * p00 + k.lx * p01;
+    const float bot = (1.f - k.lx) * p10 + k.lx * p11;
+    out[t] = (1.f - k.ly) * top + k.ly * bot;
+}
+
 // LiDAR half-sweep merge of the agent tick (leaderboard/team_code/thinktwice_agent.py:340-352): the simulator runs at
 // 20 Hz, the LiDAR at 10 Hz, so every tick delivers a 180-degree half sweep; the previous half sweep is moved into the
 // current ego frame (rigid planar transform, rows of `mat` = first three rows of inv(T_now) @ T_prev), the two halves
@@ -126,6 +242,76 @@ extern "C" int tt_preprocess_images(const uint8_t* raw_hwc, int num_images, int 
     else
         TT_REQUIRE(false, "tt_preprocess_images: bad dtype");
     return check_launch("tt_preprocess_images");
+}
+
+// every draw of the table against the output size, on the host, before anything is launched
+static int ida_fill(const char* what, const tt_ida_set* sets, int num_sets, int out_h, int out_w, IdaTable* tab) {
+    TT_REQUIRE(sets && num_sets > 0 && num_sets <= TT_IDA_MAX_SETS, "%s: need 1..%d parameter sets, got %d", what,
+               TT_IDA_MAX_SETS, num_sets);
+    for (int i = 0; i < num_sets; ++i) {
+        const tt_ida_set& p = sets[i];
+        TT_REQUIRE(p.resized_h > 0 && p.resized_w > 0, "%s: set %d: resized size %d x %d is not positive", what, i,
+                   p.resized_h, p.resized_w);
+        TT_REQUIRE(p.crop_y >= 0 && p.crop_x >= 0, "%s: set %d: negative crop origin (%d, %d)", what, i, p.crop_y, p.crop_x);
+        // (written as subtractions: no overflow for any int crop)
+        TT_REQUIRE(p.crop_y <= p.resized_h - out_h && p.crop_x <= p.resized_w - out_w,
+                   "%s: set %d: crop (%d, %d) + output %d x %d leaves the resized image %d x %d", what, i, p.crop_y, p.crop_x,
+                   out_h, out_w, p.resized_h, p.resized_w);
+        TT_REQUIRE(p.flip == 0 || p.flip == 1, "%s: set %d: flip must be 0 or 1", what, i);
+        tab->s[i] = p;
+    }
+    return 0;
+}
+
+extern "C" int tt_preprocess_images_ida(const uint8_t* raw_hwc, int B, int T, int N, int H, int W, const float* mapx,
+                                        const float* mapy, const tt_ida_set* sets, int out_h, int out_w,
+                                        const float* mean3, const float* std3, void* out_nhwc, int out_channels_padded,
+                                        int out_dtype, float* out_nchw_or_null, void* stream) {
+    TT_REQUIRE(raw_hwc && mapx && mapy && mean3 && std3 && (out_nhwc || out_nchw_or_null), "tt_preprocess_images_ida: null");
+    TT_REQUIRE(B > 0 && T > 0 && N > 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0, "tt_preprocess_images_ida: bad sizes");
+    TT_REQUIRE(out_channels_padded >= 3, "tt_preprocess_images_ida: need >= 3 output channels");
+    TT_REQUIRE(out_dtype == TT_F32 || out_dtype == TT_BF16 || out_dtype == TT_F16, "tt_preprocess_images_ida: bad dtype");
+    TT_REQUIRE((long long)B * N <= TT_IDA_MAX_SETS, "tt_preprocess_images_ida: B * N = %lld parameter sets, at most %d",
+               (long long)B * N, TT_IDA_MAX_SETS);
+    IdaTable tab;
+    if (int rc = ida_fill("tt_preprocess_images_ida", sets, B * N, out_h, out_w, &tab)) return rc;
+    const long long total = (long long)B * T * N * out_h * out_w;
+    TT_REQUIRE((long long)B * T * N <= INT_MAX && (total + 255) / 256 <= INT_MAX, "tt_preprocess_images_ida: too many pixels");
+    IdaArgs a;
+    a.NI = B * T * N; a.H = H; a.W = W; a.per_sample = T * N; a.N = N;
+    a.OH = out_h; a.OW = out_w; a.Cp = out_channels_padded;
+    a.pixel16 = out_channels_padded * (out_dtype == TT_F32 ? 4 : 2) == 16 && ((uintptr_t)out_nhwc & 15) == 0;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.inv_std[c] = 1.f / std3[c]; }
+    const dim3 grid((unsigned)div_up(total, 256));
+    if (out_dtype == TT_F32)
+        hipLaunchKernelGGL(preprocess_ida_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a, tab, raw_hwc, mapx, mapy,
+                           (float*)out_nhwc, out_nchw_or_null);
+    else if (out_dtype == TT_BF16)
+        hipLaunchKernelGGL(preprocess_ida_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, a, tab, raw_hwc, mapx,
+                           mapy, (uint16_t*)out_nhwc, out_nchw_or_null);
+    else
+        hipLaunchKernelGGL(preprocess_ida_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, a, tab, raw_hwc, mapx, mapy,
+                           (f16_t*)out_nhwc, out_nchw_or_null);
+    return check_launch("tt_preprocess_images_ida");
+}
+
+extern "C" int tt_preprocess_labels_ida(const float* maps, int B, int N, int H, int W, const float* mapx, const float* mapy,
+                                        const tt_ida_set* sets, int out_h, int out_w, float* out, void* stream) {
+    TT_REQUIRE(maps && mapx && mapy && out, "tt_preprocess_labels_ida: null");
+    TT_REQUIRE(B > 0 && N > 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0, "tt_preprocess_labels_ida: bad sizes");
+    TT_REQUIRE((long long)B * N <= TT_IDA_MAX_SETS, "tt_preprocess_labels_ida: B * N = %lld parameter sets, at most %d",
+               (long long)B * N, TT_IDA_MAX_SETS);
+    IdaTable tab;
+    if (int rc = ida_fill("tt_preprocess_labels_ida", sets, B * N, out_h, out_w, &tab)) return rc;
+    const long long total = (long long)B * N * out_h * out_w;
+    TT_REQUIRE((total + 255) / 256 <= INT_MAX, "tt_preprocess_labels_ida: too many pixels");
+    IdaArgs a;
+    a.NI = B * N; a.H = H; a.W = W; a.per_sample = N; a.N = N;
+    a.OH = out_h; a.OW = out_w; a.Cp = 1; a.pixel16 = 0;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = 0.f; a.inv_std[c] = 1.f; }
+    hipLaunchKernelGGL(preprocess_labels_ida_kernel, dim3((unsigned)div_up(total, 256)), dim3(256), 0, (hipStream_t)stream, a,
+                       tab, maps, mapx, mapy, out);
+    return check_launch("tt_preprocess_labels_ida");
 }
 
 extern "C" int tt_lidar_merge_half_sweeps(const float* prev_xyzi, int n_prev, const float* now_xyzi, int n_now,

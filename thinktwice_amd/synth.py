@@ -125,3 +125,16 @@ def raw_camera_frames(seed=17, T=2, N=4, h=900, w=1600):
     yy = (np.arange(h, dtype=np.float32)[:, None, None] % 200) * 0.9
     xx = (np.arange(w, dtype=np.float32)[None, :, None] % 320) * 0.35
     return np.clip(noise * 0.25 + yy + xx, 0, 255).astype(np.uint8)
+
+
+def raw_label_maps(seed=18, N=4, h=900, w=1600):
+    """Seeded raw label maps of the key sweep, (depth, seg) f32 [N, h, w] each: depth in [0, 100] m as noise on smooth ramps
+    (not quantised), seg as class ids 0..11 in 25x25-pixel blocks.  Golden F18 was produced from exactly these maps."""
+    rng = np.random.default_rng(seed)
+    noise = rng.random((N, h, w), dtype=np.float32) * 100.0
+    yy = (np.arange(h, dtype=np.float32)[:, None] % 200) * 0.25
+    xx = (np.arange(w, dtype=np.float32)[None, :] % 320) * 0.078125
+    depth = np.clip(noise * 0.25 + yy + xx, 0, 100).astype(np.float32)
+    blocks = rng.integers(0, 12, (N, -(-h // 25), -(-w // 25)))
+    seg = np.repeat(np.repeat(blocks, 25, axis=1), 25, axis=2)[:, :h, :w].astype(np.float32)
+    return depth, np.ascontiguousarray(seg)
