@@ -518,6 +518,74 @@ int tt_preprocess_labels_ida(const float* maps, int B, int N, int H, int W, cons
                              const tt_ida_set* sets, int out_h, int out_w, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The colour augmentation of training frames: ImageTransformMulti(aug=True) and its imgaug `augmenter(iteration)`
+ * (datasets/pipelines/transform.py:142-216): a random-order sequence of eight operators on uint8 images (GaussianBlur,
+ * AdditiveGaussianNoise, CoarseDropout, Dropout, Add, Multiply, LinearContrast, Grayscale), each under Sometimes(frequency),
+ * made deterministic per sample, so all T x N frames of a sample get the same order, parameters and per-pixel random fields.
+ *
+ * The host (thinktwice_amd/photometric.py) draws one *program* per sample and compiles it into at most TT_AUG_MAX_OPS device
+ * steps; the device only executes tables.  imgaug's random stream is not reproduced, and every rounding convention of
+ * imgaug 0.4.0 / cv2 adopted here is UNPINNED (neither is installed where this was written): each lives in one host function
+ * of photometric.py (INTEGRATION 2c lists them).  Step kinds, on integer grey levels v in 0..255 of pixel (y, x), channel c:
+ *   LUT      v = lut[c][v]                                   (Add, Multiply, LinearContrast; adjacent ones composed on the host)
+ *   NOISE    v = clip(v + k), k = -TT_AUG_NOISE_K + #{j : u >= cum[j]}: round(N(0, scale)) by its cumulative u32 thresholds
+ *   DROPOUT  v = 0 where u < threshold
+ *   COARSE   the same on the field value of cell (y * grid_h / H, x * grid_w / W) (integer division)
+ *   GRAY     g = (4899 R + 9617 G + 1868 B + 8192) >> 14; v = clip(rint(f32(v) + alpha * f32(g - v)))
+ *   BLUR     5 x 5 separable Gaussian, reflect-101 border, f32: horizontal then vertical, each summed
+ *            ((((g0 p0 + g1 p1) + g2 p2) + g3 p3) + g4 p4) without fused multiply-add, then rint and clip; at most one per program
+ * The field value u is the high 32 bits of splitmix64 at seed + 0x9E3779B97F4A7C15 * (idx + 1) (the mix of the dropout
+ * kernel), idx = (c * H + y) * W + x when per_channel, else y * W + x shared by the channels; for COARSE idx runs over
+ * the grid's cells the same way.  idx never depends on the image: every frame of a sample gets the same field.
+ *
+ * Programs are too large for kernel arguments: the caller keeps the B programs in host memory (checked by the entry before
+ * any launch, the error naming the sample) and a copy in device memory (read by the kernels).  The entries do not copy,
+ * allocate or synchronise.  A program with a BLUR needs `scratch`: tt_photometric_scratch_bytes(images, H, W) bytes (one packed
+ * 4-byte pixel per pixel; the point steps before the blur write it, the blur kernel reads it).
+ * ---------------------------------------------------------------------- */
+#define TT_AUG_MAX_OPS 8
+#define TT_AUG_NOISE_K 4
+#define TT_AUG_LUT 0
+#define TT_AUG_NOISE 1
+#define TT_AUG_DROPOUT 2
+#define TT_AUG_COARSE 3
+#define TT_AUG_GRAY 4
+#define TT_AUG_BLUR 5
+typedef struct tt_aug_op {
+    int kind;                            /* TT_AUG_* */
+    int per_channel;                     /* NOISE, DROPOUT, COARSE: a field value per channel */
+    int grid_h, grid_w;                  /* COARSE: cells, 1..H and 1..W */
+    unsigned threshold;                  /* DROPOUT, COARSE: floor(p * 2^32) */
+    float alpha;                         /* GRAY: 0..1 */
+    unsigned long long seed;             /* NOISE, DROPOUT, COARSE: field seed */
+    unsigned cum[2 * TT_AUG_NOISE_K];    /* NOISE: cum[j] = floor(2^32 * Phi((-K + j + 0.5) / scale)), non-decreasing */
+    float taps[5];                       /* BLUR: normalised, >= 0 */
+    int reserved;
+    unsigned char lut[3][256];           /* LUT: one table per channel */
+} tt_aug_op;                             /* 856 bytes */
+typedef struct tt_aug_program {
+    int num_ops;                         /* 0..TT_AUG_MAX_OPS */
+    int blur_index;                      /* index of the BLUR step, -1 without one */
+    tt_aug_op ops[TT_AUG_MAX_OPS];
+} tt_aug_program;                        /* 6856 bytes */
+
+/* Host arithmetic only: the scratch a call over `num_images` images of H x W needs when any program has a BLUR. */
+long long tt_photometric_scratch_bytes(int num_images, int H, int W);
+/* uint8 images that have been pre-processed already: in_u8 / out_u8 [B, per_sample, H, W, 3] (device; out may not alias in),
+ * image (b, k) under program b. */
+int tt_photometric_u8(const uint8_t* in_u8, int B, int per_sample, int H, int W, const tt_aug_program* programs_host,
+                      const tt_aug_program* programs_dev, void* scratch, long long scratch_bytes, uint8_t* out_u8,
+                      void* stream);
+/* The fused path: tt_preprocess_images_ida's gather (same arguments, same checks), then what the reference does between the
+ * two transforms and after: astype(uint8) -- (int)v truncation, clamped to 0..255 --, the program of the image's sample,
+ * /255 and Normalize.  With all-empty programs it differs from tt_preprocess_images_ida by that truncation alone. */
+int tt_preprocess_images_ida_aug(const uint8_t* raw_hwc, int B, int T, int N, int H, int W, const float* mapx,
+                                 const float* mapy, const tt_ida_set* sets, int out_h, int out_w, const float* mean3,
+                                 const float* std3, void* out_nhwc, int out_channels_padded, int out_dtype,
+                                 float* out_nchw_or_null, const tt_aug_program* programs_host,
+                                 const tt_aug_program* programs_dev, void* scratch, long long scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * SURVEY 8f-4 (training step), optimizer half: the reference's `optimizer_config = dict(grad_clip=dict(max_norm=100,
  * norm_type=2))` and `optimizer = dict(type='AdamW', lr=1e-4, weight_decay=1e-7)` (configs/thinktwice.py:282-287:
  * torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW through mmcv's OptimizerHook) over ONE flat f32 parameter /

@@ -1,15 +1,16 @@
 """GPU camera preprocessing -- host-side mirror of the image pipeline
-(IDAImageTransform + img_transform + ImageTransformMulti aug=False:
+(IDAImageTransform + img_transform + ImageTransformMulti:
 open_loop_training/code/datasets/pipelines/transform.py:222-378,140-166), one fused kernel per call: `ImagePreprocessor` for
 the evaluation branch (is_train=False), `IdaSampler` / `TrainImagePipeline` / `fill_batch` for the training branch
-(is_train=True: a resize, crop and flip of its own for every camera of a sample, applied to its depth / seg labels too)."""
+(is_train=True: a resize, crop and flip of its own for every camera of a sample, applied to its depth / seg labels too;
+with `augment`, ImageTransformMulti(aug=True)'s colour augmentation of photometric.py in the same pass)."""
 import collections
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _lib, calib, ops
+from . import _lib, calib, ops, photometric
 from .ops import check, lib, ptr
 
 
@@ -133,11 +134,14 @@ class TrainImagePipeline(ImagePreprocessor):
         flat = [p for per_cam in params for p in per_cam]
         return (IdaSet * len(flat))(*[IdaSet(p.resized_h, p.resized_w, p.crop_y, p.crop_x, int(bool(p.flip))) for p in flat])
 
-    def __call__(self, raw, depth=None, seg=None, params=None, sampler=None, channel_last_dtype=None, c_pad=None):
+    def __call__(self, raw, depth=None, seg=None, params=None, sampler=None, channel_last_dtype=None, c_pad=None, augment=None):
         """raw uint8 [B, T, N, H, W, 3] on the device; depth / seg f32 [B, N, H, W] (key sweep) or None.  `params`
         ([B][N] IdaParams) override `sampler` (an IdaSampler).  Returns dict(img [B, T, N, 3, fh, fw] f32 -- or, with
         `channel_last_dtype`, the channel-last padded [B*T*N, fh, fw, c_pad] tensor the LSS trunk consumes --, depth / seg
-        [B, N, fh, fw] where given, ida_mats [B, T, N, 4, 4] f32 on the host, params)."""
+        [B, N, fh, fw] where given, ida_mats [B, T, N, 4, 4] f32 on the host, params).
+        `augment` (a photometric.PhotometricSampler, or a list of B compiled photometric.Program) adds
+        ImageTransformMulti(aug=True): the frames are truncated to uint8 grey levels and every frame of sample b goes through
+        program b before the normalisation; the labels and ida_mats are untouched, and the result gains `programs`."""
         if raw.dim() != 6 or raw.dtype != torch.uint8 or raw.shape[-1] != 3 or not raw.is_contiguous():
             raise ValueError("raw must be a contiguous uint8 [B, T, N, H, W, 3] tensor")
         B, T, N, H, W, _ = raw.shape
@@ -149,10 +153,14 @@ class TrainImagePipeline(ImagePreprocessor):
             if lab is not None and (lab.dtype != torch.float32 or tuple(lab.shape) != (B, N, H, W) or not lab.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous f32 [{B}, {N}, {H}, {W}] tensor")
         table = self._table(params, B, N)               # (nothing has been launched before this line)
+        fh, fw = self.final_dim
+        programs = None
+        if augment is not None:
+            programs = augment.programs(B, fh, fw) if isinstance(augment, photometric.PhotometricSampler) else list(augment)
+            photometric.check_programs(programs, B, fh, fw)
         if (H, W) != tuple(self.mapx.shape):            # (the kernels read the map unchecked at raw-image coordinates)
             raise ValueError(f"raw frames are {H} x {W}, the undistortion map {tuple(self.mapx.shape)}")
         _lib.require_cuda(raw, depth, seg)
-        fh, fw = self.final_dim
         stream = ops.cur_stream(raw.device)
         nchw = nhwc = None
         if channel_last_dtype is None:
@@ -162,9 +170,17 @@ class TrainImagePipeline(ImagePreprocessor):
             cp = c_pad or (4 if channel_last_dtype == torch.float32 else 8)
             nhwc = torch.empty(B * T * N, fh, fw, cp, dtype=channel_last_dtype, device=raw.device)
             code = ops.dtype_code(nhwc)
-        check(lib().tt_preprocess_images_ida(ptr(raw), B, T, N, H, W, ptr(self.mapx), ptr(self.mapy), table, fh, fw, self.mean,
-                                             self.std, ptr(nhwc), cp, code, ptr(nchw), stream), "tt_preprocess_images_ida")
+        if programs is None:
+            check(lib().tt_preprocess_images_ida(ptr(raw), B, T, N, H, W, ptr(self.mapx), ptr(self.mapy), table, fh, fw, self.mean,
+                                                 self.std, ptr(nhwc), cp, code, ptr(nchw), stream), "tt_preprocess_images_ida")
+        else:
+            host, dev, scratch, nbytes = photometric.device_programs(programs, B * T * N, fh, fw, raw.device)
+            check(lib().tt_preprocess_images_ida_aug(ptr(raw), B, T, N, H, W, ptr(self.mapx), ptr(self.mapy), table, fh, fw,
+                                                     self.mean, self.std, ptr(nhwc), cp, code, ptr(nchw), host.data_ptr(), ptr(dev),
+                                                     ptr(scratch), nbytes, stream), "tt_preprocess_images_ida_aug")
         out = {"img": nchw if nhwc is None else nhwc, "params": params}
+        if programs is not None:
+            out["programs"] = programs
         for name, lab in (("depth", depth), ("seg", seg)):
             if lab is not None:
                 out[name] = torch.empty(B, N, fh, fw, dtype=torch.float32, device=raw.device)
