@@ -81,6 +81,25 @@ bool choose_x3_splitk(const ConvArgs& a, bool assume_ws, ConvChoice* c) {
     return true;
 }
 
+// ---- weight-resident sparse 3x3x3 conv (sp_conv_l2.hip): bf16x3 gathered conv with 27 taps, Cin 16 / 32, Cout 16 / 32 / 64, any
+// rulebook and stride.  A persistent launch loads 27 x 32 x Cin x 4 B of weights (110 KB at Cin = 32) into every CU's LDS once, which
+// only pays over many 32-row groups: from kSpL2MinRows allocated rows on (at most 65,536: the batch-1 allocation of the 16-channel
+// level must take this kernel).  Below it the run-staged kernel and the gathered LDS-DMA tiles keep their layers.
+// Measured crossover (profiles/sp_conv_l2.txt; us per launch, old -> new): 32 -> 32 SubM at 17 K / 64 K / 260 K rows 26.9 -> 18.8,
+// 30.0 -> 21.8, 99.3 -> 68.3; 16 -> 16 at 64 K rows 22.9 -> 11.8.  The new kernel already wins at the lowest size tried, so the
+// threshold sits at the 16,384 rows it was first set to.  The routed shapes of the B = 8 forward, serialised (ms over the calls,
+// old -> new): 32 -> 32 SubM x 4 2.43 -> 1.65; 32 -> 64 stride 2 0.80 -> 0.68; 16 -> 16 SubM x 4 (M = 523 K) 0.55 -> 0.31;
+// 16 -> 32 stride 2 0.37 -> 0.22.  Every shape wins, so none is sent back to its old kernel.
+bool choose_sp_runs_l2(const ConvArgs& a, ConvChoice* c) {
+    if (!a.gather || a.row_perm || a.KH != 1 || a.KW != 27 || a.pixel_shuffle2 || a.M < kSpL2MinRows) return false;
+    if ((a.Cin != 16 && a.Cin != 32) || (a.Cout != 16 && a.Cout != 32 && a.Cout != 64)) return false;
+    // 16 B loads of the neighbour rows, the vector epilogue's f32 stores
+    if ((a.in_cstride & 3) || (a.in_coff & 3) || !aligned16(a.in) || !a.vec_epi || a.out_dtype != TT_F32) return false;
+    set_tile(c, CONV_SP_RUNS_L2, 32, 8, 1, a.Cin * 4, 1);
+    c->gather = c->x3 = true;
+    return true;
+}
+
 // ---- run-staged sparse 3x3x3 conv (sp_conv_runs.hip): bf16x3 gathered conv with 27 taps in [kz][ky][kx] order, Cin a multiple
 // of 32, Cout 32 / 64 / 128
 bool choose_sp_runs(const ConvArgs& a, ConvChoice* c) {
@@ -108,6 +127,7 @@ bool x3_pipe_ok(const ConvArgs& a, int bn) {
 bool choose_x3(const ConvArgs& a, ConvChoice* c) {
     c->x3 = true;
     if (a.gather) {
+        if (choose_sp_runs_l2(a, c)) return true;   // 3x3x3 rulebooks with 16 / 32 channels over many rows: weights resident in LDS
         if (choose_sp_runs(a, c)) return true;      // 3x3x3 rulebooks with 32+ channels: run-staged kernel
         const bool cin_ok = a.Cin >= 16 && (a.Cin & (a.Cin - 1)) == 0;
         if (!cin_ok || a.M < 2048 || a.Cout < 16 || a.Cout > 128) return false;
@@ -321,6 +341,7 @@ void conv_label(const ConvChoice& c, int dtype, char* out, size_t bytes) {
         case CONV_H2: snprintf(out, bytes, "conv_h2_kernel<%d, %d, %d, %d, %d>", c.bn, c.waves_m, c.waves_n, c.stages / 10, c.stages % 10); break;
         case CONV_H2_PIPE: snprintf(out, bytes, "conv_h2_pipe_kernel"); break;
         case CONV_SMALL: snprintf(out, bytes, "conv_small_kernel"); break;
+        case CONV_SP_RUNS_L2: snprintf(out, bytes, "sp_conv_runs_l2_kernel<%d>", c.bkb / 4); break;
         case CONV_SP_RUNS: snprintf(out, bytes, "sp_conv_runs_kernel<%d, %d, %d>", c.bn / (32 * c.waves_n), c.waves_m, c.waves_n); break;
         case CONV_X3_PIPE: snprintf(out, bytes, "conv_x3_pipe_kernel<%s>%s%s", c.bn == 128 ? "4, 1, 128" : "4, 1", pre, tail); break;
         case CONV_X3_RUN3: snprintf(out, bytes, "conv_x3_run3_kernel<%d>%s%s", c.bn, pre, tail); break;

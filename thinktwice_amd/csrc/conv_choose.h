@@ -52,12 +52,16 @@ enum ConvFamily {
     CONV_H2,        // conv_h2.hip        conv_h2_kernel<bn, waves_m, waves_n, SA, SB>        (stages = 10 SA + SB)
     CONV_H2_PIPE,   // conv_h2.hip        conv_h2_pipe_kernel
     CONV_SMALL,     // conv_small.hip     conv_small_kernel<T>
+    CONV_SP_RUNS_L2,  // sp_conv_l2.hip   sp_conv_runs_l2_kernel<Cin>                          (bkb = 4 Cin: bytes of a weight row)
     CONV_SP_RUNS,   // sp_conv_runs.hip   sp_conv_runs_kernel<bn / (32 waves_n), waves_m, waves_n>
     CONV_X3_PIPE,   // conv_x3_pipe.hip   conv_x3_pipe_kernel<4, 1, bn, apair>
     CONV_X3_RUN3,   // conv_x3_pipe.hip   conv_x3_run3_kernel<bn, apair>
     CONV_GLDS,      // conv_igemm_glds.hip conv_igemm_glds_kernel<T, bn, waves_m, waves_n, bkb, stages, gather, x3, apair>
     CONV_IGEMM,     // conv_igemm.hip     conv_igemm_kernel<T, 128, bn, waves_m, waves_n, gather>
 };
+
+// Fewest allocated rows at which a 16- / 32-channel 3x3x3 rulebook conv takes the weight-resident kernel (conv_choose.cpp).
+constexpr int kSpL2MinRows = 16384;
 
 // What conv2d_run knows about a layer beside its validated ConvArgs.
 struct ConvFacts {

@@ -468,6 +468,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[T
 // included; never another kernel.  a.weight is the operand the family reads (pre-split weights for bf16x3, the (hi, lo) pairs for h2).
 int launch_conv_h2(const ConvChoice& c, ConvArgs& a, hipStream_t st);                      // conv_h2.hip
 int launch_conv_small(ConvArgs& a, int dtype, hipStream_t st);                             // conv_small.hip
+int launch_sp_conv_l2(const ConvChoice& c, ConvArgs& a, hipStream_t st);                   // sp_conv_l2.hip
 int launch_sp_conv_runs(const ConvChoice& c, ConvArgs& a, hipStream_t st);                 // sp_conv_runs.hip
 int launch_conv_x3_pipe(const ConvChoice& c, ConvArgs& a, hipStream_t st);                 // conv_x3_pipe.hip
 int launch_conv_glds(const ConvChoice& c, ConvArgs& a, int dtype, hipStream_t st);         // conv_igemm_glds.hip

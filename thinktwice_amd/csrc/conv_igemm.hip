@@ -423,6 +423,10 @@ extern "C" int tt_conv2d_fwd(const tt_conv_desc* d, void* stream) {
             what = "tt_conv2d_fwd(small)";
             r = launch_conv_small(a, d->dtype, st);
             break;
+        case CONV_SP_RUNS_L2:
+            what = "tt_conv2d_fwd(sp l2)";
+            r = launch_sp_conv_l2(c, a, st);
+            break;
         case CONV_SP_RUNS:
             what = "tt_conv2d_fwd(glds x3)";
             r = launch_sp_conv_runs(c, a, st);
