@@ -60,7 +60,7 @@ extern "C" int tt_deform_im2col3x3(const void* x, const float* offsets, void* co
                                    int off_cstride, int pad, int dtype, void* stream) {
     TT_REQUIRE(x && offsets && cols, "tt_deform_im2col3x3: null");
     const int vec = dtype == TT_F32 ? 4 : 8;
-    TT_REQUIRE(C % vec == 0 && off_cstride >= 18, "tt_deform_im2col3x3: bad C/off_cstride");
+    TT_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % vec == 0 && off_cstride >= 18, "tt_deform_im2col3x3: bad N/H/W/C/off_cstride");
     const long long total = (long long)N * H * W * 9 * (C / vec);
     long long blocks = (total + 255) / 256;
     if (blocks > 256LL * 32) blocks = 256LL * 32;

@@ -511,7 +511,7 @@ extern "C" int tt_bilinear_up2_pair(const float* in, float* out, int N, int H, i
 
 extern "C" int tt_spatial_pool(const void* in, float* out, int N, int HW, int C, int cstride, int coff, int mode,
                                int dtype, void* stream) {
-    TT_REQUIRE(in && out && N > 0 && HW > 0, "tt_spatial_pool: bad args");
+    TT_REQUIRE(in && out && N > 0 && HW > 0 && C > 0 && coff >= 0 && cstride >= coff + C, "tt_spatial_pool: bad args");
     TT_DISPATCH(dtype, hipLaunchKernelGGL(spatial_pool_kernel<T>, dim3((C + 63) / 64, N), dim3(256), 0,
                                           (hipStream_t)stream, (const T*)in, out, HW, C, cstride, coff, mode));
     return check_launch("tt_spatial_pool");
