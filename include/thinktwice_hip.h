@@ -216,6 +216,21 @@ int tt_conv2d_splitk_slices(const tt_conv_desc* d);
  * the error text, that the launch of `d` would return before launching. */
 int tt_conv2d_plan(const tt_conv_desc* d, char* label, int label_bytes);
 
+/* Two 1 x 1 convolutions with folded BN over the R rows of a row matrix in ONE launch (seg_res_to_image_feature.0 / .3,
+ * backbones/lss.py:409-416, over the full-resolution segmentation map):
+ *   y = act1(scale1 * (W1 . x) + shift1)   K1 -> 64        z = act2(scale2 * (W2 . y) + shift2)   64 -> N2
+ * The 64-wide intermediate never reaches global memory.  The result is bit for bit that of the two tt_conv2d_fwd launches
+ * (stage 1: weight = w1, no weight_x3; stage 2: weight = w2, weight_x3 = w2_x3) over the same R rows: each stage runs the
+ * arithmetic the convolution dispatch picks for it at this row count (exact f32 up to 65,535 rows, bf16x3 on stage 2 beyond).
+ * x: f32 rows of x_stride floats, the first K1 read (K1 = 16, or 12: columns 12-15 are then zeros, as tt_conv2d_fwd pads its K);
+ * w1 f32 [64][K1]; w2 f32 [N2][64] and w2_x3 the same in pair format (tt_conv_desc.weight_x3); N2 = 8, 16 or 32; scale / shift
+ * f32 per output channel, nullable; act1 / act2 TT_ACT_NONE or TT_ACT_RELU; out f32 rows of out_stride floats, written at
+ * channel offset out_coff.  Strides and offsets are multiples of 4 and every pointer is 16-byte aligned; anything else returns
+ * an error before the launch. */
+int tt_seg_feedback_chain(const float* x, long long R, int x_stride, int K1, const float* w1, const float* scale1,
+                          const float* shift1, int act1, const float* w2, const void* w2_x3, int N2, const float* scale2,
+                          const float* shift2, int act2, float* out, int out_stride, int out_coff, void* stream);
+
 /* ------------------------------------------------------------------------
  * A chain of nn.Linear layers over R rows in ONE launch (the decoder's row-batched MLPs:
  * thinktwice_decoder.py:26-260 query_linear / ffn / output_proj / mlp / traj_offset_module / ctrl_offset_module /

@@ -524,8 +524,13 @@ class LSS:
             depth, merge_in = self._depth_net(src, mlp_in, T)
             # keep FPN maps of the key sweep before the UNet overwrites nothing of them (offset slices)
             seg = self._seg_net(bufs)
-            f = seg
-            for i, cv in enumerate(self.seg2feat[:-1]):
+            f, first = seg, 0
+            if (ops.SEG_CHAIN and autodiff.TAPE is None and not layers.BN_TRAIN and self.dtype == torch.float32
+                    and self.seg2feat[1].w_x3 is not None):
+                # inference in the bf16x3 modes: the two full-resolution 1 x 1 layers (n_class -> 64 -> 16) as one launch, the
+                # 64-channel map between them (1.6 GB at B = 8) stays on chip; same bits as the two launches
+                f, first = ops.seg_feedback_chain(seg, self.seg2feat[0], self.seg2feat[1]), 2
+            for i, cv in enumerate(self.seg2feat[first:-1], first):
                 f = cv(f, stop_grad=(i == 0))          # lss.py:589: the seg logits enter this branch detached
             self.seg2feat[-1](f, out=merge_in, out_coff=256)
             ctx = self.merge(merge_in, out_dtype=torch.float32)

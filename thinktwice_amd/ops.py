@@ -353,6 +353,41 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
     return out
 
 
+SEG_CHAIN = os.environ.get("TT_SEG_CHAIN", "1") != "0"     # A/B knob and test hook: 0 = the two feedback convs stay two launches
+
+
+def seg_feedback_chain(x, cv1, cv2, out=None, out_coff=0):
+    """Two 1 x 1 `layers.Conv` (folded BN, none / ReLU) over the pixels of x [N, H, W, Cs] in one launch (tt_seg_feedback_chain):
+    cv1 Cs -> 64 on its plain f32 weights, cv2 64 -> 8 / 16 / 32 with its pair-format weights riding along.  Bit-equal to
+    cv2(cv1(x)); the 64-channel map between them is never written.  Inference only (nothing is taped)."""
+    require_cuda(x, cv1.w, cv2.w)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+    assert cv2.w_x3 is not None and cv1.w.dtype == torch.float32 and cv2.w.dtype == torch.float32
+    N, H, W, Cs = x.shape
+    n1, kh1, kw1, k1 = cv1.w.shape
+    n2, kh2, kw2, k2 = cv2.w.shape
+    assert (kh1, kw1, kh2, kw2) == (1, 1, 1, 1) and k1 == Cs and k2 == n1 == 64, (cv1.w.shape, cv2.w.shape, Cs)
+    assert (cv1.stride, cv1.pad, cv2.stride, cv2.pad) == (1, 0, 1, 0) and not cv1.ps2 and not cv2.ps2
+    if out is None:
+        out = torch.empty(N, H, W, n2, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() // out.shape[-1] == N * H * W
+    R = N * H * W
+    if CONV_PROFILE is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(lib().tt_seg_feedback_chain(ptr(x), R, Cs, k1, ptr(cv1.w), ptr(cv1.scale), ptr(cv1.shift), cv1.act, ptr(cv2.w),
+                                      ptr(cv2.w_x3), n2, ptr(cv2.scale), ptr(cv2.shift), cv2.act, ptr(out), out.shape[-1],
+                                      out_coff, cur_stream(x.device)), "tt_seg_feedback_chain")
+    if CONV_PROFILE is not None:
+        e1.record()
+        CONV_PROFILE.append((2.0 * R * (k1 * n1 + k2 * n2), e0, e1, f"M={R} N={n1}->{n2} K={k1} chain k1x1s1"))
+        if CONV_KERNELS is not None:
+            CONV_KERNELS.append("seg_chain_kernel")
+        if CONV_BYTES is not None:
+            CONV_BYTES.append(R * (Cs + n2) * 4 + (cv1.w.numel() + cv2.w.numel()) * 4)
+    return out
+
+
 # ----------------------------------------------------------------------------- glue kernels
 def _st(t):
     return cur_stream(t.device)
