@@ -203,6 +203,13 @@ typedef struct tt_conv_desc {
     /* 1: res1 is an f32 tensor although the operands are 16-bit (dtype TT_F16 / TT_BF16): the f32 sum chains of the mixed mode's
      * PAFPN beside its half conv inputs.  Vector epilogue only. */
     int res1_f32;
+    /* 1 (bf16x3 layers: dtype TT_F32, weight_x3 given): `in` is the low-resolution f32 map [N][H/2][W/2][Cin] and the layer reads it
+     * THROUGH nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True): H, W (both even) describe the upsampled, logical input,
+     * which never exists in memory.  The result is bit for bit that of tt_bilinear_up2_pair followed by the same layer with in_pair.
+     * Contract: 3 x 3, stride 1, pad 1, dil 1 (OH = H, OW = W), Cin % 32 == 0, Cout == 64, N*OH*OW > 4096, a contiguous source
+     * (in_cstride = Cin, in_coff = 0, in_nstride 0 or (H/2)*(W/2)*Cin), the vector epilogue; no residual, per-image shift, out2,
+     * split-K workspace or in_pair (out_pair is fine).  Anything else is refused with an error, never run on another kernel. */
+    int in_up2;
 } tt_conv_desc;
 
 int tt_conv2d_fwd(const tt_conv_desc* d, void* stream);

@@ -200,6 +200,29 @@ bool choose_x3(const ConvArgs& a, ConvChoice* c) {
     return true;
 }
 
+// ---- bf16x3 3 x 3 convolution that reads its input through the bilinear x2 upsampling (conv_x3_up2.hip, tt_conv_desc.in_up2): the
+// kernel's whole contract.  a.H / a.W are the upsampled size.  More than 4096 rows, as for in_pair: up to there a layer runs the
+// latency kernel.  Measured against the two launches it replaces in profiles/seg_up2_fusion.txt.
+int choose_up2(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
+    TT_REQUIRE(f.dtype == TT_F32 && a.out_dtype == TT_F32 && f.weight_x3 && aligned16(f.weight_x3) && !f.weight_h2,
+               "tt_conv2d_fwd: in_up2 goes with a bf16x3 layer (f32 storage, a 16-byte aligned weight_x3)");
+    TT_REQUIRE(!a.gather && !a.m_dev && !a.ws && !a.pixel_shuffle2 && !(a.flags & 32) && !a.res1 && !a.res2 && !a.shift_n && !f.out2,
+               "tt_conv2d_fwd: in_up2 takes no in_pair, residual, per-image shift, out2, split-K workspace, gather or pixel shuffle");
+    TT_REQUIRE(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.H % 2 == 0 && a.W % 2 == 0 && a.OH == a.H &&
+                   a.OW == a.W,
+               "tt_conv2d_fwd: in_up2 is a 3 x 3 / stride 1 / pad 1 layer over an even H x W (got %d x %d, k %d x %d s %d p %d d %d)", a.H,
+               a.W, a.KH, a.KW, a.stride, a.pad, a.dil);
+    TT_REQUIRE(a.Cin % 32 == 0 && a.Cout == 64 && a.M > 4096 && a.vec_epi,
+               "tt_conv2d_fwd: in_up2 layer outside the kernel's contract (Cin %% 32 == 0, Cout == 64, more than 4096 rows, aligned "
+               "output: M=%d Cin=%d Cout=%d)", a.M, a.Cin, a.Cout);
+    const long long img = (long long)(a.H / 2) * (a.W / 2) * a.Cin;
+    TT_REQUIRE(a.in_cstride == a.Cin && a.in_coff == 0 && a.in_nstride == img && img < (1ll << 30),
+               "tt_conv2d_fwd: in_up2 reads a contiguous [N][H/2][W/2][Cin] source of less than 2^30 elements per image");
+    set_tile(c, CONV_X3_UP2, 64, 8, 1, 128, 3);
+    c->x3 = true;
+    return 0;
+}
+
 // ---- the LDS-DMA kernel on exact-f32 and 16-bit operands (conv_igemm_glds.hip)
 bool choose_glds(const ConvArgs& a, int dtype, ConvChoice* c) {
     constexpr int min_tiles = 2;      // K = 64 1x1 layers: 0.43 -> 0.27 ms against the register-staged kernel
@@ -289,6 +312,7 @@ int conv_choose(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
     *c = ConvChoice{};
     c->splits = 1;
     const bool ws = a.ws || f.assume_ws;
+    if (a.flags & 256) return choose_up2(a, f, c);      // in_up2: its own kernel or an error
     if (f.weight_h2) {
         // half storage x (hi, lo) weights: the only kernel with this arithmetic -- a shape outside its contract is an error, not a
         // silent change of precision
@@ -345,6 +369,7 @@ void conv_label(const ConvChoice& c, int dtype, char* out, size_t bytes) {
         case CONV_SP_RUNS: snprintf(out, bytes, "sp_conv_runs_kernel<%d, %d, %d>", c.bn / (32 * c.waves_n), c.waves_m, c.waves_n); break;
         case CONV_X3_PIPE: snprintf(out, bytes, "conv_x3_pipe_kernel<%s>%s%s", c.bn == 128 ? "4, 1, 128" : "4, 1", pre, tail); break;
         case CONV_X3_RUN3: snprintf(out, bytes, "conv_x3_run3_kernel<%d>%s%s", c.bn, pre, tail); break;
+        case CONV_X3_UP2: snprintf(out, bytes, "conv_x3_run3_kernel<%d, up2>", c.bn); break;     // (run-staged family: one patch, nine taps)
         case CONV_GLDS:
             snprintf(out, bytes, "conv_igemm_glds_kernel<%s, %d, %d, %d, %d, %d, %s, %s>%s%s", tn, c.bn, c.waves_m, c.waves_n, c.bkb,
                      c.stages, c.gather ? "true" : "false", c.x3 ? "true" : "false", pre, c.splits > 1 ? " split-K" : tail);

@@ -39,7 +39,8 @@ struct ConvArgs {
     int m_begin;         // first output row of this launch (tail-split launches of the LDS-DMA kernel), else 0
     int ws_slices;       // split-K: > 0 = every split stores into its own [M][Cout] slice of ws (ordered finalize)
     int flags;           // bit 4: non-temporal f32 output stores (every launch of the product); bit 5: the activations are pre-split bf16 (hi, lo) pairs (tt_conv_desc.in_pair);
-                         // bit 6: write the output in that pair format (tt_conv_desc.out_pair); bit 7: res1 is f32 beside 16-bit operands (tt_conv_desc.res1_f32)
+                         // bit 6: write the output in that pair format (tt_conv_desc.out_pair); bit 7: res1 is f32 beside 16-bit operands (tt_conv_desc.res1_f32);
+                         // bit 8: `in` is the [N][H/2][W/2][Cin] f32 map read through the bilinear x2 upsampling (tt_conv_desc.in_up2)
     int res1_up_h, res1_up_w;   // > 0: res1 is a [N][res1_up_h][res1_up_w][..] map read through nearest upsampling (tt_conv_desc)
     float* out2;         // optional second, f32, row-linear copy of the output (tt_conv_desc.out2): [M][out2_cstride] at out2_coff
     int out2_cstride, out2_coff;
@@ -56,6 +57,7 @@ enum ConvFamily {
     CONV_SP_RUNS,   // sp_conv_runs.hip   sp_conv_runs_kernel<bn / (32 waves_n), waves_m, waves_n>
     CONV_X3_PIPE,   // conv_x3_pipe.hip   conv_x3_pipe_kernel<4, 1, bn, apair>
     CONV_X3_RUN3,   // conv_x3_pipe.hip   conv_x3_run3_kernel<bn, apair>
+    CONV_X3_UP2,    // conv_x3_up2.hip    conv_x3_up2_kernel (input read through the bilinear x2 upsampling, tt_conv_desc.in_up2)
     CONV_GLDS,      // conv_igemm_glds.hip conv_igemm_glds_kernel<T, bn, waves_m, waves_n, bkb, stages, gather, x3, apair>
     CONV_IGEMM,     // conv_igemm.hip     conv_igemm_kernel<T, 128, bn, waves_m, waves_n, gather>
 };

@@ -377,6 +377,12 @@ static int conv2d_prepare(const tt_conv_desc* d, ConvArgs& a, ConvFacts& f) {
         if (d->out_pair) a.flags |= 64;
     }
     if (d->res1_f32) a.flags |= 128;
+    if (d->in_up2) {
+        // `in` holds [N][H/2][W/2][Cin]: the image stride is the SOURCE's (the shape contract: conv_choose.cpp, choose_up2)
+        TT_REQUIRE(!d->in_pair, "tt_conv2d_fwd: in_up2 reads an f32 source: it does not go with in_pair");
+        a.in_nstride = d->in_nstride ? d->in_nstride : (long long)(d->H / 2) * (d->W / 2) * d->in_cstride;
+        a.flags |= 256;
+    }
     {
         const int co_vec = (d->out_dtype == TT_F32 && !d->out_pair) ? 4 : 8;
         const int osz = d->out_dtype == TT_F32 ? 4 : 2;
@@ -436,6 +442,10 @@ extern "C" int tt_conv2d_fwd(const tt_conv_desc* d, void* stream) {
             what = pair ? "tt_conv2d_fwd(glds x3, pair)" : "tt_conv2d_fwd(glds x3)";
             r = launch_conv_x3_pipe(c, a, st);
             break;
+        case CONV_X3_UP2:
+            what = "tt_conv2d_fwd(x3 up2)";
+            r = launch_conv_x3_up2(c, a, st);
+            break;
         case CONV_GLDS:
             what = !c.x3 ? "tt_conv2d_fwd(glds)" : c.splits > 1 ? "tt_conv2d_fwd(glds x3 split-K)" : pair ? "tt_conv2d_fwd(glds x3, pair)" : "tt_conv2d_fwd(glds x3)";
             if (c.splits > 1) a.ws_slices = c.slices;
@@ -463,7 +473,7 @@ extern "C" int tt_conv2d_splitk_slices(const tt_conv_desc* d) {
     ConvFacts f;
     ConvChoice c;
     if (conv2d_prepare(d, a, f)) return 0;
-    if (d->in_pair || d->out_pair || d->weight_h2 || d->res1_up_w > 0) return 0;       // layers that never take a workspace
+    if (d->in_pair || d->out_pair || d->in_up2 || d->weight_h2 || d->res1_up_w > 0) return 0;       // layers that never take a workspace
     f.assume_ws = true;
     if (conv_choose(a, f, &c)) return 0;
     return c.splits > 1 ? c.slices : 0;

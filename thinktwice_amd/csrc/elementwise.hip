@@ -2,6 +2,7 @@
 // Each replaces a torch elementwise / pooling / resize call of the reference forward; the
 // citing comment names the call site.  T = float or uint16_t (bf16 storage); math in f32.
 #include "tt_common.h"
+#include "bilinear_up2.h"
 
 namespace tt {
 
@@ -184,8 +185,6 @@ __global__ void bilinear_up2_ac_kernel(const T* __restrict__ in, T* __restrict__
 // lo = rne(v - hi): the split the consuming convolution would otherwise redo for every tap and column tile
 __global__ void bilinear_up2_ac_pair_kernel(const float* __restrict__ in, float* __restrict__ out, int N, int H, int W, int C) {
     const int cv = C / 8, OH = 2 * H, OW = 2 * W;
-    const float sh = (OH > 1) ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-    const float sw = (OW > 1) ? (float)(W - 1) / (float)(OW - 1) : 0.f;
     const long long total = (long long)N * OH * OW * cv;
     TT_GRID_STRIDE(i, total) {
         const int c = (int)(i % cv);
@@ -193,35 +192,14 @@ __global__ void bilinear_up2_ac_pair_kernel(const float* __restrict__ in, float*
         const int ox = (int)(r % OW); r /= OW;
         const int oy = (int)(r % OH);
         const long long n = r / OH;
-        const float fy = sh * oy, fx = sw * ox;
-        const int y0 = (int)fy, x0 = (int)fx;
-        const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
-        const float ly = fy - y0, lx = fx - x0;
+        const Up2Tap t = up2_tap(H, W, oy, ox);                              // the arithmetic: bilinear_up2.h
         const float* base = in + n * H * W * C + c * 8;
-        float v[8];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            Vec<float> a, b, cc, d;
-            a.load(base + ((long long)y0 * W + x0) * C + 4 * h);
-            b.load(base + ((long long)y0 * W + x1) * C + 4 * h);
-            cc.load(base + ((long long)y1 * W + x0) * C + 4 * h);
-            d.load(base + ((long long)y1 * W + x1) * C + 4 * h);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float top = (1.f - lx) * a.v[k] + lx * b.v[k];
-                const float bot = (1.f - lx) * cc.v[k] + lx * d.v[k];
-                v[4 * h + k] = (1.f - ly) * top + ly * bot;
-            }
-        }
-        uint32_t hi[4], lo[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            hi[e] = pack_bf16x2(v[2 * e], v[2 * e + 1]);
-            lo[e] = pack_bf16x2(v[2 * e] - __uint_as_float(hi[e] << 16), v[2 * e + 1] - __uint_as_float(hi[e] & 0xffff0000u));
-        }
+        uint4 hi, lo;
+        up2_pair8(base + ((long long)t.y0 * W + t.x0) * C, base + ((long long)t.y0 * W + t.x1) * C,
+                  base + ((long long)t.y1 * W + t.x0) * C, base + ((long long)t.y1 * W + t.x1) * C, t.ly, t.lx, hi, lo);
         float* g = out + (i / cv) * C + (c >> 1) * 16 + (c & 1) * 4;        // pixel row, 16-channel group, 8-channel half
-        *reinterpret_cast<uint4*>(g) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-        *reinterpret_cast<uint4*>(g + 8) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+        *reinterpret_cast<uint4*>(g) = hi;
+        *reinterpret_cast<uint4*>(g + 8) = lo;
     }
 }
 

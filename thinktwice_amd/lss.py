@@ -443,7 +443,12 @@ class LSS:
         x3 = self.u0a.w_x3 is not None
         p_up = x3 and ops.pair_ok(NI * H * W, 128, 64)
         p_mid = fused and x3 and self.seg_fused.w_x3 is not None and ops.pair_ok(NI * H * W, 64, self.seg_fused.w.shape[0])
-        d1 = self.u0a(ops.bilinear_up2(d2, out_pair=p_up), in_pair=p_up, out_pair=p_mid)
+        # ... and where the layer takes it, the upsampled map is not produced at all: unet_layer0.1 interpolates it into its operand
+        # patch (tt_conv_desc.in_up2: the same bits; TT_SEG_UP2=0 keeps the two launches)
+        if (ops.SEG_UP2 and x3 and fused and d2.is_contiguous() and ops.up2_ok(NI * H * W, d2.shape[-1], self.u0a.w.shape[0])):
+            d1 = self.u0a(d2, in_up2=True, out_pair=p_mid)
+        else:
+            d1 = self.u0a(ops.bilinear_up2(d2, out_pair=p_up), in_pair=p_up, out_pair=p_mid)
         seg = torch.zeros(NI, H, W, self.seg_cp, dtype=self.dtype, device=d1.device)
         if fused:
             self.seg_fused(d1, out=seg, in_pair=p_mid)   # conv_last o unet_layer0.3 as one convolution (load_state_dict)

@@ -110,7 +110,7 @@ class _ConvDesc(ctypes.Structure):
         ("weight_x3", ctypes.c_void_p), ("row_perm", ctypes.c_void_p), ("row_mask", ctypes.c_void_p),
         ("splitk_slices", ctypes.c_int), ("in_pair", ctypes.c_int), ("out_pair", ctypes.c_int),
         ("weight_h2", ctypes.c_void_p), ("out2", ctypes.c_void_p), ("out2_cstride", ctypes.c_int), ("out2_coff", ctypes.c_int),
-        ("res1_up_h", ctypes.c_int), ("res1_up_w", ctypes.c_int), ("res1_f32", ctypes.c_int),
+        ("res1_up_h", ctypes.c_int), ("res1_up_w", ctypes.c_int), ("res1_f32", ctypes.c_int), ("in_up2", ctypes.c_int),
     ]
 
 
@@ -233,7 +233,7 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
            res2=None, res2_coff=0, out=None, out_coff=0, in_coff=0, cin=None, pixel_shuffle2=False,
            shift_n=None, shift_n_mod=1, out_dtype=None, out_nstride=0, out_hw=None, splitk_ws=None,
            in_cstride=None, w_x3=None, _no_tape=False, stop_grad=False, bn_raw=False, in_pair=False, out_pair=False,
-           w_h2=None, out2=None, out2_coff=0, res1_up=False):
+           w_h2=None, out2=None, out2_coff=0, res1_up=False, in_up2=False):
     """Channel-last implicit-GEMM convolution on MFMA (tt_conv2d_fwd).
 
     x   [N,H,W,Cs]  (f32 or bf16); channels [in_coff, in_coff+cin) are convolved
@@ -245,6 +245,9 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
     in_pair / out_pair (bf16x3 layers only): x is / out becomes a PAIR-format tensor (an f32-typed container holding, per 16
     channels, the bf16 hi and lo halves the kernel's operand split would produce: tt_conv_desc.in_pair).  Only for tensors whose
     every reader is a bf16x3 convolution (`pair_ok(rows)` says whether a layer of that many output rows takes one).
+    in_up2 (bf16x3 3 x 3 / stride 1 / pad 1 layers with 64 output channels; `up2_ok` says which): x is the low-resolution f32 map
+    [N, h, w, C] and the layer convolves bilinear_up2(x) -- nn.Upsample(scale_factor=2, bilinear, align_corners=True) -- without that
+    tensor ever existing (tt_conv_desc.in_up2); bit for bit conv2d(bilinear_up2(x, out_pair=True), ..., in_pair=True).
     in_cstride / out_hw: "row-run" form -- the kernel reads `cin` CONTIGUOUS elements starting at pixel (ih, iw) of a
     tensor whose pixels are only Cs < cin elements apart (a run of cin/Cs pixels along W), with the output size given
     explicitly; used for the 7x7/2 stem (lss.py).
@@ -254,6 +257,10 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
     N, H, W, Cs = x.shape
     # inner (H, W, C) block must be dense; the image (batch) stride may be anything
     assert x.stride(3) == 1 and (W == 1 or x.stride(2) == Cs) and (H == 1 or x.stride(1) == W * Cs), x.stride()
+    src_px = N * H * W
+    if in_up2:          # the geometry below is that of the upsampled, logical input
+        assert x.dtype == torch.float32 and x.is_contiguous() and w_x3 is not None and not in_pair and splitk_ws is None
+        H, W = 2 * H, 2 * W
     Cout, KH, KW, Cin = w.shape
     if cin is None:
         cin = Cin
@@ -299,6 +306,10 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
         if autodiff.TAPE is not None:
             raise _lib.TTError("conv2d: pair-format activations are an inference-path layout (the tape reads f32 tensors)")
         d.in_pair, d.out_pair = int(bool(in_pair)), int(bool(out_pair))
+    if in_up2:
+        if autodiff.TAPE is not None:
+            raise _lib.TTError("conv2d: in_up2 is an inference-path fusion (the tape records bilinear_up2 and the convolution apart)")
+        d.in_up2 = 1
     if w_x3 is not None and Cout < 64 and (autodiff.TAPE is not None or _no_tape):
         # training step (taped forward, recomputations, input-gradient convolutions): the layers with fewer than 64 output channels
         # keep the exact-f32 kernels the gradient goldens were taken with (inference runs them on the 256 x 32 bf16x3 tile)
@@ -311,7 +322,7 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
         x3_splitk = autodiff.TAPE is None and not _no_tape
         if x3_splitk:
             d.weight_x3 = w_x3.data_ptr()
-    if _AUTO_SPLITK and splitk_ws is None and not (in_pair or out_pair) and w_h2 is None and not res1_up and N * OH * OW <= 4096 and KH * KW * Cin >= 2048:
+    if _AUTO_SPLITK and splitk_ws is None and not (in_pair or out_pair or in_up2) and w_h2 is None and not res1_up and N * OH * OW <= 4096 and KH * KW * Cin >= 2048:
         # few rows, very long K (BEV-update conv K=18720, flatten MLPs): cross-workgroup split-K with an f32 workspace
         # beats conv_small.hip's in-workgroup split there (277 vs 416 us on the BEV-update conv: the direct 32 B/row
         # operand loads of the small kernel waste L2 sectors on a 10 MB weight matrix).  TT_CONV_AUTO_SPLITK=0 disables.
@@ -340,7 +351,7 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
         if CONV_BYTES is not None:
             esz, osz = x.element_size(), out.element_size()
             m_out = N * OH * OW
-            in_px = min(N * H * W, m_out * KH * KW)           # a strided 1x1 layer only touches the pixels it samples
+            in_px = min(src_px, m_out * KH * KW)              # a strided 1x1 layer only touches the pixels it samples
             wsz = w.numel() * w.element_size() * (2 if w_h2 is not None else 1)
             CONV_BYTES.append(in_px * (in_cstride or Cin) * esz + m_out * Cout * osz + wsz +
                               m_out * Cout * esz * ((res1 is not None) + (res2 is not None)) +
@@ -578,6 +589,16 @@ def pair_ok(rows, cin=32, cout=64, taps=9):
     from . import autodiff
     return (PAIR and autodiff.TAPE is None and rows > 4096 and cin % 32 == 0 and taps * cin >= 64 and
             (8 <= cout <= 32 or cout >= 64))
+
+
+SEG_UP2 = os.environ.get("TT_SEG_UP2", "1") != "0"      # A/B knob and test hook: 0 = unet_layer0's upsample and its 3 x 3 conv stay two launches
+
+
+def up2_ok(rows, cin, cout):
+    """Whether a bf16x3 3 x 3 / stride 1 / pad 1 convolution with this many OUTPUT rows reads its input through the bilinear x2
+    upsampling in the kernel (conv2d(in_up2=True), tt_conv_desc.in_up2).  tests/test_conv_up2_choice.py pins this to the library's rule."""
+    from . import autodiff
+    return autodiff.TAPE is None and rows > 4096 and cin % 32 == 0 and cout == 64
 
 
 def bilinear_up2(x, out_pair=False):
