@@ -608,6 +608,68 @@ int tt_preprocess_images_ida_aug(const uint8_t* raw_hwc, int B, int T, int N, in
                                  const tt_aug_program* programs_dev, void* scratch, long long scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The two label inputs of the training image pipeline from the dataset's raw bytes: LoadDepth.__call__ and LoadSeg.__call__
+ * with red_green_yellow (open_loop_training/code/datasets/pipelines/loading.py:84-93, :96-113, :132-162).  PNG file decoding
+ * and union2one's meta merge stay on the host.  Everything but the depth quotient is integer arithmetic: the outputs are
+ * bit-identical from run to run.
+ * ---------------------------------------------------------------------- */
+/* loading.py:88-90.  CARLA depth PNG pixels uint8 [n_pixels, 3] (R, G, B) -> metres f32 [n_pixels]:
+ * f32(f32(code / 16777215.0f) * 1000.0f), code = R + 256 G + 65536 B (exact in f32), the division IEEE-rounded, nothing
+ * contracted: the bits of the numpy float32 expression for every code. */
+int tt_decode_depth_u8(const uint8_t* rgb_u8, long long n_pixels, float* out_f32, void* stream);
+
+/* loading.py:97, cv2.cvtColor(..., COLOR_RGB2HSV) on uint8 (H in 0..179).  The device executes two division tables:
+ *   v = max(R, G, B), diff = v - min(R, G, B), s = (diff * sdiv[v] + 2048) >> 12,
+ *   h0 = G - B where v == R, else B - R + 2 diff where v == G, else R - G + 4 diff,
+ *   h = (h0 * hdiv[diff] + 2048) >> 12 (arithmetic shift), plus 180 where negative.
+ * The tables are the convention of OpenCV 4.x's integer path (RGB2HSV_b) and UNPINNED (cv2 is not installed where this was
+ * written): thinktwice_amd/labels.py::hsv_tables is their one owner.  `tables` is a HOST pointer; the entry copies it into
+ * the kernel's arguments (no device buffer, the caller may reuse the memory on return).  rgb_u8 / hsv_u8 uint8 [n_pixels, 3]. */
+typedef struct tt_hsv_tables {
+    int sdiv[256];                       /* rint(255 * 4096 / i), entry 0 is 0 */
+    int hdiv[256];                       /* rint(180 * 4096 / (6 i)), entry 0 is 0 */
+} tt_hsv_tables;                         /* 2048 bytes */
+int tt_rgb2hsv_u8(const uint8_t* rgb_u8, long long n_pixels, const tt_hsv_tables* tables, uint8_t* hsv_u8, void* stream);
+
+/* loading.py:132-162 with :96-113.  tags uint8 [num_samples, cams, H, W] (CARLA semantic tags) -> class ids f32 of that shape:
+ *   - out = class_of_tag[tag] for every pixel whose tag is not light_tag (:159; a tag outside seg_label_idxs maps to 0);
+ *   - the light_tag mask of every image is split into 8-connected components (:144).  A component of fewer than min_pixels
+ *     pixels stays 0 (:153); every other one gets light_base + light_type (:157), light_type from the HSV values of its
+ *     pixels in the image's RGB frame: sat_low = sat_low_of_avg[sum S / count] (integer division, :98-99), green = #{H in
+ *     green_lo..green_hi, S >= sat_low, V >= val_low}, red likewise with red_lo..red_hi (:102-108); 0 where both < 3, 1 where
+ *     red >= green, else 2 (:109-113).
+ * rgb_u8: image (b, n) is the contiguous uint8 [H, W, 3] at rgb_u8 + b * rgb_sample_stride_bytes + n * H * W * 3, so the key
+ * sweep raw[:, -1] of a contiguous [B, T, N, H, W, 3] tensor is read in place.  `conf` is a HOST pointer, copied into the
+ * kernels' arguments.  `workspace`: tt_decode_seg_workspace_bytes(num_samples * cams, H, W) bytes, 8-byte aligned; the
+ * kernels initialise every word they read, its contents on entry never matter.
+ * Phases, one launch each, no workgroup ever waits for another: tile-local label equivalence in LDS (with the class map);
+ * unions across tile edges and corners; flattening to roots; count and sum of S per root; green / red counts per root; the
+ * write.  Labels are pixel indices within the image and only ever decrease.  Without a light tag only the first runs.
+ * Returns an error before any launch for a null pointer, a non-positive size, H * W beyond int32, a short or misaligned
+ * workspace, a light_tag outside -1..255 or a light class outside 0..253. */
+typedef struct tt_seg_decode_conf {
+    unsigned char class_of_tag[256];     /* position of the tag in seg_label_idxs, 0 for a tag that is not in it */
+    int light_tag;                       /* the traffic-light tag (18), -1 for none */
+    int light_base;                      /* its position in seg_label_idxs */
+    int min_pixels;                      /* 20 */
+    int val_low;                         /* 140 */
+    int green_lo, green_hi;              /* 70, 100 */
+    int red_lo, red_hi;                  /* 150, 180 */
+    int sat_low_of_avg[256];             /* int(avg * 1.1), filled on the host with the reference's own expression */
+    tt_hsv_tables hsv;
+} tt_seg_decode_conf;                    /* 3360 bytes */
+/* Host arithmetic only; 0 for a non-positive argument. */
+long long tt_decode_seg_workspace_bytes(long long num_images, int H, int W);
+int tt_decode_seg_u8(const uint8_t* tags_u8, int num_samples, int cams, int H, int W, const uint8_t* rgb_u8,
+                     long long rgb_sample_stride_bytes, const tt_seg_decode_conf* conf, void* workspace,
+                     long long workspace_bytes, float* out_f32, void* stream);
+/* Measurement only (thinktwice_amd/bench_labels.py times the phases by difference): the same call cut short after phase
+ * `last_phase`, 0 tile .. 5 write; only 5 leaves a complete output. */
+int tt_decode_seg_u8_phases(const uint8_t* tags_u8, int num_samples, int cams, int H, int W, const uint8_t* rgb_u8,
+                            long long rgb_sample_stride_bytes, const tt_seg_decode_conf* conf, void* workspace,
+                            long long workspace_bytes, float* out_f32, int last_phase, void* stream);
+
+/* ------------------------------------------------------------------------
  * SURVEY 8f-4 (training step), optimizer half: the reference's `optimizer_config = dict(grad_clip=dict(max_norm=100,
  * norm_type=2))` and `optimizer = dict(type='AdamW', lr=1e-4, weight_decay=1e-7)` (configs/thinktwice.py:282-287:
  * torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW through mmcv's OptimizerHook) over ONE flat f32 parameter /

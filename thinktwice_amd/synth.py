@@ -138,3 +138,49 @@ def raw_label_maps(seed=18, N=4, h=900, w=1600):
     blocks = rng.integers(0, 12, (N, -(-h // 25), -(-w // 25)))
     seg = np.repeat(np.repeat(blocks, 25, axis=1), 25, axis=2)[:, :h, :w].astype(np.float32)
     return depth, np.ascontiguousarray(seg)
+
+
+def raw_label_bytes(seed=19, N=4, h=900, w=1600):
+    """Seeded raw label BYTES of the key sweep, as the loader reads them from the dataset (loading.py:84-93, :132-162), and
+    the RGB frames of the same cameras: (depth_rgb uint8 [N, h, w, 3] -- the CARLA depth PNG's 24-bit code, every byte
+    random --, tags uint8 [N, h, w] -- CARLA semantic tags in 16 x 16 blocks, some of them absent from the config's
+    seg_label_idxs, with traffic-light (tag 18) blobs of mixed sizes and shapes on top --, rgb uint8 [N, h, w, 3] -- noise on
+    smooth structure, a random share of every blob's pixels painted red, green or yellow, the rest a dark casing).  Golden
+    F19 was produced from exactly these arrays."""
+    rng = np.random.default_rng(seed)
+    depth_rgb = rng.integers(0, 256, (N, h, w, 3), dtype=np.uint8)
+    palette = np.array([0, 1, 3, 4, 5, 6, 7, 8, 9, 10, 12, 22], dtype=np.uint8)
+    blocks = palette[rng.integers(0, len(palette), (N, -(-h // 16), -(-w // 16)))]
+    tags = np.ascontiguousarray(np.repeat(np.repeat(blocks, 16, axis=1), 16, axis=2)[:, :h, :w])
+    noise = rng.integers(0, 256, (N, h, w, 3), dtype=np.uint8).astype(np.float32)
+    yy = (np.arange(h, dtype=np.float32)[:, None, None] % 200) * 0.9
+    xx = (np.arange(w, dtype=np.float32)[None, :, None] % 320) * 0.35
+    rgb = np.clip(noise * 0.25 + yy + xx, 0, 255).astype(np.uint8)
+    colours = np.array([[225, 30, 45], [30, 220, 140], [230, 200, 40]], dtype=np.int64)      # red, green, yellow
+    for n in range(N):
+        for _ in range(max(8, h * w // 2500)):
+            cy, cx = int(rng.integers(0, h)), int(rng.integers(0, w))
+            shape = int(rng.integers(0, 5))
+            a, b = int(rng.integers(1, 9)), int(rng.integers(1, 6))
+            y0, y1, x0, x1 = max(cy - 16, 0), min(cy + 17, h), max(cx - 16, 0), min(cx + 17, w)     # every blob fits a 33 x 33 window
+            ys, xs = np.mgrid[y0:y1, x0:x1]
+            if shape == 0:                                  # box (from 3 x 3 to 17 x 11)
+                blob = (abs(ys - cy) <= a) & (abs(xs - cx) <= b)
+            elif shape == 1:                                # ellipse
+                blob = ((ys - cy) / (a + 0.5)) ** 2 + ((xs - cx) / (b + 0.5)) ** 2 <= 1
+            elif shape == 2:                                # one-pixel diagonal: connected through corners only
+                blob = (ys - cy == (xs - cx) * (1 if a & 1 else -1)) & (abs(xs - cx) <= 3 * b)
+            elif shape == 3:                                # ring
+                d2 = (ys - cy) ** 2 + (xs - cx) ** 2
+                blob = (d2 <= (a + 2) ** 2) & (d2 >= (a + 1) ** 2 - 1)
+            else:                                           # a few pixels: under the 20-pixel rule
+                blob = (abs(ys - cy) <= 1) & (abs(xs - cx) <= a % 3)
+            t, c = tags[n, y0:y1, x0:x1], rgb[n, y0:y1, x0:x1]
+            t[blob] = 18
+            lit = blob & (rng.random(blob.shape) < rng.uniform(0.0, 0.8))
+            c[blob] = np.clip(40 + rng.integers(-8, 9, (int(blob.sum()), 3)), 0, 255).astype(np.uint8)
+            k = int(lit.sum())
+            two = colours[rng.integers(0, 3, 2)]            # two colours per blob, so that red and green counts compete
+            pick = two[(rng.random(k) < 0.35).astype(np.int64)]
+            c[lit] = np.clip(pick + rng.integers(-12, 13, (k, 3)), 0, 255).astype(np.uint8)
+    return depth_rgb, tags, rgb
