@@ -122,6 +122,35 @@ bool x3_pipe_ok(const ConvArgs& a, int bn) {
     return !(a.gather || a.m_dev || (bn != 256 && bn != 128) || a.Cout % bn != 0 || a.Cin % 32 != 0 || a.KH * a.KW > 31 || a.K < 64);
 }
 
+// ---- pair-format 3 x 3 "same" convolution on halo patches (conv_x3_patch.hip): the kernel's whole contract.  Anything outside it
+// keeps its per-tap tile: a routing decision, not an error.  TT_X3_PATCH=0 (the A/B knob): the per-tap tiles everywhere.
+// Threshold kPatchMinRows = 16,384 rows, for both column-block forms.  Measured crossover (profiles/conv_patch.txt; us per launch,
+// serialised, minimum of 10, per-tap tile -> patch kernel), Cin = 64 over 128-pixel-wide images:
+//   rows       64 -> 64 (pair output)   64 -> 12        64 -> 32
+//   16,384     31.2 -> 22.9             22.5 -> 18.8    25.6 -> 17.2
+//   32,768     33.5 -> 22.1             28.7 -> 18.9    27.1 -> 18.3
+//   65,536     35.8 -> 27.5             27.5 -> 20.1    25.6 -> 20.8
+//   131,072    51.5 -> 39.4             39.8 -> 25.8    38.0 -> 25.4
+//   262,144    81.2 -> 64.0             64.9 -> 44.4    61.4 -> 42.0
+//   524,288    150.1 -> 113.5           111.2 -> 73.2   106.2 -> 73.3
+// The patch kernel already wins at the lowest size tried, so there is no crossover above the floor: the threshold sits at the
+// 16,384 rows it was first set to (it may not sit at or below 8,192: tests/conv_choice_cases.json records the per-tap tiles up to
+// there).  The model's shapes at B = 8 (ms): seg head 1.324 -> 0.883, layer1 conv2 0.457 -> 0.374 per call; at B = 1: 0.179 -> 0.117,
+// 0.081 -> 0.060.  Both forms win at the model's shapes and in the headline, so both are routed.
+bool choose_x3_patch(const ConvArgs& a, ConvChoice* c) {
+    static const bool on = env_flag("TT_X3_PATCH", true);
+    if (!on || !(a.flags & 32) || a.M < kPatchMinRows) return false;
+    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1 || a.OH != a.H || a.OW != a.W) return false;
+    if (a.Cin % 32 != 0 || !(a.Cout == 64 || (a.Cout >= 8 && a.Cout <= 32)) || !a.vec_epi || a.out_dtype != TT_F32) return false;
+    if (a.res1 || a.res2 || a.shift_n || a.out2 || a.ws || a.pixel_shuffle2 || a.gather || a.m_dev) return false;
+    if ((long long)a.H * a.W * a.in_cstride >= (1ll << 30)) return false;        // 32-bit byte offsets inside an image
+    // 64-wide with K >= 1152 (128+ input channels): the one such layer of the model is unet_layer0.1, which has its own patch kernel
+    // (in_up2); its two-launch form (TT_SEG_UP2=0) stays the per-tap tile it is compared against (tests/test_conv_up2_choice.py)
+    if (a.Cout == 64 && a.K >= 1152) return false;
+    set_tile(c, CONV_X3_PATCH, a.Cout == 64 ? 64 : 32, 8, 1, 128, 3);
+    return true;
+}
+
 // ---- bf16x3 arithmetic on f32 storage (conv_igemm_glds.hip's X3 tiles and the kernels derived from them).  false when the shape is
 // outside the LDS-DMA kernels' contract (the layer then runs the exact f32 path on the plain weights).
 bool choose_x3(const ConvArgs& a, ConvChoice* c) {
@@ -141,6 +170,7 @@ bool choose_x3(const ConvArgs& a, ConvChoice* c) {
     const bool apair = (a.flags & 32) != 0;
     if (apair && (a.in_coff % 16 != 0 || a.in_cstride % 16 != 0)) return false;
     c->apair = apair;
+    if (choose_x3_patch(a, c)) return true;
     // few output channels over many rows (the segmentation head: 3 x 3, 64 -> 12 at 224 x 448 per image; the deformable conv's
     // offset head: 3 x 3, 512 -> 18; seg_res_to_image_feature's 64 -> 16): a 256 x 32 tile, two workgroups per CU.  Below 2^16
     // rows the exact-f32 register-staged kernel keeps them
@@ -370,6 +400,7 @@ void conv_label(const ConvChoice& c, int dtype, char* out, size_t bytes) {
         case CONV_X3_PIPE: snprintf(out, bytes, "conv_x3_pipe_kernel<%s>%s%s", c.bn == 128 ? "4, 1, 128" : "4, 1", pre, tail); break;
         case CONV_X3_RUN3: snprintf(out, bytes, "conv_x3_run3_kernel<%d>%s%s", c.bn, pre, tail); break;
         case CONV_X3_UP2: snprintf(out, bytes, "conv_x3_run3_kernel<%d, up2>", c.bn); break;     // (run-staged family: one patch, nine taps)
+        case CONV_X3_PATCH: snprintf(out, bytes, "conv_x3_run3_kernel<%d, patch>%s", c.bn, pre); break;          // (the same family)
         case CONV_GLDS:
             snprintf(out, bytes, "conv_igemm_glds_kernel<%s, %d, %d, %d, %d, %d, %s, %s>%s%s", tn, c.bn, c.waves_m, c.waves_n, c.bkb,
                      c.stages, c.gather ? "true" : "false", c.x3 ? "true" : "false", pre, c.splits > 1 ? " split-K" : tail);

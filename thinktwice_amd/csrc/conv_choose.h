@@ -58,12 +58,16 @@ enum ConvFamily {
     CONV_X3_PIPE,   // conv_x3_pipe.hip   conv_x3_pipe_kernel<4, 1, bn, apair>
     CONV_X3_RUN3,   // conv_x3_pipe.hip   conv_x3_run3_kernel<bn, apair>
     CONV_X3_UP2,    // conv_x3_up2.hip    conv_x3_up2_kernel (input read through the bilinear x2 upsampling, tt_conv_desc.in_up2)
+    CONV_X3_PATCH,  // conv_x3_patch.hip  conv_x3_patch_kernel<bn / 32> (pair-format 3 x 3 input staged as halo patches by LDS-DMA)
     CONV_GLDS,      // conv_igemm_glds.hip conv_igemm_glds_kernel<T, bn, waves_m, waves_n, bkb, stages, gather, x3, apair>
     CONV_IGEMM,     // conv_igemm.hip     conv_igemm_kernel<T, 128, bn, waves_m, waves_n, gather>
 };
 
 // Fewest allocated rows at which a 16- / 32-channel 3x3x3 rulebook conv takes the weight-resident kernel (conv_choose.cpp).
 constexpr int kSpL2MinRows = 16384;
+
+// Fewest output rows at which a pair-format 3 x 3 layer takes the halo-patch kernel (conv_choose.cpp, choose_x3_patch).
+constexpr int kPatchMinRows = 16384;
 
 // What conv2d_run knows about a layer beside its validated ConvArgs.
 struct ConvFacts {

@@ -446,6 +446,10 @@ extern "C" int tt_conv2d_fwd(const tt_conv_desc* d, void* stream) {
             what = "tt_conv2d_fwd(x3 up2)";
             r = launch_conv_x3_up2(c, a, st);
             break;
+        case CONV_X3_PATCH:
+            what = "tt_conv2d_fwd(x3 patch, pair)";
+            r = launch_conv_x3_patch(c, a, st);
+            break;
         case CONV_GLDS:
             what = !c.x3 ? "tt_conv2d_fwd(glds)" : c.splits > 1 ? "tt_conv2d_fwd(glds x3 split-K)" : pair ? "tt_conv2d_fwd(glds x3, pair)" : "tt_conv2d_fwd(glds x3)";
             if (c.splits > 1) a.ws_slices = c.slices;
