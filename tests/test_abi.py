@@ -1,9 +1,13 @@
 """The C ABI is typed once, from the prototypes of include/thinktwice_hip.h (`_lib.prototypes`): `lib()` binds every entry's
 argument and result types, the plan recorder classifies an argument by its declared type, and every call site in the tree
-passes the declared number of arguments (CPU only: nothing here launches a kernel)."""
+passes the declared number of arguments.  Its structs and constants are generated from the same header (`_lib.structs`,
+`_lib.constants`) and checked against what a C compiler makes of it (CPU only: nothing here launches a kernel)."""
 import ast
 import ctypes
+import keyword
 import os
+import re
+import subprocess
 
 import pytest
 
@@ -68,4 +72,69 @@ def test_every_call_site_passes_the_declared_argument_count():
                 for t in node.targets:
                     if any(isinstance(a, ast.Attribute) and a.attr in ("restype", "argtypes") for a in ast.walk(t)):
                         bad.append(f"{rel}:{node.lineno}: restype / argtypes set outside the binding")
+            elif isinstance(node, ast.ClassDef) and rel != os.path.join("thinktwice_amd", "_lib.py"):
+                if any(ast.unparse(b).split(".")[-1] == "Structure" for b in node.bases):
+                    bad.append(f"{rel}:{node.lineno}: ctypes.Structure {node.name} written out outside the binding")
     assert calls > 200 and not bad, "\n".join(bad)
+
+
+def test_ctypes_mirrors_match_the_c_header_layout(tmp_path):
+    """The Python host talks to the C ABI through ctypes structs and integer constants that `_lib.structs()` /
+    `_lib.constants()` generate from include/thinktwice_hip.h.  The independent side: gcc compiles the header and prints sizeof
+    of every struct, offsetof of every member and the value of every constant.  A member the parser mislaid or mistyped would
+    otherwise shift every later pointer silently; a struct added to the header is covered without touching this test."""
+    from thinktwice_amd import _lib, control, labels, ops, photometric, preprocess
+    S, C = _lib.structs(), _lib.constants()
+    assert len(S) >= 10 and len(C) >= 40
+    header = open(_lib.HEADER).read()
+    assert set(re.findall(r"typedef\s+struct\s+(\w+)\s*\{", header)) == set(S)      # none skipped quietly
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "thinktwice_hip.h"', "int main(void) {"]
+    for cname, cls in S.items():
+        lines.append('  printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname))
+        for fname, _ in cls._fields_:
+            cfield = fname[:-1] if keyword.iskeyword(fname[:-1]) else fname       # `in` is spelled `in_`
+            lines.append('  printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, fname, cname, cfield))
+    lines += ['  printf("const %s %%lld\\n", (long long)%s);' % (n, n) for n in C]
+    lines += ["  return 0;", "}"]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-I", os.path.dirname(_lib.HEADER), str(src), "-o", str(exe)])
+    got = {}
+    for ln in subprocess.check_output([str(exe)], text=True).splitlines():
+        c, f, v = ln.split()
+        got[(c, f)] = int(v)
+    for cname, cls in S.items():
+        assert got[(cname, "sizeof")] == ctypes.sizeof(cls), (cname, got[(cname, "sizeof")], ctypes.sizeof(cls))
+        for fname, _ in cls._fields_:
+            assert got[(cname, fname)] == getattr(cls, fname).offset, (cname, fname)
+    for n, v in C.items():
+        assert got[("const", n)] == v, n
+    # the names the package, the tools and the tests use are these objects
+    assert (ops._ConvDesc, ops._ChainStage) == (S["tt_conv_desc"], S["tt_chain_stage"])
+    assert (control.ActionCfg, control.ActionState) == (S["tt_action_cfg"], S["tt_action_state"])
+    assert (preprocess.IdaSet, photometric.AugOp, photometric.AugProgram) == (S["tt_ida_set"], S["tt_aug_op"], S["tt_aug_program"])
+    assert (labels.HsvTables, labels.SegDecodeConf) == (S["tt_hsv_tables"], S["tt_seg_decode_conf"])
+    assert ops._ConvDesc._fields_[0] == ("in_", ctypes.c_void_p) and len(ops._ConvDesc._fields_) == 52
+    assert all(t is ctypes.c_void_p or t in _lib._SCALARS.values() for _, t in ops._ConvDesc._fields_ + ops._ChainStage._fields_)
+    assert (control.PID_WINDOW_MAX, control.ACT_STEER, control.ACT_STUCK_DETECTOR, control.ACTION_OUT) == (64, 0, 19, 24)
+    assert [getattr(photometric, k) for k in photometric.KIND_NAMES] == [C["TT_AUG_" + k] for k in photometric.KIND_NAMES]
+    assert (_lib.TT_F32, _lib.TT_BF16, _lib.TT_F16, _lib.ACT_NONE, _lib.ACT_SOFTPLUS_CLAMP) == (0, 1, 2, 0, 5)
+
+
+@pytest.mark.parametrize("member, named", [("unsigned flags : 3", "flags"), ("size_t n", "n"), ("int (*fn)(int)", "fn"),
+                                           ("union { int a; float b; } u", "u"), ("float v[n_rows]", "v")])
+def test_a_struct_member_the_parser_cannot_map_is_an_error_naming_it(tmp_path, member, named):
+    """A bit-field, an unknown type, a function pointer, a union, a non-constant dimension: TTError naming the struct and the
+    member, never a silent `int`."""
+    from thinktwice_amd import _lib
+    hdr = tmp_path / "h.h"
+    hdr.write_text("#define TT_N 4\ntypedef struct tt_ok { const float* p, *q; int a[2 * TT_N], in; } tt_ok;\n"
+                   "typedef struct tt_s { tt_ok first; /* int commented; */ %s; int last; } tt_s;\n" % member)
+    with pytest.raises(_lib.TTError, match=r"(?s)tt_s.*\b%s\b" % named):
+        _lib.structs(str(hdr))
+    good = tmp_path / "ok.h"
+    good.write_text(hdr.read_text().split("typedef struct tt_s")[0])
+    ok = _lib.structs(str(good))["tt_ok"]
+    assert ok._fields_[:2] == [("p", ctypes.c_void_p), ("q", ctypes.c_void_p)]
+    assert ok._fields_[2][1]._length_ == 8 and ok._fields_[3][0] == "in_" and ctypes.sizeof(ok) == 56

@@ -15,33 +15,20 @@ import ctypes
 import numpy as np
 import torch
 
-from ._lib import check, cur_stream, lib, ptr, raise_on_device_fault
+from ._lib import (ACT_AIM_X, ACT_AIM_Y, ACT_ANGLE, ACT_ANGLE_FINAL, ACT_ANGLE_LAST, ACT_ANGLE_TARGET, ACT_BRAKE,  # noqa: F401
+                   ACT_BRAKE_CTRL, ACT_BRAKE_TRAJ, ACT_DELTA, ACT_DESIRED_SPEED, ACT_IS_STUCK, ACT_IS_TURN, ACT_STEER,
+                   ACT_STEER_CTRL, ACT_STEER_TRAJ, ACT_STUCK_DETECTOR, ACT_THROTTLE, ACT_THROTTLE_CTRL, ACT_THROTTLE_TRAJ,
+                   ACTION_OUT, TT_PID_WINDOW_MAX as PID_WINDOW_MAX, check, cur_stream, lib, ptr, raise_on_device_fault, structs)
 
-PID_WINDOW_MAX = 64
-(ACT_STEER, ACT_THROTTLE, ACT_BRAKE, ACT_STEER_CTRL, ACT_THROTTLE_CTRL, ACT_BRAKE_CTRL, ACT_STEER_TRAJ, ACT_THROTTLE_TRAJ,
- ACT_BRAKE_TRAJ, ACT_DESIRED_SPEED, ACT_ANGLE, ACT_ANGLE_LAST, ACT_ANGLE_TARGET, ACT_ANGLE_FINAL, ACT_DELTA, ACT_AIM_X,
- ACT_AIM_Y, ACT_IS_TURN, ACT_IS_STUCK, ACT_STUCK_DETECTOR) = range(20)
-ACTION_OUT = 24
-
-
-class ActionCfg(ctypes.Structure):          # tt_action_cfg
-    _fields_ = [(n, ctypes.c_double) for n in ("turn_KP", "turn_KI", "turn_KD", "speed_KP", "speed_KI", "speed_KD",
-                                               "brake_speed", "brake_ratio", "clip_delta", "aim_dist", "angle_thresh",
-                                               "dist_thresh")] + \
-               [(n, ctypes.c_int) for n in ("turn_n", "speed_n", "stuck_threshold", "reserved")]
-
-
-class ActionState(ctypes.Structure):        # tt_action_state
-    _fields_ = [("turn_window", ctypes.c_double * PID_WINDOW_MAX), ("speed_window", ctypes.c_double * PID_WINDOW_MAX),
-                ("turn_head", ctypes.c_int), ("speed_head", ctypes.c_int), ("stuck_detector", ctypes.c_int),
-                ("reserved", ctypes.c_int)]
+ActionCfg, ActionState = structs()["tt_action_cfg"], structs()["tt_action_state"]
 
 
 def make_cfg(cfg, stuck_threshold=800):
     """tt_action_cfg from the reference's `cfg` dict (configs/thinktwice.py:44-57)."""
     c = ActionCfg()
-    for n, _ in ActionCfg._fields_[:12]:
-        setattr(c, n, float(cfg[n]))
+    for n, t in ActionCfg._fields_:
+        if t is ctypes.c_double:
+            setattr(c, n, float(cfg[n]))
     c.turn_n, c.speed_n, c.stuck_threshold = int(cfg["turn_n"]), int(cfg["speed_n"]), int(stuck_threshold)
     return c
 

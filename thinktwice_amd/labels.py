@@ -14,7 +14,7 @@ import ctypes
 
 import numpy as np
 
-from . import ops
+from . import _lib, ops
 from .ops import check, lib, ptr
 
 TRAFFIC_LIGHT_TAG = 18          # CARLA's semantic tag, literal in loading.py:140
@@ -24,17 +24,7 @@ GREEN_HUE = (70, 100)           # loading.py:102-103
 RED_HUE = (150, 180)            # loading.py:106-107
 
 
-class HsvTables(ctypes.Structure):          # tt_hsv_tables of include/thinktwice_hip.h
-    _fields_ = [("sdiv", ctypes.c_int * 256), ("hdiv", ctypes.c_int * 256)]
-
-
-class SegDecodeConf(ctypes.Structure):      # tt_seg_decode_conf
-    _fields_ = [("class_of_tag", ctypes.c_ubyte * 256), ("light_tag", ctypes.c_int), ("light_base", ctypes.c_int),
-                ("min_pixels", ctypes.c_int), ("val_low", ctypes.c_int), ("green_lo", ctypes.c_int), ("green_hi", ctypes.c_int),
-                ("red_lo", ctypes.c_int), ("red_hi", ctypes.c_int), ("sat_low_of_avg", ctypes.c_int * 256), ("hsv", HsvTables)]
-
-
-assert ctypes.sizeof(HsvTables) == 2048 and ctypes.sizeof(SegDecodeConf) == 3360
+HsvTables, SegDecodeConf = _lib.structs()["tt_hsv_tables"], _lib.structs()["tt_seg_decode_conf"]
 
 
 def hsv_tables():

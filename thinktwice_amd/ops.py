@@ -92,26 +92,7 @@ CONV_KERNELS = None   # same order as CONV_PROFILE: tt_conv_last_kernel() of the
 CONV_BYTES = None     # same order as CONV_PROFILE: compulsory HBM bytes of the launch (each operand moved once);
                       # dense: int; sparse: (bytes per live output row, fixed bytes)
 
-class _ConvDesc(ctypes.Structure):
-    _fields_ = [
-        ("in_", ctypes.c_void_p), ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("Cin", ctypes.c_int),
-        ("in_cstride", ctypes.c_int), ("in_coff", ctypes.c_int), ("in_nstride", ctypes.c_longlong),
-        ("weight", ctypes.c_void_p), ("Cout", ctypes.c_int), ("KH", ctypes.c_int), ("KW", ctypes.c_int),
-        ("stride", ctypes.c_int), ("pad", ctypes.c_int), ("dil", ctypes.c_int),
-        ("out", ctypes.c_void_p), ("OH", ctypes.c_int), ("OW", ctypes.c_int), ("out_cstride", ctypes.c_int),
-        ("out_coff", ctypes.c_int), ("out_nstride", ctypes.c_longlong),
-        ("pixel_shuffle2", ctypes.c_int),
-        ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p),
-        ("shift_n", ctypes.c_void_p), ("shift_n_mod", ctypes.c_int),
-        ("res1", ctypes.c_void_p), ("res1_cstride", ctypes.c_int), ("res1_coff", ctypes.c_int),
-        ("res2", ctypes.c_void_p), ("res2_cstride", ctypes.c_int), ("res2_coff", ctypes.c_int),
-        ("act", ctypes.c_int), ("dtype", ctypes.c_int), ("out_dtype", ctypes.c_int),
-        ("gather_idx", ctypes.c_void_p), ("m_dev", ctypes.c_void_p), ("splitk_ws", ctypes.c_void_p),
-        ("weight_x3", ctypes.c_void_p), ("row_perm", ctypes.c_void_p), ("row_mask", ctypes.c_void_p),
-        ("splitk_slices", ctypes.c_int), ("in_pair", ctypes.c_int), ("out_pair", ctypes.c_int),
-        ("weight_h2", ctypes.c_void_p), ("out2", ctypes.c_void_p), ("out2_cstride", ctypes.c_int), ("out2_coff", ctypes.c_int),
-        ("res1_up_h", ctypes.c_int), ("res1_up_w", ctypes.c_int), ("res1_f32", ctypes.c_int), ("in_up2", ctypes.c_int),
-    ]
+_ConvDesc = _lib.structs()["tt_conv_desc"]      # `in` is spelled `in_`
 
 
 def _last_conv_kernel():
@@ -860,14 +841,7 @@ def sca_reduce(x, max_len, B):
 
 
 # ----------------------------------------------------------------------------- decoder row chains (tt_mlp_chain)
-class _ChainStage(ctypes.Structure):
-    _fields_ = [
-        ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-        ("K", ctypes.c_int), ("Kp", ctypes.c_int), ("N", ctypes.c_int), ("act", ctypes.c_int), ("in_sel", ctypes.c_int),
-        ("res", ctypes.c_void_p), ("res_stride", ctypes.c_int), ("res_coff", ctypes.c_int),
-        ("side", ctypes.c_void_p), ("side_w", ctypes.c_void_p), ("side_stride", ctypes.c_int), ("side_k", ctypes.c_int),
-        ("out", ctypes.c_void_p), ("out_stride", ctypes.c_int), ("out_coff", ctypes.c_int),
-    ]
+_ChainStage = _lib.structs()["tt_chain_stage"]
 
 
 class ChainLinear:
@@ -1257,6 +1231,11 @@ def dec_bev_update(wts, bev, G, out):
     check(L.tt_dec_bev_update(B, ptr(bev), ptr(G), ptr(out), 441 * 32, None, 0, ptr(scratch), ptr(wts["w0"]),
                               ptr(wts["b0"]), wts["w2"], ptr(wts["b2"]), _st(bev)), "tt_dec_bev_update")
     return out
+
+
+_seg = _lib.structs()["tt_grad_seg"]        # GradSegTable packs it as three int64, not through ctypes
+if [(n, getattr(_seg, n).offset) for n, _ in _seg._fields_] + [ctypes.sizeof(_seg)] != [("src", 0), ("dst_off", 8), ("count", 16), 24]:
+    raise TTError("include/thinktwice_hip.h: tt_grad_seg is no longer {src, dst_off, count} of 8 bytes each, as GradSegTable packs it")
 
 
 class GradSegTable:

@@ -31,25 +31,16 @@ import math
 import numpy as np
 
 from . import _lib, ops
+from ._lib import (TT_AUG_BLUR as BLUR, TT_AUG_COARSE as COARSE, TT_AUG_DROPOUT as DROPOUT, TT_AUG_GRAY as GRAY,  # noqa: F401
+                   TT_AUG_LUT as LUT, TT_AUG_MAX_OPS, TT_AUG_NOISE as NOISE, TT_AUG_NOISE_K)
 from .ops import check, lib, ptr
 
-TT_AUG_MAX_OPS = 8
-TT_AUG_NOISE_K = 4
-LUT, NOISE, DROPOUT, COARSE, GRAY, BLUR = range(6)
 KIND_NAMES = ("LUT", "NOISE", "DROPOUT", "COARSE", "GRAY", "BLUR")
 OPERATORS = ("blur", "noise", "coarse", "dropout", "add", "multiply", "contrast", "gray")      # augmenter()'s list order
 MAX_NOISE_SCALE = 0.5        # the mass of N(0, 0.5) beyond +-4.5 is 2.3e-19; the schedule never exceeds 0.199
 
 
-class AugOp(ctypes.Structure):      # tt_aug_op of include/thinktwice_hip.h
-    _fields_ = [("kind", ctypes.c_int), ("per_channel", ctypes.c_int), ("grid_h", ctypes.c_int), ("grid_w", ctypes.c_int),
-                ("threshold", ctypes.c_uint), ("alpha", ctypes.c_float), ("seed", ctypes.c_ulonglong),
-                ("cum", ctypes.c_uint * (2 * TT_AUG_NOISE_K)), ("taps", ctypes.c_float * 5), ("reserved", ctypes.c_int),
-                ("lut", (ctypes.c_ubyte * 256) * 3)]
-
-
-class AugProgram(ctypes.Structure):     # tt_aug_program
-    _fields_ = [("num_ops", ctypes.c_int), ("blur_index", ctypes.c_int), ("ops", AugOp * TT_AUG_MAX_OPS)]
+AugOp, AugProgram = _lib.structs()["tt_aug_op"], _lib.structs()["tt_aug_program"]
 
 
 class PhotometricSchedule:

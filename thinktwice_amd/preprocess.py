@@ -65,9 +65,7 @@ class ImagePreprocessor:
 IdaParams = collections.namedtuple("IdaParams", "resize resized_h resized_w crop_y crop_x flip")
 
 
-class IdaSet(ctypes.Structure):     # tt_ida_set of include/thinktwice_hip.h
-    _fields_ = [("resized_h", ctypes.c_int), ("resized_w", ctypes.c_int), ("crop_y", ctypes.c_int), ("crop_x", ctypes.c_int),
-                ("flip", ctypes.c_int)]
+IdaSet = _lib.structs()["tt_ida_set"]
 
 
 class IdaSampler:
