@@ -48,6 +48,7 @@ _WORST = {}
 
 def _record(kernel, case, err, lim, note=""):
     print(f"PARITY {kernel:28s} {case:44s} err {err:.3e}  limit {lim:.3e} {note}")
+    _record_file()
     w = _WORST.get(kernel)
     ratio = err / lim if lim > 0 else 0.0
     n = (w[5] if w else 0) + 1
@@ -88,14 +89,25 @@ def check_equal(kernel, case, got, want):
     assert same, f"{kernel} [{case}]: not bit-equal to torch ({int((got != want).sum())} of {got.numel()} elements differ)"
 
 
+_FILES = set()
+
+
+def _record_file():
+    """The test file whose check is being recorded (the table's header names the files that were actually run)."""
+    cur = os.environ.get("PYTEST_CURRENT_TEST", "")
+    if cur:
+        _FILES.add(cur.split("::")[0])
+
+
 def _write_table():
     path = os.environ.get("TT_GLUE_PARITY_OUT")
     if not path or not _WORST:
         return
+    files = " ".join(sorted(_FILES)) or "<no test file>"
     with open(path, "w") as f:
-        f.write("# worst measured error of every glue kernel and the limit it was held to (both relative to max|ref64| of the\n"
-                "# output tensor; `bit-equal`: compared with torch.equal), over all cases of the two test files.  Produced by\n"
-                "#   TT_GLUE_PARITY_OUT=profiles/glue_ops_parity.txt python -m pytest tests/test_glue_ops.py tests/test_glue_bwd.py -m gpu -q\n"
+        f.write("# worst measured error of every kernel checked and the limit it was held to (both relative to max|ref64| of the\n"
+                "# output tensor; `bit-equal`: compared with torch.equal), over all cases of the test files run.  Produced by\n"
+                f"#   TT_GLUE_PARITY_OUT={path} python -m pytest {files} -m gpu -q\n"
                 f"# {'kernel':28s} {'checks':>6s} {'worst err':>10s} {'its limit':>10s}  case\n")
         for k in sorted(_WORST):
             ratio, err, lim, case, note, n = _WORST[k]
@@ -262,7 +274,7 @@ def ln_rows(R, D, gen):
     return x
 
 
-def _ln_terms(x, eps):
+def _ln_terms(x, eps, depth=None):
     """Float64 statistics of the rows of x and the first-order error of their f32 evaluation (u = 2^-24).  A row is summed by
     one wave: every lane adds ceil(D / 64) elements, then six butterfly steps, so no addend passes through more than
     h = ceil(D / 64) + 6 additions; the summation bound holds with h in the place of the number of addends (and is 25 x
@@ -271,8 +283,9 @@ def _ln_terms(x, eps):
       d    : x - mean, one rounding                   dd   = dm + u |d|
       var  : h additions of d^2 (+ square, division)  dvar = (h + 3) u var + mean(2 |d| dd + dd^2)
       rstd : add eps, sqrt, reciprocal (relative)     dr   = 0.5 dvar / (var + eps) + 3 u
-      xh   : d * rstd                                 dxh  = rstd dd + |xh| (dr + u)"""
-    u, h = U32, wave_sum_depth(x.shape[1])
+      xh   : d * rstd                                 dxh  = rstd dd + |xh| (dr + u)
+    `depth` replaces h for a kernel that sums its rows another way (counted next to the case that passes it)."""
+    u, h = U32, (wave_sum_depth(x.shape[1]) if depth is None else depth)
     mean = x.mean(1, keepdim=True)
     d = x - mean
     var = (d * d).mean(1, keepdim=True)
@@ -285,9 +298,9 @@ def _ln_terms(x, eps):
     return d, rstd, dd, dr, xh, rstd * dd + xh.abs() * (dr + u)
 
 
-def layernorm_bound(x, gamma, beta, eps):
+def layernorm_bound(x, gamma, beta, eps, depth=None):
     """Per-element bound of y = (x - mean) * rstd * gamma + beta in f32: |gamma| dxh + 3 u (|xh gamma| + |y|) (two products, one add)."""
-    d, rstd, dd, dr, xh, dxh = _ln_terms(x, eps)
+    d, rstd, dd, dr, xh, dxh = _ln_terms(x, eps, depth)
     y = xh * gamma + beta
     return gamma.abs() * dxh + 3 * U32 * ((xh * gamma).abs() + y.abs())
 

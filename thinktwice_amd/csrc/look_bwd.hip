@@ -139,6 +139,12 @@ __global__ __launch_bounds__(256) void sca_reduce_bwd_kernel(const float* __rest
 
 using namespace tt;
 
+static bool bwd_levels_ok(const int* hw) {
+    for (int l = 0; l < 4; ++l)
+        if (hw[2 * l] < 1 || hw[2 * l + 1] < 1) return false;
+    return true;
+}
+
 static void fill_bwd_levels(BwdLevels& m, float* const* maps, const int* hw) {
     for (int l = 0; l < 4; ++l) {
         m.p[l] = maps ? maps[l] : nullptr;
@@ -152,6 +158,9 @@ extern "C" int tt_look_gather_query_bwd(int B, const int* query_of_slot, const f
                                         float* const* dlevel_maps, const int* level_hw, void* stream) {
     TT_REQUIRE(query_of_slot && ref_packed && dout && dtemporal && dstatic && dmeas && dflat && dlevel_maps && level_hw,
                "tt_look_gather_query_bwd: null");
+    TT_REQUIRE(B > 0, "tt_look_gather_query_bwd: B %d", B);
+    TT_REQUIRE(row_stride >= 1543, "tt_look_gather_query_bwd: row_stride %d", row_stride);
+    TT_REQUIRE(bwd_levels_ok(level_hw), "tt_look_gather_query_bwd: a level with H or W < 1");
     BwdLevels m;
     fill_bwd_levels(m, dlevel_maps, level_hw);
     hipLaunchKernelGGL(look_gather_query_bwd_kernel, dim3((unsigned)(B * kBwdCams * kBwdQ)), dim3(256), 0, (hipStream_t)stream,
@@ -164,6 +173,11 @@ extern "C" int tt_msda_sample_bwd(int B, const float* value, int value_cstride, 
                                   float* dvalue, float* doffsets, float* dlogits, void* stream) {
     TT_REQUIRE(value && offsets && logits && ref_packed && level_hw && dout && dvalue && doffsets && dlogits,
                "tt_msda_sample_bwd: null");
+    TT_REQUIRE(B > 0, "tt_msda_sample_bwd: B %d", B);
+    TT_REQUIRE(value_cstride >= 256 && value_coff >= 0 && value_coff + 256 <= value_cstride,
+               "tt_msda_sample_bwd: channel window [%d, %d) outside a %d-channel row", value_coff, value_coff + 256,
+               value_cstride);
+    TT_REQUIRE(bwd_levels_ok(level_hw), "tt_msda_sample_bwd: a level with H or W < 1");
     BwdLevels m;
     fill_bwd_levels(m, nullptr, level_hw);
     int S = 0;

@@ -508,6 +508,7 @@ extern "C" int tt_look_project_pack(int B, const float* wp, const float* lidar2i
                                     int* count, int* max_len, void* stream) {
     TT_REQUIRE(wp && lidar2img && ida_mat && ref_packed && query_of_slot && count && max_len,
                "tt_look_project_pack: null");
+    TT_REQUIRE(B > 0, "tt_look_project_pack: B %d", B);
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(max_len, 0, sizeof(int), st) != hipSuccess) {
         set_error("tt_look_project_pack: memset failed");
@@ -516,6 +517,12 @@ extern "C" int tt_look_project_pack(int B, const float* wp, const float* lidar2i
     hipLaunchKernelGGL(look_project_pack_kernel, dim3(B * kCams), dim3(64), 0, st, wp, lidar2img, ida_mat, img_h,
                        img_w, ref_packed, query_of_slot, count, max_len, (float*)nullptr);
     return check_launch("tt_look_project_pack");
+}
+
+static bool levels_ok(const int* hw) {
+    for (int l = 0; l < 4; ++l)
+        if (hw[2 * l] < 1 || hw[2 * l + 1] < 1) return false;
+    return true;
 }
 
 static int fill_levels(LevelMaps& m, const void* const* maps, const int* hw) {
@@ -532,8 +539,11 @@ extern "C" int tt_look_gather_query(int B, const int* query_of_slot, const float
                                     const float* static_embedding, const float* measurement_feat,
                                     const float* flattened_feat, const void* const* level_maps,
                                     const int* level_hw, int maps_dtype, float* out, int row_stride, void* stream) {
-    TT_REQUIRE(query_of_slot && ref_packed && wp && ctrl_softplus && level_maps && level_hw && out,
+    TT_REQUIRE(query_of_slot && ref_packed && wp && ctrl_softplus && temporal_embedding && static_embedding &&
+                   measurement_feat && flattened_feat && level_maps && level_hw && out,
                "tt_look_gather_query: null");
+    TT_REQUIRE(B > 0, "tt_look_gather_query: B %d", B);
+    TT_REQUIRE(levels_ok(level_hw), "tt_look_gather_query: a level with H or W < 1");
     TT_REQUIRE(row_stride >= 1543 && row_stride <= 1543 + 256, "tt_look_gather_query: row_stride %d", row_stride);
     LevelMaps m;
     fill_levels(m, level_maps, level_hw);
@@ -558,6 +568,8 @@ extern "C" int tt_msda_sample_strided(int B, const void* value, int value_dtype,
                                       const float* offsets, const float* logits, const float* ref_packed,
                                       const int* level_hw, float* out, void* stream) {
     TT_REQUIRE(value && offsets && logits && ref_packed && level_hw && out, "tt_msda_sample: null");
+    TT_REQUIRE(B > 0, "tt_msda_sample: B %d", B);
+    TT_REQUIRE(levels_ok(level_hw), "tt_msda_sample: a level with H or W < 1");
     TT_REQUIRE(value_cstride >= 256 && value_coff >= 0 && value_coff + 256 <= value_cstride,
                "tt_msda_sample: channel window [%d, %d) outside a %d-channel row", value_coff, value_coff + 256,
                value_cstride);
@@ -586,6 +598,7 @@ extern "C" int tt_msda_sample(int B, const void* value, int value_dtype, const f
 
 extern "C" int tt_sca_reduce(int B, const float* x, const int* max_len, float* out, void* stream) {
     TT_REQUIRE(x && max_len && out, "tt_sca_reduce: null");
+    TT_REQUIRE(B > 0, "tt_sca_reduce: B %d", B);
     hipLaunchKernelGGL(sca_reduce_kernel, dim3(B * kCams), dim3(256), 0, (hipStream_t)stream, x, max_len, B, out);
     return check_launch("tt_sca_reduce");
 }
@@ -595,8 +608,11 @@ extern "C" int tt_look_query_ln(int B, const int* query_of_slot, const float* re
                                 const float* static_embedding, const float* measurement_feat, const float* flattened_feat,
                                 const void* const* level_maps, const int* level_hw, int maps_dtype, const float* gamma,
                                 const float* beta, float eps, float* out, int row_stride, void* stream) {
-    TT_REQUIRE(query_of_slot && ref_packed && wp && ctrl && level_maps && level_hw && gamma && beta && out,
+    TT_REQUIRE(query_of_slot && ref_packed && wp && ctrl && temporal_embedding && static_embedding && measurement_feat &&
+                   flattened_feat && level_maps && level_hw && gamma && beta && out,
                "tt_look_query_ln: null");
+    TT_REQUIRE(B > 0, "tt_look_query_ln: B %d", B);
+    TT_REQUIRE(levels_ok(level_hw), "tt_look_query_ln: a level with H or W < 1");
     TT_REQUIRE(row_stride >= 1543 && row_stride <= 1543 + 256, "tt_look_query_ln: row_stride %d", row_stride);
     LevelMaps m;
     fill_levels(m, level_maps, level_hw);
@@ -621,6 +637,8 @@ extern "C" int tt_msda_sample_ln(int B, const void* value, int value_dtype, int 
                "tt_msda_sample_ln: null");
     TT_REQUIRE(value_cstride >= 256 && value_coff >= 0 && value_coff + 256 <= value_cstride,
                "tt_msda_sample_ln: channel window outside the row");
+    TT_REQUIRE(B > 0, "tt_msda_sample_ln: B %d", B);
+    TT_REQUIRE(levels_ok(level_hw), "tt_msda_sample_ln: a level with H or W < 1");
     LevelMaps m;
     fill_levels(m, nullptr, level_hw);
     int S = 0;
@@ -643,6 +661,8 @@ extern "C" int tt_msda_sample_proj_ln(int B, const void* const* level_maps, cons
                                       float* out_ln, const int* max_len_or_null, void* stream) {
     TT_REQUIRE(level_maps && level_hw && offsets && logits && ref_packed && wvT && bias && vshift && gamma && beta && out && out_ln,
                "tt_msda_sample_proj_ln: null");
+    TT_REQUIRE(B > 0, "tt_msda_sample_proj_ln: B %d", B);
+    TT_REQUIRE(levels_ok(level_hw), "tt_msda_sample_proj_ln: a level with H or W < 1");
     LevelMaps m;
     fill_levels(m, level_maps, level_hw);
     const long long rows_n = (long long)B * kCams * kQ;
@@ -654,6 +674,7 @@ extern "C" int tt_msda_sample_proj_ln(int B, const void* const* level_maps, cons
 extern "C" int tt_sca_reduce_ln(int B, const float* x, const int* max_len, const float* gamma, const float* beta,
                                 float eps, float* out, void* stream) {
     TT_REQUIRE(x && max_len && gamma && beta && out, "tt_sca_reduce_ln: null");
+    TT_REQUIRE(B > 0, "tt_sca_reduce_ln: B %d", B);
     hipLaunchKernelGGL(sca_reduce_ln_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, max_len, B, gamma, beta, eps,
                        out);
     return check_launch("tt_sca_reduce_ln");
@@ -663,6 +684,7 @@ extern "C" int tt_dec_merge_in(int B, const float* fflat, const float* look, con
                                const float* measurement_feat, const float* gamma, const float* beta, float eps,
                                float* out, void* stream) {
     TT_REQUIRE(fflat && look && temporal_embedding && measurement_feat && gamma && beta && out, "tt_dec_merge_in: null");
+    TT_REQUIRE(B > 0, "tt_dec_merge_in: B %d", B);
     hipLaunchKernelGGL(dec_merge_in_kernel, dim3(B * 4), dim3(256), 0, (hipStream_t)stream, fflat, look,
                        temporal_embedding, measurement_feat, gamma, beta, eps, out);
     return check_launch("tt_dec_merge_in");
