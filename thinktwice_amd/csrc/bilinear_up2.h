@@ -3,7 +3,7 @@
 // the operand of a 3 x 3 convolution; the two give the same bits because both call these two functions (the library is built with
 // -ffp-contract=off: every product and sum below rounds on its own).
 #pragma once
-#include "tt_common.h"
+#include "bf16x3.h"
 
 namespace tt {
 
@@ -28,8 +28,7 @@ __device__ __forceinline__ Up2Tap up2_tap(int H, int W, int oy, int ox) {
 }
 
 // Eight consecutive channels of one output pixel from their four source vectors (p00 = row y0, column x0; p01 = row y0, column x1;
-// p10 / p11 = row y1), in ATen's upsample_bilinear2d operation order, split into the bf16 pair format's halves: hi = rne(v),
-// lo = rne(v - hi) with the subtraction exact in f32 (the split of conv_igemm_glds.hip's split_frag).
+// p10 / p11 = row y1), in ATen's upsample_bilinear2d operation order, split into the bf16 pair format's halves (bf16x3.h).
 __device__ __forceinline__ void up2_pair8(const float* p00, const float* p01, const float* p10, const float* p11, float ly, float lx,
                                           uint4& hi, uint4& lo) {
     float v[8];
@@ -46,14 +45,7 @@ __device__ __forceinline__ void up2_pair8(const float* p00, const float* p01, co
             v[4 * h + k] = (1.f - ly) * top + ly * bot;
         }
     }
-    uint32_t hw[4], lw[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        hw[e] = pack_bf16x2(v[2 * e], v[2 * e + 1]);
-        lw[e] = pack_bf16x2(v[2 * e] - __uint_as_float(hw[e] << 16), v[2 * e + 1] - __uint_as_float(hw[e] & 0xffff0000u));
-    }
-    hi = make_uint4(hw[0], hw[1], hw[2], hw[3]);
-    lo = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+    split8(v, hi, lo);
 }
 
 }  // namespace tt

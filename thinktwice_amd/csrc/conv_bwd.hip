@@ -36,20 +36,6 @@ struct WgradArgs {
 // the MFMAs (measured on the 64 x 64 kernel: the conditional loads are FASTER there, 55 vs 36 TF/s, so it keeps them)
 __device__ __forceinline__ float masked(float v, bool ok) { return v * (ok ? 1.f : 0.f); }
 
-// f32 x 8 -> bf16 (hi, lo) operand pair: hi = bf16(x) round-to-nearest-even, lo = bf16(x - hi)
-__device__ __forceinline__ void split8(const float (&x)[8], uint4& hi, uint4& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        h[e] = pack_bf16x2(x[2 * e], x[2 * e + 1]);
-        const float q0 = x[2 * e] - __uint_as_float(h[e] << 16);           // exact in f32
-        const float q1 = x[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u);
-        l[e] = pack_bf16x2(q0, q1);
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
 constexpr int kWgUnroll = 4;       // pixel pairs in flight per wave (each: 2 + 2 dword loads, 4 MFMAs)
 
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
@@ -389,7 +375,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_lds_kernel(const WgradArgs 
                 for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(rb[j][e]));
                 split8(rb[j], bh[j], bl[j]);
             }
-            // term-major: consecutive MFMAs write different accumulators; small terms first
+            // term-major: consecutive MFMAs write different accumulators; per accumulator the one-accumulator order of bf16x3.h
 #pragma unroll
             for (int i = 0; i < BI; ++i)
 #pragma unroll

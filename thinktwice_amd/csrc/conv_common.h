@@ -1,41 +1,14 @@
-// Shared definitions of the implicit-GEMM convolution kernels: MFMA wrappers, the fused epilogue, the launch entries.  (Their arguments
-// and the choice of a layer's kernel are in conv_choose.h, the data movement of the LDS-DMA kernels in conv_lds_dma.h.)
+// Shared definitions of the implicit-GEMM convolution kernels: the fused epilogue, the launch entries.  (Their arguments and the choice
+// of a layer's kernel are in conv_choose.h, the data movement of the LDS-DMA kernels in conv_lds_dma.h, the MFMA wrappers and the
+// bf16x3 arithmetic in bf16x3.h.)
 #pragma once
 #include <type_traits>
+#include "bf16x3.h"
 #include "conv_choose.h"
 
 namespace tt {
 extern thread_local char g_conv_kernel[96];   // common.cpp: label of the kernel the last conv launch used (conv_label)
 extern long long* g_conv_trace;               // common.cpp: tt_conv_set_trace (measurement aid; null in the product)
-
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> struct Mfma;
-template <> struct Mfma<float> {
-    // one 16 B vector (4 floats) per lane = 4 MFMAs of K=2 (lanes 0-31: k, lanes 32-63: k+4)
-    __device__ static __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-    }
-};
-template <> struct Mfma<uint16_t> {
-    // one 16 B vector (8 bf16) per lane = 1 MFMA of K=16
-    __device__ static __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                    __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mfma<f16_t> {
-    // one 16 B vector (8 halves) per lane = 1 MFMA of K=16, same rate as bf16
-    __device__ static __forceinline__ void run(const uint4& a, const uint4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
 
 // A wave's accumulator blocks, element by element (compile-time indices: they stay registers)
 template <int TN>
@@ -193,21 +166,10 @@ __device__ __forceinline__ void conv_epilogue_vec(const ConvArgs& p, f32x16 (&ac
             if (nt_store) __builtin_nontemporal_store(f4v{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4v*>(reinterpret_cast<float*>(p.out) + o));
             else *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + o) = make_float4(v[0], v[1], v[2], v[3]);
         } else if (sizeof(T) == 4 && (p.flags & 64)) {
-            // pair-format output (tt_conv_desc.out_pair): the eight channels' bf16 hi halves go to the first 32 B of their 16-channel
-            // group (second 16 B for channels 8-15 of the group), the lo halves 32 B further -- hi = rne(v), lo = rne(v - hi), the
-            // consumer kernel's own split (conv_igemm_glds.hip split_frag), done once per element here
+            // pair-format output (tt_conv_desc.out_pair): the consumer kernel's own split (bf16x3.h), done once per element here
             uint4 hi, lo;
-            uint32_t* hp = reinterpret_cast<uint32_t*>(&hi);
-            uint32_t* lp = reinterpret_cast<uint32_t*>(&lo);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const uint32_t h = pack_bf16x2(v[2 * e], v[2 * e + 1]);
-                hp[e] = h;
-                lp[e] = pack_bf16x2(v[2 * e] - __uint_as_float(h << 16), v[2 * e + 1] - __uint_as_float(h & 0xffff0000u));
-            }
-            float* g = reinterpret_cast<float*>(p.out) + (o & ~15ll) + ((o & 8) ? 4 : 0);
-            *reinterpret_cast<uint4*>(g) = hi;
-            *reinterpret_cast<uint4*>(g + 8) = lo;
+            split8(v, hi, lo);
+            pair_store8(reinterpret_cast<float*>(p.out), o, hi, lo);
         } else {
             // 16-bit output: the storage type of the operands, or (f32 operands: a bf16x3 layer feeding a half-storage stage of
             // the mixed mode) the type out_dtype names

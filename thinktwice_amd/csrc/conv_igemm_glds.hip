@@ -33,7 +33,7 @@ namespace tt {
 // 16/3 of the exact-f32 MFMA rate.  This is the precision mode whose outputs meet the 1e-3 tolerance.
 // APAIR (X3 only): the ACTIVATIONS arrive pre-split too -- the tensor holds, per 16 channels, 64 B = [hi c0-7 | hi c8-15 | lo c0-7 |
 // lo c8-15] in bf16 (the weights' pair format along the channel axis, same footprint as f32), written by the producer's epilogue
-// (tt_conv_desc.out_pair) or by an elementwise producer (tt_bilinear_up2_pair).  The hi / lo values are the ones split_frag computes,
+// (tt_conv_desc.out_pair) or by an elementwise producer (tt_bilinear_up2_pair).  The hi / lo values are the ones the split of bf16x3.h computes,
 // so the sums are bit-identical; what disappears is the split itself: 6 VALU per element pair per USE (a 3 x 3 layer splits every
 // input element 9 x per column tile) against once per element at the producer.  For tensors whose ONLY readers are bf16x3 convolutions.
 template <typename T, int BN, int WAVES_M, int WAVES_N, int BKB, int STAGES = 3, bool GATHER = false, bool X3 = false, bool APAIR = false>
@@ -376,19 +376,7 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
                     lo_out = __builtin_bit_cast(uint4, ra1[i]);
                     return;
                 }
-                const float x[8] = {__uint_as_float(ra0[i].x), __uint_as_float(ra0[i].y), __uint_as_float(ra0[i].z),
-                                    __uint_as_float(ra0[i].w), __uint_as_float(ra1[i].x), __uint_as_float(ra1[i].y),
-                                    __uint_as_float(ra1[i].z), __uint_as_float(ra1[i].w)};
-                uint32_t h[4], l[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    h[e] = pack_bf16x2(x[2 * e], x[2 * e + 1]);                       // round to nearest even
-                    const float r0 = x[2 * e] - __uint_as_float(h[e] << 16);           // exact in f32
-                    const float r1 = x[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u);
-                    l[e] = pack_bf16x2(r0, r1);
-                }
-                hi_out = make_uint4(h[0], h[1], h[2], h[3]);
-                lo_out = make_uint4(l[0], l[1], l[2], l[3]);
+                split8(ra0[i], ra1[i], hi_out, lo_out);
             };
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
@@ -464,7 +452,7 @@ void conv_igemm_glds_kernel(const ConvArgs p, const void* zero_page,
                 const uint4 bhv = __builtin_bit_cast(uint4, bh[buf]);
                 const uint4 blv = __builtin_bit_cast(uint4, bl[buf]);
                 // term-major order: consecutive MFMAs write different accumulators (a back-to-back pair on the same
-                // accumulator waits for the first one's last pass); small terms first
+                // accumulator waits for the first one's last pass); per accumulator the one-accumulator order of bf16x3.h
                 if (!(TT_GLDS_DEBUG && p.act == 94)) {       // debug 94: one MFMA per fragment pair instead of three
 #pragma unroll
                     for (int i = 0; i < TM; ++i) Mfma<uint16_t>::run(al[ab][i], bhv, acc[i][j]);

@@ -15,7 +15,7 @@
 // The patch is single-buffered (a barrier in front of every production): two workgroups share a CU and one's production runs beside
 // the other's MFMAs.
 // Sums: channel chunk outer, taps (kh, kw) ascending inside it, two 16-channel k-steps per (chunk, tap), per k-step a_lo*b_hi,
-// a_hi*b_lo, a_hi*b_hi on v_mfma_f32_32x32x16_bf16 into one f32 accumulator -- the order of the pair-format X3 body of
+// a_hi*b_lo, a_hi*b_hi on v_mfma_f32_32x32x16_bf16 into one f32 accumulator (bf16x3.h) -- the order of the pair-format X3 body of
 // conv_igemm_glds.hip, bit for bit.
 #pragma once
 #include "conv_lds_dma.h"
@@ -112,7 +112,7 @@ __device__ __forceinline__ void patch_k_loop(const ConvArgs& p, const float* __r
     issue_w(1);
     auto mfma_k = [&](const u32x4& ah, const u32x4& al, const u32x4 (&bh)[NCB], const u32x4 (&bl)[NCB]) {
         const uint4 ahv = __builtin_bit_cast(uint4, ah), alv = __builtin_bit_cast(uint4, al);
-        // term-major: consecutive MFMAs write different accumulators; per accumulator the order is lo*hi, hi*lo, hi*hi
+        // term-major: consecutive MFMAs write different accumulators; per accumulator the one-accumulator order of bf16x3.h
 #pragma unroll
         for (int j = 0; j < NCB; ++j) Mfma<uint16_t>::run(alv, __builtin_bit_cast(uint4, bh[j]), acc[0][j]);
 #pragma unroll

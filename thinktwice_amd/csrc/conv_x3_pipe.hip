@@ -166,14 +166,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
 #else
 #define TT_MFMA(c, a, b) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b))
 #endif
-    // the split of one element pair in two 3-VALU halves (cvt_pk, shift, and | sub, sub, cvt_pk): bf16 hi = rne(x),
-    // lo = rne(x - hi) with the subtraction exact in f32 -- the arithmetic of conv_igemm_glds.hip's split_frag
-    auto split_a = [](float x0, float x1, uint32_t& h, float& t0, float& t1) {
-        h = pack_bf16x2(x0, x1);
-        t0 = __uint_as_float(h << 16);
-        t1 = __uint_as_float(h & 0xffff0000u);
-    };
-    auto split_b = [](float x0, float x1, float t0, float t1) { return pack_bf16x2(x0 - t0, x1 - t1); };
+    // (the split of one element pair comes in two 3-VALU halves, cvt_pk, shift, and | sub, sub, cvt_pk: split_hi / split_lo of bf16x3.h)
 
     u32x4 ah[2][TM], al[2][TM];       // [K step parity][row block]: split activation fragments
     u32x4 bh[TN], bl[TN];             // weight fragments of the current K step (refilled behind their last use)
@@ -212,8 +205,8 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float t0, t1;
-                split_a(x[2 * e], x[2 * e + 1], h[e], t0, t1);
-                l[e] = split_b(x[2 * e], x[2 * e + 1], t0, t1);
+                split_hi(x[2 * e], x[2 * e + 1], h[e], t0, t1);
+                l[e] = split_lo(x[2 * e], x[2 * e + 1], t0, t1);
             }
             ah[0][i] = u32x4{h[0], h[1], h[2], h[3]};
             al[0][i] = u32x4{l[0], l[1], l[2], l[3]};
@@ -261,11 +254,11 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
                     return;
                 }
                 if ((s & 1) == 0) {
-                    split_a(x0, x1, sh[e], st0, st1);
+                    split_hi(x0, x1, sh[e], st0, st1);
                     asm volatile("" : "+v"(sh[e]), "+v"(st0), "+v"(st1));
                 } else {
                     asm volatile("" : "+v"(st0), "+v"(st1));
-                    sl[e] = split_b(x0, x1, st0, st1);
+                    sl[e] = split_lo(x0, x1, st0, st1);
                     asm volatile("" : "+v"(sl[e]));
                 }
             };
@@ -548,13 +541,6 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
     f32x16 acc[TM][TN];
     zero_acc(acc);
 
-    auto split_a = [](float x0, float x1, uint32_t& h, float& t0, float& t1) {
-        h = pack_bf16x2(x0, x1);
-        t0 = __uint_as_float(h << 16);
-        t1 = __uint_as_float(h & 0xffff0000u);
-    };
-    auto split_b = [](float x0, float x1, float t0, float t1) { return pack_bf16x2(x0 - t0, x1 - t1); };
-
     u32x4 ah[2][TM], al[2][TM], bh[TN], bl[TN], ra0, ra1;
     const unsigned zaddr = lds_base + Z_OFF;
 
@@ -592,8 +578,8 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float t0, t1;
-                split_a(x[2 * e], x[2 * e + 1], h[e], t0, t1);
-                l[e] = split_b(x[2 * e], x[2 * e + 1], t0, t1);
+                split_hi(x[2 * e], x[2 * e + 1], h[e], t0, t1);
+                l[e] = split_lo(x[2 * e], x[2 * e + 1], t0, t1);
             }
             ah[0][i] = u32x4{h[0], h[1], h[2], h[3]};
             al[0][i] = u32x4{l[0], l[1], l[2], l[3]};
@@ -642,11 +628,11 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
                     const float x0 = __uint_as_float(e == 0 ? ra0.x : e == 1 ? ra0.z : e == 2 ? ra1.x : ra1.z);
                     const float x1 = __uint_as_float(e == 0 ? ra0.y : e == 1 ? ra0.w : e == 2 ? ra1.y : ra1.w);
                     if ((s & 1) == 0) {
-                        split_a(x0, x1, sh[e], st0, st1);
+                        split_hi(x0, x1, sh[e], st0, st1);
                         asm volatile("" : "+v"(sh[e]), "+v"(st0), "+v"(st1));
                     } else {
                         asm volatile("" : "+v"(st0), "+v"(st1));
-                        sl[e] = split_b(x0, x1, st0, st1);
+                        sl[e] = split_lo(x0, x1, st0, st1);
                         asm volatile("" : "+v"(sl[e]));
                     }
                 };

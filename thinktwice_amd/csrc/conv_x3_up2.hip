@@ -5,7 +5,7 @@
 // staged patch instead of nine DMA'd row tiles.
 //
 // Same arithmetic as tt_bilinear_up2_pair followed by the pair-format X3 body of conv_igemm_glds.hip, bit for bit: the interpolation
-// and the operand split are the two functions of bilinear_up2.h; the sums run channel chunk outer, taps (kh, kw) ascending inside it,
+// and the operand split are the two functions of bilinear_up2.h (the split itself: bf16x3.h); the sums run channel chunk outer, taps (kh, kw) ascending inside it,
 // two 16-channel k-steps per (chunk, tap), per k-step a_lo*b_hi, a_hi*b_lo, a_hi*b_hi on v_mfma_f32_32x32x16_bf16 into one f32
 // accumulator; the epilogue is the shared one.
 //

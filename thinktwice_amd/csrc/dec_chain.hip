@@ -55,36 +55,7 @@ struct ChainArgs {
     ChainStage st[kChainMaxStages];
 };
 
-__device__ __forceinline__ void split8(const float (&x)[8], uint4& hi, uint4& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        h[e] = pack_bf16x2(x[2 * e], x[2 * e + 1]);
-        const float r0 = x[2 * e] - __uint_as_float(h[e] << 16);
-        const float r1 = x[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u);
-        l[e] = pack_bf16x2(r0, r1);
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
-// the cross terms and the main term go to two accumulators (summed in the epilogue): a back-to-back MFMA pair on the
-// same accumulator waits for the first one's last pass
-__device__ __forceinline__ void mfma3(const uint4& ah, const uint4& al, const uint4& bh, const uint4& bl, f32x16& c,
-                                      f32x16& c2) {
-    Mfma<uint16_t>::run(al, bh, c2);
-    Mfma<uint16_t>::run(ah, bh, c);
-    Mfma<uint16_t>::run(ah, bl, c2);
-}
-
-// store one f32 value as a (hi, lo) bf16 pair at element (row, col) of a pair-format LDS buffer
-__device__ __forceinline__ void lds_store_pair(unsigned char* buf, int stride, int row, int col, float v) {
-    const uint16_t hi = f32_to_bf16(v);
-    const uint16_t lo = f32_to_bf16(v - bf16_to_f32(hi));
-    unsigned char* p = buf + (size_t)row * stride + (col >> 4) * 64 + ((col >> 3) & 1) * 16 + (col & 7) * 2;
-    *reinterpret_cast<uint16_t*>(p) = hi;
-    *reinterpret_cast<uint16_t*>(p + 32) = lo;
-}
+// (The operand split, the pair-format LDS buffers and the two-accumulator product of these kernels: bf16x3.h.)
 
 __global__ __launch_bounds__(kChainWaves * 64) void mlp_chain_kernel(const ChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -220,7 +191,7 @@ __global__ __launch_bounds__(kChainWaves * 64) void mlp_chain_kernel(const Chain
                     v = apply_act(v, S.act);
                     if (!ok) v = 0.f;
                     if (S.out && ok) S.out[mr * S.out_stride + S.out_coff + n] = v;
-                    if (S.lds_off >= 0) lds_store_pair(smem + S.lds_off, S.lds_stride, rr, n, v);
+                    if (S.lds_off >= 0) pair_store(smem + S.lds_off + (size_t)rr * S.lds_stride, n, v);
                 }
             }
         }

@@ -22,37 +22,8 @@
 
 namespace tt {
 
-// the three products of a K step go to TWO accumulators (summed at the end): a back-to-back MFMA pair on the same
-// accumulator waits for the first one's last pass, and these kernels have a single output block per wave
-__device__ __forceinline__ void mfma3s(const uint4& ah, const uint4& al, const uint4& bh, const uint4& bl, f32x16& c,
-                                       f32x16& c2) {
-    Mfma<uint16_t>::run(al, bh, c2);
-    Mfma<uint16_t>::run(ah, bh, c);
-    Mfma<uint16_t>::run(ah, bl, c2);
-}
-
-__device__ __forceinline__ void pair_store(unsigned char* map, int PS, int pix, int c, float v) {
-    const uint16_t hi = f32_to_bf16(v);
-    const uint16_t lo = f32_to_bf16(v - bf16_to_f32(hi));
-    unsigned char* p = map + (size_t)pix * PS + (c >> 4) * 64 + ((c >> 3) & 1) * 16 + (c & 7) * 2;
-    *reinterpret_cast<uint16_t*>(p) = hi;
-    *reinterpret_cast<uint16_t*>(p + 32) = lo;
-}
-
-__device__ __forceinline__ float pair_load(const unsigned char* map, int PS, int pix, int c) {
-    const unsigned char* p = map + (size_t)pix * PS + (c >> 4) * 64 + ((c >> 3) & 1) * 16 + (c & 7) * 2;
-    return bf16_to_f32(*reinterpret_cast<const uint16_t*>(p)) + bf16_to_f32(*reinterpret_cast<const uint16_t*>(p + 32));
-}
-
-// four consecutive channels c .. c + 3 (c % 4 == 0) of one pixel: two 8-byte LDS stores
-__device__ __forceinline__ void pair_store4(unsigned char* map, int PS, int pix, int c, const float4& v) {
-    unsigned char* p = map + (size_t)pix * PS + (c >> 4) * 64 + ((c >> 3) & 1) * 16 + (c & 7) * 2;
-    const uint16_t h0 = f32_to_bf16(v.x), h1 = f32_to_bf16(v.y), h2 = f32_to_bf16(v.z), h3 = f32_to_bf16(v.w);
-    const uint16_t l0 = f32_to_bf16(v.x - bf16_to_f32(h0)), l1 = f32_to_bf16(v.y - bf16_to_f32(h1));
-    const uint16_t l2 = f32_to_bf16(v.z - bf16_to_f32(h2)), l3 = f32_to_bf16(v.w - bf16_to_f32(h3));
-    *reinterpret_cast<uint2*>(p) = make_uint2((unsigned)h0 | ((unsigned)h1 << 16), (unsigned)h2 | ((unsigned)h3 << 16));
-    *reinterpret_cast<uint2*>(p + 32) = make_uint2((unsigned)l0 | ((unsigned)l1 << 16), (unsigned)l2 | ((unsigned)l3 << 16));
-}
+// (The pair-format LDS maps of these kernels -- row stride PS bytes per pixel -- and their two-accumulator product: bf16x3.h.  These
+// kernels have a single output block per wave.)
 
 // a 441 x 32 f32 map (16 B aligned) from global memory into a pair-format LDS map: every load of a thread issued before its
 // first store (one element per step left each step waiting for its own L2 round trip)
@@ -71,7 +42,7 @@ __device__ __forceinline__ void load_map32(unsigned char* map, const float* src,
 #pragma unroll
         for (int u = 0; u < kBatch; ++u) {
             const int e = tid + (u0 + u) * NT;
-            if (e < kN4) pair_store4(map, 144, e >> 3, (e & 7) * 4, v[u]);
+            if (e < kN4) pair_store4(map + (size_t)(e >> 3) * 144, (e & 7) * 4, v[u]);
         }
     }
 }
@@ -144,7 +115,7 @@ __device__ __forceinline__ void conv_lds(const unsigned char* in_map, int H, int
                     const uint4 al = *reinterpret_cast<const uint4*>(ok ? ap + 32 : ap);
 #pragma unroll
                     for (int q = 0; q < NBG; ++q)
-                        if (live[q]) mfma3s(ah, al, bh[p][q], bl[p][q], acc[q], acc2[q]);
+                        if (live[q]) mfma3(ah, al, bh[p][q], bl[p][q], acc[q], acc2[q]);
                 }
                 {
                     const int kn = ks + PF < last ? ks + PF : last;
@@ -236,7 +207,7 @@ __device__ __forceinline__ void conv3x3_map32(const unsigned char* in_map, const
                     al[q] = *reinterpret_cast<const uint4*>(sel + toff + 32);
                 }
 #pragma unroll
-                for (int q = 0; q < MBG; ++q) Mfma<uint16_t>::run(al[q], bh[p], acc2[q]);
+                for (int q = 0; q < MBG; ++q) Mfma<uint16_t>::run(al[q], bh[p], acc2[q]);     // term-major; the two-accumulator order of bf16x3.h
 #pragma unroll
                 for (int q = 0; q < MBG; ++q) Mfma<uint16_t>::run(ah[q], bh[p], acc[q]);
 #pragma unroll
@@ -415,7 +386,7 @@ __global__ __launch_bounds__(kGruWaves * 64) void dec_gru_kernel(const GruArgs a
         fresh_rows();
         conv3x3_map32<2>(Smap, zero, a.w0[cv], wave, kGruWaves, lane, [&](int, int q, int i, float v) {
             v += Gc[(cv * 16 + cls_of(q, i)) * 32 + r];
-            pair_store(Hmap, kPS32, row_of(q, i), r, v > 0.f ? v : 0.f);
+            pair_store(Hmap + (size_t)row_of(q, i) * kPS32, r, v > 0.f ? v : 0.f);
         });
     };
     if (role == 0) {
@@ -432,9 +403,9 @@ __global__ __launch_bounds__(kGruWaves * 64) void dec_gru_kernel(const GruArgs a
             conv3x3_map32<2>(Hmap, zero, a.w2[1], wave, kGruWaves, lane, [&](int, int q, int i, float v) {
                 const int m = row_of(q, i);
                 const float rg = sigmoid_fast(v + b2r);
-                const float s = pair_load(Smap, kPS32, m, r);
+                const float s = pair_load(Smap + (size_t)m * kPS32, r);
                 sg[m * kMapC + r] = s;
-                pair_store(Smap, kPS32, m, r, (1.f - rg) * s);        // own element only: no other reader now
+                pair_store(Smap + (size_t)m * kPS32, r, (1.f - rg) * s);        // own element only: no other reader now
             });
             __syncthreads();
             stamp();
@@ -449,7 +420,7 @@ __global__ __launch_bounds__(kGruWaves * 64) void dec_gru_kernel(const GruArgs a
                 const float u = ug[m * kMapC + r];
                 float ns = (1.f - u) * sg[m * kMapC + r] + u * cand;
                 if (poisoned) ns = kNaN;
-                pair_store(Smap, kPS32, m, r, ns);
+                pair_store(Smap + (size_t)m * kPS32, r, ns);
                 sn[m * kMapC + r] = ns;
             });
             flag_post(f_state, (unsigned)(t + 1));
@@ -479,7 +450,7 @@ __global__ __launch_bounds__(kGruWaves * 64) void dec_gru_kernel(const GruArgs a
                 fresh_rows();
                 conv3x3_map32<2>(Smap, zero, a.wd0, wave, kGruWaves, lane, [&](int, int q, int i, float v) {
                     v += bd0;
-                    pair_store(Hmap, kPS32, row_of(q, i), r, v > 0.f ? v : 0.f);
+                    pair_store(Hmap + (size_t)row_of(q, i) * kPS32, r, v > 0.f ? v : 0.f);
                 });
                 __syncthreads();
                 float* fo = a.fut + (((size_t)b * 4 + (t - 1)) * kMapPix) * kMapC;
@@ -526,11 +497,11 @@ __device__ __forceinline__ void se_block(const FlatArgs& a, int set, int HW, int
                                          int lane, int tid, Stamp stamp) {
     const int PS = ps_of(C), PS1 = ps_of(2 * C), M = HW * HW;
     conv_lds<1, 4>(X, HW, HW, C, PS, zero, 1, 1, 3, 3, a.w[set], 2 * C, HW, HW, wave, kFlatWaves, lane,
-                   [&](int m, int n, float v, int) { v += a.b[set][n]; pair_store(Y1, PS1, m, n, v > 0.f ? v : 0.f); });
+                   [&](int m, int n, float v, int) { v += a.b[set][n]; pair_store(Y1 + (size_t)m * PS1, n, v > 0.f ? v : 0.f); });
     __syncthreads();
     stamp();
     conv_lds<1, 4>(Y1, HW, HW, 2 * C, PS1, zero, 1, 1, 3, 3, a.w[set + 1], C, HW, HW, wave, kFlatWaves, lane,
-                   [&](int m, int n, float v, int) { v += a.b[set + 1][n]; pair_store(Y2, PS, m, n, v > 0.f ? v : 0.f); });
+                   [&](int m, int n, float v, int) { v += a.b[set + 1][n]; pair_store(Y2 + (size_t)m * PS, n, v > 0.f ? v : 0.f); });
     __syncthreads();
     stamp();
     unsigned char* s0 = vec;                       // pooled vector as a 1-pixel map
@@ -542,7 +513,7 @@ __device__ __forceinline__ void se_block(const FlatArgs& a, int set, int HW, int
         const int nparts = kFlatWaves * 64 / C, c = tid % C, part = tid / C;
         float sum = 0.f, mx = -INFINITY;
         for (int m = part; m < M; m += nparts) {
-            const float v = pair_load(Y2, PS, m, c);
+            const float v = pair_load(Y2 + (size_t)m * PS, c);
             sum += v;
             mx = fmaxf(mx, v);
         }
@@ -554,13 +525,13 @@ __device__ __forceinline__ void se_block(const FlatArgs& a, int set, int HW, int
                 sum += red[(q * C + tid) * 2];
                 mx = fmaxf(mx, red[(q * C + tid) * 2 + 1]);
             }
-            pair_store(s0, PS, 0, tid, 0.5f * (sum / (float)M) + 0.5f * mx);
+            pair_store(s0, tid, 0.5f * (sum / (float)M) + 0.5f * mx);
         }
     }
     __syncthreads();
     stamp();
     conv_lds<1, 4>(s0, 1, 1, C, PS, zero, 1, 0, 1, 1, a.w[set + 2], C, 1, 1, wave, kFlatWaves, lane,
-                   [&](int, int n, float v, int) { v += a.b[set + 2][n]; pair_store(s1, PS, 0, n, v > 0.f ? v : 0.f); });
+                   [&](int, int n, float v, int) { v += a.b[set + 2][n]; pair_store(s1, n, v > 0.f ? v : 0.f); });
     __syncthreads();
     conv_lds<1, 4>(s1, 1, 1, C, PS, zero, 1, 0, 1, 1, a.w[set + 3], C, 1, 1, wave, kFlatWaves, lane,
                    [&](int, int n, float v, int) { gate[n] = 1.f / (1.f + expf(-(v + a.b[set + 3][n]))); });
@@ -568,8 +539,8 @@ __device__ __forceinline__ void se_block(const FlatArgs& a, int set, int HW, int
     stamp();
     for (int e = tid; e < M * C; e += kFlatWaves * 64) {
         const int m = e / C, c = e - m * C;
-        const float v = pair_load(Y2, PS, m, c) * gate[c] + pair_load(X, PS, m, c);
-        pair_store(X, PS, m, c, v > 0.f ? v : 0.f);
+        const float v = pair_load(Y2 + (size_t)m * PS, c) * gate[c] + pair_load(X + (size_t)m * PS, c);
+        pair_store(X + (size_t)m * PS, c, v > 0.f ? v : 0.f);
     }
     __syncthreads();
 }
@@ -604,14 +575,14 @@ __global__ __launch_bounds__(kFlatWaves * 64) void dec_flatten_kernel(const Flat
     stamp();
     // conv21_10: 3x3 stride 2, no padding, 32 -> 64, ReLU
     conv_lds<1, 4>(Rin, kMapHW, kMapHW, 32, kPS32, zero, 2, 0, 3, 3, a.w[0], 64, 10, 10, wave, kFlatWaves, lane,
-                   [&](int m, int n, float v, int) { v += a.b[0][n]; pair_store(X10, ps_of(64), m, n, v > 0.f ? v : 0.f); });
+                   [&](int m, int n, float v, int) { v += a.b[0][n]; pair_store(X10 + (size_t)m * ps_of(64), n, v > 0.f ? v : 0.f); });
     __syncthreads();
     stamp();
     se_block(a, 1, 10, 64, X10, Y10a, Y10b, vec, zero, wave, lane, tid, stamp);     // X10 updated in place
     stamp();
     float* mid = a.mids ? a.mids + (size_t)map * (100 * 64 + 16 * 128 + 4 * 256) : nullptr;
     if (mid)
-        for (int e = tid; e < 100 * 64; e += kFlatWaves * 64) mid[e] = pair_load(X10, ps_of(64), e >> 6, e & 63);
+        for (int e = tid; e < 100 * 64; e += kFlatWaves * 64) mid[e] = pair_load(X10 + (size_t)(e >> 6) * ps_of(64), e & 63);
     // conv10_4: 3x3 stride 2, no padding, 64 -> 128, ReLU -- straight to global memory: the 4x4 and 2x2 levels and the two
     // linears are weight streams (15.6 of the network's 16.8 MB) and run as the column-split stages below
     float* x4 = a.x4 + (size_t)map * 16 * 128;
@@ -667,12 +638,7 @@ __global__ __launch_bounds__(kTailWaves * 64) void dec_tail_conv_kernel(const Ta
     const int C4 = C >> 2, per_map4 = HW2 * C4, ngr = nm * per_map4;
     auto put4 = [&](int ml, int q4, float4 v) {
         const int pix = q4 / C4, c = (q4 - pix * C4) * 4;
-        unsigned char* p = Xs + (size_t)(ml * HW2 + pix) * PS + (c >> 4) * 64 + ((c >> 3) & 1) * 16 + (c & 7) * 2;
-        const uint16_t h0 = f32_to_bf16(v.x), h1 = f32_to_bf16(v.y), h2 = f32_to_bf16(v.z), h3 = f32_to_bf16(v.w);
-        const uint16_t l0 = f32_to_bf16(v.x - bf16_to_f32(h0)), l1 = f32_to_bf16(v.y - bf16_to_f32(h1));
-        const uint16_t l2 = f32_to_bf16(v.z - bf16_to_f32(h2)), l3 = f32_to_bf16(v.w - bf16_to_f32(h3));
-        *reinterpret_cast<uint2*>(p) = make_uint2((unsigned)h0 | ((unsigned)h1 << 16), (unsigned)h2 | ((unsigned)h3 << 16));
-        *reinterpret_cast<uint2*>(p + 32) = make_uint2((unsigned)l0 | ((unsigned)l1 << 16), (unsigned)l2 | ((unsigned)l3 << 16));
+        pair_store4(Xs + (size_t)(ml * HW2 + pix) * PS, c, v);
     };
     const float4* in4 = reinterpret_cast<const float4*>(a.in);
     for (int e0 = tid; e0 < ngr; e0 += kStep * kStageUn) {
@@ -777,7 +743,7 @@ __global__ __launch_bounds__(kTailWaves * 64) void dec_tail_conv_kernel(const Ta
                     const unsigned char* ap = ok ? Xs + base[q] + toff : zero + h * 16;
                     const uint4 ah = *reinterpret_cast<const uint4*>(ap);
                     const uint4 al = *reinterpret_cast<const uint4*>(ok ? ap + 32 : ap);
-                    mfma3s(ah, al, bh[p], bl[p], acc[q], acc2[q]);
+                    mfma3(ah, al, bh[p], bl[p], acc[q], acc2[q]);
                 }
             }
             if (i + kTailPF < mine) load_b(step + kTailWaves * kTailPF, p);    // wave-uniform: the last round reloads nothing
@@ -874,7 +840,7 @@ __global__ __launch_bounds__(kBevWaves * 64) void dec_bev_update_kernel(const Be
     conv3x3_map32<2>(Bmap, zero, a.w0 + (size_t)c * 32 * (9 * 32 * 4), wave, kBevWaves, lane,
                      [&](int, int q, int i, float v) {
                          v += Gc[(int)((clsp[q] >> (4 * i)) & 15ull) * 32 + r];
-                         pair_store(Hmap, kPS32, ml + q * 32 + (i & 3) + 8 * (i >> 2), r, v > 0.f ? v : 0.f);
+                         pair_store(Hmap + (size_t)(ml + q * 32 + (i & 3) + 8 * (i >> 2)) * kPS32, r, v > 0.f ? v : 0.f);
                      });
     __syncthreads();
     // the chunk's partial output: all 448 rows of the padded map (the buffer is padded likewise), read back by one workgroup

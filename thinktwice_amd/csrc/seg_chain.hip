@@ -14,7 +14,7 @@
 //   SMALL  (R <= 4096)   conv_small_kernel on both: exact f32, K steps of 8 dealt over four partial sums added ((p0 + p1) + p2) + p3
 //   F32    (R < 65536)   conv_igemm_kernel<float> on both: exact f32, one chain over K
 //   X3     (else)        conv_igemm_kernel<float> on stage 1, the 256 x 32 bf16x3 tile of conv_igemm_glds.hip on stage 2: y split
-//                        into bf16 (hi, lo) = (rne(y), rne(y - hi)), per 16-wide k-step a_lo*b_hi, a_hi*b_lo, a_hi*b_hi
+//                        into bf16 (hi, lo) and multiplied in the one-accumulator order of bf16x3.h, per 16-wide k-step
 #include "conv_common.h"
 
 namespace tt {
@@ -40,22 +40,6 @@ struct SegChainArgs {
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 __device__ __forceinline__ float act01(float v, int act) { return act == TT_ACT_RELU ? (v > 0.f ? v : 0.f) : v; }
-
-// conv_igemm_glds.hip split_frag: eight f32 of one row -> their bf16 hi and lo halves
-__device__ __forceinline__ void split_x3(const uint4& r0, const uint4& r1, uint4& hi_out, uint4& lo_out) {
-    const float x[8] = {__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w),
-                        __uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z), __uint_as_float(r1.w)};
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        h[e] = pack_bf16x2(x[2 * e], x[2 * e + 1]);                       // round to nearest even
-        const float d0 = x[2 * e] - __uint_as_float(h[e] << 16);           // exact in f32
-        const float d1 = x[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u);
-        l[e] = pack_bf16x2(d0, d1);
-    }
-    hi_out = make_uint4(h[0], h[1], h[2], h[3]);
-    lo_out = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 __device__ __forceinline__ void zero16(f32x16& a) {
 #pragma unroll
@@ -169,10 +153,8 @@ __global__ __launch_bounds__(256) void seg_chain_kernel(const SegChainArgs p) {
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 uint4 ah, al;
-                split_x3(r0[ks], r1[ks], ah, al);
-                Mfma<uint16_t>::run(al, b2[ks], acc2);        // small terms first (conv_igemm_glds.hip)
-                Mfma<uint16_t>::run(ah, b2[4 + ks], acc2);
-                Mfma<uint16_t>::run(ah, b2[ks], acc2);
+                split8(r0[ks], r1[ks], ah, al);
+                mfma3(ah, al, b2[ks], b2[4 + ks], acc2);
             }
         } else {
             uint4 a[8];

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(kL2Waves * 64, 1) void sp_conv_runs_l2_kernel(const
     unsigned boff[KS];                              // byte offset of this lane's hi fragment of k-step ks inside a tap's block
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) boff[ks] = frag_off<ROWB>(lane & 31, 4u * ks + kb);
-    constexpr unsigned LO = 32u;                    // chunk ^ 2: the lo half of a pair-format fragment
+    constexpr unsigned LO = kPairLo;                // chunk ^ 2: the lo half of a pair-format fragment (bf16x3.h)
 
     // Every load of the main loop is UNCONDITIONAL -- a lane without work reads a harmless address and drops the value: a load inside
     // a divergent branch may or may not have been issued, so the compiler must assume it was not and waits for the newest loads
@@ -127,20 +127,9 @@ __global__ __launch_bounds__(kL2Waves * 64, 1) void sp_conv_runs_l2_kernel(const
             for (int ks = 0; ks < KS; ++ks) {
                 const uint4 bh = *reinterpret_cast<const uint4*>(wt + boff[ks]);
                 const uint4 bl = *reinterpret_cast<const uint4*>(wt + (boff[ks] ^ LO));
-                const float4 r0 = a[t % 3][ks][0], r1 = a[t % 3][ks][1];
-                const float x[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-                uint32_t h[4], l[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    h[q] = pack_bf16x2(x[2 * q], x[2 * q + 1]);                       // round to nearest even
-                    const float q0 = x[2 * q] - __uint_as_float(h[q] << 16);           // exact in f32
-                    const float q1 = x[2 * q + 1] - __uint_as_float(h[q] & 0xffff0000u);
-                    l[q] = pack_bf16x2(q0, q1);
-                }
-                const uint4 ah = uint4{h[0], h[1], h[2], h[3]}, al = uint4{l[0], l[1], l[2], l[3]};
-                Mfma<uint16_t>::run(al, bh, acc[0][0]);
-                Mfma<uint16_t>::run(ah, bl, acc[0][0]);
-                Mfma<uint16_t>::run(ah, bh, acc[0][0]);
+                uint4 ah, al;
+                split8(a[t % 3][ks][0], a[t % 3][ks][1], ah, al);
+                mfma3(ah, al, bh, bl, acc[0][0]);
             }
         }
         // the wave's own slab: neighbouring waves are mid-loop, nothing here synchronises with them

@@ -337,16 +337,16 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
                 u32x4 r0 = ra[cur][0], r1 = ra[cur][1];
                 asm volatile("" : "+v"(r0));
                 asm volatile("" : "+v"(r1));
+                // the split of bf16x3.h from its two halves, on scalars: through split8's arrays the 2 x 8 x 1 tile's schedule moves
                 const float x[8] = {__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z),
                                     __uint_as_float(r0.w), __uint_as_float(r1.x), __uint_as_float(r1.y),
                                     __uint_as_float(r1.z), __uint_as_float(r1.w)};
                 uint32_t h[4], l[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    h[e] = pack_bf16x2(x[2 * e], x[2 * e + 1]);                       // round to nearest even
-                    const float q0 = x[2 * e] - __uint_as_float(h[e] << 16);           // exact in f32
-                    const float q1 = x[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u);
-                    l[e] = pack_bf16x2(q0, q1);
+                    float t0, t1;
+                    split_hi(x[2 * e], x[2 * e + 1], h[e], t0, t1);
+                    l[e] = split_lo(x[2 * e], x[2 * e + 1], t0, t1);
                 }
                 uint4 ah = uint4{h[0], h[1], h[2], h[3]}, al = uint4{l[0], l[1], l[2], l[3]};
                 if (dbg_no_split) {
@@ -361,6 +361,7 @@ __global__ __launch_bounds__(WR * WC * 64, 1) void sp_conv_runs_kernel(const Con
                     asm volatile("" : "+v"(bh[j]));
                     asm volatile("" : "+v"(bl[j]));
                 }
+                // term-major over the column blocks; per accumulator the one-accumulator order of bf16x3.h
 #pragma unroll
                 for (int j = 0; j < NCB; ++j) Mfma<uint16_t>::run(al, __builtin_bit_cast(uint4, bh[j]), acc[j]);
 #pragma unroll

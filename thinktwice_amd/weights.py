@@ -50,7 +50,8 @@ def vec_of(dtype):
 def split_pairs_x3(w):
     """f32 weights [Cout, ..., K-contiguous] with K % 16 == 0 -> the same shape (f32-typed bit container) holding, per
     16 K elements, 64 B = [hi k0-7 | hi k8-15 | lo k0-7 | lo k8-15] in bf16 with hi = bf16(w), lo = bf16(w - hi)
-    (round to nearest even both): the B operand of conv_igemm_glds_kernel<..., X3>."""
+    (round to nearest even both): the B operand of conv_igemm_glds_kernel<..., X3>.  csrc/bf16x3.h is the device-side
+    statement of the same split and layout."""
     assert w.dtype == torch.float32 and w.is_contiguous()
     co = w.shape[0]
     k = w.numel() // co
@@ -72,7 +73,8 @@ def split_pairs_frag(w):
     operand straight from memory (csrc/dec_chain.hip, csrc/dec_spatial.hip): per (32-row block nb, 16-wide K step ks)
     2 KiB = [hi plane: lane 0..63 x 16 B | lo plane: lane x 16 B], lane = (k half h) * 32 + (row r), the 16 B being the
     8 bf16 of W[nb*32 + r][ks*16 + h*8 : +8].  A wave's fragment load is then ONE contiguous KiB (8 full cache lines)
-    instead of 64 rows x 16 B scattered over 64 lines.  Returned as an f32-typed bit container of N*K elements."""
+    instead of 64 rows x 16 B scattered over 64 lines.  Returned as an f32-typed bit container of N*K elements.  The
+    split is the one csrc/bf16x3.h states for the device (hi = rne(w), lo = rne(w - hi))."""
     assert w.dtype == torch.float32 and w.dim() == 2 and w.shape[0] % 32 == 0 and w.shape[1] % 16 == 0
     N, K = w.shape
     hi = w.to(torch.bfloat16)
