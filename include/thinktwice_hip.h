@@ -772,13 +772,27 @@ int tt_conv2d_wgrad(const float* x, int N, int H, int W, int Cin, int x_cstride,
                     int OW, int Cout, int dy_cstride, int dy_coff, int KH, int KW, int stride, int pad, int dil,
                     int cin_pad, int accumulate, float* dw, void* workspace, long long workspace_bytes, void* stream);
 /* Same contract in the forward's bf16x3 arithmetic (dy and x split into bf16 hi + lo, three MFMAs per product, f32
- * accumulation: ~2^-17 relative per product): layers with >= 128 channels on both sides run on an LDS-staged
- * v_mfma_f32_32x32x16_bf16 kernel (the contraction index -- the pixel -- is the slow index of both operands: tiles of 32
- * pixels are staged as they lie in memory and read column-wise); everything else falls through to tt_conv2d_wgrad's kernels.
- * Same workspace query, same determinism. */
+ * accumulation: ~2^-17 relative per product) on an LDS-staged v_mfma_f32_32x32x16_bf16 kernel (the contraction index -- the
+ * pixel -- is the slow index of both operands: tiles of 32 pixels are staged as they lie in memory and read column-wise).
+ * That kernel takes a layer with Cout >= 64 and Cin >= 64; Cout, Cin, x_cstride, x_coff, dy_cstride and dy_coff multiples of
+ * 4; x and dy 16-byte aligned; and output rows of OW >= 16 pixels -- where a 1 x 1 / stride 1 / pad 0 layer with OW < 128
+ * counts as regrouped into pseudo-rows of >= 128 pixels whenever its N * OH rows have a divisor that reaches them (a linear
+ * layer over rows, OW = 1, qualifies from 128 rows on).  Every other layer runs tt_conv2d_wgrad's kernels in exact f32: a
+ * routing decision, not an error.  Same workspace query (it is sized for tt_conv2d_wgrad's choice, and the row split of the
+ * LDS-staged kernel is clamped to the slices it holds), same determinism.  All of it is csrc/wgrad_choose.cpp. */
 int tt_conv2d_wgrad_x3(const float* x, int N, int H, int W, int Cin, int x_cstride, int x_coff, const float* dy, int OH,
                     int OW, int Cout, int dy_cstride, int dy_coff, int KH, int KW, int stride, int pad, int dil,
                     int cin_pad, int accumulate, float* dw, void* workspace, long long workspace_bytes, void* stream);
+/* Host only: which kernel tt_conv2d_wgrad (x3 = 0) / tt_conv2d_wgrad_x3 (x3 = 1) would run these arguments on.  Runs the
+ * validation and the dispatch of a launch and writes into `label` (label_bytes bytes, NUL-terminated)
+ *   "<kernel with its template arguments, as rocprofv3 prints it> grid <x> x <y> lds <dynamic bytes> reduce <slices>"
+ * followed, for a regrouped 1 x 1 layer, by " as N=.. OH=.. OW=.. H=.. W=.." (the geometry the kernel is launched with).
+ * Dereferences no pointer (null-ness and alignment are all it looks at) and touches no device; returns the non-zero code,
+ * with the error text, that the launch would return before launching. */
+int tt_conv2d_wgrad_plan(const float* x, int N, int H, int W, int Cin, int x_cstride, int x_coff, const float* dy, int OH,
+                         int OW, int Cout, int dy_cstride, int dy_coff, int KH, int KW, int stride, int pad, int dil,
+                         int cin_pad, int accumulate, float* dw, void* workspace, long long workspace_bytes, int x3,
+                         char* label, int label_bytes);
 /* Backward of tt_conv2d_fwd's fused epilogue  y = act(scale[c]*conv + shift[c] + res1 + res2)  from dy and the saved
  * output y (all [M][*] channel-last f32 with channel stride / offset):  g = dy * act'(.)  (TT_ACT_NONE / RELU / SIGMOID);
  * dconv = g * scale[c] (feeds tt_conv2d_wgrad and the dgrad convolution); dres / dres2 (optional): g added to
@@ -808,6 +822,10 @@ long long tt_gather_conv_wgrad_workspace_bytes(long long M, int Cout, int Cin, i
 int tt_gather_conv_wgrad(const float* x, int x_cstride, int Cin, const int* nbr, const int* m_dev, long long M, int taps,
                          const float* dy, int dy_cstride, int Cout, int cin_pad, int accumulate, float* dw, void* workspace,
                          long long workspace_bytes, void* stream);
+/* Host only: tt_conv2d_wgrad_plan for the gathered layer (x3 is accepted and changes nothing: one arithmetic, exact f32). */
+int tt_gather_conv_wgrad_plan(const float* x, int x_cstride, int Cin, const int* nbr, const int* m_dev, long long M, int taps,
+                              const float* dy, int dy_cstride, int Cout, int cin_pad, int accumulate, float* dw,
+                              void* workspace, long long workspace_bytes, int x3, char* label, int label_bytes);
 int tt_sp_inverse_rulebook(const int* nbr, const int* m_dev, long long M, int taps, int* inv_prefilled_minus1, void* stream);
 int tt_sp_from_dense(const float* gdense, const int* coords, const int* num_rows, long long max_rows, int C, int D, int H,
                      int W, float* grows, void* stream);

@@ -23,13 +23,18 @@ CASES = [
     (2, 24, 31, 32, 12, 3, 1, 1, 1),       # 32-channel wave tiles on both sides (segmentation head), Cout tail, odd width
     (2, 12, 16, 24, 256, 1, 1, 0, 1),      # narrow input, wide output
     (2, 12, 16, 200, 20, 3, 1, 1, 1),      # wide input, narrow output
-    # >= 128 channels on both sides: the LDS-staged bf16x3 kernel under x3 (128- / 256-channel workgroup tiles a side)
+    # wider layers under x3: the LDS-staged bf16x3 kernel's 128- / 256-channel workgroup tiles a side
     (2, 30, 40, 128, 512, 3, 2, 1, 1),     # stride 2, 256-wide dy tile x 128-wide x tile
     (2, 20, 70, 384, 128, 1, 1, 0, 1),     # 1x1, three 32-pixel segments per row with a tail, x tile 256 wide with a channel tail
     (2, 24, 24, 256, 128, 3, 1, 6, 6),     # dilation 6: most tap rows / pixels fall outside the image
     (3, 9, 33, 256, 512, 3, 1, 1, 1),      # 256 x 256 tiles, several tiles a side, rows split over workgroups
     (3840, 1, 1, 1544, 512, 1, 1, 0, 1),   # a linear layer over rows (OW = 1): 1x1 pixels regrouped into pseudo-rows
     (40, 8, 8, 128, 128, 3, 1, 1, 1),      # rows shorter than 16 pixels and not 1x1: stays on the f32 kernels under x3 too
+    # tiny 1x1 layers, regrouped under x3: 20 rows of 8 pixels have no divisor from 16 rows on but 20 itself (one pseudo-row of 160),
+    # 7 rows of 9 pixels would need 15 (not regrouped: f32 kernels), 32 rows of 16 pixels merge 8 at a time (4 pseudo-rows of 128)
+    (1, 20, 8, 64, 64, 1, 1, 0, 1),
+    (1, 7, 9, 64, 64, 1, 1, 0, 1),
+    (2, 16, 16, 64, 64, 1, 1, 0, 1),
 ]
 
 
@@ -44,8 +49,9 @@ def _ref(x, w, dy, stride, pad, dil):
 @pytest.mark.parametrize("x3", [False, True], ids=["f32", "bf16x3"])
 @pytest.mark.parametrize("case", CASES)
 def test_conv_wgrad_matches_autograd(case, x3):
-    """tt_conv2d_wgrad (exact f32 products) and tt_conv2d_wgrad_x3 (the forward's bf16x3 arithmetic: layers with >= 128
-    channels on both sides take the LDS-staged bf16-MFMA kernel, the rest falls through to the f32 kernels)."""
+    """tt_conv2d_wgrad (exact f32 products) and tt_conv2d_wgrad_x3 (the forward's bf16x3 arithmetic: layers with >= 64 channels
+    on both sides, channel counts / strides / offsets in multiples of 4 and rows of >= 16 pixels -- after the regrouping of a
+    1 x 1 layer -- take the LDS-staged bf16-MFMA kernel, the rest falls through to the f32 kernels: csrc/wgrad_choose.cpp)."""
     from thinktwice_amd import ops, weights
     N, H, W, Cin, Cout, k, stride, pad, dil = case
     g = torch.Generator().manual_seed(Cin * 7 + Cout + k)

@@ -16,6 +16,7 @@
 // gridDim.y row ranges ("splits") write their partial tiles to a workspace that a second kernel adds in split order:
 // deterministic, no atomics.
 #include "conv_lds_dma.h"
+#include "wgrad_choose.h"
 
 namespace tt {
 
@@ -27,7 +28,6 @@ struct WgradArgs {
     int OH, OW, Cout, dy_cstride, dy_coff;
     int KH, KW, stride, pad, dil, cin_p;
     int ci_tiles, rows_per_split;
-    int xcd_tiles;         // > 0: number of real tiles of an XCD-remapped grid (see the kernel); 0: identity mapping
 };
 
 // v if ok else 0, as a MULTIPLY on an always-executed load of a clamped (valid, finite) element: a select or a bit mask is
@@ -36,18 +36,56 @@ struct WgradArgs {
 // the MFMAs (measured on the 64 x 64 kernel: the conditional loads are FASTER there, 55 vs 36 TF/s, so it keeps them)
 __device__ __forceinline__ float masked(float v, bool ok) { return v * (ok ? 1.f : 0.f); }
 
+// The 64 x 64 workgroup-tile kernels add their four waves' tiles through LDS, in the fixed order wave 0 + 1 + 2 + 3: waves 1-3 park
+// their accumulators here (ends with a barrier), wave 0 adds them on its way to the workspace (store_slice's `parked`).
+typedef float ParkedTiles[3][64 * 64];
+__device__ __forceinline__ void park_waves(const f32x16 (&acc)[2][2], ParkedTiles& red, int wave, int c, int k) {
+    if (wave > 0) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int row = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * k;
+                    red[wave - 1][row * 64 + 32 * j + c] = acc[i][j][e];
+                }
+    }
+    __syncthreads();
+}
+
+// Epilogue of every weight-gradient kernel: a wave's BI x BJ accumulator blocks, whose corner is (output channel co0, input channel
+// ci0) of filter tap `tap`, go into one partial-sum slice [Cout][taps][cin_p] of the workspace; padding channels are written as 0.
+// C/D map of the 32x32 MFMA: col = c = lane & 31 (input channel), row = (e & 3) + 8 * (e >> 2) + 4 * k, k = lane >> 5 (output channel)
+template <int BI, int BJ>
+__device__ __forceinline__ void store_slice(const f32x16 (&acc)[BI][BJ], float* slice, int co0, int ci0, int tap, int taps,
+                                            int Cout, int Cin, int cin_p, int c, int k, const ParkedTiles* parked = nullptr) {
+#pragma unroll
+    for (int i = 0; i < BI; ++i)
+#pragma unroll
+        for (int j = 0; j < BJ; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * k;
+                const int col = 32 * j + c;
+                float v = acc[i][j][e];
+                if (parked) {
+#pragma unroll
+                    for (int w = 0; w < 3; ++w) v += (*parked)[w][row * 64 + col];
+                }
+                if (co0 + row < Cout && ci0 + col < cin_p)
+                    slice[((long long)(co0 + row) * taps + tap) * cin_p + ci0 + col] = (ci0 + col < Cin) ? v : 0.f;
+            }
+}
+
 constexpr int kWgUnroll = 4;       // pixel pairs in flight per wave (each: 2 + 2 dword loads, 4 MFMAs)
 
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
-    __shared__ float red[3][64 * 64];
+    __shared__ ParkedTiles red;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, k = lane >> 5;                 // channel within a 32-block, pixel of the pair
     const int taps = a.KH * a.KW;
     int t = blockIdx.x;
-    if (a.xcd_tiles) {      // workgroup i runs on XCD i % 8: give every XCD a contiguous run of tiles, so that the taps of one
-        t = (t & 7) * (gridDim.x >> 3) + (t >> 3);      // (co, ci) tile -- which read the same dy rows and shifted x rows --
-        if (t >= a.xcd_tiles) return;                   // share that XCD's L2 (the grid is padded to a multiple of 8)
-    }
     const int tap = t % taps;
     t /= taps;
     const int ci0 = (t % a.ci_tiles) * 64, co0 = (t / a.ci_tiles) * 64;
@@ -95,39 +133,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
         }
     }
 
-    // add the four waves' tiles (fixed order: wave 0 + 1 + 2 + 3), then store this split's partial tile
-    // C/D map of the 32x32 MFMA: col = lane & 31 (input channel), row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5) (output channel)
-    if (wave > 0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int row = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * k;
-                    red[wave - 1][row * 64 + 32 * j + c] = acc[i][j][e];
-                }
-    }
-    __syncthreads();
+    // add the four waves' tiles, then store this split's partial tile
+    park_waves(acc, red, wave, c, k);
     if (wave > 0) return;
-    float* ws = a.ws + (long long)blockIdx.y * a.Cout * taps * a.cin_p;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * k;
-                const int col = 32 * j + c;
-                float v = acc[i][j][e];
-#pragma unroll
-                for (int w = 0; w < 3; ++w) v += red[w][row * 64 + col];
-                if (co0 + row < a.Cout && ci0 + col < a.cin_p)
-                    ws[((long long)(co0 + row) * taps + tap) * a.cin_p + ci0 + col] = (ci0 + col < a.Cin) ? v : 0.f;
-            }
+    store_slice(acc, a.ws + (long long)blockIdx.y * a.Cout * taps * a.cin_p, co0, ci0, tap, taps, a.Cout, a.Cin, a.cin_p, c, k, &red);
 }
 
-// Wide variant for layers with >= 128 channels on a side: every WAVE owns a (32 BI) x (32 BJ) tile of dW[.][tap][.] (up to
+// Per-wave-tile variant for every layer whose tile (wgrad_blocks) is not 2 x 2 -- a side with >= 128 channels or with <= 32:
+// every WAVE owns a (32 BI) x (32 BJ) tile of dW[.][tap][.] (up to
 // 128 x 128 = 256 accumulator registers) over its share of the rows, so a pixel pair costs BI + BJ dword loads per BI * BJ
 // MFMAs (0.5 per MFMA at 4 x 4, against 1.0 in the 64 x 64 kernel above: that kernel is bound by its operand loads, not by the
 // f32 MFMA pipe).  No cross-wave reduction in the workgroup: each wave stores its partial tile as its own split slice
@@ -210,18 +223,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_wide_kernel(const WgradArgs a)
             }
         }
     }
-    float* ws = a.ws + ((long long)blockIdx.y * 4 + wave) * a.Cout * taps * a.cin_p;
-#pragma unroll
-    for (int i = 0; i < BI; ++i)
-#pragma unroll
-        for (int j = 0; j < BJ; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * k;
-                const int col = 32 * j + c;
-                if (co0 + row < a.Cout && ci0 + col < a.cin_p)
-                    ws[((long long)(co0 + row) * taps + tap) * a.cin_p + ci0 + col] = (ci0 + col < a.Cin) ? acc[i][j][e] : 0.f;
-            }
+    store_slice(acc, a.ws + ((long long)blockIdx.y * 4 + wave) * a.Cout * taps * a.cin_p, co0, ci0, tap, taps, a.Cout, a.Cin, a.cin_p,
+                c, k);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -393,19 +396,8 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_lds_kernel(const WgradArgs 
         buf ^= 1;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // C/D map of the 32x32 MFMA: col = lane & 31 (input channel), row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5) (output channel)
-    float* ws = a.ws + (long long)blockIdx.y * a.Cout * taps * a.cin_p;
-#pragma unroll
-    for (int i = 0; i < BI; ++i)
-#pragma unroll
-        for (int j = 0; j < BJ; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = co0 + wy * 32 * BI + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * kg;
-                const int col = ci0 + wx * 32 * BJ + 32 * j + c;
-                if (row < a.Cout && col < a.cin_p)
-                    ws[((long long)row * taps + tap) * a.cin_p + col] = (col < a.Cin) ? acc[i][j][e] : 0.f;
-            }
+    store_slice(acc, a.ws + (long long)blockIdx.y * a.Cout * taps * a.cin_p, co0 + wy * 32 * BI, ci0 + wx * 32 * BJ, tap, taps, a.Cout,
+                a.Cin, a.cin_p, c, kg);
 #endif
 }
 
@@ -438,20 +430,13 @@ struct GatherWgradArgs {
     const float* x; const float* dy; const int* nbr; const int* m_dev; float* ws;
     long long M;
     int Cin, x_cstride, Cout, dy_cstride, taps, cin_p, ci_tiles;
-    long long pairs_per_split;
-    int xcd_tiles;
-    int skip_empty;        // per-wave-tile kernel: skip row pairs without an input at the tap (TT_GATHER_WGRAD_SKIP=0: never)
 };
 
 __global__ __launch_bounds__(256) void gather_wgrad_kernel(const GatherWgradArgs a) {
-    __shared__ float red[3][64 * 64];
+    __shared__ ParkedTiles red;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, k = lane >> 5;
     int t = blockIdx.x;
-    if (a.xcd_tiles) {      // XCD-contiguous tile order, as in conv_wgrad_kernel
-        t = (t & 7) * (gridDim.x >> 3) + (t >> 3);
-        if (t >= a.xcd_tiles) return;
-    }
     const int tap = t % a.taps;
     t /= a.taps;
     const int ci0 = (t % a.ci_tiles) * 64, co0 = (t / a.ci_tiles) * 64;
@@ -488,34 +473,9 @@ __global__ __launch_bounds__(256) void gather_wgrad_kernel(const GatherWgradArgs
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][i], bv[u][j], acc[i][j], 0, 0, 0);
     }
-    if (wave > 0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int row = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * k;
-                    red[wave - 1][row * 64 + 32 * j + c] = acc[i][j][e];
-                }
-    }
-    __syncthreads();
+    park_waves(acc, red, wave, c, k);
     if (wave > 0) return;
-    float* ws = a.ws + (long long)blockIdx.y * a.Cout * a.taps * a.cin_p;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * k;
-                const int col = 32 * j + c;
-                float v = acc[i][j][e];
-#pragma unroll
-                for (int w = 0; w < 3; ++w) v += red[w][row * 64 + col];
-                if (co0 + row < a.Cout && ci0 + col < a.cin_p)
-                    ws[((long long)(co0 + row) * a.taps + tap) * a.cin_p + ci0 + col] = (ci0 + col < a.Cin) ? v : 0.f;
-            }
+    store_slice(acc, a.ws + (long long)blockIdx.y * a.Cout * a.taps * a.cin_p, co0, ci0, tap, a.taps, a.Cout, a.Cin, a.cin_p, c, k, &red);
 }
 
 // Transposed rulebook of a strided sparse convolution: inv[j][t] = the output row m with nbr[m][t] == j (at most one: the
@@ -705,7 +665,7 @@ __global__ __launch_bounds__(256) void gather_wgrad_wide_kernel(const GatherWgra
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const bool x_ok = m_ok[u] && jr[u] >= 0;
-            any[u] = !a.skip_empty || __builtin_amdgcn_ballot_w64(x_ok) != 0;
+            any[u] = __builtin_amdgcn_ballot_w64(x_ok) != 0;
             if (any[u]) {
                 const float* dp = a.dy + mc[u] * a.dy_cstride;
                 const float* xp = a.x + (long long)(x_ok ? jr[u] : 0) * a.x_cstride;
@@ -725,18 +685,8 @@ __global__ __launch_bounds__(256) void gather_wgrad_wide_kernel(const GatherWgra
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][i], bv[u][j], acc[i][j], 0, 0, 0);
             }
     }
-    float* ws = a.ws + ((long long)blockIdx.y * 4 + wave) * a.Cout * a.taps * a.cin_p;
-#pragma unroll
-    for (int i = 0; i < BI; ++i)
-#pragma unroll
-        for (int j = 0; j < BJ; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = 32 * i + (e & 3) + 8 * (e >> 2) + 4 * k;
-                const int col = 32 * j + c;
-                if (co0 + row < a.Cout && ci0 + col < a.cin_p)
-                    ws[((long long)(co0 + row) * a.taps + tap) * a.cin_p + ci0 + col] = (ci0 + col < a.Cin) ? acc[i][j][e] : 0.f;
-            }
+    store_slice(acc, a.ws + ((long long)blockIdx.y * 4 + wave) * a.Cout * a.taps * a.cin_p, co0, ci0, tap, a.taps, a.Cout, a.Cin, a.cin_p,
+                c, k);
 }
 
 // per-channel sums of the workgroups' partials [blocks][2][C], in a fixed order (deterministic): 16 channels per workgroup,
@@ -769,36 +719,35 @@ __global__ __launch_bounds__(256) void conv_epilogue_bwd_finish_kernel(const flo
     }
 }
 
-// TT_WGRAD_XCD=1: XCD-contiguous workgroup -> tile order.  Measured (MI355X, 3x3 layers of the camera trunk at batch 8): no gain
-// where the grid is large (256 -> 256: 65.0 vs 63.8 TF/s) and a loss where it is small (64 -> 64: 36.3 vs 55.1 TF/s; a
-// training iteration 1701 vs 1368 ms), so the default is the identity mapping.
-// tile of one wave in 32-channel blocks per side: 4 (128 channels) where the side has >= 128, 1 where it has <= 32 (the
-// segmentation / depth heads, the stem's 3 input channels: a 64-wide tile would multiply mostly zeros), else 2.  2 x 2 is the
-// 64 x 64 workgroup-tile kernel, everything else the per-wave-tile kernel.  TT_WGRAD_WIDE=0: always 2 x 2.
-static void wgrad_blocks(int Cout, int Cin, int* bi, int* bj) {
-    *bi = Cout >= 128 ? 4 : (Cout <= 32 ? 1 : 2);
-    *bj = Cin >= 128 ? 4 : (Cin <= 32 ? 1 : 2);
+// ---- a choice (wgrad_choose.cpp) -> its template instantiation: one (bi, bj) table per family
+#define TT_WGRAD_TILE(K, BI_, BJ_) case BI_ * 8 + BJ_: return K<BI_, BJ_>;
+// the per-wave-tile family, dense and gathered: every tile of wgrad_blocks but 2 x 2 (the 64 x 64 workgroup-tile kernels)
+#define TT_WGRAD_WAVE_TABLE(K)                                                                                                  \
+    switch (bi * 8 + bj) {                                                                                                      \
+        TT_WGRAD_TILE(K, 4, 4) TT_WGRAD_TILE(K, 4, 2) TT_WGRAD_TILE(K, 2, 4) TT_WGRAD_TILE(K, 4, 1) TT_WGRAD_TILE(K, 1, 4)      \
+        TT_WGRAD_TILE(K, 2, 1) TT_WGRAD_TILE(K, 1, 2) TT_WGRAD_TILE(K, 1, 1)                                                    \
+        default: return nullptr;                                                                                                \
+    }
+typedef void (*WgradKernel)(const WgradArgs);
+typedef void (*WgradLdsKernel)(const WgradArgs, const float*);
+typedef void (*GatherWgradKernel)(const GatherWgradArgs);
+static WgradKernel wgrad_wave_kernel(int bi, int bj) { TT_WGRAD_WAVE_TABLE(conv_wgrad_wide_kernel) }
+static GatherWgradKernel gather_wgrad_wave_kernel(int bi, int bj) { TT_WGRAD_WAVE_TABLE(gather_wgrad_wide_kernel) }
+static WgradLdsKernel wgrad_lds_kernel(int bi, int bj) {
+    switch (bi * 8 + bj) {
+        TT_WGRAD_TILE(conv_wgrad_lds_kernel, 4, 4) TT_WGRAD_TILE(conv_wgrad_lds_kernel, 4, 2) TT_WGRAD_TILE(conv_wgrad_lds_kernel, 4, 1)
+        TT_WGRAD_TILE(conv_wgrad_lds_kernel, 2, 4) TT_WGRAD_TILE(conv_wgrad_lds_kernel, 2, 2) TT_WGRAD_TILE(conv_wgrad_lds_kernel, 2, 1)
+        TT_WGRAD_TILE(conv_wgrad_lds_kernel, 1, 4) TT_WGRAD_TILE(conv_wgrad_lds_kernel, 1, 2) TT_WGRAD_TILE(conv_wgrad_lds_kernel, 1, 1)
+        default: return nullptr;
+    }
 }
+#undef TT_WGRAD_WAVE_TABLE
+#undef TT_WGRAD_TILE
 
-static int wgrad_splits(int N, int OH, int Cout, int Cin, int taps) {
-    int bi, bj;
-    wgrad_blocks(Cout, Cin, &bi, &bj);
-    const long long tiles = (long long)div_up(Cout, 32 * bi) * div_up(Cin, 32 * bj) * taps;
-    // aim at >= 4 workgroups per CU, 2 for the 128-wide wave tiles (one wave per SIMD each, and every split costs four
-    // partial slices)
-    long long s = ((bi * bj >= 8 ? 2LL : 4LL) * kNumCU + tiles - 1) / tiles;
-    const int rows = N * OH;
-    if (s > rows / 4) s = rows / 4;                          // every wave of a workgroup gets at least one row
-    if (s < 1) s = 1;
-    if (s > 1024) s = 1024;
-    return (int)s;
-}
-
-// partial-sum slices in the workspace: one per split, x 4 in the wide kernel (one per wave)
-static int wgrad_slices(int N, int OH, int Cout, int Cin, int taps) {
-    int bi, bj;
-    wgrad_blocks(Cout, Cin, &bi, &bj);
-    return wgrad_splits(N, OH, Cout, Cin, taps) * ((bi == 2 && bj == 2) ? 1 : 4);
+// the ordered sum of the workspace's slices into dw, behind every weight-gradient kernel
+static void wgrad_reduce(const void* workspace, long long n, int slices, int accumulate, float* dw, hipStream_t st) {
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)div_up(n, 32)), dim3(256), 0, st, (const float*)workspace, n, slices,
+                       accumulate, dw);
 }
 
 }  // namespace tt
@@ -806,109 +755,57 @@ static int wgrad_slices(int N, int OH, int Cout, int Cin, int taps) {
 using namespace tt;
 
 extern "C" long long tt_conv2d_wgrad_workspace_bytes(int N, int OH, int Cout, int Cin, int cin_pad, int KH, int KW) {
-    return (long long)wgrad_slices(N, OH, Cout, Cin, KH * KW) * Cout * KH * KW * cin_pad * 4;
+    return (long long)wgrad_workspace_slices(N, OH, Cout, Cin, KH * KW) * Cout * KH * KW * cin_pad * 4;
+}
+
+// Validate -> choose: everything a dense launch does before it touches the device (tt_conv2d_wgrad_plan stops here).
+static int wgrad_prepare(const float* x, int N, int H, int W, int Cin, int x_cstride, int x_coff, const float* dy, int OH, int OW,
+                         int Cout, int dy_cstride, int dy_coff, int KH, int KW, int stride, int pad, int dil, int cin_pad,
+                         const float* dw, void* workspace, long long workspace_bytes, bool x3, WgradArgs& a, WgradChoice& c) {
+    TT_REQUIRE(x && dy && dw && workspace && N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && OH > 0 && OW > 0 &&
+                   KH > 0 && KW > 0 && stride > 0 && dil > 0 && cin_pad >= Cin,
+               "tt_conv2d_wgrad: bad argument");
+    TT_REQUIRE(x_cstride >= x_coff + Cin && dy_cstride >= dy_coff + Cout, "tt_conv2d_wgrad: channel window outside the row");
+    TT_REQUIRE(workspace_bytes >= tt_conv2d_wgrad_workspace_bytes(N, OH, Cout, Cin, cin_pad, KH, KW),
+               "tt_conv2d_wgrad: workspace too small");
+    WgradLayer l;
+    l.x = x; l.dy = dy; l.N = N; l.H = H; l.W = W; l.Cin = Cin; l.x_cstride = x_cstride; l.x_coff = x_coff;
+    l.OH = OH; l.OW = OW; l.Cout = Cout; l.dy_cstride = dy_cstride; l.dy_coff = dy_coff;
+    l.KH = KH; l.KW = KW; l.stride = stride; l.pad = pad; l.cin_pad = cin_pad; l.x3 = x3;
+    c = wgrad_choose(l);
+    a.x = x; a.dy = dy; a.ws = (float*)workspace;
+    a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = Cin; a.x_cstride = x_cstride; a.x_coff = x_coff;
+    a.OH = c.OH; a.OW = c.OW; a.Cout = Cout; a.dy_cstride = dy_cstride; a.dy_coff = dy_coff;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dil; a.cin_p = cin_pad;
+    a.ci_tiles = c.ci_tiles; a.rows_per_split = c.rows_per_split;
+    return 0;
 }
 
 static int wgrad_run(const float* x, int N, int H, int W, int Cin, int x_cstride, int x_coff, const float* dy,
                      int OH, int OW, int Cout, int dy_cstride, int dy_coff, int KH, int KW, int stride, int pad,
                      int dil, int cin_pad, int accumulate, float* dw, void* workspace, long long workspace_bytes,
                      void* stream, bool x3) {
-    TT_REQUIRE(x && dy && dw && workspace && N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && OH > 0 && OW > 0 &&
-                   KH > 0 && KW > 0 && stride > 0 && dil > 0 && cin_pad >= Cin,
-               "tt_conv2d_wgrad: bad argument");
-    TT_REQUIRE(x_cstride >= x_coff + Cin && dy_cstride >= dy_coff + Cout, "tt_conv2d_wgrad: channel window outside the row");
-    const int taps = KH * KW;
-    const int splits = wgrad_splits(N, OH, Cout, Cin, taps);
-    TT_REQUIRE(workspace_bytes >= tt_conv2d_wgrad_workspace_bytes(N, OH, Cout, Cin, cin_pad, KH, KW),
-               "tt_conv2d_wgrad: workspace too small");
     WgradArgs a;
-    a.x = x; a.dy = dy; a.ws = (float*)workspace;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.x_cstride = x_cstride; a.x_coff = x_coff;
-    a.OH = OH; a.OW = OW; a.Cout = Cout; a.dy_cstride = dy_cstride; a.dy_coff = dy_coff;
-    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dil; a.cin_p = cin_pad;
+    WgradChoice c;
+    if (int rc = wgrad_prepare(x, N, H, W, Cin, x_cstride, x_coff, dy, OH, OW, Cout, dy_cstride, dy_coff, KH, KW, stride, pad, dil,
+                               cin_pad, dw, workspace, workspace_bytes, x3, a, c))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    // >= 64 channels on both sides: the LDS-staged bf16x3 kernel (iteration 962 -> 820 ms against the f32-MFMA wave-tile form)
-    if (x3 && Cout >= 64 && Cin >= 64 && Cout % 4 == 0 && Cin % 4 == 0 && x_cstride % 4 == 0 && x_coff % 4 == 0 &&
-        dy_cstride % 4 == 0 && dy_coff % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0) {
-        // the kernel walks image rows in 32-pixel segments: a 1x1 / stride-1 / unpadded layer (linear layers over rows: OW = 1)
-        // is the same sum over ANY regrouping of its pixels, so short rows are merged into pseudo-rows of >= 128 pixels;
-        // other layers with rows shorter than 16 pixels (the 1 x 9 grouped deformable-conv GEMM) keep the f32 kernels
-        WgradArgs al = a;
-        if (KH == 1 && KW == 1 && stride == 1 && pad == 0 && OW < 128) {
-            const long long prow = (long long)N * OH;
-            long long m = (128 + OW - 1) / OW;
-            while (m < prow && prow % m) ++m;
-            if (m <= prow && prow % m == 0) {
-                al.N = 1;
-                al.OW = al.W = (int)(OW * m);
-                al.OH = al.H = (int)(prow / m);
-            }
-        }
-        const int cap = wgrad_slices(N, OH, Cout, Cin, taps);         // partial-sum slices the caller's workspace holds
-        if (al.OW >= 16) {
-            const float* zp = static_cast<const float*>(zero_page("conv_wgrad_lds_kernel"));
-            if (!zp) return -1;
-            WgradArgs& a = al;      // (shadows the caller's view for this launch)
-            const int N = a.N, OH = a.OH;
-            const int BI = Cout >= 256 ? 4 : (Cout >= 128 ? 2 : 1), BJ = Cin >= 256 ? 4 : (Cin >= 128 ? 2 : 1);
-            a.ci_tiles = div_up(cin_pad, 64 * BJ);
-            const long long tiles = (long long)div_up(Cout, 64 * BI) * a.ci_tiles * taps;
-            const int rows = N * OH;
-            const long long per_cu = BI * BJ >= 16 ? 2 : (BI * BJ >= 4 ? 3 : 4);     // resident workgroups (LDS) x ~1.5 rounds
-            long long sp = (per_cu * kNumCU + tiles - 1) / tiles;
-            if (sp > cap) sp = cap;
-            if (sp > rows) sp = rows;
-            if (sp < 1) sp = 1;
-            a.rows_per_split = div_up(rows, (int)sp);
-            const int nsplit = div_up(rows, a.rows_per_split);
-            a.xcd_tiles = 0;
-            const dim3 grid((unsigned)tiles, (unsigned)nsplit);
-            const size_t smem = (size_t)2 * 32 * (64 * BI + 64 * BJ) * 4;
-            void (*kern)(const WgradArgs, const float*);
-            switch (BI * 8 + BJ) {
-                case 4 * 8 + 4: kern = conv_wgrad_lds_kernel<4, 4>; break;
-                case 4 * 8 + 2: kern = conv_wgrad_lds_kernel<4, 2>; break;
-                case 4 * 8 + 1: kern = conv_wgrad_lds_kernel<4, 1>; break;
-                case 2 * 8 + 4: kern = conv_wgrad_lds_kernel<2, 4>; break;
-                case 2 * 8 + 2: kern = conv_wgrad_lds_kernel<2, 2>; break;
-                case 2 * 8 + 1: kern = conv_wgrad_lds_kernel<2, 1>; break;
-                case 1 * 8 + 4: kern = conv_wgrad_lds_kernel<1, 4>; break;
-                case 1 * 8 + 2: kern = conv_wgrad_lds_kernel<1, 2>; break;
-                default: kern = conv_wgrad_lds_kernel<1, 1>; break;
-            }
-            if (lds_opt_in(reinterpret_cast<const void*>(kern), smem, "conv_wgrad_lds_kernel")) return -1;
-            hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, a, zp);
-            const long long n = (long long)Cout * taps * cin_pad;
-            hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)div_up(n, 32)), dim3(256), 0, st, (const float*)workspace,
-                               n, nsplit, accumulate, dw);
-            return check_launch("tt_conv2d_wgrad");
-        }
-    }
-    int bi, bj;
-    wgrad_blocks(Cout, Cin, &bi, &bj);
-    a.ci_tiles = div_up(cin_pad, 32 * bj);
-    a.rows_per_split = div_up(N * OH, splits);
-    const unsigned tiles = (unsigned)(div_up(Cout, 32 * bi) * a.ci_tiles * taps);
-    int slices = splits;
-    if (bi == 2 && bj == 2) {
-        // (an XCD-contiguous tile order measured slower here: 36 vs 55 TF/s on 64 -> 64; identity mapping)
-        a.xcd_tiles = 0;
-        hipLaunchKernelGGL(conv_wgrad_kernel, dim3(tiles, (unsigned)splits), dim3(256), 0, st, a);
+    const dim3 grid((unsigned)c.tiles, (unsigned)c.splits);
+    if (c.family == WGRAD_LDS) {
+        const float* zp = static_cast<const float*>(zero_page("conv_wgrad_lds_kernel"));
+        if (!zp) return -1;
+        const WgradLdsKernel kern = wgrad_lds_kernel(c.bi, c.bj);
+        if (lds_opt_in(reinterpret_cast<const void*>(kern), c.lds_bytes, "conv_wgrad_lds_kernel")) return -1;
+        hipLaunchKernelGGL(kern, grid, dim3(256), c.lds_bytes, st, a, zp);
+    } else if (c.family == WGRAD_TILE64) {
+        hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, st, a);
     } else {
-        a.xcd_tiles = 0;
-        slices = splits * 4;
-        const dim3 grid(tiles, (unsigned)splits);
-        switch (bi * 8 + bj) {
-#define TT_WG(BI_, BJ_) \
-    case BI_ * 8 + BJ_: hipLaunchKernelGGL((conv_wgrad_wide_kernel<BI_, BJ_>), grid, dim3(256), 0, st, a); break;
-            TT_WG(4, 4) TT_WG(4, 2) TT_WG(2, 4) TT_WG(4, 1) TT_WG(1, 4) TT_WG(2, 1) TT_WG(1, 2) TT_WG(1, 1)
-#undef TT_WG
-            default: TT_REQUIRE(false, "tt_conv2d_wgrad: no kernel for wave tile %d x %d", bi, bj);
-        }
+        const WgradKernel kern = wgrad_wave_kernel(c.bi, c.bj);
+        TT_REQUIRE(kern, "tt_conv2d_wgrad: no kernel for wave tile %d x %d", c.bi, c.bj);
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, a);
     }
-    const long long n = (long long)Cout * taps * cin_pad;
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)div_up(n, 32)), dim3(256), 0, st, (const float*)workspace, n,
-                       slices, accumulate, dw);
+    wgrad_reduce(workspace, (long long)Cout * KH * KW * cin_pad, c.slices, accumulate, dw, st);
     return check_launch("tt_conv2d_wgrad");
 }
 
@@ -926,6 +823,21 @@ extern "C" int tt_conv2d_wgrad_x3(const float* x, int N, int H, int W, int Cin, 
                                   long long workspace_bytes, void* stream) {
     return wgrad_run(x, N, H, W, Cin, x_cstride, x_coff, dy, OH, OW, Cout, dy_cstride, dy_coff, KH, KW, stride, pad, dil,
                      cin_pad, accumulate, dw, workspace, workspace_bytes, stream, true);
+}
+
+extern "C" int tt_conv2d_wgrad_plan(const float* x, int N, int H, int W, int Cin, int x_cstride, int x_coff, const float* dy,
+                                    int OH, int OW, int Cout, int dy_cstride, int dy_coff, int KH, int KW, int stride, int pad,
+                                    int dil, int cin_pad, int accumulate, float* dw, void* workspace, long long workspace_bytes,
+                                    int x3, char* label, int label_bytes) {
+    (void)accumulate;
+    WgradArgs a;
+    WgradChoice c;
+    if (int rc = wgrad_prepare(x, N, H, W, Cin, x_cstride, x_coff, dy, OH, OW, Cout, dy_cstride, dy_coff, KH, KW, stride, pad, dil,
+                               cin_pad, dw, workspace, workspace_bytes, x3 != 0, a, c))
+        return rc;
+    TT_REQUIRE(label && label_bytes > 0, "tt_conv2d_wgrad_plan: no room for the label");
+    wgrad_label(c, false, label, (size_t)label_bytes);
+    return 0;
 }
 
 extern "C" long long tt_conv_epilogue_bwd_workspace_bytes(int C) { return (long long)kEpiBlocks * 2 * C * 4; }
@@ -959,63 +871,60 @@ extern "C" int tt_conv_epilogue_bwd(const float* dy, int dy_cstride, int dy_coff
     return check_launch("tt_conv_epilogue_bwd");
 }
 
-// splits of the live rows (and, in the per-wave-tile kernel, four partial slices per split)
-static int gather_wgrad_splits(long long M, int Cout, int Cin, int cin_pad, int taps, int* slices) {
-    int bi, bj;
-    wgrad_blocks(Cout, Cin, &bi, &bj);
-    const long long tiles = (long long)div_up(Cout, 32 * bi) * div_up(cin_pad, 32 * bj) * taps;
-    long long s = ((bi * bj >= 8 ? 2LL : 4LL) * kNumCU + tiles - 1) / tiles;
-    if (s > (M + 63) / 64) s = (M + 63) / 64;
-    if (s < 1) s = 1;
-    if (s > 1024) s = 1024;
-    *slices = (int)s * ((bi == 2 && bj == 2) ? 1 : 4);
-    return (int)s;
+extern "C" long long tt_gather_conv_wgrad_workspace_bytes(long long M, int Cout, int Cin, int cin_pad, int taps) {
+    return (long long)gather_wgrad_choose(M, Cout, Cin, cin_pad, taps).slices * Cout * taps * cin_pad * 4;
 }
 
-extern "C" long long tt_gather_conv_wgrad_workspace_bytes(long long M, int Cout, int Cin, int cin_pad, int taps) {
-    int slices;
-    gather_wgrad_splits(M, Cout, Cin, cin_pad, taps, &slices);
-    return (long long)slices * Cout * taps * cin_pad * 4;
+// Validate -> choose, as wgrad_prepare (tt_gather_conv_wgrad_plan stops here).
+static int gather_wgrad_prepare(const float* x, int x_cstride, int Cin, const int* nbr, const int* m_dev, long long M, int taps,
+                                const float* dy, int dy_cstride, int Cout, int cin_pad, const float* dw, void* workspace,
+                                long long workspace_bytes, GatherWgradArgs& a, WgradChoice& c) {
+    TT_REQUIRE(x && nbr && dy && dw && workspace && M > 0 && taps > 0 && Cin > 0 && Cout > 0 && cin_pad >= Cin,
+               "tt_gather_conv_wgrad: bad argument");
+    TT_REQUIRE(workspace_bytes >= tt_gather_conv_wgrad_workspace_bytes(M, Cout, Cin, cin_pad, taps),
+               "tt_gather_conv_wgrad: workspace too small");
+    c = gather_wgrad_choose(M, Cout, Cin, cin_pad, taps);
+    a.x = x; a.dy = dy; a.nbr = nbr; a.m_dev = m_dev; a.ws = (float*)workspace;
+    a.M = M; a.Cin = Cin; a.x_cstride = x_cstride; a.Cout = Cout; a.dy_cstride = dy_cstride; a.taps = taps;
+    a.cin_p = cin_pad; a.ci_tiles = c.ci_tiles;
+    return 0;
 }
 
 extern "C" int tt_gather_conv_wgrad(const float* x, int x_cstride, int Cin, const int* nbr, const int* m_dev, long long M,
                                     int taps, const float* dy, int dy_cstride, int Cout, int cin_pad, int accumulate,
                                     float* dw, void* workspace, long long workspace_bytes, void* stream) {
-    TT_REQUIRE(x && nbr && dy && dw && workspace && M > 0 && taps > 0 && Cin > 0 && Cout > 0 && cin_pad >= Cin,
-               "tt_gather_conv_wgrad: bad argument");
-    const long long need = tt_gather_conv_wgrad_workspace_bytes(M, Cout, Cin, cin_pad, taps);
-    TT_REQUIRE(workspace_bytes >= need, "tt_gather_conv_wgrad: workspace too small");
-    const long long n = (long long)Cout * taps * cin_pad;
-    int slices, bi, bj;
-    const int splits = gather_wgrad_splits(M, Cout, Cin, cin_pad, taps, &slices);
-    wgrad_blocks(Cout, Cin, &bi, &bj);
     GatherWgradArgs a;
-    a.x = x; a.dy = dy; a.nbr = nbr; a.m_dev = m_dev; a.ws = (float*)workspace;
-    a.M = M; a.Cin = Cin; a.x_cstride = x_cstride; a.Cout = Cout; a.dy_cstride = dy_cstride; a.taps = taps;
-    a.cin_p = cin_pad; a.ci_tiles = div_up(cin_pad, 32 * bj);
-    a.pairs_per_split = div_up(div_up(M, 2), (long long)splits);
-    a.skip_empty = 0;
+    WgradChoice c;
+    if (int rc = gather_wgrad_prepare(x, x_cstride, Cin, nbr, m_dev, M, taps, dy, dy_cstride, Cout, cin_pad, dw, workspace,
+                                      workspace_bytes, a, c))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    const unsigned tiles = (unsigned)(div_up(Cout, 32 * bi) * a.ci_tiles * taps);
-    if (bi == 2 && bj == 2) {
-        // (an XCD-contiguous tile order measured slower here: 36 vs 55 TF/s on 64 -> 64; identity mapping)
-        a.xcd_tiles = 0;
-        hipLaunchKernelGGL(gather_wgrad_kernel, dim3(tiles, (unsigned)splits), dim3(256), 0, st, a);
+    const dim3 grid((unsigned)c.tiles, (unsigned)c.splits);
+    if (c.family == WGRAD_TILE64) {
+        hipLaunchKernelGGL(gather_wgrad_kernel, grid, dim3(256), 0, st, a);
     } else {
-        a.xcd_tiles = 0;
-        a.skip_empty = 1;
-        const dim3 grid(tiles, (unsigned)splits);
-        switch (bi * 8 + bj) {
-#define TT_GW(BI_, BJ_) \
-    case BI_ * 8 + BJ_: hipLaunchKernelGGL((gather_wgrad_wide_kernel<BI_, BJ_>), grid, dim3(256), 0, st, a); break;
-            TT_GW(4, 4) TT_GW(4, 2) TT_GW(2, 4) TT_GW(4, 1) TT_GW(1, 4) TT_GW(2, 1) TT_GW(1, 2) TT_GW(1, 1)
-#undef TT_GW
-            default: TT_REQUIRE(false, "tt_gather_conv_wgrad: no kernel for wave tile %d x %d", bi, bj);
-        }
+        const GatherWgradKernel kern = gather_wgrad_wave_kernel(c.bi, c.bj);
+        TT_REQUIRE(kern, "tt_gather_conv_wgrad: no kernel for wave tile %d x %d", c.bi, c.bj);
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, a);
     }
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)div_up(n, 32)), dim3(256), 0, st, (const float*)workspace, n,
-                       slices, accumulate, dw);
+    wgrad_reduce(workspace, (long long)Cout * taps * cin_pad, c.slices, accumulate, dw, st);
     return check_launch("tt_gather_conv_wgrad");
+}
+
+extern "C" int tt_gather_conv_wgrad_plan(const float* x, int x_cstride, int Cin, const int* nbr, const int* m_dev, long long M,
+                                         int taps, const float* dy, int dy_cstride, int Cout, int cin_pad, int accumulate,
+                                         float* dw, void* workspace, long long workspace_bytes, int x3, char* label,
+                                         int label_bytes) {
+    (void)accumulate;
+    (void)x3;       // the gathered layer has one arithmetic (exact f32)
+    GatherWgradArgs a;
+    WgradChoice c;
+    if (int rc = gather_wgrad_prepare(x, x_cstride, Cin, nbr, m_dev, M, taps, dy, dy_cstride, Cout, cin_pad, dw, workspace,
+                                      workspace_bytes, a, c))
+        return rc;
+    TT_REQUIRE(label && label_bytes > 0, "tt_gather_conv_wgrad_plan: no room for the label");
+    wgrad_label(c, true, label, (size_t)label_bytes);
+    return 0;
 }
 
 extern "C" int tt_sp_inverse_rulebook(const int* nbr, const int* m_dev, long long M, int taps, int* inv_prefilled_minus1,

@@ -88,7 +88,8 @@ def lift_splat_bwd(depth_logits, context, geom_xyz, voxel_num, batch_size, num_c
 # ----------------------------------------------------------------------------- conv / linear
 _AUTO_SPLITK = os.environ.get("TT_CONV_AUTO_SPLITK", "1") == "1"
 CONV_PROFILE = None   # bench.py sets this to a list to collect (flops, start, end, shape) per launch
-CONV_KERNELS = None   # same order as CONV_PROFILE: tt_conv_last_kernel() of the launch
+CONV_KERNELS = None   # same order as CONV_PROFILE: tt_conv_last_kernel() of the launch (a weight gradient: its plan label); plus one
+                      # entry per gather_conv_wgrad, which has no CONV_PROFILE record -- do not zip the two over a sparse backward
 CONV_BYTES = None     # same order as CONV_PROFILE: compulsory HBM bytes of the launch (each operand moved once);
                       # dense: int; sparse: (bytes per live output row, fixed bytes)
 
@@ -177,6 +178,11 @@ def gather_conv_wgrad(feats, nbr, m_dev, dy, taps, cin_pad=None):
     assert feats.is_contiguous() and dy.is_contiguous() and nbr.is_contiguous() and feats.dtype == torch.float32
     check(L.tt_gather_conv_wgrad(ptr(feats), Cin, Cin, ptr(nbr), ptr(m_dev), M, taps, ptr(dy), Cout,
                                  Cout, cin_pad, 0, ptr(out), ptr(ws), nb, _st(dy)), "tt_gather_conv_wgrad")
+    if CONV_KERNELS is not None:      # (no CONV_PROFILE record goes with it: this launch is not timed)
+        label = ctypes.create_string_buffer(192)
+        check(L.tt_gather_conv_wgrad_plan(ptr(feats), Cin, Cin, ptr(nbr), ptr(m_dev), M, taps, ptr(dy), Cout, Cout, cin_pad, 0,
+                                          ptr(out), ptr(ws), nb, 0, label, len(label)), "tt_gather_conv_wgrad_plan")
+        CONV_KERNELS.append(label.value.decode())
     return out
 
 
@@ -973,7 +979,7 @@ def conv2d_wgrad(x, dy, kh, kw, stride=1, pad=0, dil=1, cin=None, in_coff=0, cou
     if CONV_PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    name = "tt_conv2d_wgrad_x3" if x3 else "tt_conv2d_wgrad"   # x3: the forward's bf16x3 arithmetic (wide layers: LDS-staged kernel)
+    name = "tt_conv2d_wgrad_x3" if x3 else "tt_conv2d_wgrad"   # x3: the forward's bf16x3 arithmetic (csrc/wgrad_choose.cpp: which layers)
     check(getattr(L, name)(ptr(x), N, H, W, cin, Cs, in_coff, ptr(dy), OH, OW, cout, Cd, dy_coff, kh, kw, stride, pad, dil,
                            cin_pad, 1 if accumulate else 0, ptr(out), ptr(ws), nb, _st(x)), name)
     if CONV_PROFILE is not None:
@@ -981,7 +987,11 @@ def conv2d_wgrad(x, dy, kh, kw, stride=1, pad=0, dil=1, cin=None, in_coff=0, cou
         CONV_PROFILE.append((2.0 * N * OH * OW * cout * kh * kw * cin, e0, e1,
                              f"wgrad M={N * OH * OW} N={cout} K={kh * kw * cin} k{kh}x{kw}s{stride}"))
         if CONV_KERNELS is not None:
-            CONV_KERNELS.append("conv_wgrad_kernel")
+            label = ctypes.create_string_buffer(192)
+            check(L.tt_conv2d_wgrad_plan(ptr(x), N, H, W, cin, Cs, in_coff, ptr(dy), OH, OW, cout, Cd, dy_coff, kh, kw, stride, pad,
+                                         dil, cin_pad, 1 if accumulate else 0, ptr(out), ptr(ws), nb, int(x3), label, len(label)),
+                  "tt_conv2d_wgrad_plan")
+            CONV_KERNELS.append(label.value.decode())
         if CONV_BYTES is not None:
             CONV_BYTES.append((x.numel() + dy.numel() + out.numel()) * 4)
     return out
