@@ -891,6 +891,39 @@ int tt_lidar_merge_half_sweeps(const float* prev_xyzi, int n_prev, const float* 
                                const float* rel_transform_3x4, float z_shift, float* out_xyzi, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The multi-sweep cloud of a TRAINING batch: union2one's "dense-fusion" (open_loop_training/code/datasets/carla_dataset.py:
+ * 314-328) for every sample of a batch, and the zero rows mmcv's collate pads the ragged clouds with, in one launch.
+ *
+ * points_xyzi: device f32 rows (x, y, z, intensity), `num_rows` of them, base 16-byte aligned.  `sweeps` is a HOST pointer to
+ * B * T tt_union_sweep, entry b * T + t for sweep t of sample b (t = T - 1 is the key sweep, t = 0 the oldest): rows
+ * first_row .. first_row + count - 1 of points_xyzi, in any order, with gaps, count = 0 allowed.  The entry checks every
+ * segment and copies the table into the kernel's arguments (by value, like tt_ida_set: no device buffer, no copy, no
+ * synchronisation, no workspace), which bounds a call to TT_UNION_MAX_SWEEPS = B * T sweeps.
+ *
+ * out f32 [B, Np, 5]; for sample b, in this order:
+ *   key sweep     the rows of sweep T - 1 copied bit for bit, column 4 = 0.0; its matrix is NOT read (:315-318)
+ *   older sweeps  for t = T - 2 .. 0 the rows of sweep t, columns 0..3 = M[b, t] . (x, y, z, i) -- all four rows of the
+ *                 matrix, the intensity in the place of the homogeneous coordinate (:323) --, column 4 = (float)(t - (T - 1))
+ *   padding       every remaining row up to Np: five +0.0 (the caller does not clear `out`)
+ * A transformed component j is, in f32:  fmaf(m[4j+3], i, fmaf(m[4j+2], z, fmaf(m[4j+1], y, m[4j] * x)))  -- one rounded
+ * product, then three fused multiply-adds in column order -- so the result is defined and the same from run to run.
+ *
+ * Returns an error, before any launch, for: a null `sweeps` or `out`, a null `points_xyzi` with a non-empty segment or one
+ * that is not 16-byte aligned; B < 1, T < 2, Np < 0; B * T > TT_UNION_MAX_SWEEPS; a negative first_row or count, a segment
+ * that ends after num_rows; a sample whose counts sum to more than Np; B * Np above 2^31 - 1024 (the kernel indexes
+ * output rows with an int).
+ * ---------------------------------------------------------------------- */
+#define TT_UNION_MAX_SWEEPS 32
+typedef struct tt_union_sweep {
+    long long first_row;        /* first row of the segment in points_xyzi */
+    int count;                  /* rows of the segment */
+    int reserved;               /* (keeps the matrix at offset 16; not read) */
+    float m[16];                /* row-major 4x4 curr2key of the sweep; not read for the key sweep */
+} tt_union_sweep;               /* 80 bytes */
+int tt_lidar_union_sweeps(const float* points_xyzi, long long num_rows, const tt_union_sweep* sweeps, int B, int T, int Np,
+                          float* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * train-mode BatchNorm (batch statistics) over channel-last rows -- what every nn.BatchNorm2d / BatchNorm1d
  * (torch.nn.SyncBatchNorm under configs/thinktwice.py:39 SyncBN=True, apis/mmdet_train.py:86-87) computes under
  * model.train() (norm_eval=False, configs/thinktwice.py:146).  The convolution in front writes its raw output z (bias in);
