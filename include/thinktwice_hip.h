@@ -58,9 +58,15 @@ int tt_voxel_pool_fwd(int batch_size, int num_points, int num_channels,
                       const int32_t* geom_xyz, const float* input_features,
                       float* output_features, int32_t* pos_memo, void* stream);
 
-/* Same operator with a caller-provided workspace: atomics-free two-phase reduce (LDS-privatised
- * per-chunk cell sums, then an ordered per-cell gather).  Falls back to tt_voxel_pool_fwd when the
- * workspace is missing/small or the shape is unsupported (bytes query returns 0). */
+/* Same operator with a caller-provided workspace.  Three arms, chosen per call in csrc/voxel_pool_choose.cpp:
+ *   counting sort  the in-range points are sorted by (sample, cell) per launch (vp_cs_count / _scan / _scatter) and streamed by
+ *                  the planned kernels: no atomics, deterministic, bit-identical to the static plan below.  From 32,768 points,
+ *                  <= 1024 cells, <= 524,288 points per sample, C a multiple of 4 up to 1024; TT_VP_SORT=0 turns it off.
+ *   two-phase      per-chunk cell sums in LDS order (voxel_pool_p1_kernel), then an ordered per-cell gather (_p2_kernel).  From
+ *                  8,192 points, <= 2048 cells, the same C.
+ *   atomic         tt_voxel_pool_fwd's single-pass kernels, when the workspace is missing or too small for the other two, a
+ *                  buffer is not 16-byte aligned (the table in voxel_pool_choose.h), or the shape fits neither.
+ * tt_voxel_pool_workspace_bytes is the most any arm takes for the sizes (0: only the atomic arm takes them). */
 long long tt_voxel_pool_workspace_bytes(int batch_size, int num_points, int num_channels,
                                         int num_voxel_x, int num_voxel_y);
 int tt_voxel_pool_fwd_ws(int batch_size, int num_points, int num_channels,
@@ -68,6 +74,18 @@ int tt_voxel_pool_fwd_ws(int batch_size, int num_points, int num_channels,
                          const int32_t* geom_xyz, const float* input_features,
                          float* output_features, int32_t* pos_memo,
                          void* workspace, long long workspace_bytes, void* stream);
+/* Host only: which kernels tt_voxel_pool_fwd_ws (ws_entry != 0) / tt_voxel_pool_fwd (ws_entry = 0: the workspace is ignored) would
+ * run these arguments on, assuming the device grants the counting sort its dynamic LDS.  Runs the validation and the dispatch of a
+ * launch and writes into `label` (label_bytes bytes, NUL-terminated) the launches in order, joined by " + ", each
+ *   "<kernel with its template arguments, as rocprofv3 prints it> grid <workgroups> block <threads> lds <dynamic bytes>"
+ * followed by " ws <workspace bytes the arm needs>" (a call that launches nothing: "ws 0").  Dereferences no pointer (null-ness
+ * and alignment are all it looks at) and touches no device; returns the non-zero code, with the error text, that the launch
+ * would return before launching. */
+int tt_voxel_pool_fwd_plan(int batch_size, int num_points, int num_channels,
+                           int num_voxel_x, int num_voxel_y, int num_voxel_z,
+                           const int32_t* geom_xyz, const float* input_features,
+                           float* output_features, int32_t* pos_memo,
+                           void* workspace, long long workspace_bytes, int ws_entry, char* label, int label_bytes);
 
 /* Planned forward for STATIC geometry (fixed camera rig: the same geom_xyz every frame; closed-loop ticks, the bench).
  * tt_voxel_pool_plan_build sorts the in-range points by (sample, cell) once; tt_voxel_pool_fwd_planned then streams
@@ -128,6 +146,13 @@ int tt_lift_splat_fwd_ws(int batch_size, int num_cams, int D, int fH, int fW, in
                          const void* depth_logits, const void* context, int dtype,
                          const int32_t* geom_xyz, float* out, int out_cstride,
                          int out_coff, int rot_flip, void* ws, long long ws_bytes, void* stream);
+/* Host only: tt_voxel_pool_fwd_plan for tt_lift_splat_fwd_ws (ws == NULL: tt_lift_splat_fwd): the per-pixel atomic kernel, the
+ * strip kernel with atomics, or the strip kernel + lift_splat_cells_kernel (csrc/voxel_pool_choose.cpp: lift_splat_choose). */
+int tt_lift_splat_fwd_plan(int batch_size, int num_cams, int D, int fH, int fW, int C,
+                           int num_voxel_x, int num_voxel_y, int num_voxel_z,
+                           const void* depth_logits, const void* context, int dtype,
+                           const int32_t* geom_xyz, float* out, int out_cstride,
+                           int out_coff, int rot_flip, void* ws, long long ws_bytes, char* label, int label_bytes);
 
 /* ------------------------------------------------------------------------
  * Implicit-GEMM convolution / linear on MFMA, channel-last activations.

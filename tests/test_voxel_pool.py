@@ -204,7 +204,8 @@ def test_counting_sort_path_matches_oracle_and_the_static_plan(B, Np, C, grid, m
     """Round 5: `tt_voxel_pool_fwd_ws` sorts the in-range points by (sample, cell) PER LAUNCH (counting sort: vp_cs_count /
     scan / scatter) and runs the planned streaming kernels, for any geometry with <= 1024 cells and <= 524,288 points per
     sample.  Sums vs the C oracle, pos_memo bit-exact, bit-identical to the static plan (same row order inside a cell) and to
-    itself, accumulation into a pre-filled output; with a workspace that is too small the call still answers (older paths)."""
+    itself, accumulation into a pre-filled output; with a workspace that is too small for the counting sort and for the two-phase
+    kernels the call still answers, on the single-pass atomic kernel."""
     import ctypes
     from thinktwice_amd import _lib
     from thinktwice_amd.voxel_pooling import VoxelPoolPlan
@@ -239,6 +240,12 @@ def test_counting_sort_path_matches_oracle_and_the_static_plan(B, Np, C, grid, m
         torch.cuda.synchronize()
         return out, pm
 
+    def arm(ws_bytes):
+        label = ctypes.create_string_buffer(512)
+        _lib.check(L.tt_voxel_pool_fwd_plan(B, Np, C, X, Y, Z, 4096, 8192, 12288, 16384, 20480, ws_bytes, 1, label, 512), "tt_voxel_pool_fwd_plan")
+        return label.value.decode()
+
+    assert arm(nbytes).startswith("vp_cs_count_kernel") and arm(1024).startswith("voxel_pool_rows_kernel<")
     a, pm = run(nbytes)
     np.testing.assert_allclose(a.cpu().numpy(), ref, rtol=1e-4, atol=2e-4)
     np.testing.assert_array_equal(pm.cpu().numpy(), memo)

@@ -1,10 +1,13 @@
-// Lift-Splat "splat" kernels for gfx950 (wave64).
+// The op-boundary voxel pool ("splat") for gfx950 (wave64): kernels and entries.
 //
-//  tt_voxel_pool_fwd       op-boundary drop-in for the reference CUDA kernel
-//                          (ops/voxel_pooling/src/voxel_pooling_forward_cuda.cu:9-36).
-//  tt_voxel_pool_bwd       VoxelPooling.backward (ops/voxel_pooling/voxel_pooling.py:57-69).
-//  tt_frustum_voxel_index  LSS.get_geometry + voxel index (backbones/lss.py:474-512,629-631).
-//  tt_lift_splat_fwd       fused depth-softmax (x) context -> BEV (lss.py:583-615 + splat).
+//  tt_voxel_pool_fwd / _fwd_ws   op-boundary drop-in for the reference CUDA kernel
+//                                (ops/voxel_pooling/src/voxel_pooling_forward_cuda.cu:9-36): the single-pass atomic kernels
+//                                (rows, scalar), the two-phase reduce and the per-launch counting sort.
+//  tt_voxel_pool_plan_build / _fwd_planned   the same sums over a plan sorted once, for static geometry.
+//  tt_voxel_pool_bwd             VoxelPooling.backward (ops/voxel_pooling/voxel_pooling.py:57-69).
+//
+// Which of them a call runs on, with which grids and workspace offsets, is decided in voxel_pool_choose.cpp; every entry
+// here validates, asks the chooser and launches what it answers.  The fused lift-splat of the forward is lift_splat.hip.
 //
 // Design (HBM-bound): the reference walks one point per THREAD
 // (64 lanes 1 KiB apart => every load and atomic uncoalesced).  Here one WAVE
@@ -17,6 +20,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "tt_common.h"
+#include "voxel_pool_choose.h"
 
 namespace tt {
 
@@ -147,9 +151,6 @@ __global__ __launch_bounds__(256) void voxel_pool_rows_kernel(
 // Cells beyond the slot budget (never the case for Lift-Splat geometry; random indices in tests do
 // hit it) fall back to global atomics inside phase 1.
 // ---------------------------------------------------------------------------
-constexpr int kChunk = 2048;
-constexpr int kMaxCells = 2048;
-
 // Point rows are read exactly once: a non-temporal 16 B load keeps them from displacing the index / partial lines in
 // L2 and MALL (measured 0.61 -> 0.75 of HBM peak on the planned path, profiles/r02_voxel_pool_*).
 typedef float vp_f4 __attribute__((ext_vector_type(4)));
@@ -426,550 +427,6 @@ __global__ __launch_bounds__(256) void voxel_pool_bwd_scalar_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// frustum -> ego -> voxel index.  Products and sums are written as separate
-// IEEE roundings in k order (no FMA contraction) so the oracle can restate the
-// exact same arithmetic.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ float dot4_seq(const float* m, float a, float b, float c, float d) {
-#pragma clang fp contract(off)
-    float s = __fmul_rn(m[0], a);
-    s = __fadd_rn(s, __fmul_rn(m[1], b));
-    s = __fadd_rn(s, __fmul_rn(m[2], c));
-    s = __fadd_rn(s, __fmul_rn(m[3], d));
-    return s;
-}
-
-__global__ __launch_bounds__(256) void frustum_voxel_index_kernel(
-    int B, int ncam, int D, int fH, int fW, const float* __restrict__ frustum,
-    const float* __restrict__ mats, float lox, float loy, float loz, float sx, float sy, float sz,
-    int32_t* __restrict__ geom_xyz, float* __restrict__ geom_f32) {
-#pragma clang fp contract(off)
-    const long long per_cam = (long long)D * fH * fW;
-    const long long total = (long long)B * ncam * per_cam;
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const long long bc = t / per_cam;
-    const long long q = t % per_cam;
-    const float* iida = mats + bc * 32;
-    const float* comb = iida + 16;
-    const float4 f = reinterpret_cast<const float4*>(frustum)[q];
-    float p0 = dot4_seq(iida + 0, f.x, f.y, f.z, f.w);
-    float p1 = dot4_seq(iida + 4, f.x, f.y, f.z, f.w);
-    float p2 = dot4_seq(iida + 8, f.x, f.y, f.z, f.w);
-    float p3 = dot4_seq(iida + 12, f.x, f.y, f.z, f.w);
-    p0 = __fmul_rn(p0, p2);
-    p1 = __fmul_rn(p1, p2);
-    const float gx = dot4_seq(comb + 0, p0, p1, p2, p3);
-    const float gy = dot4_seq(comb + 4, p0, p1, p2, p3);
-    const float gz = dot4_seq(comb + 8, p0, p1, p2, p3);
-    if (geom_f32) {
-        geom_f32[t * 3 + 0] = gx;
-        geom_f32[t * 3 + 1] = gy;
-        geom_f32[t * 3 + 2] = gz;
-    }
-    // (geom - lo) / size, truncated toward zero like Tensor.int() (lss.py:630-631)
-    geom_xyz[t * 3 + 0] = (int)__fdiv_rn(__fsub_rn(gx, lox), sx);
-    geom_xyz[t * 3 + 1] = (int)__fdiv_rn(__fsub_rn(gy, loy), sy);
-    geom_xyz[t * 3 + 2] = (int)__fdiv_rn(__fsub_rn(gz, loz), sz);
-}
-
-// ---------------------------------------------------------------------------
-// fused lift-splat: one wave per image pixel (b, cam, h, w).
-//   prob[d] = softmax_d(depth_logits[pix, :]);  out[cell(pix,d), :] += prob[d] * ctx[pix, :]
-// Consecutive depth bins of one ray that fall in the same BEV cell are merged
-// (sum of probabilities) before touching memory.
-// ---------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void lift_splat_kernel(
-    int B, int ncam, int D, int fH, int fW, int C, int X, int Y, int Z,
-    const T* __restrict__ depth_logits, const T* __restrict__ ctx,
-    const int32_t* __restrict__ geom, float* __restrict__ out, int out_cstride, int out_coff,
-    int rot_flip) {
-    const int lane = threadIdx.x & 63;
-    const long long pix = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long npix = (long long)B * ncam * fH * fW;
-    if (pix >= npix) return;
-    const int hw = (int)(pix % ((long long)fH * fW));
-    const int bc = (int)(pix / ((long long)fH * fW));
-    const int b = bc / ncam;
-    const int cam = bc % ncam;
-
-    // ---- softmax over D (D <= 128: two bins per lane)
-    const T* lg = depth_logits + pix * D;
-    float l0 = (lane < D) ? Elem<T>::ld(lg + lane) : -INFINITY;
-    float l1 = (lane + 64 < D) ? Elem<T>::ld(lg + lane + 64) : -INFINITY;
-    float m = fmaxf(l0, l1);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float e0 = (lane < D) ? expf(l0 - m) : 0.f;
-    float e1 = (lane + 64 < D) ? expf(l1 - m) : 0.f;
-    float s = e0 + e1;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float inv = 1.f / s;
-    e0 *= inv;
-    e1 *= inv;
-
-    // ---- cell per depth bin
-    const long long per_cam = (long long)D * fH * fW;
-    const int32_t* g = geom + ((long long)b * ncam * per_cam + (long long)cam * per_cam) * 3;
-    int cell0 = -1, cell1 = -1;
-    if (lane < D) {
-        const int32_t* q = g + ((long long)lane * fH * fW + hw) * 3;
-        const int x = q[0], y = q[1], z = q[2];
-        if (x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z) cell0 = y * X + x;
-    }
-    if (lane + 64 < D) {
-        const int32_t* q = g + ((long long)(lane + 64) * fH * fW + hw) * 3;
-        const int x = q[0], y = q[1], z = q[2];
-        if (x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z) cell1 = y * X + x;
-    }
-
-    // ---- context row in registers (C <= 1024: up to 4 float4-chunks per lane)
-    const int c4 = C >> 2;
-    float4 cv[4];
-    const T* crow = ctx + pix * C;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const int ch = lane + 64 * v;
-        if (ch < c4) {
-            cv[v].x = Elem<T>::ld(crow + ch * 4 + 0);
-            cv[v].y = Elem<T>::ld(crow + ch * 4 + 1);
-            cv[v].z = Elem<T>::ld(crow + ch * 4 + 2);
-            cv[v].w = Elem<T>::ld(crow + ch * 4 + 3);
-        } else {
-            cv[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-
-    int cur = -1;
-    float w = 0.f;
-    auto flush = [&](int cell, float wsum) {
-        int y = cell / X, x = cell % X;
-        int oi = y, oj = x;
-        if (rot_flip) {  // rot90(flip(bev,[2]),1,[2,3]): out[i][j] = bev[Y-1-j][X-1-i]
-            oi = X - 1 - x;
-            oj = Y - 1 - y;
-        }
-        const int OW = rot_flip ? Y : X;
-        const int OH = rot_flip ? X : Y;
-        float* dst = out + (((long long)b * OH + oi) * OW + oj) * out_cstride + out_coff;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int ch = lane + 64 * v;
-            if (ch < c4) {
-                unsafeAtomicAdd(dst + ch * 4 + 0, wsum * cv[v].x);
-                unsafeAtomicAdd(dst + ch * 4 + 1, wsum * cv[v].y);
-                unsafeAtomicAdd(dst + ch * 4 + 2, wsum * cv[v].z);
-                unsafeAtomicAdd(dst + ch * 4 + 3, wsum * cv[v].w);
-            }
-        }
-    };
-    for (int d = 0; d < D; ++d) {
-        const int src_lane = d & 63;
-        const int c = (d < 64) ? __builtin_amdgcn_readlane(cell0, src_lane)
-                               : __builtin_amdgcn_readlane(cell1, src_lane);
-        const float pr = __uint_as_float(
-            (d < 64) ? __builtin_amdgcn_readlane(__float_as_uint(e0), src_lane)
-                     : __builtin_amdgcn_readlane(__float_as_uint(e1), src_lane));
-        if (c != cur) {
-            if (cur >= 0) flush(cur, w);
-            cur = c;
-            w = 0.f;
-        }
-        w += pr;
-    }
-    if (cur >= 0) flush(cur, w);
-}
-
-
-// ---------------------------------------------------------------------------
-// fused lift-splat v2: workgroup-level pre-reduction.  One workgroup owns a full-height strip of
-// kStripW image columns of one camera: all its rays share (almost) the same azimuth, so the strip's
-// 28 x kStripW x 80 frustum points fall into only ~10-30 BEV cells.  The block
-//   1. softmaxes every pixel's depth logits into LDS and tags each (pixel, depth) with its cell,
-//   2. gives the touched cells LDS slots (ballot compaction) and builds W[slot][pixel] = sum of the
-//      depth probabilities that pixel sends to that cell,
-//   3. forms sum_pixel W[slot][pixel] * context[pixel, :] with one wave per slot (context rows are
-//      coalesced 1 KiB loads, L2 resident) and issues ONE atomic row per (strip, cell)
-// -- ~13x fewer global atomics than the one-wave-per-pixel kernel above.
-// With a workspace (tt_lift_splat_fwd_ws) there are no atomics at all: step 2 builds W with one thread per pixel
-// walking its ray in depth order, step 3 stores the (strip, cell) partial rows to ws_rows[block][slot][C] and the
-// block's cell -> slot table to slot_of[block][cell]; lift_splat_cells_kernel then adds every cell's partial rows to
-// the output in block order.  Same inputs => bit-identical output.
-// ---------------------------------------------------------------------------
-constexpr int kStripW = 2;
-constexpr int kMaxStripPix = 64;     // fH * kStripW <= 64
-constexpr int kMaxSlots = 64;
-constexpr int kMaxD = 128;
-
-// dynamic LDS: W f32 [kMaxStripPix][kWS] | table int [cells] | slot_cell int [kMaxSlots] | a region that holds
-// { prob f32 [kMaxStripPix][PD], tag short [D][npx] } until W is built and the staged context rows
-// f32 [kMaxStripPix][min(C, kStageC)] afterwards  (50 KiB at the thinktwice.py shapes: three workgroups per CU)
-constexpr int kStageC = 128;
-constexpr int kWS = kMaxSlots + 4;        // W row stride: 16 B rows, = 4 mod 8 words
-__host__ __device__ inline int lift_splat_prob_stride(int D) {      // 16 B rows, = 4 mod 8 words: 16 rows on 16 bank quads
-    int pd = (D + 3) & ~3;
-    if ((pd & 4) == 0) pd += 4;
-    return pd;
-}
-__host__ __device__ inline int lift_splat_table_words(int cells) { return (cells + kMaxSlots + 3) & ~3; }
-static size_t lift_splat_strip_lds(int D, int C, int cells) {
-    const size_t a = (size_t)kMaxStripPix * lift_splat_prob_stride(D) * 4 + (size_t)kMaxStripPix * D * 2;
-    const size_t c = (size_t)kMaxStripPix * (C < kStageC ? C : kStageC) * 4;
-    const size_t b = (size_t)kWS * kMaxStripPix * 4 + (size_t)lift_splat_table_words(cells) * 4 + (a > c ? a : c);
-    return (b + 15) / 16 * 16;
-}
-
-struct __attribute__((packed, aligned(4))) GeomPoint { int x, y, z; };
-
-template <typename T>
-__global__ __launch_bounds__(256) void lift_splat_strip_kernel(
-    int B, int ncam, int D, int fH, int fW, int C, int X, int Y, int Z, const T* __restrict__ depth_logits,
-    const T* __restrict__ ctx, const int32_t* __restrict__ geom, float* __restrict__ out, int out_cstride,
-    int out_coff, int rot_flip, float* __restrict__ ws_rows, unsigned char* __restrict__ slot_of) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char ls_smem[];
-    __shared__ int nslots_sh;
-    const int cells = X * Y;
-    const int CW = min(C, kStageC);                 // channels per staged chunk of the context rows
-    const int PD = lift_splat_prob_stride(D);
-    float* Wt = reinterpret_cast<float*>(ls_smem);                          // [p][slot]
-    int* table = reinterpret_cast<int*>(Wt + kWS * kMaxStripPix);
-    int* slot_cell = table + cells;
-    float* prob = reinterpret_cast<float*>(table + lift_splat_table_words(cells));      // [p][PD]
-    short* tag = reinterpret_cast<short*>(prob + kMaxStripPix * PD);        // [d][npx]: cell, then slot
-    float* ctxs = prob;                                                     // [p][CW], once prob / tag are spent
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int strips = (fW + kStripW - 1) / kStripW;
-    // workgroup -> strip: hardware deals consecutive workgroups to the 8 XCDs in turn; give every XCD a CONTIGUOUS range of
-    // strips, so that the neighbouring image columns that share 128 B lines of geom_xyz (10.7 points per line, 2 per strip
-    // row) are fetched through the same L2
-    const int nblk = gridDim.x, xcd = blockIdx.x & 7, full = nblk >> 3, rem = nblk & 7;
-    const int vb = xcd * full + min(xcd, rem) + (blockIdx.x >> 3);
-    const int bc = vb / strips;            // b * ncam + cam
-    const int strip = vb % strips;
-    const int b = bc / ncam, cam = bc % ncam;
-    const int w0 = strip * kStripW;
-    const int sw = min(kStripW, fW - w0);
-    const int npx = fH * sw;                        // pixels in this strip: p -> (h = p / sw, w = w0 + p % sw)
-
-    // context rows of one channel chunk: global -> registers (issued early, under other work) -> LDS as f32
-    constexpr int kS = kMaxStripPix * (kStageC / 4) / 256;         // 8 float4 pieces per thread at the limits
-    float4 cv[kS];
-    auto ctx_fetch = [&](int c0) {
-        const int cw4 = min(kStageC, C - c0) >> 2, tot = npx * cw4;
-#pragma unroll
-        for (int k = 0; k < kS; ++k) {
-            const int i = k * 256 + tid;
-            cv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < tot) {
-                const int p = i / cw4, j = i - p * cw4;
-                const int h = p / sw, w = w0 + p - h * sw;
-                const T* crow = ctx + (((long long)bc * fH + h) * fW + w) * C + c0 + j * 4;
-                if constexpr (sizeof(T) == 4) {
-                    cv[k] = *reinterpret_cast<const float4*>(crow);
-                } else {
-                    cv[k].x = Elem<T>::ld(crow + 0); cv[k].y = Elem<T>::ld(crow + 1);
-                    cv[k].z = Elem<T>::ld(crow + 2); cv[k].w = Elem<T>::ld(crow + 3);
-                }
-            }
-        }
-    };
-    auto ctx_commit = [&](int c0) {
-        const int cw4 = min(kStageC, C - c0) >> 2, tot = npx * cw4;
-#pragma unroll
-        for (int k = 0; k < kS; ++k) {
-            const int i = k * 256 + tid;
-            if (i < tot) {
-                const int p = i / cw4, j = i - p * cw4;
-                reinterpret_cast<float4*>(ctxs + p * CW)[j] = cv[k];
-            }
-        }
-    };
-
-    for (int i = tid; i < cells; i += 256) table[i] = -1;
-    for (int i = tid; i < kWS * kMaxStripPix; i += 256) Wt[i] = 0.f;
-    // depth logits of the strip: coalesced 16 B pieces -> registers now, LDS after the geometry pass
-    constexpr int kL = kMaxStripPix * (kMaxD / 4) / 256;          // 8 pieces per thread at the limits
-    const bool logits16 = (D & 3) == 0 && sizeof(T) == 4;
-    float4 lv[kL];
-    if (logits16) {
-        const int d4 = D >> 2, tot4 = npx * d4;
-#pragma unroll
-        for (int k = 0; k < kL; ++k) {
-            const int i = k * 256 + tid;
-            lv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < tot4) {
-                const int p = i / d4, j = i - p * d4;
-                const int h = p / sw, w = w0 + p - h * sw;
-                lv[k] = reinterpret_cast<const float4*>(depth_logits + (((long long)bc * fH + h) * fW + w) * D)[j];
-            }
-        }
-    }
-    __syncthreads();
-    const long long per_cam = (long long)D * fH * fW;
-    const GeomPoint* g = reinterpret_cast<const GeomPoint*>(geom) + ((long long)b * ncam + cam) * per_cam;
-    // 1a. cell tags: every thread takes (depth, pixel) pairs, one 12 B load per point, a batch of loads before the first use
-    {
-        constexpr int kG = 18;
-        const int tot = D * npx;
-        for (int i0 = 0; i0 < tot; i0 += 256 * kG) {
-            GeomPoint gp[kG];
-#pragma unroll
-            for (int k = 0; k < kG; ++k) {
-                const int i = i0 + k * 256 + tid;
-                gp[k].x = -1; gp[k].y = -1; gp[k].z = -1;
-                if (i < tot) {
-                    const int d = i / npx, p = i - d * npx;
-                    const int h = p / sw, w = w0 + p - h * sw;
-                    gp[k] = g[(long long)d * fH * fW + (long long)h * fW + w];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kG; ++k) {
-                const int i = i0 + k * 256 + tid;
-                if (i < tot) {
-                    const int d = i / npx, p = i - d * npx;
-                    const int x = gp[k].x, y = gp[k].y, z = gp[k].z;
-                    int c = -1;
-                    if (x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z) {
-                        c = y * X + x;
-                        table[c] = -2;
-                    }
-                    tag[i] = (short)c;
-                }
-            }
-        }
-    }
-    // 1b. softmax over depth: logits -> LDS (coalesced rows), then four adjacent lanes per pixel (depth bins q, q+4, ...)
-    // with two quad-shuffle steps per reduction
-    {
-        if (logits16) {
-            const int d4 = D >> 2, tot4 = npx * d4;
-#pragma unroll
-            for (int k = 0; k < kL; ++k) {
-                const int i = k * 256 + tid;
-                if (i < tot4) {
-                    const int p = i / d4, j = i - p * d4;
-                    reinterpret_cast<float4*>(prob + p * PD)[j] = lv[k];
-                }
-            }
-        } else {
-            for (int i = tid; i < npx * D; i += 256) {
-                const int p = i / D, d = i - p * D;
-                const int h = p / sw, w = w0 + p - h * sw;
-                prob[p * PD + d] = Elem<T>::ld(depth_logits + (((long long)bc * fH + h) * fW + w) * D + d);
-            }
-        }
-        __syncthreads();
-        const int p = tid >> 2, q = tid & 3;
-        if (p < npx) {                              // whole quads take the branch together
-            float* pr = prob + p * PD;
-            float m = -INFINITY;
-            for (int d = q; d < D; d += 4) m = fmaxf(m, pr[d]);
-            m = fmaxf(m, __shfl_xor(m, 1));
-            m = fmaxf(m, __shfl_xor(m, 2));
-            float ssum = 0.f;
-            for (int d = q; d < D; d += 4) {
-                const float e = expf(pr[d] - m);
-                pr[d] = e;
-                ssum += e;
-            }
-            ssum += __shfl_xor(ssum, 1);
-            ssum += __shfl_xor(ssum, 2);
-            const float inv = 1.f / ssum;
-            for (int d = q; d < D; d += 4) pr[d] *= inv;
-        }
-    }
-    __syncthreads();
-    // 2. slots
-    if (wave == 0) {
-        int base = 0;
-        for (int c0 = 0; c0 < cells; c0 += 64) {
-            const int c = c0 + lane;
-            const bool hit = (c < cells) && (table[c] == -2);
-            const unsigned long long mk = __ballot(hit);
-            if (hit) {
-                const int sidx = base + __popcll(mk & ((1ull << lane) - 1ull));
-                table[c] = sidx;
-                if (sidx < kMaxSlots) slot_cell[sidx] = c;
-            }
-            base += __popcll(mk);
-        }
-        if (lane == 0) nslots_sh = base;
-    }
-    __syncthreads();
-    const int ns = nslots_sh;
-    auto out_row = [&](int cell) {
-        const int y = cell / X, x = cell % X;
-        int oi = y, oj = x;
-        if (rot_flip) { oi = X - 1 - x; oj = Y - 1 - y; }
-        const int OW = rot_flip ? Y : X, OH = rot_flip ? X : Y;
-        return out + (((long long)b * OH + oi) * OW + oj) * out_cstride + out_coff;
-    };
-    if (slot_of) {
-        for (int i = tid; i < cells; i += 256) {
-            const int t = table[i];
-            slot_of[(long long)vb * cells + i] = (unsigned char)((t >= 0 && t < kMaxSlots) ? t : 255);
-        }
-    }
-    // cell tags -> slot tags (over-budget cells keep their cell as -(cell + 2))
-    {
-        constexpr int kT = 4;
-        const int tot = D * npx;
-        for (int i0 = 0; i0 < tot; i0 += 256 * kT) {
-            int c[kT], t[kT];
-#pragma unroll
-            for (int k = 0; k < kT; ++k) {
-                const int i = i0 + k * 256 + tid;
-                c[k] = (i < tot) ? (int)tag[i] : -1;
-            }
-#pragma unroll
-            for (int k = 0; k < kT; ++k) t[k] = table[c[k] < 0 ? 0 : c[k]];
-#pragma unroll
-            for (int k = 0; k < kT; ++k) {
-                const int i = i0 + k * 256 + tid;
-                if (i < tot && c[k] >= 0) tag[i] = (short)(t[k] < kMaxSlots ? t[k] : -(c[k] + 2));
-            }
-        }
-    }
-    ctx_fetch(0);           // first chunk of context rows: in flight under the W build
-    __syncthreads();
-    // W[pixel][slot] += prob, one thread per pixel walking its ray front to back.  ds_add_f32 is used as a fire-and-forget
-    // add (no read-modify-write round trip per depth bin): every address has exactly one writer thread and the LDS executes a
-    // wave's operations in program order, so the sum is formed in depth order -- deterministic.  Pairs whose slot is over
-    // budget go straight to global atomics below.
-    if (tid < npx) {
-        constexpr int kW = 8;
-        for (int d0 = 0; d0 < D; d0 += kW) {
-            int sg[kW];
-            float pr[kW];
-#pragma unroll
-            for (int k = 0; k < kW; ++k) {
-                const int d = min(d0 + k, D - 1);
-                sg[k] = tag[d * npx + tid];
-                pr[k] = prob[tid * PD + d];
-            }
-#pragma unroll
-            for (int k = 0; k < kW; ++k)
-                if (d0 + k < D && sg[k] >= 0) atomicAdd(&Wt[tid * kWS + sg[k]], pr[k]);
-        }
-    }
-    __syncthreads();
-    if (ns > kMaxSlots) {   // rare (never with Lift-Splat geometry): per-(pixel,depth) atomics for the excess cells
-        for (int i = wave; i < npx * D; i += 4) {
-            const int tg = tag[i];
-            if (tg >= -1) continue;
-            const int c = -tg - 2;
-            const int d = i / npx, p = i - d * npx;
-            const float wgt = prob[p * PD + d];
-            const int h = p / sw, w = w0 + p % sw;
-            const T* crow = ctx + (((long long)bc * fH + h) * fW + w) * C;
-            float* dst = out_row(c);
-            for (int ch = lane; ch < C; ch += 64) unsafeAtomicAdd(dst + ch, wgt * Elem<T>::ld(crow + ch));
-        }
-    }
-    const int nsl = min(ns, kMaxSlots);
-    // 3. rows[slot][:] = sum_p W[p][slot] * ctx[p][:] as a small dense product, kStageC channels at a time: the strip's
-    // context rows are staged in LDS (f32); a task = (4 slots, one float4 column): 2 x 16 B of LDS per 16 FMAs, only live
-    // slots get tasks, pixels in index order
-    for (int c0 = 0; c0 < C; c0 += kStageC) {
-        const int cw4 = min(kStageC, C - c0) >> 2;
-        __syncthreads();        // prob / tag (first chunk) or the previous chunk's rows are no longer read
-        ctx_commit(c0);
-        __syncthreads();
-        if (c0 + kStageC < C) ctx_fetch(c0 + kStageC);     // next chunk's rows fly under this chunk's product
-        const int ntask = (kStageC / 4) * ((nsl + 3) >> 2);
-        for (int task = tid; task < ntask; task += 256) {
-            const int j = task & (kStageC / 4 - 1), sgp = task / (kStageC / 4);
-            if (j >= cw4) continue;
-            float4 acc[4];
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-            for (int p = 0; p < npx; ++p) {
-                const float4 wq = *reinterpret_cast<const float4*>(Wt + p * kWS + sgp * 4);
-                const float4 x = reinterpret_cast<const float4*>(ctxs + p * CW)[j];
-                acc[0].x += wq.x * x.x; acc[0].y += wq.x * x.y; acc[0].z += wq.x * x.z; acc[0].w += wq.x * x.w;
-                acc[1].x += wq.y * x.x; acc[1].y += wq.y * x.y; acc[1].z += wq.y * x.z; acc[1].w += wq.y * x.w;
-                acc[2].x += wq.z * x.x; acc[2].y += wq.z * x.y; acc[2].z += wq.z * x.z; acc[2].w += wq.z * x.w;
-                acc[3].x += wq.w * x.x; acc[3].y += wq.w * x.y; acc[3].z += wq.w * x.z; acc[3].w += wq.w * x.w;
-            }
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int slot = sgp * 4 + v;
-                if (slot >= nsl) continue;
-                if (ws_rows) {
-                    reinterpret_cast<float4*>(ws_rows + ((long long)vb * kMaxSlots + slot) * C + c0)[j] = acc[v];
-                } else {
-                    float* dst = out_row(slot_cell[slot]) + c0 + j * 4;
-                    unsafeAtomicAdd(dst + 0, acc[v].x);
-                    unsafeAtomicAdd(dst + 1, acc[v].y);
-                    unsafeAtomicAdd(dst + 2, acc[v].z);
-                    unsafeAtomicAdd(dst + 3, acc[v].w);
-                }
-            }
-        }
-    }
-}
-
-// second pass of the atomics-free lift-splat: one wave per (sample, BEV cell) finds the strips that produced a partial
-// row for the cell (slot_of[block][cell], the blocks of one sample are contiguous) and adds them in block order.
-__global__ __launch_bounds__(256) void lift_splat_cells_kernel(int B, int blocks_per_sample, int C, int X, int Y,
-                                                               const float* __restrict__ ws_rows,
-                                                               const unsigned char* __restrict__ slot_of,
-                                                               float* __restrict__ out, int out_cstride, int out_coff,
-                                                               int rot_flip) {
-    const int lane = threadIdx.x & 63;
-    const int cells = X * Y;
-    const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (wid >= (long long)B * cells) return;
-    const int b = (int)(wid / cells), cell = (int)(wid % cells);
-    const int c4 = C >> 2;
-    float4 acc[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool any = false;
-    for (int k0 = 0; k0 < blocks_per_sample; k0 += 64) {
-        const int k = k0 + lane;
-        int s = 255;
-        if (k < blocks_per_sample) s = slot_of[((long long)b * blocks_per_sample + k) * cells + cell];
-        unsigned long long mk = __ballot(s != 255);
-        while (mk) {
-            const int l = __ffsll((long long)mk) - 1;
-            mk &= mk - 1;
-            const int sl = __shfl(s, l);
-            const float4* wr = reinterpret_cast<const float4*>(
-                ws_rows + (((long long)b * blocks_per_sample + k0 + l) * kMaxSlots + sl) * C);
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int ch = lane + 64 * v;
-                if (ch < c4) {
-                    const float4 r = wr[ch];
-                    acc[v].x += r.x; acc[v].y += r.y; acc[v].z += r.z; acc[v].w += r.w;
-                }
-            }
-            any = true;
-        }
-    }
-    if (!any) return;
-    const int y = cell / X, x = cell % X;
-    int oi = y, oj = x;
-    if (rot_flip) { oi = X - 1 - x; oj = Y - 1 - y; }
-    const int OW = rot_flip ? Y : X, OH = rot_flip ? X : Y;
-    float4* dst = reinterpret_cast<float4*>(out + (((long long)b * OH + oi) * OW + oj) * out_cstride + out_coff);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const int ch = lane + 64 * v;
-        if (ch < c4) {
-            float4 o = dst[ch];
-            o.x += acc[v].x; o.y += acc[v].y; o.z += acc[v].z; o.w += acc[v].w;
-            dst[ch] = o;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
 // Planned forward for STATIC geometry (a fixed camera rig: geom_xyz is the same every frame).  The plan sorts the
 // in-range points by (sample, BEV cell) once (CSR: `order` = point indices grouped by cell, `cell_start`) and cuts
 // every cell's run into segments of kSeg rows.  A forward is then pure streaming with no index work:
@@ -978,7 +435,6 @@ __global__ __launch_bounds__(256) void lift_splat_cells_kernel(int B, int blocks
 //   cells kernel    : one wave per (sample, cell) adds its segments' partial rows, in order, to the caller's output.
 // No atomics, deterministic; HBM traffic = the in-range rows + 4 B per row of indices + 2 x 1/kSeg of the rows.
 // ---------------------------------------------------------------------------
-constexpr int kSeg = 64;
 constexpr int kSegRF = 16;
 
 __global__ void vp_plan_keys_kernel(long long total, int num_points, int X, int Y, int Z, const int32_t* __restrict__ geom,
@@ -1176,10 +632,6 @@ __global__ __launch_bounds__(256) void vp_planned_cells_kernel(int C, int cpg, i
 // add the same rows in the same order: bit-identical outputs.  Then the planned streaming kernels run as they are.
 // Traffic on top of the rows: geom 12 B + 4 B written + 4 B read per point, 4 B per in-range point, < 1 MB of tables.
 // ---------------------------------------------------------------------------
-constexpr int kCsChunk = 8192;
-constexpr int kCsWaves = 16;
-constexpr int kCsMaxCells = 1024;
-constexpr int kCsMaxChunksPerSample = 64;
 constexpr int kCsRankBits = 13;          // rank within a chunk < 8192
 
 __global__ __launch_bounds__(kCsWaves * 64) void vp_cs_count_kernel(int num_points, int X, int Y, int Z, int cps,
@@ -1328,203 +780,159 @@ __global__ __launch_bounds__(256) void vp_cs_scatter_kernel(long long total, int
     order[table[((long long)b * cps + cis) * cells + key] + rank] = (int)p;
 }
 
+// The two streaming kernels of the planned forward over the groups of a CSR plan (see vp_planned_segments_kernel).
+static void launch_planned(int C, const VpCsrLayout& L, const VpLaunch* seg, const VpLaunch* cel, int nv, const char* csr_base,
+                           const float* input_features, float* output_features, float* partial, hipStream_t st) {
+    const int* order = reinterpret_cast<const int*>(csr_base + L.order);
+    const int* cell_start = reinterpret_cast<const int*>(csr_base + L.cell_start);
+    const int* seg_off = reinterpret_cast<const int*>(csr_base + L.seg_off);
+    const int cpg = (int)L.cpg, segcap = (int)L.segcap;
+    if (nv == 1) {
+        hipLaunchKernelGGL((vp_planned_segments_kernel<1, 32, true>), dim3(seg->grid), dim3(seg->block), seg->lds, st, C, cpg, segcap,
+                           L.ngroups, order, cell_start, seg_off, input_features, partial);
+        hipLaunchKernelGGL(vp_planned_cells_kernel<1>, dim3(cel->grid), dim3(cel->block), cel->lds, st, C, cpg, segcap, seg_off, partial,
+                           output_features);
+    } else {
+        hipLaunchKernelGGL((vp_planned_segments_kernel<4, 4, true>), dim3(seg->grid), dim3(seg->block), seg->lds, st, C, cpg, segcap,
+                           L.ngroups, order, cell_start, seg_off, input_features, partial);
+        hipLaunchKernelGGL(vp_planned_cells_kernel<4>, dim3(cel->grid), dim3(cel->block), cel->lds, st, C, cpg, segcap, seg_off, partial,
+                           output_features);
+    }
+}
+
 }  // namespace tt
 
 using namespace tt;
+
+// Validate -> choose: everything a forward does before it touches the device (tt_voxel_pool_fwd_plan stops here).  *launches:
+// whether there is anything to launch (no points: the call returns 0).
+static int pool_prepare(const VoxelPoolCall& k, int num_voxel_z, VoxelPoolChoice& c, bool* launches) {
+    c = voxel_pool_choose(k);
+    *launches = true;
+    if (c.arm == VP_SORT || c.arm == VP_TWO_PHASE) {
+        TT_REQUIRE(k.geom && k.feats && k.out, "tt_voxel_pool_fwd_ws: null pointer");
+        return 0;
+    }
+    TT_REQUIRE(k.B >= 0 && k.Np >= 0 && k.C > 0, "tt_voxel_pool_fwd: bad sizes B=%d Np=%d C=%d", k.B, k.Np, k.C);
+    TT_REQUIRE(k.X > 0 && k.Y > 0 && num_voxel_z > 0, "tt_voxel_pool_fwd: bad voxel grid");
+    *launches = c.nlaunch > 0;
+    if (!*launches) return 0;
+    TT_REQUIRE(k.geom && k.feats && k.out, "tt_voxel_pool_fwd: null pointer");
+    return 0;
+}
+
+static int pool_run(VoxelPoolCall k, int num_voxel_z, const int32_t* geom_xyz, const float* input_features, float* output_features,
+                    int32_t* pos_memo, void* workspace, void* stream) {
+    // > 64 KiB of dynamic LDS needs the opt-in (441 cells: 70 KiB, 1024: 160 KiB = the whole CU, which the opt-in asks for).  A
+    // device that refuses it takes the next arm down instead -- the one launcher with a fallback, so no error text
+    static_assert(kCsWaves * kCsMaxCells * (sizeof(unsigned short) + sizeof(unsigned long long)) <= 160 * 1024, "VP_SORT LDS");
+    VoxelPoolChoice c;
+    bool launches;
+    if (int rc = pool_prepare(k, num_voxel_z, c, &launches)) return rc;
+    if (c.arm == VP_SORT && lds_opt_in(reinterpret_cast<const void*>(vp_cs_count_kernel), 160 * 1024, nullptr) != 0) {
+        k.lds_granted = false;
+        if (int rc = pool_prepare(k, num_voxel_z, c, &launches)) return rc;
+    }
+    if (!launches) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = k.B, Np = k.Np, C = k.C, X = k.X, Y = k.Y, Z = num_voxel_z, cells = X * Y;
+    const long long total = (long long)B * Np;
+    char* w = static_cast<char*>(workspace);
+    const VpLaunch* l = c.launch;
+    switch (c.arm) {
+        case VP_SORT: {
+            unsigned* keyrank = reinterpret_cast<unsigned*>(w + c.keyrank);
+            int* table = reinterpret_cast<int*>(w + c.table);
+            hipLaunchKernelGGL(vp_cs_count_kernel, dim3(l[0].grid), dim3(l[0].block), l[0].lds, st, Np, X, Y, Z, c.cps, geom_xyz,
+                               pos_memo, keyrank, table);
+            hipLaunchKernelGGL(vp_cs_scan_kernel, dim3(l[1].grid), dim3(l[1].block), l[1].lds, st, Np, cells, c.cps, table,
+                               reinterpret_cast<int*>(w + c.csr.cell_start), reinterpret_cast<int*>(w + c.csr.seg_off));
+            hipLaunchKernelGGL(vp_cs_scatter_kernel, dim3(l[2].grid), dim3(l[2].block), l[2].lds, st, total, Np, cells, c.cps, keyrank,
+                               table, reinterpret_cast<int*>(w + c.csr.order));
+            launch_planned(C, c.csr, l + 3, l + 4, c.nv, w, input_features, output_features, reinterpret_cast<float*>(w + c.partial), st);
+            return check_launch("tt_voxel_pool_fwd_ws");
+        }
+        case VP_TWO_PHASE: {
+            float* partial = reinterpret_cast<float*>(w + c.partial);
+            int* slot_table = reinterpret_cast<int*>(w + c.slot_table);
+#define TT_P1(NV, RF)                                                                                                          \
+    hipLaunchKernelGGL((voxel_pool_p1_kernel<NV, RF, true>), dim3(l[0].grid), dim3(l[0].block), l[0].lds, st, Np, C, X, Y, Z, c.cps, \
+                       kSlotBudget, geom_xyz, input_features, output_features, pos_memo, partial, slot_table)
+            if (c.nv == 1) {
+                TT_P1(1, 16);
+            } else {
+                TT_P1(4, 4);
+            }
+#undef TT_P1
+            hipLaunchKernelGGL(voxel_pool_p2_kernel, dim3(l[1].grid), dim3(l[1].block), l[1].lds, st, C, cells, c.cps, kSlotBudget,
+                               partial, slot_table, output_features);
+            return check_launch("tt_voxel_pool_fwd_ws");
+        }
+        case VP_ROWS:
+#define LAUNCH(NV)                                                                                                              \
+    hipLaunchKernelGGL(voxel_pool_rows_kernel<NV>, dim3(l[0].grid), dim3(l[0].block), l[0].lds, st, total, Np, C, X, Y, Z, geom_xyz, \
+                       input_features, output_features, pos_memo)
+            switch (c.nv) {
+                case 1: LAUNCH(1); break;
+                case 2: LAUNCH(2); break;
+                case 3: LAUNCH(3); break;
+                default: LAUNCH(4); break;
+            }
+#undef LAUNCH
+            break;
+        default:
+            hipLaunchKernelGGL(voxel_pool_scalar_kernel, dim3(l[0].grid), dim3(l[0].block), l[0].lds, st, total, Np, C, X, Y, Z,
+                               geom_xyz, input_features, output_features, pos_memo);
+            break;
+    }
+    return check_launch("tt_voxel_pool_fwd");
+}
+
+static VoxelPoolCall pool_call(int B, int Np, int C, int X, int Y, const void* geom, const void* feats, const void* out,
+                               const void* ws, long long ws_bytes, bool ws_entry) {
+    VoxelPoolCall k;
+    k.B = B; k.Np = Np; k.C = C; k.X = X; k.Y = Y; k.geom = geom; k.feats = feats; k.out = out;
+    k.ws = ws_entry ? ws : nullptr; k.ws_bytes = ws_entry ? ws_bytes : 0; k.ws_entry = ws_entry; k.lds_granted = true;
+    return k;
+}
 
 extern "C" int tt_voxel_pool_fwd(int batch_size, int num_points, int num_channels,
                                  int num_voxel_x, int num_voxel_y, int num_voxel_z,
                                  const int32_t* geom_xyz, const float* input_features,
                                  float* output_features, int32_t* pos_memo, void* stream) {
-    TT_REQUIRE(batch_size >= 0 && num_points >= 0 && num_channels > 0,
-               "tt_voxel_pool_fwd: bad sizes B=%d Np=%d C=%d", batch_size, num_points, num_channels);
-    TT_REQUIRE(num_voxel_x > 0 && num_voxel_y > 0 && num_voxel_z > 0,
-               "tt_voxel_pool_fwd: bad voxel grid");
-    const long long total = (long long)batch_size * num_points;
-    if (total == 0) return 0;
-    TT_REQUIRE(geom_xyz && input_features && output_features, "tt_voxel_pool_fwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const int C = num_channels;
-    if (C % 4 == 0 && C <= 1024 &&
-        (reinterpret_cast<uintptr_t>(input_features) & 15) == 0) {
-        const long long nchunks = (total + 63) / 64;
-        // ~8 chunks per wave keeps 2048+ blocks on big inputs and still fills the chip on small ones
-        long long blocks = (nchunks + 4 * 8 - 1) / (4 * 8);
-        if (blocks < 1) blocks = 1;
-        if (blocks > kNumCU * 16) blocks = kNumCU * 16;
-        const int nv = (C / 4 + 63) / 64;
-#define LAUNCH(NV)                                                                             \
-    hipLaunchKernelGGL(voxel_pool_rows_kernel<NV>, dim3((unsigned)blocks), dim3(256), 0, st,  \
-                       total, num_points, C, num_voxel_x, num_voxel_y, num_voxel_z, geom_xyz, \
-                       input_features, output_features, pos_memo)
-        switch (nv) {
-            case 1: LAUNCH(1); break;
-            case 2: LAUNCH(2); break;
-            case 3: LAUNCH(3); break;
-            default: LAUNCH(4); break;
-        }
-#undef LAUNCH
-    } else {
-        const long long threads = total * C;
-        hipLaunchKernelGGL(voxel_pool_scalar_kernel, dim3((unsigned)div_up(threads, 256)), dim3(256),
-                           0, st, total, num_points, C, num_voxel_x, num_voxel_y, num_voxel_z,
-                           geom_xyz, input_features, output_features, pos_memo);
-    }
-    return check_launch("tt_voxel_pool_fwd");
-}
-
-
-// The two streaming kernels of the planned forward over `ngroups` groups of `cpg` cells (see vp_planned_segments_kernel).
-static void launch_planned(int C, int cpg, int segcap, int ngroups, const int* order, const int* cell_start, const int* seg_off,
-                           const float* input_features, float* output_features, float* partial, hipStream_t st) {
-    const unsigned blocks = (unsigned)div_up((long long)segcap * ngroups, 4);          // 4 waves per workgroup
-    // 32 rows in flight per wave, non-temporal row loads (measured against 8 / 16 rows and plain loads: profiles/r02_voxel_pool_*)
-#define TT_VP_SEG(NV_, RF_, NT_)                                                                                          \
-    hipLaunchKernelGGL((vp_planned_segments_kernel<NV_, RF_, NT_>), dim3(blocks), dim3(256), 0, st, C, cpg, segcap, ngroups, \
-                       order, cell_start, seg_off, input_features, partial)
-    if (C <= 256) {
-        TT_VP_SEG(1, 32, true);
-        hipLaunchKernelGGL(vp_planned_cells_kernel<1>, dim3((unsigned)(cpg * ngroups)), dim3(256), 0, st, C, cpg, segcap, seg_off,
-                           partial, output_features);
-    } else {
-        TT_VP_SEG(4, 4, true);
-        hipLaunchKernelGGL(vp_planned_cells_kernel<4>, dim3((unsigned)(cpg * ngroups)), dim3(256), 0, st, C, cpg, segcap, seg_off,
-                           partial, output_features);
-    }
-#undef TT_VP_SEG
-}
-
-static int v2_smax(int C) {
-    (void)C;
-    return 64;   // workspace rows per chunk (Lift-Splat chunks touch <= ~40 cells)
-}
-
-static bool v2_ok(long long total, int C, int X, int Y) {
-    return C % 4 == 0 && C <= 1024 && (long long)X * Y <= kMaxCells && v2_smax(C) >= 8 && total >= 4 * kChunk;
-}
-
-// ---- v3: per-launch counting sort + the planned streaming kernels (vp_cs_* above)
-static bool v3_ok(long long total, int num_points, int C, int X, int Y) {
-    static const bool on = env_flag("TT_VP_SORT", true);   // A/B knob
-    const long long cps = ((long long)num_points + kCsChunk - 1) / kCsChunk;
-    return on && C % 4 == 0 && C <= 1024 && (long long)X * Y <= kCsMaxCells && cps <= kCsMaxChunksPerSample &&
-           total >= 4 * kCsChunk && total < (1ll << 31);
-}
-
-struct V3Layout {
-    size_t keyrank, table, order, cell_start, seg_off, partial, bytes;
-    int cps, segcap;
-};
-
-static V3Layout v3_layout(int B, int num_points, int C, int cells) {
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    V3Layout L;
-    const size_t total = (size_t)B * num_points;
-    L.cps = (num_points + kCsChunk - 1) / kCsChunk;
-    L.segcap = num_points / kSeg + cells + 1;             // a sample's segments: <= floor(rows / 64) + one ragged one per cell
-    size_t off = 0;
-    L.keyrank = off; off += al(4 * total);
-    L.table = off; off += al(4 * (size_t)B * L.cps * cells);
-    L.order = off; off += al(4 * total);
-    L.cell_start = off; off += al(4 * (size_t)B * (cells + 1));
-    L.seg_off = off; off += al(4 * (size_t)B * (cells + 1));
-    L.partial = off; off += al(4 * (size_t)B * L.segcap * C);
-    L.bytes = off;
-    return L;
+    return pool_run(pool_call(batch_size, num_points, num_channels, num_voxel_x, num_voxel_y, geom_xyz, input_features, output_features,
+                              nullptr, 0, false),
+                    num_voxel_z, geom_xyz, input_features, output_features, pos_memo, nullptr, stream);
 }
 
 extern "C" long long tt_voxel_pool_workspace_bytes(int batch_size, int num_points, int num_channels,
                                                    int num_voxel_x, int num_voxel_y) {
-    const long long total = (long long)batch_size * num_points;
-    long long need = 0;
-    if (v2_ok(total, num_channels, num_voxel_x, num_voxel_y)) {
-        const long long cps = (num_points + kChunk - 1) / kChunk;
-        const long long nchunks = cps * batch_size;
-        const long long part = nchunks * v2_smax(num_channels) * num_channels * 4;
-        const long long tab = (long long)batch_size * num_voxel_x * num_voxel_y * cps * 4;
-        need = part + tab + 256;
-    }
-    if (v3_ok(total, num_points, num_channels, num_voxel_x, num_voxel_y)) {
-        const long long n3 = (long long)v3_layout(batch_size, num_points, num_channels, num_voxel_x * num_voxel_y).bytes;
-        if (n3 > need) need = n3;
-    }
-    return need;
-}
-
-static long long v2_workspace_bytes(int batch_size, int num_points, int num_channels, int num_voxel_x, int num_voxel_y) {
-    const long long total = (long long)batch_size * num_points;
-    if (!v2_ok(total, num_channels, num_voxel_x, num_voxel_y)) return 0;
-    const long long cps = (num_points + kChunk - 1) / kChunk;
-    const long long nchunks = cps * batch_size;
-    return nchunks * v2_smax(num_channels) * num_channels * 4 + (long long)batch_size * num_voxel_x * num_voxel_y * cps * 4 + 256;
+    return voxel_pool_workspace_bytes(batch_size, num_points, num_channels, num_voxel_x, num_voxel_y);
 }
 
 extern "C" int tt_voxel_pool_fwd_ws(int batch_size, int num_points, int num_channels, int num_voxel_x,
                                     int num_voxel_y, int num_voxel_z, const int32_t* geom_xyz,
                                     const float* input_features, float* output_features, int32_t* pos_memo,
                                     void* workspace, long long workspace_bytes, void* stream) {
-    const long long total = (long long)batch_size * num_points;
-    const bool aligned = !(reinterpret_cast<uintptr_t>(input_features) & 15) && !(reinterpret_cast<uintptr_t>(output_features) & 15) &&
-                         !(reinterpret_cast<uintptr_t>(workspace) & 15);
-    // > 64 KiB of dynamic LDS needs the opt-in (441 cells: 70 KiB, 1024: 160 KiB = the whole CU, which the opt-in asks for).  A
-    // device that refuses it takes the two-phase kernel below instead -- the one launcher with a fallback, so no error text
-    static_assert(kCsWaves * kCsMaxCells * (sizeof(unsigned short) + sizeof(unsigned long long)) <= 160 * 1024, "v3 LDS");
-    if (workspace && aligned && v3_ok(total, num_points, num_channels, num_voxel_x, num_voxel_y) &&
-        lds_opt_in(reinterpret_cast<const void*>(vp_cs_count_kernel), 160 * 1024, nullptr) == 0) {
-        const int cells = num_voxel_x * num_voxel_y;
-        const V3Layout L = v3_layout(batch_size, num_points, num_channels, cells);
-        if (workspace_bytes >= (long long)L.bytes) {
-            TT_REQUIRE(geom_xyz && input_features && output_features, "tt_voxel_pool_fwd_ws: null pointer");
-            hipStream_t st = (hipStream_t)stream;
-            char* w = static_cast<char*>(workspace);
-            unsigned* keyrank = reinterpret_cast<unsigned*>(w + L.keyrank);
-            int* table = reinterpret_cast<int*>(w + L.table);
-            int* order = reinterpret_cast<int*>(w + L.order);
-            int* cell_start = reinterpret_cast<int*>(w + L.cell_start);
-            int* seg_off = reinterpret_cast<int*>(w + L.seg_off);
-            float* partial = reinterpret_cast<float*>(w + L.partial);
-            const int nchunks = L.cps * batch_size;
-            const size_t lds = (size_t)kCsWaves * ((cells + 63) & ~63) * (sizeof(unsigned short) + sizeof(unsigned long long));
-            hipLaunchKernelGGL(vp_cs_count_kernel, dim3((unsigned)nchunks), dim3(kCsWaves * 64), lds, st, num_points, num_voxel_x,
-                               num_voxel_y, num_voxel_z, L.cps, geom_xyz, pos_memo, keyrank, table);
-            hipLaunchKernelGGL(vp_cs_scan_kernel, dim3((unsigned)batch_size), dim3(1024), 0, st, num_points, cells, L.cps, table,
-                               cell_start, seg_off);
-            hipLaunchKernelGGL(vp_cs_scatter_kernel, dim3((unsigned)div_up(total, 256)), dim3(256), 0, st, total, num_points, cells,
-                               L.cps, keyrank, table, order);
-            launch_planned(num_channels, cells, L.segcap, batch_size, order, cell_start, seg_off, input_features, output_features,
-                           partial, st);
-            return check_launch("tt_voxel_pool_fwd_ws");
-        }
-    }
-    const long long need = v2_workspace_bytes(batch_size, num_points, num_channels, num_voxel_x, num_voxel_y);
-    if (need == 0 || !workspace || workspace_bytes < need ||
-        (reinterpret_cast<uintptr_t>(input_features) & 15) || (reinterpret_cast<uintptr_t>(output_features) & 15))
-        return tt_voxel_pool_fwd(batch_size, num_points, num_channels, num_voxel_x, num_voxel_y, num_voxel_z,
-                                 geom_xyz, input_features, output_features, pos_memo, stream);
-    TT_REQUIRE(geom_xyz && input_features && output_features, "tt_voxel_pool_fwd_ws: null pointer");
-    (void)total;
-    hipStream_t st = (hipStream_t)stream;
-    const int C = num_channels, cells = num_voxel_x * num_voxel_y;
-    const int cps = (num_points + kChunk - 1) / kChunk;
-    const int nchunks = cps * batch_size;
-    const int smax = v2_smax(C);
-    float* partial = reinterpret_cast<float*>(workspace);
-    const long long part_bytes = (long long)nchunks * smax * C * 4;
-    int* slot_table = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + ((part_bytes + 255) / 256) * 256);
-    // 16 rows in flight per wave (0.302 / 0.287 / 0.277 ms per launch for 4 / 8 / 16, profiles/r02_voxel_pool_*), non-temporal loads
-#define TT_P1(NV, RF)                                                                                              \
-    hipLaunchKernelGGL((voxel_pool_p1_kernel<NV, RF, true>), dim3((unsigned)nchunks), dim3(512), 0, st,            \
-                       num_points, C, num_voxel_x, num_voxel_y, num_voxel_z, cps, smax, geom_xyz,                  \
-                       input_features, output_features, pos_memo, partial, slot_table)
-    if (C <= 256) {
-        TT_P1(1, 16);
-    } else {
-        TT_P1(4, 4);
-    }
-#undef TT_P1
-    hipLaunchKernelGGL(voxel_pool_p2_kernel, dim3((unsigned)(batch_size * cells)), dim3(64), 0, st, C, cells, cps,
-                       smax, partial, slot_table, output_features);
-    return check_launch("tt_voxel_pool_fwd_ws");
+    return pool_run(pool_call(batch_size, num_points, num_channels, num_voxel_x, num_voxel_y, geom_xyz, input_features, output_features,
+                              workspace, workspace_bytes, true),
+                    num_voxel_z, geom_xyz, input_features, output_features, pos_memo, workspace, stream);
+}
+
+extern "C" int tt_voxel_pool_fwd_plan(int batch_size, int num_points, int num_channels, int num_voxel_x, int num_voxel_y,
+                                      int num_voxel_z, const int32_t* geom_xyz, const float* input_features,
+                                      float* output_features, int32_t* pos_memo, void* workspace, long long workspace_bytes,
+                                      int ws_entry, char* label, int label_bytes) {
+    (void)pos_memo;
+    VoxelPoolChoice c;
+    bool launches;
+    if (int rc = pool_prepare(pool_call(batch_size, num_points, num_channels, num_voxel_x, num_voxel_y, geom_xyz, input_features,
+                                        output_features, workspace, workspace_bytes, ws_entry != 0),
+                              num_voxel_z, c, &launches))
+        return rc;
+    TT_REQUIRE(label && label_bytes > 0, "tt_voxel_pool_fwd_plan: no room for the label");
+    vp_label(c.launch, launches ? c.nlaunch : 0, c.nv, c.rf, nullptr, c.ws_bytes, label, (size_t)label_bytes);
+    return 0;
 }
 
 extern "C" int tt_voxel_pool_bwd(int batch_size, int num_points, int num_channels,
@@ -1548,126 +956,23 @@ extern "C" int tt_voxel_pool_bwd(int batch_size, int num_points, int num_channel
     return check_launch("tt_voxel_pool_bwd");
 }
 
-extern "C" int tt_frustum_voxel_index(int batch_size, int num_cams, int D, int fH, int fW,
-                                      const float* frustum, const float* mats,
-                                      const float* voxel_lo, const float* voxel_size,
-                                      int32_t* geom_xyz, float* geom_f32_or_null, void* stream) {
-    TT_REQUIRE(frustum && mats && voxel_lo && voxel_size && geom_xyz,
-               "tt_frustum_voxel_index: null pointer");
-    const long long total = (long long)batch_size * num_cams * D * fH * fW;
-    if (total == 0) return 0;
-    // voxel_lo / voxel_size are HOST pointers (3 floats each): module constants.
-    hipLaunchKernelGGL(frustum_voxel_index_kernel, dim3((unsigned)div_up(total, 256)), dim3(256), 0,
-                       (hipStream_t)stream, batch_size, num_cams, D, fH, fW, frustum, mats,
-                       voxel_lo[0], voxel_lo[1], voxel_lo[2], voxel_size[0], voxel_size[1],
-                       voxel_size[2], geom_xyz, geom_f32_or_null);
-    return check_launch("tt_frustum_voxel_index");
-}
-
-static size_t vp_align(size_t v) { return (v + 255) / 256 * 256; }
-
-static bool lift_splat_strip_ok(int D, int fH, int X, int Y) {
-    return fH * kStripW <= kMaxStripPix && D <= kMaxD && X * Y <= kMaxCells;
-}
-
-extern "C" long long tt_lift_splat_workspace_bytes(int batch_size, int num_cams, int D, int fH, int fW, int C,
-                                                   int num_voxel_x, int num_voxel_y) {
-    if (!lift_splat_strip_ok(D, fH, num_voxel_x, num_voxel_y)) return 0;
-    const long long blocks = (long long)batch_size * num_cams * div_up(fW, kStripW);
-    return (long long)vp_align((size_t)blocks * kMaxSlots * C * sizeof(float)) +
-           (long long)vp_align((size_t)blocks * num_voxel_x * num_voxel_y);
-}
-
-template <typename T>
-static int launch_lift_splat(int batch_size, int num_cams, int D, int fH, int fW, int C, int X, int Y, int Z,
-                             const void* depth_logits, const void* context, const int32_t* geom_xyz, float* out,
-                             int out_cstride, int out_coff, int rot_flip, float* ws_rows, unsigned char* slot_of,
-                             hipStream_t st) {
-    if (lift_splat_strip_ok(D, fH, X, Y)) {
-        const int strips = div_up(fW, kStripW);
-        const unsigned sblocks = (unsigned)(batch_size * num_cams * strips);
-        const size_t lds = lift_splat_strip_lds(D, C, X * Y);
-        const size_t lds_max = lift_splat_strip_lds(kMaxD, kStageC, kMaxCells);     // the largest request the limits allow
-        if (lds_opt_in(reinterpret_cast<const void*>(lift_splat_strip_kernel<T>), lds_max, "lift_splat_strip_kernel")) return -1;
-        hipLaunchKernelGGL(lift_splat_strip_kernel<T>, dim3(sblocks), dim3(256), lds, st, batch_size, num_cams, D, fH, fW, C,
-                           X, Y, Z, (const T*)depth_logits, (const T*)context, geom_xyz, out, out_cstride, out_coff,
-                           rot_flip, ws_rows, slot_of);
-        if (ws_rows) {
-            const long long waves = (long long)batch_size * X * Y;
-            hipLaunchKernelGGL(lift_splat_cells_kernel, dim3((unsigned)div_up(waves, 4)), dim3(256), 0, st, batch_size,
-                               num_cams * strips, C, X, Y, ws_rows, slot_of, out, out_cstride, out_coff, rot_flip);
-        }
-        return 0;
-    }
-    const long long npix = (long long)batch_size * num_cams * fH * fW;
-    hipLaunchKernelGGL(lift_splat_kernel<T>, dim3((unsigned)div_up(npix, 4)), dim3(256), 0, st, batch_size, num_cams, D,
-                       fH, fW, C, X, Y, Z, (const T*)depth_logits, (const T*)context, geom_xyz, out, out_cstride,
-                       out_coff, rot_flip);
-    return 0;
-}
-
-// `ws` (tt_lift_splat_workspace_bytes, contents don't matter) selects the atomics-free, bit-reproducible form; without
-// it (or for shapes outside the strip kernel's limits) the partial rows are added with f32 atomics.
-extern "C" int tt_lift_splat_fwd_ws(int batch_size, int num_cams, int D, int fH, int fW, int C,
-                                    int num_voxel_x, int num_voxel_y, int num_voxel_z,
-                                    const void* depth_logits, const void* context, int dtype,
-                                    const int32_t* geom_xyz, float* out, int out_cstride, int out_coff,
-                                    int rot_flip, void* ws, long long ws_bytes, void* stream) {
-    TT_REQUIRE(depth_logits && context && geom_xyz && out, "tt_lift_splat_fwd: null pointer");
-    TT_REQUIRE(D > 0 && D <= 128, "tt_lift_splat_fwd: D=%d unsupported (1..128)", D);
-    TT_REQUIRE(C > 0 && C % 4 == 0 && C <= 1024, "tt_lift_splat_fwd: C=%d unsupported", C);
-    TT_REQUIRE(out_cstride % 4 == 0 && out_coff % 4 == 0 || !ws, "tt_lift_splat_fwd: workspace form needs 16 B aligned rows");
-    const long long npix = (long long)batch_size * num_cams * fH * fW;
-    if (npix == 0) return 0;
-    float* ws_rows = nullptr;
-    unsigned char* slot_of = nullptr;
-    const long long need = tt_lift_splat_workspace_bytes(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y);
-    if (ws && need > 0) {
-        TT_REQUIRE(ws_bytes >= need, "tt_lift_splat_fwd_ws: workspace %lld B < %lld B", ws_bytes, need);
-        const long long blocks = (long long)batch_size * num_cams * div_up(fW, kStripW);
-        ws_rows = (float*)ws;
-        slot_of = (unsigned char*)ws + vp_align((size_t)blocks * kMaxSlots * C * sizeof(float));
-    }
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == TT_F32)
-        rc = launch_lift_splat<float>(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
-                                      context, geom_xyz, out, out_cstride, out_coff, rot_flip, ws_rows, slot_of, st);
-    else if (dtype == TT_BF16)
-        rc = launch_lift_splat<uint16_t>(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
-                                         context, geom_xyz, out, out_cstride, out_coff, rot_flip, ws_rows, slot_of, st);
-    else if (dtype == TT_F16)
-        rc = launch_lift_splat<f16_t>(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
-                                      context, geom_xyz, out, out_cstride, out_coff, rot_flip, ws_rows, slot_of, st);
-    else
-        TT_REQUIRE(false, "tt_lift_splat_fwd: bad dtype %d", dtype);
-    return rc ? rc : check_launch("tt_lift_splat_fwd");
-}
-
-extern "C" int tt_lift_splat_fwd(int batch_size, int num_cams, int D, int fH, int fW, int C,
-                                 int num_voxel_x, int num_voxel_y, int num_voxel_z,
-                                 const void* depth_logits, const void* context, int dtype,
-                                 const int32_t* geom_xyz, float* out, int out_cstride, int out_coff,
-                                 int rot_flip, void* stream) {
-    return tt_lift_splat_fwd_ws(batch_size, num_cams, D, fH, fW, C, num_voxel_x, num_voxel_y, num_voxel_z, depth_logits,
-                                context, dtype, geom_xyz, out, out_cstride, out_coff, rot_flip, nullptr, 0, stream);
-}
-
 // ---- static-geometry plan ------------------------------------------------------------------------------------
 
 extern "C" long long tt_voxel_pool_plan_bytes(int batch_size, int num_points, int num_voxel_x, int num_voxel_y) {
-    const long long total = (long long)batch_size * num_points;
-    const long long nkeys = (long long)batch_size * num_voxel_x * num_voxel_y;
-    // order [total] + cell_start [nkeys + 1] + seg_off [nkeys + 1]
-    return (long long)(vp_align(4 * total) + 2 * vp_align(4 * (nkeys + 1)));
+    return (long long)vp_static_plan_layout(batch_size, num_points, num_voxel_x, num_voxel_y).end;
+}
+
+// The build's workspace: keys | vals | keys_sorted (u32 [total] each, vp_align'ed) | the radix sort's own
+static size_t plan_sort_bytes(long long total) {
+    size_t sort_bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr,
+                                       (unsigned*)nullptr, (int)total);
+    return sort_bytes;
 }
 
 extern "C" long long tt_voxel_pool_plan_workspace_bytes(int batch_size, int num_points) {
     const long long total = (long long)batch_size * num_points;
-    size_t sort_bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr,
-                                       (unsigned*)nullptr, (int)total);
-    return (long long)(3 * vp_align(4 * total) + vp_align(sort_bytes));
+    return (long long)(3 * vp_align(4 * total) + vp_align(plan_sort_bytes(total)));
 }
 
 extern "C" int tt_voxel_pool_plan_build(int batch_size, int num_points, int num_voxel_x, int num_voxel_y, int num_voxel_z,
@@ -1677,20 +982,21 @@ extern "C" int tt_voxel_pool_plan_build(int batch_size, int num_points, int num_
     const long long total = (long long)batch_size * num_points;
     const long long nkeys = (long long)batch_size * num_voxel_x * num_voxel_y;
     TT_REQUIRE(total > 0 && total < (1ll << 31) && nkeys < (1ll << 30), "tt_voxel_pool_plan_build: sizes");
-    TT_REQUIRE(workspace_bytes >= tt_voxel_pool_plan_workspace_bytes(batch_size, num_points) &&
-                   plan_bytes >= tt_voxel_pool_plan_bytes(batch_size, num_points, num_voxel_x, num_voxel_y),
+    const VpCsrLayout L = vp_static_plan_layout(batch_size, num_points, num_voxel_x, num_voxel_y);
+    TT_REQUIRE(workspace_bytes >= tt_voxel_pool_plan_workspace_bytes(batch_size, num_points) && plan_bytes >= (long long)L.end,
                "tt_voxel_pool_plan_build: buffers too small");
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)workspace;
+    const size_t col = vp_align(4 * total);
     unsigned* keys = (unsigned*)w;
-    unsigned* vals = (unsigned*)(w + vp_align(4 * total));
-    unsigned* keys_sorted = (unsigned*)(w + 2 * vp_align(4 * total));
-    void* tmp = w + 3 * vp_align(4 * total);
-    size_t tmp_bytes = (size_t)(workspace_bytes - 3 * (long long)vp_align(4 * total));
+    unsigned* vals = (unsigned*)(w + col);
+    unsigned* keys_sorted = (unsigned*)(w + 2 * col);
+    void* tmp = w + 3 * col;
+    size_t tmp_bytes = (size_t)(workspace_bytes - 3 * (long long)col);
     char* pl = (char*)plan;
-    int* order = (int*)pl;
-    int* cell_start = (int*)(pl + vp_align(4 * total));
-    int* seg_off = (int*)(pl + vp_align(4 * total) + vp_align(4 * (nkeys + 1)));
+    int* order = (int*)(pl + L.order);
+    int* cell_start = (int*)(pl + L.cell_start);
+    int* seg_off = (int*)(pl + L.seg_off);
     hipLaunchKernelGGL(vp_plan_keys_kernel, dim3((unsigned)div_up(total, 256)), dim3(256), 0, st, total, num_points,
                        num_voxel_x, num_voxel_y, num_voxel_z, geom_xyz, keys, vals, (unsigned)nkeys);
     int bits = 1;
@@ -1708,9 +1014,7 @@ extern "C" int tt_voxel_pool_plan_build(int batch_size, int num_points, int num_
 
 extern "C" long long tt_voxel_pool_planned_workspace_bytes(int batch_size, int num_points, int num_channels,
                                                            int num_voxel_x, int num_voxel_y) {
-    const long long total = (long long)batch_size * num_points;
-    const long long nkeys = (long long)batch_size * num_voxel_x * num_voxel_y;
-    return (total / kSeg + nkeys + 1) * (long long)num_channels * 4;       // one partial row per segment (upper bound)
+    return vp_static_plan_layout(batch_size, num_points, num_voxel_x, num_voxel_y).partial_bytes(num_channels);
 }
 
 extern "C" int tt_voxel_pool_fwd_planned(int batch_size, int num_points, int num_channels, int num_voxel_x,
@@ -1720,16 +1024,12 @@ extern "C" int tt_voxel_pool_fwd_planned(int batch_size, int num_points, int num
     const int C = num_channels;
     TT_REQUIRE(C % 4 == 0 && C <= 1024 && !(reinterpret_cast<uintptr_t>(input_features) & 15) &&
                    !(reinterpret_cast<uintptr_t>(output_features) & 15), "tt_voxel_pool_fwd_planned: C %% 4, 16 B alignment");
-    TT_REQUIRE(workspace_bytes >= tt_voxel_pool_planned_workspace_bytes(batch_size, num_points, C, num_voxel_x, num_voxel_y),
-               "tt_voxel_pool_fwd_planned: workspace too small");
-    const long long total = (long long)batch_size * num_points;
-    const long long nkeys = (long long)batch_size * num_voxel_x * num_voxel_y;
-    const char* pl = (const char*)plan;
-    const int* order = (const int*)pl;
-    const int* cell_start = (const int*)(pl + vp_align(4 * total));
-    const int* seg_off = (const int*)(pl + vp_align(4 * total) + vp_align(4 * (nkeys + 1)));
-    const long long max_seg = total / kSeg + nkeys + 1;
-    launch_planned(C, (int)nkeys, (int)max_seg, 1, order, cell_start, seg_off, input_features, output_features,
-                   (float*)workspace, (hipStream_t)stream);
+    const VpCsrLayout L = vp_static_plan_layout(batch_size, num_points, num_voxel_x, num_voxel_y);
+    TT_REQUIRE(workspace_bytes >= L.partial_bytes(C), "tt_voxel_pool_fwd_planned: workspace too small");
+    int nv, rf;
+    VpLaunch l[2];
+    vp_planned_launches(C, L, &nv, &rf, l);
+    launch_planned(C, L, l, l + 1, nv, (const char*)plan, input_features, output_features, (float*)workspace, (hipStream_t)stream);
     return check_launch("tt_voxel_pool_fwd_planned");
 }
+

@@ -17,8 +17,10 @@ from . import _lib
 
 
 def _pool_launch(B, Np, C, vx, vy, vz, geom_xyz, input_features, out, pos_memo):
-    """tt_voxel_pool_fwd_ws with a torch-allocated workspace (atomics-free two-phase kernel); the
-    library itself falls back to the single-pass atomic kernel for shapes the fast path does not cover."""
+    """tt_voxel_pool_fwd_ws with a torch-allocated workspace of tt_voxel_pool_workspace_bytes: the per-launch counting sort +
+    planned streaming kernels from 32,768 points on, the two-phase kernels from 8,192, else (or for shapes neither takes: the
+    query answers 0) the single-pass atomic kernel.  The library chooses (csrc/voxel_pool_choose.cpp); tt_voxel_pool_fwd_plan
+    spells the choice."""
     L = _lib.lib()
     ws_bytes = int(L.tt_voxel_pool_workspace_bytes(B, Np, C, vx, vy))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input_features.device) if ws_bytes > 0 else None
