@@ -634,9 +634,9 @@ int tt_preprocess_images_ida_aug(const uint8_t* raw_hwc, int B, int T, int N, in
 
 /* ------------------------------------------------------------------------
  * The two label inputs of the training image pipeline from the dataset's raw bytes: LoadDepth.__call__ and LoadSeg.__call__
- * with red_green_yellow (open_loop_training/code/datasets/pipelines/loading.py:84-93, :96-113, :132-162).  PNG file decoding
- * and union2one's meta merge stay on the host.  Everything but the depth quotient is integer arithmetic: the outputs are
- * bit-identical from run to run.
+ * with red_green_yellow (open_loop_training/code/datasets/pipelines/loading.py:84-93, :96-113, :132-162).  The PNG files are
+ * decoded by tt_png_decode_u8 (below); union2one's meta merge stays on the host.  Everything but the depth quotient is integer
+ * arithmetic: the outputs are bit-identical from run to run.
  * ---------------------------------------------------------------------- */
 /* loading.py:88-90.  CARLA depth PNG pixels uint8 [n_pixels, 3] (R, G, B) -> metres f32 [n_pixels]:
  * f32(f32(code / 16777215.0f) * 1000.0f), code = R + 256 G + 65536 B (exact in f32), the division IEEE-rounded, nothing
@@ -693,6 +693,69 @@ int tt_decode_seg_u8(const uint8_t* tags_u8, int num_samples, int cams, int H, i
 int tt_decode_seg_u8_phases(const uint8_t* tags_u8, int num_samples, int cams, int H, int W, const uint8_t* rgb_u8,
                             long long rgb_sample_stride_bytes, const tt_seg_decode_conf* conf, void* workspace,
                             long long workspace_bytes, float* out_f32, int last_phase, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The dataset's PNG files decoded on the device: what `np.array(Image.open(...))` returns for the camera frames, the depth
+ * maps and the segmentation maps (open_loop_training/code/datasets/pipelines/loading.py:40-49, :127-131), from the files'
+ * zlib streams.  The files are PIL's (`Image.fromarray(a).save(path)`): 8-bit, non-interlaced, colour type 2 (RGB) or 0
+ * (grey), one zlib stream over the IDAT chunks, a filter type per row.  The decoder is specified for that family: chunk
+ * walking is the caller's (thinktwice_amd/png.py::parse_png); the device gets the concatenated IDAT payload.
+ *
+ * One call decodes `num_images` images in two stream-ordered launches, nothing between them on the host:
+ *   inflate   one 64-lane workgroup per image: RFC 1950 wrapper (CM = 8, window <= 32 KiB, no preset dictionary), RFC 1951
+ *             stored, fixed and dynamic blocks -> the filtered scanlines, H * (1 + W * C) bytes, in the workspace.  The window
+ *             is a 32 KiB ring in LDS; a match of any overlap gives byte i = out[pos - dist + (i mod dist)].
+ *   unfilter  one 64-lane workgroup per image, 64 consecutive rows as a skewed wavefront (PNG specification section 9:
+ *             None, Sub, Up, Average, Paeth) -> uint8 [H, W, C] at out_base + dst_offset, the filter bytes dropped.
+ * Layouts.  packed_dev: one device buffer, 16-byte aligned, that holds every stream (and may hold images_dev); image i's
+ * stream is its bytes [stream_offset, stream_offset + stream_bytes).  The table lives in host memory (images_host, validated
+ * by the entry before any launch) and in device memory (images_dev, read by the kernels): it is past what kernel arguments
+ * hold.  dst_offset lets one call fill slots of several tensors (raw[b, t, n], depth[b, n], seg[b, n]): offsets are relative
+ * to out_base, destinations may lie in any order and must not overlap.  workspace: tt_png_workspace_bytes(...) bytes, 256-byte
+ * aligned; image i's scanlines start at the sum of the earlier images' sizes, each rounded up to 256.  Its contents on entry
+ * never matter.  status_dev: int32 [num_images], written by the kernels: TT_PNG_OK or the first error of the image.  An
+ * image with an error leaves its destination untouched and does not affect the others.
+ * NOT checked: the Adler-32 trailer of the zlib stream (its four bytes must be present, their value is not read), and
+ * nothing of the PNG container (chunk CRC-32s are the host parser's, optional there).
+ * Returns an error before any launch for: a null pointer; num_images < 1 or > TT_PNG_MAX_IMAGES; channels not 1 or 3; a
+ * non-positive width or height; width > TT_PNG_MAX_WIDTH; H * (1 + W * C) above 2^31 - 1; a stream range outside
+ * packed_bytes, shorter than 6 bytes or longer than 2^31 - 17; a destination range outside out_bytes; destinations that
+ * overlap; a packed buffer or workspace that is misaligned; a workspace that is too small.  No allocation, no copy, no
+ * synchronisation.
+ * ---------------------------------------------------------------------- */
+#define TT_PNG_MAX_IMAGES 1024
+#define TT_PNG_MAX_WIDTH 8192            /* pixels per row: the unfilter keeps one row of packed pixels in LDS */
+enum tt_png_status {
+    TT_PNG_OK = 0,
+    TT_PNG_TRUNCATED = 1,                /* the stream ends inside a header, a code, extra bits, stored bytes or the Adler-32 */
+    TT_PNG_BAD_ZLIB_HEADER = 2,          /* CM != 8, window > 32 KiB, FCHECK, or a preset dictionary */
+    TT_PNG_BAD_BLOCK_TYPE = 3,           /* BTYPE 3 */
+    TT_PNG_BAD_STORED_LEN = 4,           /* LEN != ~NLEN */
+    TT_PNG_BAD_CODE_LENGTHS = 5,         /* over-subscribed or unacceptably incomplete code, a repeat with no previous length,
+                                            a run past the last code, HLIT > 286, HDIST > 30, no end-of-block code */
+    TT_PNG_BAD_SYMBOL = 6,               /* a bit pattern no code has; length symbol 286 / 287, distance symbol 30 / 31 */
+    TT_PNG_BAD_DISTANCE = 7,             /* a distance before the first output byte or beyond the stream's window */
+    TT_PNG_OUTPUT_OVERRUN = 8,           /* more than H * (1 + W * C) bytes */
+    TT_PNG_OUTPUT_SHORT = 9,             /* fewer */
+    TT_PNG_BAD_FILTER = 10               /* a row's filter type above 4 */
+};
+typedef struct tt_png_image {
+    long long stream_offset;             /* of the zlib stream in packed_dev, bytes */
+    long long stream_bytes;              /* >= 6 */
+    long long dst_offset;                /* of the image's uint8 [H, W, C] in out_base, bytes */
+    int width, height;
+    int channels;                        /* 1 (grey) or 3 (RGB) */
+    int reserved;                        /* not read */
+} tt_png_image;                          /* 40 bytes */
+/* Host arithmetic only; 0 for a null table, a bad count or an image the entry would refuse for its sizes. */
+long long tt_png_workspace_bytes(const tt_png_image* images_host, int num_images);
+int tt_png_decode_u8(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
+                     const tt_png_image* images_dev, int num_images, void* workspace, long long workspace_bytes,
+                     uint8_t* out_base, long long out_bytes, int32_t* status_dev, void* stream);
+/* Measurement only (thinktwice_amd/bench_png.py): the same call with only the inflate launch (phases = 1) or both (2). */
+int tt_png_decode_u8_phases(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
+                            const tt_png_image* images_dev, int num_images, void* workspace, long long workspace_bytes,
+                            uint8_t* out_base, long long out_bytes, int32_t* status_dev, int phases, void* stream);
 
 /* ------------------------------------------------------------------------
  * SURVEY 8f-4 (training step), optimizer half: the reference's `optimizer_config = dict(grad_clip=dict(max_norm=100,

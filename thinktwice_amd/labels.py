@@ -1,7 +1,7 @@
 """The two label inputs of the training image pipeline from the dataset's raw bytes, on the device: LoadDepth.__call__ and
 LoadSeg.__call__ with red_green_yellow (open_loop_training/code/datasets/pipelines/loading.py:84-93, :96-113, :132-162).  The
 host side: the class map, the thresholds and the HSV division tables of tt_seg_decode_conf (include/thinktwice_hip.h); the
-kernels (csrc/labels.hip) execute them.  PNG file decoding stays in the loader (union2one's merge: sweeps.py).
+kernels (csrc/labels.hip) execute them.  The PNG files themselves are decoded by png.py (union2one's merge: sweeps.py).
 
     decoder = labels.RawLabelDecoder(cfg.seg_label_idxs)
     depth, seg = decoder(raw, depth_rgb_u8, seg_tags_u8)       # raw [B, T, N, H, W, 3], [B, N, H, W, 3], [B, N, H, W], uint8

@@ -1,0 +1,250 @@
+"""The dataset's PNG files decoded on the device: what `np.array(Image.open(path))` returns in LoadMultiImages and LoadSeg
+(open_loop_training/code/datasets/pipelines/loading.py:40-49, :127-131), from the file bytes.  The host walks the chunks
+(`parse_png`) and packs the zlib streams; inflate and unfilter run on the device (csrc/png.hip, tt_png_decode_u8 in
+include/thinktwice_hip.h).  What stays in the loader is reading the files.
+
+    decoder = png.PngDecoder()
+    raw, depth_png, seg_png = decoder.decode_sample_batch(rgb_files, depth_files, seg_files)   # [B][T][N], [B][N], [B][N] of bytes
+    depth, seg = labels.RawLabelDecoder(cfg.seg_label_idxs)(raw, depth_png, seg_png)
+
+Specified for the files PIL writes (`Image.fromarray(a).save(path)`): 8-bit, non-interlaced, colour type 0 or 2.  Anything
+else is a ValueError on the host.  Not checked: the zlib stream's Adler-32 (never), the chunks' CRC-32 (only with
+verify_crc=True, on the host)."""
+import collections
+import ctypes
+import struct
+import zlib
+
+import numpy as np
+
+from . import _lib
+from .ops import check, lib, ptr
+
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PngInfo = collections.namedtuple("PngInfo", "width height channels zlib_stream")
+PngImage = _lib.structs()["tt_png_image"]
+STATUS_NAMES = {v: k for k, v in _lib.constants().items() if k.startswith("TT_PNG_") and not k.startswith("TT_PNG_MAX")}
+
+
+class PngDecodeError(_lib.TTError):
+    """Some images of a call did not decode: `failed` is [(index, status name)], in call order."""
+
+    def __init__(self, failed):
+        self.failed = failed
+        super().__init__("PNG decode failed for " + ", ".join(f"image {i}: {name}" for i, name in failed))
+
+
+def parse_png(data, verify_crc=False):
+    """file bytes -> PngInfo(width, height, channels, zlib_stream): the IDAT chunks' payload, concatenated.  Host only.
+    ValueError, naming what was found, for anything but an 8-bit non-interlaced grey or RGB file with consecutive IDAT chunks
+    and an IEND at its end.  verify_crc: check every chunk's CRC-32 (zlib.crc32); off by default, it is host time."""
+    width, height, channels, parts = _walk(data, verify_crc)
+    return PngInfo(width, height, channels, bytes(parts[0]) if len(parts) == 1 else b"".join(parts))
+
+
+def _walk(data, verify_crc):
+    """(width, height, channels, [the IDAT bodies as views of `data`]): nothing is copied."""
+    data = memoryview(data if isinstance(data, (bytes, bytearray, memoryview)) else bytes(data)).cast("B")
+    if len(data) < 8 or bytes(data[:8]) != SIGNATURE:
+        raise ValueError("not a PNG file: bad signature")
+    pos, ihdr, idat, state = 8, None, [], "before"         # of the IDAT run: before, inside, after
+    while True:
+        if pos + 12 > len(data):
+            raise ValueError(f"PNG: the file ends at byte {len(data)} inside a chunk header (no IEND)")
+        n, kind = struct.unpack_from(">I4s", data, pos)
+        if pos + 12 + n > len(data):
+            raise ValueError(f"PNG: chunk {kind!r} at byte {pos} has length {n}, which runs past the file's {len(data)} bytes")
+        body = data[pos + 8:pos + 8 + n]
+        if verify_crc:
+            want, = struct.unpack_from(">I", data, pos + 8 + n)
+            if zlib.crc32(body, zlib.crc32(kind)) != want:
+                raise ValueError(f"PNG: chunk {kind!r} at byte {pos} fails its CRC-32")
+        pos += 12 + n
+        if ihdr is None and kind != b"IHDR":
+            raise ValueError(f"PNG: the first chunk is {kind!r}, not IHDR")
+        if kind == b"IHDR":
+            if ihdr is not None or n != 13:
+                raise ValueError("PNG: a second or malformed IHDR")
+            ihdr = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            if state == "after":
+                raise ValueError("PNG: IDAT chunks are not consecutive")
+            state = "inside"
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+        else:
+            if not kind[0] & 0x20:
+                raise ValueError(f"PNG: critical chunk {kind!r} is not supported" + (" (a palette file)" if kind == b"PLTE" else ""))
+            if state == "inside":
+                state = "after"
+    if pos != len(data):
+        raise ValueError(f"PNG: {len(data) - pos} bytes after IEND")
+    width, height, depth, colour, compression, filter_method, interlace = ihdr
+    if depth != 8:
+        raise ValueError(f"PNG: bit depth {depth}, only 8 is supported")
+    if colour not in (0, 2):
+        what = {3: "palette", 4: "grey + alpha", 6: "RGBA"}.get(colour, "unknown")
+        raise ValueError(f"PNG: colour type {colour} ({what}), only 0 (grey) and 2 (RGB) are supported")
+    if compression != 0 or filter_method != 0:
+        raise ValueError(f"PNG: compression method {compression}, filter method {filter_method}: only 0 / 0 exist")
+    if interlace != 0:
+        raise ValueError(f"PNG: interlace method {interlace} (Adam7), only non-interlaced files are supported")
+    if width < 1 or height < 1:
+        raise ValueError(f"PNG: {width} x {height} pixels")
+    if not idat:
+        raise ValueError("PNG: no IDAT chunk")
+    return width, height, 1 if colour == 0 else 3, idat
+
+
+def _parts(info):
+    """The pieces of an image's zlib stream: PngDecoder parses into views of the file bytes (a PngInfo whose zlib_stream is
+    the tuple of IDAT bodies) and writes them straight into the staging buffer; a PngInfo from parse_png holds one piece."""
+    z = info.zlib_stream
+    return z if isinstance(z, tuple) else (z,)
+
+
+def _up(n, a):
+    return (n + a - 1) // a * a
+
+
+class PngDecoder:
+    """Decodes batches of PNG files on `device`.  Holds and reuses the pinned staging buffer, the device copy of it, the
+    workspace and the status array: they grow when a batch needs more and never shrink.  One call = one pinned host-to-device
+    copy (the image table and every stream), two launches, and -- with check=True -- one small copy of the statuses back.
+    The streams are copied once on the host, from the file bytes into the staging buffer.  The buffers are reused from call
+    to call without synchronising, so all calls of one decoder must be on ONE stream (the current stream at each call); use a
+    decoder per stream otherwise."""
+
+    def __init__(self, device="cuda", verify_crc=False):
+        import torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("PngDecoder needs a GPU device: there is no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.verify_crc = verify_crc
+        self._stage = self._packed = self._work = self._status = self._copied = None
+
+    def _grow(self, name, n, **kw):
+        import torch
+        t = getattr(self, name)
+        if t is None or t.numel() < n:
+            t = torch.empty(_up(max(n, 1), 1 << 16), **kw)
+            setattr(self, name, t)
+        return t
+
+    def _pack(self, infos, dst_offsets):
+        """The call's one host buffer, in the pinned staging tensor: the image table, then every stream at a 16-byte aligned
+        offset -> (table, its bytes)."""
+        import torch
+        n = len(infos)
+        if not 1 <= n <= _lib.TT_PNG_MAX_IMAGES:
+            raise ValueError(f"{n} images in one call, 1..{_lib.TT_PNG_MAX_IMAGES}")
+        table = (PngImage * n)()
+        pos = _up(ctypes.sizeof(table), 256)
+        for i, (info, dst) in enumerate(zip(infos, dst_offsets)):
+            im = table[i]
+            nbytes = sum(len(part) for part in _parts(info))
+            im.stream_offset, im.stream_bytes, im.dst_offset = pos, nbytes, dst
+            im.width, im.height, im.channels = info.width, info.height, info.channels
+            pos = _up(pos + nbytes, 16)
+        if self._copied is not None:
+            self._copied.synchronize()                      # the previous call's copy has left the staging buffer
+        host = self._grow("_stage", pos, dtype=torch.uint8, pin_memory=True).numpy()
+        host[:ctypes.sizeof(table)] = np.frombuffer(table, dtype=np.uint8)
+        for im, info in zip(table, infos):                   # the one copy of the streams on the host
+            at = im.stream_offset
+            for part in _parts(info):
+                host[at:at + len(part)] = np.frombuffer(part, dtype=np.uint8)
+                at += len(part)
+        return table, pos
+
+    def _run(self, infos, dst_offsets, out_base, out_bytes, check_status):
+        """infos: [PngInfo]; image i goes to byte dst_offsets[i] of the uint8 device tensor out_base (out_bytes long)."""
+        import torch
+        n = len(infos)
+        table, total = self._pack(infos, dst_offsets)
+        stage = self._stage
+        packed = self._grow("_packed", total, dtype=torch.uint8, device=self.device)
+        need = int(lib().tt_png_workspace_bytes(table, n))
+        if need <= 0:                                       # the sizes tt_png_decode_u8 refuses
+            raise ValueError(f"an image is wider than {_lib.TT_PNG_MAX_WIDTH} pixels or has more than 2^31 - 1 scanline bytes")
+        work = self._grow("_work", need, dtype=torch.uint8, device=self.device)
+        status = self._grow("_status", 4 * n, dtype=torch.uint8, device=self.device)[:4 * n].view(torch.int32)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            packed[:total].copy_(stage[:total], non_blocking=True)
+            self._copied = torch.cuda.Event()
+            self._copied.record(stream)
+            check(lib().tt_png_decode_u8(ptr(packed), total, table, ptr(packed), n, ptr(work), work.numel(), ptr(out_base),
+                                         out_bytes, ptr(status), stream.cuda_stream), "tt_png_decode_u8")
+        self.last_packed_bytes = total
+        if not check_status:
+            return status.clone()
+        failed = [(i, STATUS_NAMES.get(s, str(s))) for i, s in enumerate(status.cpu().tolist()) if s != 0]
+        if failed:
+            raise PngDecodeError(failed)
+        return None
+
+    def _parse(self, files):
+        out = []
+        for f in files:
+            width, height, channels, parts = _walk(f, self.verify_crc)
+            out.append(PngInfo(width, height, channels, tuple(parts)))
+        return out
+
+    def decode(self, files, out=None, check=True):
+        """A list of file bytes of equal (H, W, C) -> uint8 [n, H, W, 3] on the device ([n, H, W] for grey files), freshly
+        allocated or `out` (contiguous, that shape).  check=True reads the statuses back and raises PngDecodeError if any
+        image failed; check=False stays asynchronous and returns (images, int32 status tensor [n])."""
+        import torch
+        infos = self._parse(files)
+        if not infos:
+            raise ValueError("no files")
+        w, h, c = infos[0][:3]
+        for i, info in enumerate(infos):
+            if tuple(info[:3]) != (w, h, c):
+                raise ValueError(f"file {i} is {info.height} x {info.width} x {info.channels}, file 0 is {h} x {w} x {c}")
+        shape = (len(infos), h, w, 3) if c == 3 else (len(infos), h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device
+              or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on {self.device}")
+        status = self._run(infos, [i * h * w * c for i in range(len(infos))], out, out.numel(), check)
+        return out if check else (out, status)
+
+    def decode_sample_batch(self, rgb_files, depth_files, seg_files, check=True):
+        """The nested lists [B][T][N] (camera frames), [B][N] (depth maps) and [B][N] (segmentation maps) of file bytes ->
+        (raw uint8 [B, T, N, H, W, 3], depth_png uint8 [B, N, H, W, 3], seg_png uint8 [B, N, H, W]) from ONE tt_png_decode_u8
+        call: what labels.RawLabelDecoder and preprocess.TrainImagePipeline take.  Camera order within N is the caller's."""
+        import torch
+        B = len(rgb_files)
+        T = len(rgb_files[0]) if B else 0
+        N = len(rgb_files[0][0]) if T else 0
+        if not (B and T and N):
+            raise ValueError("rgb_files must be a non-empty [B][T][N] nest of file bytes")
+        if any(len(s) != T or any(len(t) != N for t in s) for s in rgb_files):
+            raise ValueError(f"rgb_files is ragged: every sample needs {T} sweeps of {N} cameras")
+        for what, nest in (("depth_files", depth_files), ("seg_files", seg_files)):
+            if len(nest) != B or any(len(s) != N for s in nest):
+                raise ValueError(f"{what} must be a [{B}][{N}] nest of file bytes")
+        rgb = self._parse([f for s in rgb_files for t in s for f in t])
+        dep = self._parse([f for s in depth_files for f in s])
+        seg = self._parse([f for s in seg_files for f in s])
+        w, h = rgb[0].width, rgb[0].height
+        for what, infos, c in (("rgb", rgb, 3), ("depth", dep, 3), ("seg", seg, 1)):
+            for i, info in enumerate(infos):
+                if (info.width, info.height, info.channels) != (w, h, c):
+                    raise ValueError(f"{what} file {i} is {info.height} x {info.width} x {info.channels}, expected {h} x {w} x {c}")
+        n_raw, n_dep, n_seg = len(rgb) * h * w * 3, len(dep) * h * w * 3, len(seg) * h * w
+        o_dep = _up(n_raw, 256)
+        o_seg = o_dep + _up(n_dep, 256)
+        buf = torch.empty(o_seg + n_seg, dtype=torch.uint8, device=self.device)        # the three tensors are views of it
+        offsets = ([i * h * w * 3 for i in range(len(rgb))] + [o_dep + i * h * w * 3 for i in range(len(dep))]
+                   + [o_seg + i * h * w for i in range(len(seg))])
+        status = self._run(rgb + dep + seg, offsets, buf, buf.numel(), check)
+        out = (buf[:n_raw].view(B, T, N, h, w, 3), buf[o_dep:o_dep + n_dep].view(B, N, h, w, 3),
+               buf[o_seg:o_seg + n_seg].view(B, N, h, w))
+        return out if check else out + (status,)
