@@ -716,7 +716,8 @@ int tt_decode_seg_u8_phases(const uint8_t* tags_u8, int num_samples, int cams, i
  * never matter.  status_dev: int32 [num_images], written by the kernels: TT_PNG_OK or the first error of the image.  An
  * image with an error leaves its destination untouched and does not affect the others.
  * NOT checked: the Adler-32 trailer of the zlib stream (its four bytes must be present, their value is not read), and
- * nothing of the PNG container (chunk CRC-32s are the host parser's, optional there).
+ * nothing of the PNG container (chunk CRC-32s are the host parser's, optional there): tt_png_decode_u8_verified, below,
+ * checks both on the device.
  * Returns an error before any launch for: a null pointer; num_images < 1 or > TT_PNG_MAX_IMAGES; channels not 1 or 3; a
  * non-positive width or height; width > TT_PNG_MAX_WIDTH; H * (1 + W * C) above 2^31 - 1; a stream range outside
  * packed_bytes, shorter than 6 bytes or longer than 2^31 - 17; a destination range outside out_bytes; destinations that
@@ -756,6 +757,79 @@ int tt_png_decode_u8(const uint8_t* packed_dev, long long packed_bytes, const tt
 int tt_png_decode_u8_phases(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
                             const tt_png_image* images_dev, int num_images, void* workspace, long long workspace_bytes,
                             uint8_t* out_base, long long out_bytes, int32_t* status_dev, int phases, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Checksums of byte ranges of one device buffer: what `zlib.adler32(data, value)` (kind TT_CHECKSUM_ADLER32) and
+ * `zlib.crc32(data, value)` (TT_CHECKSUM_CRC32) return for data = data_dev[offset, offset + bytes), bit for bit.
+ * ranges: a table of num_ranges entries, in host memory (validated by the entry before any launch) and in device memory
+ * (read by the kernels), the same contents.  Ranges may have any length including 0, start at any byte, lie in any order,
+ * touch or overlap.  start_dev_or_null: uint32 [num_ranges], the running value of each range (zlib's second argument); null
+ * means 1 for Adler-32 and 0 for CRC-32.  out_dev: uint32 [num_ranges].
+ * Three stream-ordered launches (csrc/checksum.hip, csrc/png_checksum.h): a range is cut into tiles of TT_CHECKSUM_TILE bytes,
+ * one 256-lane workgroup per tile, each lane a contiguous slice; one lane per range then folds the range's tiles in order and
+ * applies the start value.  workspace: tt_checksum_workspace_bytes(...) bytes, 256-byte aligned, contents irrelevant.
+ * Returns an error before any launch for: a null pointer (start excepted); num_ranges < 1 or > TT_CHECKSUM_MAX_RANGES; a
+ * negative `bytes`; a range outside [0, data_bytes); an unknown kind; more than 2^31 - 1 tiles; a misaligned table, start,
+ * output or workspace; a workspace that is too small.  No allocation, no copy, no synchronisation.
+ * ---------------------------------------------------------------------- */
+#define TT_CHECKSUM_TILE 65536           /* bytes per workgroup: the IDAT chunk size PIL writes */
+#define TT_CHECKSUM_MAX_RANGES 1048576
+enum tt_checksum_kind {
+    TT_CHECKSUM_ADLER32 = 0,
+    TT_CHECKSUM_CRC32 = 1
+};
+typedef struct tt_checksum_range {
+    long long offset;                    /* of the range's first byte in data_dev */
+    long long bytes;                     /* >= 0 */
+} tt_checksum_range;                     /* 16 bytes */
+/* Host arithmetic only; 0 for a null table, a bad count, a negative length or more than 2^31 - 1 tiles. */
+long long tt_checksum_workspace_bytes(const tt_checksum_range* ranges_host, int num_ranges);
+int tt_checksum_ranges_u8(const uint8_t* data_dev, long long data_bytes, const tt_checksum_range* ranges_host,
+                          const tt_checksum_range* ranges_dev, int num_ranges, int kind, const uint32_t* start_dev_or_null,
+                          uint32_t* out_dev, void* workspace, long long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * tt_png_decode_u8 with the files' checksums verified on the device, between the inflate and the unfilter:
+ *   TT_PNGV_ADLER32  the zlib stream's Adler-32 (RFC 1950): the four big-endian bytes that follow the final block's padding
+ *                    to a byte boundary (NOT the stream's last four bytes: bytes after the trailer are accepted, as before)
+ *                    against zlib.adler32 of the H * (1 + W * C) scanline bytes the inflate wrote.  This is what PIL and
+ *                    zlib.decompress check ("incorrect data check"); the plain entry accepts such a stream.
+ *   TT_PNGV_CRC32    every IDAT chunk's CRC-32 field against zlib.crc32(body, zlib.crc32(b"IDAT")) of its body in packed_dev.
+ *                    Beyond PIL, which accepts an IDAT chunk with a wrong CRC field.
+ * verify_flags is an OR of the two; 0 gives the bytes and statuses of tt_png_decode_u8 (the tables may then be null).
+ * chunks (host and device copy, as the image table): one entry per IDAT chunk, the chunks of image 0 first, then image 1's,
+ * ...; an image's chunks must tile its stream [stream_offset, stream_offset + stream_bytes) exactly and in order (a chunk
+ * may be empty, and may start at any byte).  Only read with TT_PNGV_CRC32.
+ * Status of an image, first match: the inflate's own error; TT_PNGV_BAD_CRC32 if any of its chunks fails; TT_PNGV_BAD_ADLER32;
+ * the unfilter's TT_PNG_BAD_FILTER.  The two codes continue enum tt_png_status (11, 12) under a prefix of their own: only this
+ * entry returns them.  As with every other status, a failed image's destination is untouched.
+ * Launches: the tile plan, the inflate (which also hands out each stream's trailer), the checksum tiles over every image's
+ * scanlines and every chunk, fold + compare + status (one lane per range), the unfilter.
+ * workspace: tt_png_verify_workspace_bytes(...) bytes, 256-byte aligned; it begins with tt_png_decode_u8's workspace.
+ * Returns an error before any launch for everything tt_png_decode_u8 refuses, and for: unknown flag bits; a null chunk table
+ * or num_chunks < 1 with TT_PNGV_CRC32; num_chunks > TT_PNG_MAX_CHUNKS; a chunk whose image is out of range or below the
+ * previous chunk's; a negative chunk length; chunks that do not tile their image's stream; an image without chunks.
+ * ---------------------------------------------------------------------- */
+#define TT_PNG_MAX_CHUNKS 1000000
+enum tt_png_verify {
+    TT_PNGV_ADLER32 = 1,
+    TT_PNGV_CRC32 = 2,
+    TT_PNGV_BAD_ADLER32 = 11,            /* status: the scanlines' Adler-32 is not the stream's trailer */
+    TT_PNGV_BAD_CRC32 = 12               /* status: an IDAT chunk's CRC-32 is not its CRC field */
+};
+typedef struct tt_png_chunk {
+    long long offset;                    /* of the chunk's body in packed_dev, bytes */
+    long long bytes;                     /* >= 0 */
+    unsigned crc;                        /* the chunk's CRC field: over the type bytes "IDAT" and the body */
+    int image;                           /* index into the image table */
+} tt_png_chunk;                          /* 24 bytes */
+/* Host arithmetic only; 0 where the entry would refuse the tables. */
+long long tt_png_verify_workspace_bytes(const tt_png_image* images_host, int num_images, const tt_png_chunk* chunks_host,
+                                        int num_chunks, int verify_flags);
+int tt_png_decode_u8_verified(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
+                              const tt_png_image* images_dev, int num_images, const tt_png_chunk* chunks_host,
+                              const tt_png_chunk* chunks_dev, int num_chunks, int verify_flags, void* workspace,
+                              long long workspace_bytes, uint8_t* out_base, long long out_bytes, int32_t* status_dev, void* stream);
 
 /* ------------------------------------------------------------------------
  * SURVEY 8f-4 (training step), optimizer half: the reference's `optimizer_config = dict(grad_clip=dict(max_norm=100,

@@ -10,7 +10,15 @@ with 1 and with 16 processes, before this process touches the device (the pool f
 after one warm-up round, the variants alternating in one process: the whole decode_sample_batch call (parse, pack, copy, two
 launches, status read-back) twice (A/A), the host-to-device copy alone, the inflate launch alone (tt_png_decode_u8_phases) and
 both launches; the unfilter is their difference.  --train-step-ms: the train_step time of `bench.py --full` at the parent
-commit on the same machine, which the whole call is set against."""
+commit on the same machine, which the whole call is set against.
+
+    python -m thinktwice_amd.bench_png --verify [--batch 8] [--repeats 5] [--out profiles/train_png_verify.txt]
+
+--verify measures instead what PngDecoder(verify=...) adds (tt_png_decode_u8_verified: the Adler-32 of every stream and the
+CRC-32 of every IDAT chunk, on the device): the whole decode_sample_batch call with verification off, off again (A/A), with
+("adler32",) and with ("adler32", "crc32"), and the inflate launch alone, alternating in one process; then the checksum
+kernels on their own (png.device_adler32 / device_crc32 over the same number of bytes).  The cost of verification is the
+verify-on median minus the verify-off median, to be read against the A/A spread.  Without the switch the output is as before."""
 import argparse
 import io
 import multiprocessing
@@ -170,12 +178,74 @@ def main(B, repeats, train_step_ms, emit):
                  f"{pil[0] * 1e3 / train_step_ms:.1f}")
 
 
+def main_verify(B, repeats, emit):
+    import torch
+    from . import png
+    from .ops import check, cur_stream, lib, ptr
+    write, writer = _writer()
+    t0 = time.perf_counter()
+    (rgb_f, ramp_f, _, seg_f), (rgb_a, ramp_a, _, seg_a) = make_batch(B, write)
+    flat = [f for s in rgb_f for t in s for f in t] + [f for s in ramp_f for f in s] + [f for s in seg_f for f in s]
+    decoded = B * (T + 1) * N * H * W * 3 + B * N * H * W
+    chunks = sum(len(png._walk(f, False)[3]) for f in flat)
+    emit(f"B = {B}: {len(flat)} files of {H} x {W} written by {writer}; made in {time.perf_counter() - t0:.0f} s; {sum(map(len, flat))} file "
+         f"bytes in {chunks} IDAT chunks, {decoded} decoded bytes")
+    emit(f"build {build.source_fingerprint()} device {torch.cuda.get_device_name(0)}")
+    decoders = {"off": png.PngDecoder(), "off'": png.PngDecoder(), "adler32": png.PngDecoder(verify=("adler32",)),
+                "adler32 + crc32": png.PngDecoder(verify=True)}
+    for name, dec in decoders.items():
+        raw, depth, seg = dec.decode_sample_batch(rgb_f, ramp_f, seg_f)
+        bad = int((raw.cpu() != torch.from_numpy(np.array(rgb_a))).sum()) + int((depth.cpu() != torch.from_numpy(np.array(ramp_a))).sum())
+        bad += int((seg.cpu() != torch.from_numpy(np.array(seg_a))).sum())
+        emit(f"  [verify {name}] every status TT_PNG_OK; device against the source arrays: {bad} of {decoded} bytes differ")
+        del raw, depth, seg
+    dec = decoders["off"]
+    infos = [png.parse_png(f) for f in flat]
+    offsets, pos = [], 0
+    for i in infos:
+        offsets.append(pos)
+        pos += i.width * i.height * i.channels
+    out = torch.empty(pos, dtype=torch.uint8, device="cuda")
+    table, total = dec._pack(infos, offsets)
+    staged = dec._stage[:total].clone()
+    packed, work = staged.cuda(), dec._work
+    status = torch.zeros(len(infos), dtype=torch.int32, device="cuda")
+    stream = cur_stream(out.device)
+    lines, at = [], 0                                                  # every image's scanlines in the workspace
+    for i in infos:
+        lines.append((at, i.height * (1 + i.width * i.channels)))
+        at += (lines[-1][1] + 255) // 256 * 256
+    bodies = [(int(im.stream_offset), int(im.stream_bytes)) for im in table]
+
+    def inflate():
+        check(lib().tt_png_decode_u8_phases(ptr(packed), total, table, ptr(packed), len(infos), ptr(work), work.numel(), ptr(out), pos,
+                                            ptr(status), 1, stream), "tt_png_decode_u8_phases")
+
+    fns = {k: (lambda d=d: d.decode_sample_batch(rgb_f, ramp_f, seg_f)) for k, d in decoders.items()}
+    fns["inflate"] = inflate
+    fns["adler kernels"] = lambda: png.device_adler32(work, lines)
+    fns["crc kernels"] = lambda: png.device_crc32(packed, bodies)
+    ms = _events(fns, repeats)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    emit(f"  device events around each call, {repeats} rounds after 1 warm-up round, the variants alternating in one process")
+    labels = {"off": "decode_sample_batch, verify=()", "off'": "the same again (A/A)", "adler32": 'decode_sample_batch, verify=("adler32",)',
+              "adler32 + crc32": 'decode_sample_batch, verify=("adler32", "crc32")', "inflate": "inflate launch alone (tt_png_decode_u8_phases)",
+              "adler kernels": f"device_adler32 alone: {len(lines)} ranges, {sum(n for _, n in lines)} bytes (table upload + 3 launches)",
+              "crc kernels": f"device_crc32 alone: {len(bodies)} ranges, {sum(n for _, n in bodies)} bytes (table upload + 3 launches)"}
+    for k, label in labels.items():
+        emit(f"    {label:88s} median {med[k]:9.2f} ms (min {min(ms[k]):.2f}, max {max(ms[k]):.2f})")
+    spread = med["off'"] - med["off"]
+    emit(f"    A/A spread {spread:+.2f} ms; adler32 - off {med['adler32'] - med['off']:+.2f} ms; "
+         f"adler32 + crc32 - off {med['adler32 + crc32'] - med['off']:+.2f} ms; inflate launch {med['inflate']:.2f} ms")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--train-step-ms", type=float, default=750.0)
     ap.add_argument("--out", default=None, help="also write the report to this file")
+    ap.add_argument("--verify", action="store_true", help="measure what PngDecoder(verify=...) adds instead")
     a = ap.parse_args()
     lines = []
 
@@ -183,7 +253,10 @@ if __name__ == "__main__":
         print(s, flush=True)
         lines.append(s)
 
-    main(a.batch, a.repeats, a.train_step_ms, emit)
+    if a.verify:
+        main_verify(a.batch, a.repeats, emit)
+    else:
+        main(a.batch, a.repeats, a.train_step_ms, emit)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

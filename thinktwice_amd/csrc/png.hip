@@ -10,34 +10,17 @@
 //            its row in LDS for lane 0 of the next band: different threads of one wave, ordered by the barrier between bands
 //            and, inside a band, by lane 63 writing x = s - 63 only after lane 0 has read x = s.
 // Neither kernel waits for another workgroup, and every loop is bounded by the image's sizes or the stream's length.
+// tt_png_decode_u8_verified (csrc/png_verify.hip) puts the checksum launches between the two and reuses this file's argument
+// checks and unfilter (png_launch.h): the unfilter skips every image whose status is not TT_PNG_OK, the checksum codes included.
 #include <limits.h>
 
 #include <algorithm>
 
 #include "tt_common.h"          // (first: png_inflate.h's barrier is the HIP runtime's)
 #include "png_inflate.h"
+#include "png_launch.h"
 
 namespace tt {
-
-constexpr long long kPngSlotAlign = 256;
-
-static inline __host__ __device__ long long png_expect(const tt_png_image& im) {
-    return (long long)im.height * (1 + (long long)im.width * im.channels);
-}
-static inline __host__ __device__ long long png_slot(const tt_png_image& im) {
-    return (png_expect(im) + kPngSlotAlign - 1) / kPngSlotAlign * kPngSlotAlign;
-}
-
-// the workspace offset of image `img`: the sum of the earlier slots, by the whole wave
-__device__ __forceinline__ long long png_slot_offset(const tt_png_image* images, int img) {
-    long long off = 0;
-    for (int j = (int)threadIdx.x; j < img; j += kWave) off += png_slot(images[j]);
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) off += __shfl_xor(off, o, kWave);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)off);          // the same in every lane: scalar
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)off >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
 
 __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t* __restrict__ packed, long long packed_bytes,
                                                          const tt_png_image* __restrict__ images, uint8_t* __restrict__ ws,
@@ -115,7 +98,7 @@ __global__ __launch_bounds__(64) void png_unfilter_kernel(const tt_png_image* __
 }
 
 // every check of the entry that needs only the table's sizes; 0 or the expected byte count
-static long long png_sizes_ok(const tt_png_image& im) {
+long long png_sizes_ok(const tt_png_image& im) {
     if (im.channels != 1 && im.channels != 3) return 0;
     if (im.width <= 0 || im.height <= 0 || im.width > TT_PNG_MAX_WIDTH) return 0;
     const long long e = png_expect(im);
@@ -136,10 +119,10 @@ extern "C" long long tt_png_workspace_bytes(const tt_png_image* images_host, int
     return total;
 }
 
-extern "C" int tt_png_decode_u8_phases(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
-                                       const tt_png_image* images_dev, int num_images, void* workspace, long long workspace_bytes,
-                                       uint8_t* out_base, long long out_bytes, int32_t* status_dev, int phases, void* stream) {
-    TT_REQUIRE(phases == 1 || phases == 2, "tt_png_decode_u8: %d phases, 1 or 2", phases);
+// every refusal of tt_png_decode_u8 but the workspace's size: 0, or -1 with the error text set
+int tt::png_check_args(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
+                          const tt_png_image* images_dev, int num_images, void* workspace, uint8_t* out_base, long long out_bytes,
+                          int32_t* status_dev) {
     TT_REQUIRE(packed_dev && images_host && images_dev && workspace && out_base && status_dev, "tt_png_decode_u8: null pointer");
     TT_REQUIRE(num_images >= 1 && num_images <= TT_PNG_MAX_IMAGES, "tt_png_decode_u8: %d images, 1..%d", num_images,
                TT_PNG_MAX_IMAGES);
@@ -175,6 +158,15 @@ extern "C" int tt_png_decode_u8_phases(const uint8_t* packed_dev, long long pack
     for (int i = 1; i < num_images; ++i)
         TT_REQUIRE(dst[i].lo >= dst[i - 1].hi, "tt_png_decode_u8: the destinations [%lld, %lld) and [%lld, %lld) overlap", dst[i - 1].lo,
                    dst[i - 1].hi, dst[i].lo, dst[i].hi);
+    return 0;
+}
+
+extern "C" int tt_png_decode_u8_phases(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
+                                       const tt_png_image* images_dev, int num_images, void* workspace, long long workspace_bytes,
+                                       uint8_t* out_base, long long out_bytes, int32_t* status_dev, int phases, void* stream) {
+    TT_REQUIRE(phases == 1 || phases == 2, "tt_png_decode_u8: %d phases, 1 or 2", phases);
+    if (png_check_args(packed_dev, packed_bytes, images_host, images_dev, num_images, workspace, out_base, out_bytes, status_dev))
+        return -1;
     const long long need = tt_png_workspace_bytes(images_host, num_images);
     TT_REQUIRE(need > 0 && workspace_bytes >= need, "tt_png_decode_u8: need %lld bytes of workspace, got %lld", need, workspace_bytes);
 
@@ -192,4 +184,13 @@ extern "C" int tt_png_decode_u8(const uint8_t* packed_dev, long long packed_byte
                                 uint8_t* out_base, long long out_bytes, int32_t* status_dev, void* stream) {
     return tt_png_decode_u8_phases(packed_dev, packed_bytes, images_host, images_dev, num_images, workspace, workspace_bytes,
                                    out_base, out_bytes, status_dev, 2, stream);
+}
+
+void tt::png_launch_unverified(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_dev, int num_images,
+                               uint8_t* workspace, uint8_t* out_base, int32_t* status_dev, bool inflate, hipStream_t st) {
+    if (inflate)
+        hipLaunchKernelGGL(png_inflate_kernel, dim3((unsigned)num_images), dim3(kWave), 0, st, packed_dev, packed_bytes, images_dev,
+                           workspace, status_dev);
+    hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)num_images), dim3(kWave), 0, st, images_dev, (const uint8_t*)workspace,
+                       out_base, status_dev);
 }

@@ -20,7 +20,8 @@
 // or no code at all (using it is TT_PNG_BAD_SYMBOL); the code-length code must be complete.  A bit pattern no code has, and
 // the symbols 286, 287 (length) and 30, 31 (distance), are TT_PNG_BAD_SYMBOL.
 //
-// NOT verified: the Adler-32 trailer.  Its four bytes must be present (else TT_PNG_TRUNCATED); their value is not read.
+// NOT verified here: the Adler-32 trailer.  Its four bytes must be present (else TT_PNG_TRUNCATED); inflate_zlib hands their
+// value out on request and tt_png_decode_u8_verified compares it with the checksum of the scanlines (png_checksum.h).
 #pragma once
 #include <stdint.h>
 
@@ -410,9 +411,11 @@ TT_HD inline int huffman_block(State& S, Reader& R, Output& O, int window, int l
 
 // The zlib stream in bytes [start, end) of `base` (4-byte aligned, readable in [0, limit), start < 4, end <= 2^31 - 8) ->
 // exactly `expect` bytes at `out` (16-byte aligned).  Returns a TT_PNG_* status; on an error `out` holds an unspecified
-// prefix.  start, end, expect (and limit, out) are the same in every lane.
+// prefix.  start, end, expect (and limit, out) are the same in every lane.  trailer, if not null: where the stream's Adler-32
+// field goes, written once, and only when the status is TT_PNG_OK: the four big-endian bytes after the final block's padding
+// to a byte boundary, wherever the stream ends.  Comparing it is the caller's (csrc/png.hip, png_checksum.h).
 TT_HD inline int inflate_zlib(State& S, const uint8_t* base, int start, int end, long long limit, uint8_t* out, int expect, int lane,
-                              int nlanes) {
+                              int nlanes, uint32_t* trailer = nullptr) {
     Reader R;
     R.base = base; R.start = start; R.end = end; R.limit = limit;
     R.next_word = 0; R.buf_word0 = 0; R.bits = 0; R.cnt = 0;
@@ -444,7 +447,12 @@ TT_HD inline int inflate_zlib(State& S, const uint8_t* base, int start, int end,
     flush_tail(S, O, lane, nlanes);
     take(R, R.cnt & 7);
     const int unread = R.end - 4 * R.next_word;
-    if ((R.cnt >> 3) + (unread > 0 ? unread : 0) < 4) return TT_PNG_TRUNCATED;      // the Adler-32: present, not verified
+    if ((R.cnt >> 3) + (unread > 0 ? unread : 0) < 4) return TT_PNG_TRUNCATED;      // the Adler-32: present, not verified here
+    if (trailer) {                                                // (four more bytes exist: need() cannot fail)
+        need(S, R, 32, lane, nlanes);
+        const uint32_t v = take(R, 32);                           // the stream's next four bytes, the first one lowest
+        if (lane == 0) *trailer = (v << 24) | ((v & 0xff00u) << 8) | ((v >> 8) & 0xff00u) | (v >> 24);
+    }
     return TT_PNG_OK;
 }
 

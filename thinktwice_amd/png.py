@@ -8,8 +8,16 @@ include/thinktwice_hip.h).  What stays in the loader is reading the files.
     depth, seg = labels.RawLabelDecoder(cfg.seg_label_idxs)(raw, depth_png, seg_png)
 
 Specified for the files PIL writes (`Image.fromarray(a).save(path)`): 8-bit, non-interlaced, colour type 0 or 2.  Anything
-else is a ValueError on the host.  Not checked: the zlib stream's Adler-32 (never), the chunks' CRC-32 (only with
-verify_crc=True, on the host)."""
+else is a ValueError on the host.
+
+Checksums.  By default none is checked.  `PngDecoder(verify=("adler32",))` verifies every zlib stream's Adler-32 on the device
+against the scanlines the inflate wrote: that is the check `np.array(Image.open(path))` makes ("broken data stream"), so it
+is the setting for parity with the reference loader.  `verify=("adler32", "crc32")`, or `verify=True`, also verifies every
+IDAT chunk's CRC-32 on the device (tt_png_decode_u8_verified; the few dozen bytes of the other chunks are checked on the
+host), which PIL does not.  A file that fails is an image status like any other decode error (TT_PNGV_BAD_ADLER32,
+TT_PNGV_BAD_CRC32) and leaves its destination untouched.  `verify_crc=True` is the older all-host CRC check (zlib.crc32 over
+every chunk: host time over the whole batch's file bytes).  `device_adler32` and `device_crc32` are the checksum kernels on
+their own (tt_checksum_ranges_u8): zlib.adler32 / zlib.crc32 of byte ranges of a device tensor."""
 import collections
 import ctypes
 import struct
@@ -21,9 +29,14 @@ from . import _lib
 from .ops import check, lib, ptr
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
-PngInfo = collections.namedtuple("PngInfo", "width height channels zlib_stream")
+# idat_crcs: the CRC field of every IDAT chunk, one per piece of zlib_stream; only PngDecoder(verify="crc32") collects them
+PngInfo = collections.namedtuple("PngInfo", "width height channels zlib_stream idat_crcs", defaults=(None,))
 PngImage = _lib.structs()["tt_png_image"]
+PngChunk = _lib.structs()["tt_png_chunk"]
+ChecksumRange = _lib.structs()["tt_checksum_range"]
 STATUS_NAMES = {v: k for k, v in _lib.constants().items() if k.startswith("TT_PNG_") and not k.startswith("TT_PNG_MAX")}
+STATUS_NAMES.update({_lib.TT_PNGV_BAD_ADLER32: "TT_PNGV_BAD_ADLER32", _lib.TT_PNGV_BAD_CRC32: "TT_PNGV_BAD_CRC32"})
+VERIFY_FLAGS = {"adler32": _lib.TT_PNGV_ADLER32, "crc32": _lib.TT_PNGV_CRC32}
 
 
 class PngDecodeError(_lib.TTError):
@@ -42,8 +55,9 @@ def parse_png(data, verify_crc=False):
     return PngInfo(width, height, channels, bytes(parts[0]) if len(parts) == 1 else b"".join(parts))
 
 
-def _walk(data, verify_crc):
-    """(width, height, channels, [the IDAT bodies as views of `data`]): nothing is copied."""
+def _walk(data, verify_crc, idat_crcs=None):
+    """(width, height, channels, [the IDAT bodies as views of `data`]): nothing is copied.  idat_crcs: a list that receives
+    the CRC field of every IDAT chunk, for the device to verify; every other chunk is then verified here (zlib.crc32)."""
     data = memoryview(data if isinstance(data, (bytes, bytearray, memoryview)) else bytes(data)).cast("B")
     if len(data) < 8 or bytes(data[:8]) != SIGNATURE:
         raise ValueError("not a PNG file: bad signature")
@@ -55,7 +69,7 @@ def _walk(data, verify_crc):
         if pos + 12 + n > len(data):
             raise ValueError(f"PNG: chunk {kind!r} at byte {pos} has length {n}, which runs past the file's {len(data)} bytes")
         body = data[pos + 8:pos + 8 + n]
-        if verify_crc:
+        if verify_crc or (idat_crcs is not None and kind != b"IDAT"):
             want, = struct.unpack_from(">I", data, pos + 8 + n)
             if zlib.crc32(body, zlib.crc32(kind)) != want:
                 raise ValueError(f"PNG: chunk {kind!r} at byte {pos} fails its CRC-32")
@@ -71,6 +85,8 @@ def _walk(data, verify_crc):
                 raise ValueError("PNG: IDAT chunks are not consecutive")
             state = "inside"
             idat.append(body)
+            if idat_crcs is not None:
+                idat_crcs.append(struct.unpack_from(">I", data, pos - 4)[0])
         elif kind == b"IEND":
             break
         else:
@@ -111,20 +127,32 @@ def _up(n, a):
 class PngDecoder:
     """Decodes batches of PNG files on `device`.  Holds and reuses the pinned staging buffer, the device copy of it, the
     workspace and the status array: they grow when a batch needs more and never shrink.  One call = one pinned host-to-device
-    copy (the image table and every stream), two launches, and -- with check=True -- one small copy of the statuses back.
+    copy (the image table, the chunk table if CRC-32s are verified, and every stream), two launches (five with `verify`), and
+    -- with check=True -- one small copy of the statuses back.
     The streams are copied once on the host, from the file bytes into the staging buffer.  The buffers are reused from call
     to call without synchronising, so all calls of one decoder must be on ONE stream (the current stream at each call); use a
     decoder per stream otherwise."""
 
-    def __init__(self, device="cuda", verify_crc=False):
+    def __init__(self, device="cuda", verify_crc=False, verify=()):
+        """verify: a subset of {"adler32", "crc32"} to verify on the device (True: both; see the module text); the default
+        verifies nothing.  verify_crc=True is the all-host CRC-32 check and excludes "crc32"."""
         import torch
+        verify = ("adler32", "crc32") if verify is True else (() if verify in (False, None) else
+                                                              ((verify,) if isinstance(verify, str) else tuple(verify)))
+        unknown = [v for v in verify if v not in VERIFY_FLAGS]
+        if unknown:
+            raise ValueError(f"verify: {unknown} not in {sorted(VERIFY_FLAGS)}")
+        if verify_crc and "crc32" in verify:
+            raise ValueError('verify_crc=True checks every CRC-32 on the host, verify="crc32" on the device: choose one')
+        self.verify = tuple(sorted(set(verify)))
+        self.verify_flags = sum(VERIFY_FLAGS[v] for v in self.verify)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("PngDecoder needs a GPU device: there is no CPU path")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.verify_crc = verify_crc
-        self._stage = self._packed = self._work = self._status = self._copied = None
+        self._stage = self._packed = self._work = self._status = self._copied = self._chunks = None
 
     def _grow(self, name, n, **kw):
         import torch
@@ -135,24 +163,46 @@ class PngDecoder:
         return t
 
     def _pack(self, infos, dst_offsets):
-        """The call's one host buffer, in the pinned staging tensor: the image table, then every stream at a 16-byte aligned
-        offset -> (table, its bytes)."""
+        """The call's one host buffer, in the pinned staging tensor: the image table, with verify="crc32" the chunk table
+        (self._chunks: the table and its offset, else None), then every stream at a 16-byte aligned offset ->
+        (table, its bytes)."""
         import torch
         n = len(infos)
         if not 1 <= n <= _lib.TT_PNG_MAX_IMAGES:
             raise ValueError(f"{n} images in one call, 1..{_lib.TT_PNG_MAX_IMAGES}")
         table = (PngImage * n)()
         pos = _up(ctypes.sizeof(table), 256)
+        self._chunks = None
+        if self.verify_flags & VERIFY_FLAGS["crc32"]:
+            if any(info.idat_crcs is None or len(info.idat_crcs) != len(_parts(info)) for info in infos):
+                raise ValueError('verify="crc32" needs every IDAT chunk\'s CRC field: decode files, not bare streams')
+            chunks = (PngChunk * sum(len(info.idat_crcs) for info in infos))()
+            if len(chunks) > _lib.TT_PNG_MAX_CHUNKS:
+                raise ValueError(f"{len(chunks)} IDAT chunks in one call, at most {_lib.TT_PNG_MAX_CHUNKS}")
+            self._chunks = (chunks, pos)
+            pos = _up(pos + ctypes.sizeof(chunks), 256)
         for i, (info, dst) in enumerate(zip(infos, dst_offsets)):
             im = table[i]
             nbytes = sum(len(part) for part in _parts(info))
             im.stream_offset, im.stream_bytes, im.dst_offset = pos, nbytes, dst
             im.width, im.height, im.channels = info.width, info.height, info.channels
             pos = _up(pos + nbytes, 16)
+        if self._chunks:
+            j = 0
+            for i, (im, info) in enumerate(zip(table, infos)):
+                at = im.stream_offset
+                for part, crc in zip(_parts(info), info.idat_crcs):
+                    ch = self._chunks[0][j]
+                    ch.offset, ch.bytes, ch.crc, ch.image = at, len(part), crc, i
+                    at += len(part)
+                    j += 1
         if self._copied is not None:
             self._copied.synchronize()                      # the previous call's copy has left the staging buffer
         host = self._grow("_stage", pos, dtype=torch.uint8, pin_memory=True).numpy()
         host[:ctypes.sizeof(table)] = np.frombuffer(table, dtype=np.uint8)
+        if self._chunks:
+            chunks, at = self._chunks
+            host[at:at + ctypes.sizeof(chunks)] = np.frombuffer(chunks, dtype=np.uint8)
         for im, info in zip(table, infos):                   # the one copy of the streams on the host
             at = im.stream_offset
             for part in _parts(info):
@@ -167,9 +217,12 @@ class PngDecoder:
         table, total = self._pack(infos, dst_offsets)
         stage = self._stage
         packed = self._grow("_packed", total, dtype=torch.uint8, device=self.device)
-        need = int(lib().tt_png_workspace_bytes(table, n))
-        if need <= 0:                                       # the sizes tt_png_decode_u8 refuses
+        if int(lib().tt_png_workspace_bytes(table, n)) <= 0:        # the sizes tt_png_decode_u8 refuses
             raise ValueError(f"an image is wider than {_lib.TT_PNG_MAX_WIDTH} pixels or has more than 2^31 - 1 scanline bytes")
+        chunks, chunks_at = self._chunks or (None, 0)
+        need = int(lib().tt_png_verify_workspace_bytes(table, n, chunks, len(chunks) if chunks else 0, self.verify_flags))
+        if need <= 0:
+            raise _lib.TTError("tt_png_verify_workspace_bytes: " + lib().tt_last_error().decode())
         work = self._grow("_work", need, dtype=torch.uint8, device=self.device)
         status = self._grow("_status", 4 * n, dtype=torch.uint8, device=self.device)[:4 * n].view(torch.int32)
         with torch.cuda.device(self.device):
@@ -177,8 +230,14 @@ class PngDecoder:
             packed[:total].copy_(stage[:total], non_blocking=True)
             self._copied = torch.cuda.Event()
             self._copied.record(stream)
-            check(lib().tt_png_decode_u8(ptr(packed), total, table, ptr(packed), n, ptr(work), work.numel(), ptr(out_base),
-                                         out_bytes, ptr(status), stream.cuda_stream), "tt_png_decode_u8")
+            if self.verify_flags:
+                check(lib().tt_png_decode_u8_verified(ptr(packed), total, table, ptr(packed), n, chunks,
+                                                      ptr(packed) + chunks_at if chunks else None, len(chunks) if chunks else 0,
+                                                      self.verify_flags, ptr(work), work.numel(), ptr(out_base), out_bytes,
+                                                      ptr(status), stream.cuda_stream), "tt_png_decode_u8_verified")
+            else:
+                check(lib().tt_png_decode_u8(ptr(packed), total, table, ptr(packed), n, ptr(work), work.numel(), ptr(out_base),
+                                             out_bytes, ptr(status), stream.cuda_stream), "tt_png_decode_u8")
         self.last_packed_bytes = total
         if not check_status:
             return status.clone()
@@ -190,8 +249,9 @@ class PngDecoder:
     def _parse(self, files):
         out = []
         for f in files:
-            width, height, channels, parts = _walk(f, self.verify_crc)
-            out.append(PngInfo(width, height, channels, tuple(parts)))
+            crcs = [] if self.verify_flags & VERIFY_FLAGS["crc32"] else None
+            width, height, channels, parts = _walk(f, self.verify_crc, crcs)
+            out.append(PngInfo(width, height, channels, tuple(parts), None if crcs is None else tuple(crcs)))
         return out
 
     def decode(self, files, out=None, check=True):
@@ -248,3 +308,40 @@ class PngDecoder:
         out = (buf[:n_raw].view(B, T, N, h, w, 3), buf[o_dep:o_dep + n_dep].view(B, N, h, w, 3),
                buf[o_seg:o_seg + n_seg].view(B, N, h, w))
         return out if check else out + (status,)
+
+
+def _device_checksum(kind, data, ranges, start):
+    import torch
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or not data.is_cuda or not data.is_contiguous() or data.dim() != 1:
+        raise ValueError("data must be a contiguous one-dimensional uint8 device tensor")
+    ranges = [(0, data.numel())] if ranges is None else [(int(o), int(n)) for o, n in ranges]
+    n = len(ranges)
+    if not 1 <= n <= _lib.TT_CHECKSUM_MAX_RANGES:
+        raise ValueError(f"{n} ranges in one call, 1..{_lib.TT_CHECKSUM_MAX_RANGES}")
+    table = (ChecksumRange * n)()
+    for entry, (offset, nbytes) in zip(table, ranges):
+        entry.offset, entry.bytes = offset, nbytes
+    if start is not None:
+        start = torch.as_tensor(np.asarray(start, dtype=np.uint32).reshape(n).view(np.int32)).to(data.device)
+    need = int(lib().tt_checksum_workspace_bytes(table, n))
+    if need <= 0:
+        raise ValueError("a range has a negative length, or the ranges make more than 2^31 - 1 tiles")
+    table_dev = torch.from_numpy(np.frombuffer(table, dtype=np.uint8).copy()).to(data.device)
+    work = torch.empty(need, dtype=torch.uint8, device=data.device)
+    out = torch.empty(n, dtype=torch.int32, device=data.device)
+    with torch.cuda.device(data.device):
+        check(lib().tt_checksum_ranges_u8(ptr(data), data.numel(), table, ptr(table_dev), n, kind, ptr(start), ptr(out), ptr(work),
+                                          need, torch.cuda.current_stream(data.device).cuda_stream), "tt_checksum_ranges_u8")
+    return out.view(torch.uint32)
+
+
+def device_adler32(data, ranges=None, start=None):
+    """zlib.adler32(data[o:o + n], start) for every (o, n) of `ranges` (None: the whole tensor), on the device
+    (tt_checksum_ranges_u8).  data: a contiguous 1-D uint8 device tensor; ranges may have any length, alignment and order;
+    start: None (1) or one uint32 per range.  Returns a uint32 device tensor [len(ranges)]; asynchronous."""
+    return _device_checksum(_lib.TT_CHECKSUM_ADLER32, data, ranges, start)
+
+
+def device_crc32(data, ranges=None, start=None):
+    """zlib.crc32(data[o:o + n], start) for every (o, n) of `ranges`: as device_adler32, start None meaning 0."""
+    return _device_checksum(_lib.TT_CHECKSUM_CRC32, data, ranges, start)
