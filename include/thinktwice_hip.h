@@ -237,7 +237,38 @@ typedef struct tt_conv_desc {
     int in_up2;
 } tt_conv_desc;
 
+/* A JOINED STAGE for tt_conv2d_fwd_next (bf16x3 layers: dtype TT_F32, weight_x3 given): the 1 x 1 / stride 1 convolution that reads the
+ * layer's output runs in the SAME launch, on each row tile of `out` while it is still on chip,
+ *   next_out = next_act(next_scale * (next_weight . out) + next_shift),
+ * so `out` (still written: it has other readers) is not read back.  Both tensors are, bit for bit, those of tt_conv2d_fwd(d) followed
+ * by tt_conv2d_fwd of the second layer on `out` (a ResNet bottleneck's conv3 and the next block's conv1).  (Its own struct and entry,
+ * beside tt_conv_desc: the descriptor's layout stays what its callers were built against.)
+ *   next_weight     f32 [next_cout][1][1][Cout]: only the shape carrier, as `weight` is for a bf16x3 layer;
+ *   next_weight_x3  the same in pair format (see tt_conv_desc.weight_x3), 16-byte aligned: what the kernel reads;
+ *   next_scale / next_shift  folded BN of the second layer (nullable: 1 / 0);  next_act  TT_ACT_NONE or TT_ACT_RELU;
+ *   next_out        [N, OH, OW, next_out_cstride] at channel offset next_out_coff, 64-byte aligned, contiguous images;
+ *   next_out_pair   must be 1: next_out is written in pair format (out_pair's rules: next_cout / next_out_cstride / next_out_coff
+ *                   multiples of 16).
+ * Contract of the layer `d`: 1 x 1, stride 1, pad 0 (OH = H, OW = W), Cin = 64, 128 or 256, Cout = 4 Cin, with next_cout = 64 or 128
+ * (Cin = 64), 128 or 256 (Cin = 128), 256 (Cin = 256); `in` f32 or in_pair, row-linear (in_nstride 0 or H*W*in_cstride; in_pair:
+ * in_cstride / in_coff multiples of 16); `out` f32 (no out_pair), row-linear, the vector epilogue; at most res1 (f32, 16-byte
+ * aligned rows, its own res1_cstride / res1_coff); act TT_ACT_NONE or TT_ACT_RELU; N*OH*OW > 4096 (it pays from kJoinMinRows =
+ * 32,768 rows on, csrc/conv_choose.h: below, tt_conv_last_kernel's label ends in " below kJoinMinRows"); no res2, shift_n, out2,
+ * res1_up_*, split-K workspace, gather or pixel shuffle.  Each stage alone, at this row count, must run on a bf16x3 LDS-DMA tile (no
+ * split-K, not the exact-f32 path): those are the kernels whose sums the joined kernel reproduces.  Anything outside this is refused
+ * with an error naming the field; tt_conv2d_fwd_next never runs as two launches. */
+typedef struct tt_conv_next {
+    const void* next_weight; const void* next_weight_x3;
+    int next_cout;
+    const float* next_scale; const float* next_shift;
+    int next_act;
+    void* next_out; int next_out_cstride, next_out_coff;
+    int next_out_pair;
+} tt_conv_next;
+
 int tt_conv2d_fwd(const tt_conv_desc* d, void* stream);
+/* tt_conv2d_fwd of `d` with the joined stage `next` (non-null) in the same launch: the contract above. */
+int tt_conv2d_fwd_next(const tt_conv_desc* d, const tt_conv_next* next, void* stream);
 /* K splits tt_conv2d_fwd would use for this descriptor if it is given a split-K workspace (0: the layer does not split).  Asks the
  * dispatch function of a launch, so a descriptor whose launch would be refused (tt_conv2d_plan != 0: out2 / res1 without the vector
  * epilogue, a misaligned weight_x3, ...) answers 0 and leaves that refusal in tt_last_error. */
@@ -247,6 +278,8 @@ int tt_conv2d_splitk_slices(const tt_conv_desc* d);
  * data pointer of the descriptor (null-ness and alignment are all it looks at) and touches no device; returns the non-zero code, with
  * the error text, that the launch of `d` would return before launching. */
 int tt_conv2d_plan(const tt_conv_desc* d, char* label, int label_bytes);
+/* the same for tt_conv2d_fwd_next(d, next, ..) */
+int tt_conv2d_plan_next(const tt_conv_desc* d, const tt_conv_next* next, char* label, int label_bytes);
 
 /* Two 1 x 1 convolutions with folded BN over the R rows of a row matrix in ONE launch (seg_res_to_image_feature.0 / .3,
  * backbones/lss.py:409-416, over the full-resolution segmentation map):

@@ -253,6 +253,68 @@ int choose_up2(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
     return 0;
 }
 
+// ---- a 1 x 1 bf16x3 layer with a joined stage (conv_x3_join.hip, tt_conv2d_fwd_next): the kernel's whole contract.  A call
+// that names a next stage (tt_conv_next) runs here or is refused -- it never becomes two launches.  `a` / f.join are the two stages as the layers
+// they would be alone; each is put to conv_choose by itself, since the joined kernel reproduces the sums of the bf16x3 LDS-DMA tiles
+// (k ascending in 16-wide steps, bf16x3.h's one-accumulator order) and of nothing else.
+// Forms <Cin, next_cout, waves>: <64, 64, 8> <64, 128, 8> <128, 128, 8> <128, 256, 4> <256, 256, 4>; a workgroup covers 32 rows per wave.
+// Threshold kJoinMinRows = 32,768 rows, one value for every form.  Measured crossover (profiles/bottleneck_join.txt; us, serialised,
+// minimum of 10, the two launches -> the joined one; one image 128 pixels wide, residual and ReLU):
+//   rows       64 -> 256 -> 64   64 -> 256 -> 128   128 -> 512 -> 128   128 -> 512 -> 256   256 -> 1024 -> 256
+//   4,608      33.0 -> 30.2      33.2 -> 35.2       44.8 -> 63.3        44.6 -> 67.0        71.8 -> 133.4
+//   8,192      33.0 -> 30.7      32.9 -> 37.1       46.6 -> 64.4        46.4 -> 68.0        78.8 -> 134.0
+//   16,384     36.0 -> 31.7      35.9 -> 35.8       58.3 -> 66.9        59.2 -> 72.5        102.0 -> 138.0
+//   32,768     45.7 -> 33.4      46.8 -> 40.0       76.1 -> 69.2        86.8 -> 78.8        165.6 -> 154.2
+//   65,536     65.0 -> 38.5      71.3 -> 46.5       125.1 -> 83.0       143.8 -> 146.9      303.9 -> 322.3
+//   131,072    112.3 -> 78.0     128.1 -> 93.5      248.4 -> 166.2      282.2 -> 288.6      567.9 -> 596.2
+//   262,144    202.4 -> 155.2    245.2 -> 183.8     456.1 -> 309.6      521.0 -> 524.9      1091.6 -> 1152.2
+// The three eight-wave forms win from 32,768 rows on (64 -> 256 -> 64 already from the floor, by 2 - 4 us); below, 64 -> 256 -> 128 and
+// 128 -> 512 -> 128 lose.  The two four-wave forms (one wave per SIMD) win at 32,768 rows only and lose at the model's row counts
+// (B = 8: 819 -> 835 and 497 -> 586 us; B = 1: 125 -> 132 and 95 -> 136): callers leave them to two launches (ops.JOIN_ROUTED); the
+// kernel keeps them.  The model's routed shapes (us): B = 8 1074 -> 805, 1297 -> 961, 710 -> 501; B = 1 160 -> 137, 202 -> 158, 108 -> 72.
+// The threshold is the CALLERS' rule: a call below it is still run here (label " below kJoinMinRows"), down to kJoinFloorRows.
+int choose_join(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
+    const ConvArgs& n = *f.join;
+    TT_REQUIRE(f.dtype == TT_F32 && a.out_dtype == TT_F32 && f.weight_x3 && aligned16(f.weight_x3) && !f.weight_h2,
+               "tt_conv2d_fwd: next_out goes with a bf16x3 layer (dtype / out_dtype TT_F32, a 16-byte aligned weight_x3)");
+    TT_REQUIRE(f.join_weight_x3 && aligned16(f.join_weight_x3), "tt_conv2d_fwd: next_weight_x3 must be given and 16-byte aligned");
+    TT_REQUIRE(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.OH == a.H && a.OW == a.W,
+               "tt_conv2d_fwd: next_out needs a 1 x 1 / stride 1 / pad 0 layer (got k %d x %d s %d p %d)", a.KH, a.KW, a.stride, a.pad);
+    TT_REQUIRE(!a.gather && !a.m_dev && !a.ws && !a.pixel_shuffle2 && !a.res2 && !a.shift_n && !f.out2 && !f.res1_up && !(a.flags & (64 | 256)),
+               "tt_conv2d_fwd: next_out takes no res2, shift_n, out2, res1_up, out_pair, in_up2, splitk_ws, gather_idx or pixel_shuffle2");
+    TT_REQUIRE((a.Cin == 64 || a.Cin == 128 || a.Cin == 256) && a.Cout == 4 * a.Cin,
+               "tt_conv2d_fwd: next_out needs Cin = 64, 128 or 256 and Cout = 4 Cin (got Cin=%d Cout=%d)", a.Cin, a.Cout);
+    TT_REQUIRE(n.Cout == a.Cin || (n.Cout == 2 * a.Cin && a.Cin <= 128),
+               "tt_conv2d_fwd: next_cout = %d has no joined kernel beside Cin = %d (64 or 128 / 128 or 256 / 256)", n.Cout, a.Cin);
+    TT_REQUIRE(a.act == TT_ACT_NONE || a.act == TT_ACT_RELU, "tt_conv2d_fwd: next_out needs act none or ReLU (got %d)", a.act);
+    TT_REQUIRE(n.act == TT_ACT_NONE || n.act == TT_ACT_RELU, "tt_conv2d_fwd: next_act must be none or ReLU (got %d)", n.act);
+    TT_REQUIRE(a.M >= kJoinFloorRows, "tt_conv2d_fwd: next_out needs N*OH*OW of at least %d rows (got %d)", kJoinFloorRows, a.M);
+    TT_REQUIRE(a.in_nstride == (long long)a.H * a.W * a.in_cstride && (!(a.flags & 32) || (a.in_cstride % 16 == 0 && a.in_coff % 16 == 0)),
+               "tt_conv2d_fwd: next_out needs a row-linear `in` (in_nstride 0 or H*W*in_cstride; in_pair: in_cstride / in_coff multiples of 16)");
+    TT_REQUIRE(a.out_fast && a.vec_epi && a.res_vec, "tt_conv2d_fwd: next_out needs a row-linear `out` and 16-byte aligned out / res1 rows");
+    TT_REQUIRE((n.flags & 64) && n.out_fast && n.vec_epi,
+               "tt_conv2d_fwd: next_out_pair must be 1, with a row-linear next_out and next_cout / next_out_cstride / next_out_coff multiples of 16");
+    // each stage alone: a bf16x3 LDS-DMA tile without split-K, or no joined form
+    ConvFacts f1 = f, f2{};
+    f1.join = nullptr;
+    f1.join_weight_x3 = nullptr;
+    f2.dtype = TT_F32;
+    f2.weight_x3 = f.join_weight_x3;
+    ConvChoice s1, s2;
+    if (conv_choose(a, f1, &s1) || conv_choose(n, f2, &s2)) return -1;
+    auto same_sums = [](const ConvChoice& s) { return s.family == CONV_GLDS && s.x3 && !s.gather && s.splits <= 1; };
+    TT_REQUIRE(same_sums(s1), "tt_conv2d_fwd: next_out: this layer alone (M=%d Cin=%d Cout=%d) would not run on a bf16x3 LDS-DMA tile", a.M,
+               a.Cin, a.Cout);
+    TT_REQUIRE(same_sums(s2), "tt_conv2d_fwd: next_out: the next layer alone (M=%d %d -> next_cout=%d) would not run on a bf16x3 LDS-DMA tile",
+               n.M, n.Cin, n.Cout);
+    const int nw = (n.Cout == 256) ? 4 : 8;
+    set_tile(c, CONV_X3_JOIN, n.Cout, nw, 1, a.Cin * 4, 2);      // (bkb = 4 Cin: bytes of a weight row of this layer)
+    c->x3 = true;
+    c->apair = (a.flags & 32) != 0;
+    c->below_min = a.M < kJoinMinRows;
+    return 0;
+}
+
 // ---- the LDS-DMA kernel on exact-f32 and 16-bit operands (conv_igemm_glds.hip)
 bool choose_glds(const ConvArgs& a, int dtype, ConvChoice* c) {
     constexpr int min_tiles = 2;      // K = 64 1x1 layers: 0.43 -> 0.27 ms against the register-staged kernel
@@ -342,6 +404,7 @@ int conv_choose(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
     *c = ConvChoice{};
     c->splits = 1;
     const bool ws = a.ws || f.assume_ws;
+    if (f.join) return choose_join(a, f, c);            // tt_conv_next: the joined kernel or an error
     if (a.flags & 256) return choose_up2(a, f, c);      // in_up2: its own kernel or an error
     if (f.weight_h2) {
         // half storage x (hi, lo) weights: the only kernel with this arithmetic -- a shape outside its contract is an error, not a
@@ -401,6 +464,7 @@ void conv_label(const ConvChoice& c, int dtype, char* out, size_t bytes) {
         case CONV_X3_RUN3: snprintf(out, bytes, "conv_x3_run3_kernel<%d>%s%s", c.bn, pre, tail); break;
         case CONV_X3_UP2: snprintf(out, bytes, "conv_x3_run3_kernel<%d, up2>", c.bn); break;     // (run-staged family: one patch, nine taps)
         case CONV_X3_PATCH: snprintf(out, bytes, "conv_x3_run3_kernel<%d, patch>%s", c.bn, pre); break;          // (the same family)
+        case CONV_X3_JOIN: snprintf(out, bytes, "conv_x3_join_kernel<%d, %d, %d>%s%s", c.bkb / 4, c.bn, c.waves_m, pre, c.below_min ? " below kJoinMinRows" : ""); break;
         case CONV_GLDS:
             snprintf(out, bytes, "conv_igemm_glds_kernel<%s, %d, %d, %d, %d, %d, %s, %s>%s%s", tn, c.bn, c.waves_m, c.waves_n, c.bkb,
                      c.stages, c.gather ? "true" : "false", c.x3 ? "true" : "false", pre, c.splits > 1 ? " split-K" : tail);

@@ -59,6 +59,7 @@ enum ConvFamily {
     CONV_X3_RUN3,   // conv_x3_pipe.hip   conv_x3_run3_kernel<bn, apair>
     CONV_X3_UP2,    // conv_x3_up2.hip    conv_x3_up2_kernel (input read through the bilinear x2 upsampling, tt_conv_desc.in_up2)
     CONV_X3_PATCH,  // conv_x3_patch.hip  conv_x3_patch_kernel<bn / 32> (pair-format 3 x 3 input staged as halo patches by LDS-DMA)
+    CONV_X3_JOIN,   // conv_x3_join.hip   conv_x3_join_kernel<bkb / 4, bn, waves_m> (this 1 x 1 layer and the next one in one launch, tt_conv2d_fwd_next)
     CONV_GLDS,      // conv_igemm_glds.hip conv_igemm_glds_kernel<T, bn, waves_m, waves_n, bkb, stages, gather, x3, apair>
     CONV_IGEMM,     // conv_igemm.hip     conv_igemm_kernel<T, 128, bn, waves_m, waves_n, gather>
 };
@@ -69,6 +70,12 @@ constexpr int kSpL2MinRows = 16384;
 // Fewest output rows at which a pair-format 3 x 3 layer takes the halo-patch kernel (conv_choose.cpp, choose_x3_patch).
 constexpr int kPatchMinRows = 16384;
 
+// Joined stage (tt_conv2d_fwd_next, tt_conv_next; conv_choose.cpp, choose_join).  kJoinFloorRows: fewest output rows the kernel's contract takes
+// (its pair-format output needs more than 4,096).  kJoinMinRows: fewest rows at which every routed form beats its two launches --
+// what callers route by (ops.join_ok); a launch below it still runs the joined kernel and its label says " below kJoinMinRows".
+constexpr int kJoinFloorRows = 4097;
+constexpr int kJoinMinRows = 32768;
+
 // What conv2d_run knows about a layer beside its validated ConvArgs.
 struct ConvFacts {
     int dtype;                  // operand storage type (TT_F32 / TT_BF16 / TT_F16)
@@ -76,6 +83,8 @@ struct ConvFacts {
     const void* weight_h2;
     bool out2, res1_up, res1_f32;
     bool assume_ws;             // tt_conv2d_splitk_slices: choose as if a split-K workspace of any size were given
+    const ConvArgs* join;       // tt_conv2d_fwd_next: the joined stage as the validated layer it would be alone (null: none)
+    const void* join_weight_x3; //   "   its weight_x3
 };
 
 struct ConvChoice {
@@ -86,6 +95,7 @@ struct ConvChoice {
     int main_rows;              // > 0: tail split -- the main launch covers this many 256-row tiles, the rest runs as 256 x 64 tiles
     int splits;                 // K ranges (gridDim.y), 1 = no split-K
     int slices;                 // split-K: workspace slices the ordered form writes (0: the atomic form); under assume_ws: slices to provide
+    bool below_min;             // CONV_X3_JOIN: fewer than kJoinMinRows rows (the label says so)
 };
 
 // The kernel tt_conv2d_fwd runs a validated layer on.  0, or -1 with the error text set where the layer's operands name an arithmetic

@@ -436,5 +436,6 @@ int launch_conv_x3_pipe(const ConvChoice& c, ConvArgs& a, hipStream_t st);      
 int launch_conv_glds(const ConvChoice& c, ConvArgs& a, int dtype, hipStream_t st);         // conv_igemm_glds.hip
 int launch_conv_x3_up2(const ConvChoice& c, ConvArgs& a, hipStream_t st);                  // conv_x3_up2.hip
 int launch_conv_x3_patch(const ConvChoice& c, ConvArgs& a, hipStream_t st);                // conv_x3_patch.hip
+int launch_conv_x3_join(const ConvChoice& c, ConvArgs& a, const ConvArgs& a2, hipStream_t st);     // conv_x3_join.hip (a2: the joined stage)
 
 }  // namespace tt

@@ -301,7 +301,7 @@ using namespace tt;
 
 // Validation of a descriptor and its translation into the kernels' arguments and the facts conv_choose takes.  Dereferences no data
 // pointer and touches no device: tt_conv2d_fwd, tt_conv2d_plan and tt_conv2d_splitk_slices all start here.
-static int conv2d_prepare(const tt_conv_desc* d, ConvArgs& a, ConvFacts& f) {
+static int conv2d_prepare(const tt_conv_desc* d, const tt_conv_next* n, ConvArgs& a, ConvFacts& f, ConvArgs& a2) {
     TT_REQUIRE(d && d->in && d->weight && d->out, "tt_conv2d_fwd: null pointer");
     TT_REQUIRE(d->dtype == TT_F32 || d->dtype == TT_BF16 || d->dtype == TT_F16, "tt_conv2d_fwd: bad dtype %d", d->dtype);
     TT_REQUIRE(d->out_dtype == TT_F32 || d->out_dtype == d->dtype ||
@@ -403,15 +403,48 @@ static int conv2d_prepare(const tt_conv_desc* d, ConvArgs& a, ConvFacts& f) {
     f.res1_up = d->res1_up_w > 0;
     f.res1_f32 = d->res1_f32 != 0;
     f.assume_ws = false;
+    f.join = nullptr;
+    f.join_weight_x3 = nullptr;
+    if (n) {
+        TT_REQUIRE(n->next_out, "tt_conv2d_fwd_next: next_out is null");
+        // the joined stage as the layer it would be alone: a 1 x 1 / stride 1 convolution over `out`'s pixels (the kernel's own
+        // contract: conv_choose.cpp, choose_join)
+        TT_REQUIRE(n->next_weight && (reinterpret_cast<uintptr_t>(n->next_weight) & 15) == 0 && n->next_cout > 0,
+                   "tt_conv2d_fwd: next_out needs next_weight (16-byte aligned) and next_cout > 0");
+        TT_REQUIRE(n->next_out_cstride > 0 && n->next_out_coff >= 0 && n->next_out_coff + n->next_cout <= n->next_out_cstride,
+                   "tt_conv2d_fwd: next_out_cstride=%d / next_out_coff=%d do not hold next_cout=%d channels", n->next_out_cstride,
+                   n->next_out_coff, n->next_cout);
+        TT_REQUIRE(!n->next_out_pair || (n->next_cout % 16 == 0 && n->next_out_cstride % 16 == 0 && n->next_out_coff % 16 == 0 &&
+                                         (reinterpret_cast<uintptr_t>(n->next_out) & 63) == 0),
+                   "tt_conv2d_fwd: next_out_pair needs next_cout / next_out_cstride / next_out_coff multiples of 16 and a 64-byte aligned next_out");
+        a2 = ConvArgs{};
+        a2.in = d->out; a2.weight = n->next_weight; a2.out = n->next_out;
+        a2.scale = n->next_scale; a2.shift = n->next_shift;
+        a2.N = d->N; a2.H = d->OH; a2.W = d->OW; a2.Cin = d->Cout; a2.in_cstride = d->out_cstride; a2.in_coff = d->out_coff;
+        a2.in_nstride = a.out_nstride;
+        a2.Cout = n->next_cout; a2.KH = a2.KW = a2.stride = a2.dil = 1;
+        a2.OH = d->OH; a2.OW = d->OW; a2.out_cstride = n->next_out_cstride; a2.out_coff = n->next_out_coff;
+        a2.out_nstride = (long long)d->OH * d->OW * n->next_out_cstride;
+        a2.shift_n_mod = 1;
+        a2.act = n->next_act; a2.out_dtype = TT_F32;
+        a2.M = a.M; a2.K = d->Cout;
+        a2.out_fast = 1; a2.tiles_n = 1;
+        a2.vec_epi = (n->next_cout % 8 == 0 && n->next_out_cstride % 8 == 0 && n->next_out_coff % 8 == 0 &&
+                      (reinterpret_cast<uintptr_t>(n->next_out) & 15) == 0) ? 1 : 0;
+        a2.res_vec = 1;
+        a2.flags = 16 | (n->next_out_pair ? 64 : 0);
+        f.join = &a2;
+        f.join_weight_x3 = n->next_weight_x3;
+    }
     return 0;
 }
 
 // validate -> choose -> launch
-extern "C" int tt_conv2d_fwd(const tt_conv_desc* d, void* stream) {
-    ConvArgs a;
+static int conv2d_run(const tt_conv_desc* d, const tt_conv_next* n, void* stream) {
+    ConvArgs a, a2;
     ConvFacts f;
     ConvChoice c;
-    if (const int r = conv2d_prepare(d, a, f)) return r;
+    if (const int r = conv2d_prepare(d, n, a, f, a2)) return r;
     if (const int r = conv_choose(a, f, &c)) return r;
     hipStream_t st = (hipStream_t)stream;
     const bool pair = d->in_pair || d->out_pair;
@@ -450,6 +483,11 @@ extern "C" int tt_conv2d_fwd(const tt_conv_desc* d, void* stream) {
             what = "tt_conv2d_fwd(x3 patch, pair)";
             r = launch_conv_x3_patch(c, a, st);
             break;
+        case CONV_X3_JOIN:
+            what = "tt_conv2d_fwd(x3 join)";
+            a2.weight = n->next_weight_x3;
+            r = launch_conv_x3_join(c, a, a2, st);
+            break;
         case CONV_GLDS:
             what = !c.x3 ? "tt_conv2d_fwd(glds)" : c.splits > 1 ? "tt_conv2d_fwd(glds x3 split-K)" : pair ? "tt_conv2d_fwd(glds x3, pair)" : "tt_conv2d_fwd(glds x3)";
             if (c.splits > 1) a.ws_slices = c.slices;
@@ -472,24 +510,38 @@ extern "C" int tt_conv2d_fwd(const tt_conv_desc* d, void* stream) {
     return check_launch(what);
 }
 
+extern "C" int tt_conv2d_fwd(const tt_conv_desc* d, void* stream) { return conv2d_run(d, nullptr, stream); }
+
+extern "C" int tt_conv2d_fwd_next(const tt_conv_desc* d, const tt_conv_next* next, void* stream) {
+    TT_REQUIRE(next, "tt_conv2d_fwd_next: null tt_conv_next");
+    return conv2d_run(d, next, stream);
+}
+
 extern "C" int tt_conv2d_splitk_slices(const tt_conv_desc* d) {
-    ConvArgs a;
+    ConvArgs a, a2;
     ConvFacts f;
     ConvChoice c;
-    if (conv2d_prepare(d, a, f)) return 0;
+    if (conv2d_prepare(d, nullptr, a, f, a2)) return 0;
     if (d->in_pair || d->out_pair || d->in_up2 || d->weight_h2 || d->res1_up_w > 0) return 0;       // layers that never take a workspace
     f.assume_ws = true;
     if (conv_choose(a, f, &c)) return 0;
     return c.splits > 1 ? c.slices : 0;
 }
 
-extern "C" int tt_conv2d_plan(const tt_conv_desc* d, char* label, int label_bytes) {
-    ConvArgs a;
+static int conv2d_plan(const tt_conv_desc* d, const tt_conv_next* n, char* label, int label_bytes) {
+    ConvArgs a, a2;
     ConvFacts f;
     ConvChoice c;
-    if (const int r = conv2d_prepare(d, a, f)) return r;
+    if (const int r = conv2d_prepare(d, n, a, f, a2)) return r;
     if (const int r = conv_choose(a, f, &c)) return r;
     TT_REQUIRE(label && label_bytes > 0, "tt_conv2d_plan: no room for the label");
     conv_label(c, d->dtype, label, (size_t)label_bytes);
     return 0;
+}
+
+extern "C" int tt_conv2d_plan(const tt_conv_desc* d, char* label, int label_bytes) { return conv2d_plan(d, nullptr, label, label_bytes); }
+
+extern "C" int tt_conv2d_plan_next(const tt_conv_desc* d, const tt_conv_next* next, char* label, int label_bytes) {
+    TT_REQUIRE(next, "tt_conv2d_plan_next: null tt_conv_next");
+    return conv2d_plan(d, next, label, label_bytes);
 }

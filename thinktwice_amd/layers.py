@@ -56,7 +56,10 @@ class Conv:
         self.ps2 = pixel_shuffle2
         self.cin = w.shape[-1]
 
-    def __call__(self, x, **kw):
+    def __call__(self, x, join=None, **kw):
+        if join is not None:      # `join`: the 1 x 1 Conv that reads this layer's output, run in the same launch (ops.conv2d nxt=);
+            assert not BN_TRAIN   # returns (this layer's output, the next layer's pair-format output)
+            kw["nxt"] = (join.w, join.w_x3, join.scale, join.shift, join.act)
         if BN_TRAIN and self.bn is not None:
             return self._bn_train(x, **kw)
         return ops.conv2d(x, self.w, stride=self.stride, pad=self.pad, dil=self.dil, scale=self.scale,

@@ -79,18 +79,40 @@ class _ResNet50:
             y = self.stem(x, stop_grad=True)      # (training tape: the image is a leaf without a gradient)
         x = ops.maxpool3x3s2(y)
         outs = []
-        for stage in self.blocks:
-            for blk in stage:
-                idt = blk["ds"](x) if blk["ds"] is not None else x
-                # conv1's output has one reader, the 3 x 3 conv2: produced pre-split (pair format, tt_conv_desc.in_pair) -- the
-                # operand split once per element in conv1's epilogue instead of nine times per column tile in conv2's K loop
-                c2 = blk["c2"]
-                rows2 = x.shape[0] * (x.shape[1] // c2.stride) * (x.shape[2] // c2.stride)
-                pr = (c2.w_x3 is not None and not layers.BN_TRAIN and
-                      ops.pair_ok(min(rows2, x.shape[0] * x.shape[1] * x.shape[2]), c2.w.shape[-1], c2.w.shape[0]))
-                y = c2(blk["c1"](x, out_pair=pr), in_pair=pr)
-                x = blk["c3"](y, res1=idt)          # relu(bn3(conv3) + identity)
-            outs.append(x)
+
+        def pair_c1(blk, shape):
+            # conv1's output has one reader, the 3 x 3 conv2: produced pre-split (pair format, tt_conv_desc.in_pair) -- the
+            # operand split once per element in conv1's epilogue instead of nine times per column tile in conv2's K loop
+            c2 = blk["c2"]
+            rows2 = shape[0] * (shape[1] // c2.stride) * (shape[2] // c2.stride)
+            return (c2.w_x3 is not None and not layers.BN_TRAIN and
+                    ops.pair_ok(min(rows2, shape[0] * shape[1] * shape[2]), c2.w.shape[-1], c2.w.shape[0]))
+
+        from . import autodiff
+        flat = [blk for stage in self.blocks for blk in stage]
+        last = [len(stage) for stage in self.blocks]
+        last = [sum(last[:i + 1]) - 1 for i in range(len(last))]          # index of each stage's last block
+        y1 = None           # this block's conv1 output, when the previous block's conv3 launch produced it
+        for i, blk in enumerate(flat):
+            idt = blk["ds"](x) if blk["ds"] is not None else x
+            pr = pair_c1(blk, x.shape)
+            if y1 is None:
+                y1 = blk["c1"](x, out_pair=pr)
+            y = blk["c2"](y1, in_pair=pr)
+            # conv3 and the NEXT block's conv1 in one launch (tt_conv2d_fwd_next): the block output x is still written -- the next
+            # block's identity / downsample and `outs` read it -- but conv1 takes its tile of x from the workgroup that made it
+            # instead of reading all of x back.  Also across the layer1 -> 2 and layer2 -> 3 boundaries; layer 4's conv1 (512 wide)
+            # and the taped / train-mode / 16-bit paths keep two launches.  TT_BNECK_JOIN=0: two launches everywhere
+            c3, nb = blk["c3"], flat[i + 1] if i + 1 < len(flat) else None
+            rows = y.shape[0] * y.shape[1] * y.shape[2]
+            if (nb is not None and autodiff.TAPE is None and not layers.BN_TRAIN and c3.w_x3 is not None and
+                    nb["c1"].w_x3 is not None and pair_c1(nb, y.shape) and
+                    ops.join_ok(rows, c3.w.shape[-1], c3.w.shape[0], nb["c1"].w.shape[0])):
+                x, y1 = c3(y, res1=idt, join=nb["c1"])
+            else:
+                x, y1 = c3(y, res1=idt), None          # relu(bn3(conv3) + identity)
+            if i in last:
+                outs.append(x)
         return outs
 
 

@@ -94,6 +94,7 @@ CONV_BYTES = None     # same order as CONV_PROFILE: compulsory HBM bytes of the 
                       # dense: int; sparse: (bytes per live output row, fixed bytes)
 
 _ConvDesc = _lib.structs()["tt_conv_desc"]      # `in` is spelled `in_`
+_ConvNext = _lib.structs()["tt_conv_next"]      # the joined stage of tt_conv2d_fwd_next
 
 
 def _last_conv_kernel():
@@ -220,7 +221,7 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
            res2=None, res2_coff=0, out=None, out_coff=0, in_coff=0, cin=None, pixel_shuffle2=False,
            shift_n=None, shift_n_mod=1, out_dtype=None, out_nstride=0, out_hw=None, splitk_ws=None,
            in_cstride=None, w_x3=None, _no_tape=False, stop_grad=False, bn_raw=False, in_pair=False, out_pair=False,
-           w_h2=None, out2=None, out2_coff=0, res1_up=False, in_up2=False):
+           w_h2=None, out2=None, out2_coff=0, res1_up=False, in_up2=False, nxt=None, nxt_out=None, nxt_out_coff=0):
     """Channel-last implicit-GEMM convolution on MFMA (tt_conv2d_fwd).
 
     x   [N,H,W,Cs]  (f32 or bf16); channels [in_coff, in_coff+cin) are convolved
@@ -235,6 +236,11 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
     in_up2 (bf16x3 3 x 3 / stride 1 / pad 1 layers with 64 output channels; `up2_ok` says which): x is the low-resolution f32 map
     [N, h, w, C] and the layer convolves bilinear_up2(x) -- nn.Upsample(scale_factor=2, bilinear, align_corners=True) -- without that
     tensor ever existing (tt_conv_desc.in_up2); bit for bit conv2d(bilinear_up2(x, out_pair=True), ..., in_pair=True).
+    nxt (bf16x3 1 x 1 / stride 1 layers; `join_ok` says which): (w, w_x3, scale, shift, act) of the 1 x 1 convolution that reads this
+    layer's output.  It runs in the SAME launch on each row tile of `out` while that is still on chip (tt_conv2d_fwd_next), and
+    conv2d returns (out, next_out) with next_out [N, OH, OW, w.shape[0]] in PAIR format; both are bit for bit what the two conv2d
+    calls give (a ResNet bottleneck's conv3 and the next block's conv1).  nxt_out / nxt_out_coff: the tensor (and channel offset)
+    next_out is written into instead of a new one.  Inference only.
     in_cstride / out_hw: "row-run" form -- the kernel reads `cin` CONTIGUOUS elements starting at pixel (ih, iw) of a
     tensor whose pixels are only Cs < cin elements apart (a run of cin/Cs pixels along W), with the output size given
     explicitly; used for the 7x7/2 stem (lss.py).
@@ -297,6 +303,19 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
         if autodiff.TAPE is not None:
             raise _lib.TTError("conv2d: in_up2 is an inference-path fusion (the tape records bilinear_up2 and the convolution apart)")
         d.in_up2 = 1
+    nout, dn = None, None
+    if nxt is not None:
+        if autodiff.TAPE is not None:
+            raise _lib.TTError("conv2d: a joined stage is an inference-path fusion (the tape records the two convolutions apart)")
+        nw, nw_x3, nscale, nshift, nact = nxt
+        assert w_x3 is not None and nw_x3 is not None and x.dtype == torch.float32 and out.dtype == torch.float32 and splitk_ws is None
+        assert nw.is_contiguous() and nw_x3.is_contiguous() and tuple(nw.shape[1:]) == (1, 1, Cout) and nw_x3.shape == nw.shape
+        nout = nxt_out if nxt_out is not None else torch.empty(N, OH, OW, nw.shape[0], dtype=torch.float32, device=x.device)
+        assert nout.dtype == torch.float32 and nout.is_contiguous() and tuple(nout.shape[:3]) == (N, OH, OW)
+        dn = _ConvNext()
+        dn.next_weight = nw.data_ptr(); dn.next_weight_x3 = nw_x3.data_ptr(); dn.next_cout = nw.shape[0]
+        dn.next_scale = ptr(nscale); dn.next_shift = ptr(nshift); dn.next_act = nact
+        dn.next_out = nout.data_ptr(); dn.next_out_cstride = nout.shape[-1]; dn.next_out_coff = nxt_out_coff; dn.next_out_pair = 1
     if w_x3 is not None and Cout < 64 and (autodiff.TAPE is not None or _no_tape):
         # training step (taped forward, recomputations, input-gradient convolutions): the layers with fewer than 64 output channels
         # keep the exact-f32 kernels the gradient goldens were taken with (inference runs them on the 256 x 32 bf16x3 tile)
@@ -327,11 +346,16 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
     if CONV_PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    rc = lib().tt_conv2d_fwd(ctypes.byref(d), cur_stream(x.device))
+    if dn is not None:
+        rc = lib().tt_conv2d_fwd_next(ctypes.byref(d), ctypes.byref(dn), cur_stream(x.device))
+    else:
+        rc = lib().tt_conv2d_fwd(ctypes.byref(d), cur_stream(x.device))
     check(rc, "tt_conv2d_fwd")
     if CONV_PROFILE is not None:
         e1.record()
-        CONV_PROFILE.append((2.0 * N * OH * OW * Cout * KH * KW * Cin, e0, e1,
+        n2 = 0 if nout is None else nxt[0].shape[0]
+        CONV_PROFILE.append((2.0 * N * OH * OW * Cout * (KH * KW * Cin + n2), e0, e1,
+                             f"M={N * OH * OW} N={Cout}->{n2} K={Cin} join k1x1s1" if n2 else
                              f"M={N * OH * OW} N={Cout} K={KH * KW * Cin} k{KH}x{KW}s{stride}"))
         if CONV_KERNELS is not None:
             CONV_KERNELS.append(_last_conv_kernel())
@@ -342,13 +366,14 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
             wsz = w.numel() * w.element_size() * (2 if w_h2 is not None else 1)
             CONV_BYTES.append(in_px * (in_cstride or Cin) * esz + m_out * Cout * osz + wsz +
                               m_out * Cout * esz * ((res1 is not None) + (res2 is not None)) +
-                              (m_out * Cout * 4 if out2 is not None else 0))
+                              (m_out * Cout * 4 if out2 is not None else 0) +
+                              (m_out * n2 * 4 + nxt[0].numel() * 4 if n2 else 0))     # a joined stage: its output and weights
     if not _no_tape:
         from . import autodiff
         if autodiff.TAPE is not None:
             autodiff.TAPE.conv(x, w, out, stride, pad, dil, scale, shift, act, in_coff, cin, out_coff, res1, res1_coff,
                                res2, res2_coff, pixel_shuffle2, in_cstride, shift_n, shift_n_mod, stop_grad, bn_raw)
-    return out
+    return out if nout is None else (out, nout)
 
 
 SEG_CHAIN = os.environ.get("TT_SEG_CHAIN", "1") != "0"     # A/B knob and test hook: 0 = the two feedback convs stay two launches
@@ -576,6 +601,21 @@ def pair_ok(rows, cin=32, cout=64, taps=9):
     from . import autodiff
     return (PAIR and autodiff.TAPE is None and rows > 4096 and cin % 32 == 0 and taps * cin >= 64 and
             (8 <= cout <= 32 or cout >= 64))
+
+
+BNECK_JOIN = os.environ.get("TT_BNECK_JOIN", "1") != "0"      # A/B knob and test hook: 0 = a bottleneck's conv3 and the next block's conv1 stay two launches
+JOIN_MIN_ROWS = 32768                                       # csrc/conv_choose.h: kJoinMinRows
+# the (Cin, Cout, next Cout) forms of the joined kernel that are faster than their two launches at the model's row counts
+# (profiles/bottleneck_join.txt); the library also takes (128, 512, 256) and (256, 1024, 256), which lose there
+JOIN_ROUTED = ((64, 256, 64), (64, 256, 128), (128, 512, 128))
+
+
+def join_ok(rows, k1, cout, next_cout):
+    """Whether a bf16x3 1 x 1 / stride 1 convolution k1 -> cout over this many rows also produces the next 1 x 1 layer's cout ->
+    next_cout output in its own launch (conv2d(nxt=...), tt_conv2d_fwd_next): the library's contract (csrc/conv_choose.cpp,
+    choose_join) restricted to the routed forms.  tests/test_conv_join_choice.py pins this to the library's rule."""
+    from . import autodiff
+    return BNECK_JOIN and autodiff.TAPE is None and rows >= JOIN_MIN_ROWS and (k1, cout, next_cout) in JOIN_ROUTED
 
 
 SEG_UP2 = os.environ.get("TT_SEG_UP2", "1") != "0"      # A/B knob and test hook: 0 = unet_layer0's upsample and its 3 x 3 conv stay two launches
