@@ -3,6 +3,7 @@
 All functions take device tensors and launch on torch's current stream.  No function here
 computes anything in PyTorch: allocation and stream handling only.
 """
+import contextlib
 import ctypes
 import os
 
@@ -11,6 +12,41 @@ import torch
 from . import _lib
 from ._lib import (TT_BF16, TT_F16, TT_F32, TTError, check, clear_device_faults, cur_stream, device_faults, lib, ptr,  # noqa: F401
                    raise_on_device_fault, require_cuda)
+# The only reference to the training tape.  autodiff imports this module in turn; whichever of the two is imported first sees the
+# other half-initialised, which is fine because neither touches the other at import time: autodiff.TAPE is read per call.
+from . import autodiff
+
+
+def _active_tape():
+    """The tape that records this call's backward (autodiff.TAPE, read at call time: the trainer and the tests assign to it)."""
+    return autodiff.TAPE
+
+
+def _tape(op, *args):
+    """The tape hook of every differentiable wrapper: TAPE.<op>(*args) while a tape is active, nothing otherwise."""
+    tape = _active_tape()
+    if tape is not None:
+        getattr(tape, op)(*args)
+
+
+def _st(t):
+    """The current stream of this tensor's device."""
+    return cur_stream(t.device)
+
+
+def _cs(t):
+    """Channel stride (the last dimension) of an optional channel-last operand."""
+    return 0 if t is None else t.shape[-1]
+
+
+def _workspace(nbytes, device):
+    """Scratch bytes for one launch, sized by the entry's own *_workspace_bytes query."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def _level_hw(level_hw):
+    """(H, W) of the four feature levels as the int[8] the look-module entries take."""
+    return (ctypes.c_int * 8)(*[v for pair in level_hw for v in pair])
 
 
 def dtype_code(t):
@@ -34,7 +70,7 @@ def frustum_voxel_index(frustum, mats, voxel_lo, voxel_size, batch_size, num_cam
     lo = (ctypes.c_float * 3)(*[float(v) for v in voxel_lo])
     sz = (ctypes.c_float * 3)(*[float(v) for v in voxel_size])
     rc = lib().tt_frustum_voxel_index(batch_size, num_cams, D, fH, fW, ptr(frustum), ptr(mats), lo, sz, ptr(geom), ptr(gf),
-                                      cur_stream(frustum.device))
+                                      _st(frustum))
     check(rc, "tt_frustum_voxel_index")
     return (geom, gf) if want_f32 else geom
 
@@ -60,16 +96,13 @@ def lift_splat(depth_logits, context, geom_xyz, voxel_num, batch_size, num_cams,
     if not _LIFT_SPLAT_ATOMIC:
         ws_bytes = int(lib().tt_lift_splat_workspace_bytes(batch_size, num_cams, D, fH, fW, C, vx, vy))
         if ws_bytes > 0:
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=context.device)
+            ws = _workspace(ws_bytes, context.device)
     rc = lib().tt_lift_splat_fwd_ws(batch_size, num_cams, D, fH, fW, C, vx, vy, vz, ptr(depth_logits), ptr(context),
                                     dtype_code(context), ptr(geom_xyz), ptr(out), out.shape[-1], out_coff, 1 if rot_flip else 0,
-                                    ptr(ws), ws_bytes, cur_stream(context.device))
+                                    ptr(ws), ws_bytes, _st(context))
     check(rc, "tt_lift_splat_fwd_ws")
     if record:
-        from . import autodiff
-        if autodiff.TAPE is not None:
-            autodiff.TAPE.lift_splat(depth_logits, context, geom_xyz, (vx, vy, vz), batch_size, num_cams, out, out_coff,
-                                     rot_flip)
+        _tape("lift_splat", depth_logits, context, geom_xyz, (vx, vy, vz), batch_size, num_cams, out, out_coff, rot_flip)
     return out
 
 
@@ -82,7 +115,7 @@ def lift_splat_bwd(depth_logits, context, geom_xyz, voxel_num, batch_size, num_c
     assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (depth_logits, context, gout, gdepth, gctx))
     check(lib().tt_lift_splat_bwd(batch_size, num_cams, D, fH, fW, C, vx, vy, vz,
                                   ptr(depth_logits), ptr(context), ptr(geom_xyz), ptr(gout), gout.shape[-1],
-                                  out_coff, ptr(gdepth), ptr(gctx), cur_stream(context.device)), "tt_lift_splat_bwd")
+                                  out_coff, ptr(gdepth), ptr(gctx), _st(context)), "tt_lift_splat_bwd")
 
 
 # ----------------------------------------------------------------------------- conv / linear
@@ -102,6 +135,128 @@ def _last_conv_kernel():
     return L.tt_conv_last_kernel().decode()
 
 
+class _Launch:
+    """The launch recorder of the convolution wrappers:
+
+        with _launch() as rec:
+            check(lib().tt_...(...))
+        if rec is not None:
+            rec.log(flops, shape, kernel=..., nbytes=...)
+
+    While the bench collects (CONV_PROFILE is a list) the block runs between two timing events and `log` files the launch in the
+    three lists; otherwise `_launch()` hands out the shared idle recorder: `rec` is None, no event, no label query."""
+
+    def __enter__(self):
+        self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        self.e0.record()
+        return self
+
+    def __exit__(self, *exc):
+        self.e1.record()
+
+    def log(self, flops, shape, *sparse, kernel, nbytes):
+        """CONV_PROFILE gets (flops, start, end, shape) -- a sparse launch adds its three (m_dev, M, per-row taps) entries;
+        CONV_KERNELS the label: a string, or a function asked only when the list is kept; CONV_BYTES `nbytes`."""
+        CONV_PROFILE.append((flops, self.e0, self.e1, shape) + sparse)
+        if CONV_KERNELS is not None:
+            CONV_KERNELS.append(kernel if isinstance(kernel, str) else kernel())
+        if CONV_BYTES is not None:
+            CONV_BYTES.append(nbytes)
+
+
+_IDLE = contextlib.nullcontext()      # `with _IDLE as rec`: rec is None
+
+
+def _launch():
+    return _IDLE if CONV_PROFILE is None else _Launch()
+
+
+def conv_geometry(x_shape, w_shape, stride=1, pad=0, dil=1, out_hw=None, pixel_shuffle2=False, in_up2=False):
+    """The sizes of a dense convolution, from plain numbers: (H, W, OH, OW, out_shape).  H, W: the logical input (in_up2: the
+    upsampled map, twice the source tensor's); OH, OW: the usual formula, or `out_hw` where the caller states them (row-run form);
+    out_shape: the tensor the layer writes when it allocates it (pixel_shuffle2: the four channel groups spread 2 x 2)."""
+    N, H, W, _ = x_shape
+    if in_up2:
+        H, W = 2 * H, 2 * W
+    Cout, KH, KW, _ = w_shape
+    OH = (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1
+    OW = (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1
+    if out_hw is not None:
+        OH, OW = out_hw
+    return H, W, OH, OW, ((N, 2 * OH, 2 * OW, Cout // 4) if pixel_shuffle2 else (N, OH, OW, Cout))
+
+
+def conv_desc(x, x_shape, x_strides, w, w_shape, out, out_shape, out_strides, dtype, out_dtype,
+              stride=1, pad=0, dil=1, out_hw=None, pixel_shuffle2=False, in_up2=False,
+              in_coff=0, in_cstride=None, out_coff=0, out_nstride=0,
+              scale=None, shift=None, shift_n=None, shift_n_mod=1, act=0,
+              res1=None, res1_shape=None, res1_dtype=None, res1_coff=0, res1_up=False, res2=None, res2_shape=None, res2_coff=0,
+              weight_x3=None, weight_h2=None, in_pair=False, out_pair=False, out2=None, out2_shape=None, out2_coff=0,
+              gather=None, plan=None):
+    """The filled tt_conv_desc of one launch, from plain numbers: no tensor comes in.  x / w / out / scale / shift / shift_n /
+    res1 / res2 / weight_x3 / weight_h2 / out2: element addresses (int, None = absent); *_shape / *_strides: the tensors' own, in
+    elements; dtype / out_dtype / res1_dtype: TT_F32 / TT_BF16 / TT_F16 (res1_dtype None: the operands'); the rest as conv2d names them.
+    gather = (rulebook address, m_dev address, M) makes it the sparse form of gather_conv -- x_shape [R_in, Cin] rows, one "pixel"
+    per output row, the taps along KW, `stride` only a hint to the dispatch -- and plan = (row_perm, row_mask) addresses its tile plan.
+    The split-K fields are the caller's to set once the library has answered the query about this descriptor.
+    The signature has one line per group.  conv2d, which runs a few hundred times per forward, passes the groups by position, line
+    for line (matching forty keywords costs more than filling the forty fields): whoever moves a parameter moves it there too."""
+    Cout, KH, KW, Cin = w_shape
+    if gather is None:
+        N, Cs = x_shape[0], x_shape[3]
+        H, W, OH, OW, _ = conv_geometry(x_shape, w_shape, stride, pad, dil, out_hw, pixel_shuffle2, in_up2)
+        in_nstride = x_strides[0] if N > 1 else 0        # one image: no batch stride to trust
+        out_nstride = out_nstride or (out_strides[0] if (len(out_shape) == 4 and N > 1) else 0)
+    else:
+        N, Cs = gather[2], x_shape[1]
+        H = W = OH = OW = 1
+        in_nstride = out_nstride = 0
+    d = _ConvDesc()         # all zeroes: an absent operand or an unused mode below leaves its fields so
+    d.in_ = x; d.N = N; d.H = H; d.W = W; d.Cin = Cin; d.in_cstride = in_cstride or Cs; d.in_coff = in_coff
+    d.in_nstride = in_nstride
+    d.weight = w; d.Cout = Cout; d.KH = KH; d.KW = KW; d.stride = stride; d.pad = pad; d.dil = dil
+    d.out = out; d.OH = OH; d.OW = OW
+    d.out_cstride = out_shape[-1]; d.out_coff = out_coff
+    d.out_nstride = out_nstride
+    d.act = act; d.dtype = dtype; d.out_dtype = out_dtype
+    d.shift_n_mod = shift_n_mod
+    if scale is not None:
+        d.scale = scale
+    if shift is not None:
+        d.shift = shift
+    if shift_n is not None:
+        d.shift_n = shift_n
+    d.res1_coff = res1_coff
+    if res1 is not None:
+        d.res1 = res1; d.res1_cstride = res1_shape[-1]
+        if res1_dtype == TT_F32 and dtype != TT_F32:
+            d.res1_f32 = 1              # an f32 sum chain beside half conv inputs (mixed mode's PAFPN)
+    if res1_up:                         # res1 is the coarser map, added through nearest upsampling
+        d.res1_up_h, d.res1_up_w = res1_shape[1], res1_shape[2]
+    d.res2_coff = res2_coff
+    if res2 is not None:
+        d.res2 = res2; d.res2_cstride = res2_shape[-1]
+    if out2 is not None:
+        d.out2 = out2; d.out2_cstride = out2_shape[-1]; d.out2_coff = out2_coff
+    if weight_x3 is not None:
+        d.weight_x3 = weight_x3
+    if weight_h2 is not None:
+        d.weight_h2 = weight_h2
+    if pixel_shuffle2:
+        d.pixel_shuffle2 = 1
+    if in_pair:
+        d.in_pair = 1
+    if out_pair:
+        d.out_pair = 1
+    if in_up2:
+        d.in_up2 = 1
+    if gather is not None:
+        d.gather_idx, d.m_dev = gather[0], gather[1]
+    if plan is not None:
+        d.row_perm, d.row_mask = plan
+    return d
+
+
 SPARSE_PAIRS = None   # bench.py: device int64 counter of existing (row, tap) pairs, filled by sp_tile_plan
 
 
@@ -110,12 +265,11 @@ def sp_tile_plan(nbr, m_dev):
     rows sorted by tap-occupancy mask, so that a 256-row tile of the gathered GEMM only visits the union of its taps."""
     require_cuda(nbr, m_dev)
     M, KV = nbr.shape
-    ws_bytes = int(lib().tt_sp_tile_plan_workspace_bytes(M))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=nbr.device)
+    ws = _workspace(lib().tt_sp_tile_plan_workspace_bytes(M), nbr.device)
     perm = torch.empty(M, dtype=torch.int32, device=nbr.device)
     mask = torch.empty(M, dtype=torch.int32, device=nbr.device)
-    check(lib().tt_sp_tile_plan(ptr(nbr), ptr(m_dev), M, KV, ptr(ws), ws_bytes, ptr(perm), ptr(mask),
-                                ptr(SPARSE_PAIRS), cur_stream(nbr.device)), "tt_sp_tile_plan")
+    check(lib().tt_sp_tile_plan(ptr(nbr), ptr(m_dev), M, KV, ptr(ws), ws.numel(), ptr(perm), ptr(mask),
+                                ptr(SPARSE_PAIRS), _st(nbr)), "tt_sp_tile_plan")
     return perm, mask
 
 
@@ -132,37 +286,22 @@ def gather_conv(feats, nbr, m_dev, w, *, scale=None, shift=None, act=0, res=None
     if out is None:
         out = torch.empty(M, Cout, dtype=out_dtype or feats.dtype, device=feats.device)
     assert tuple(out.shape) == (M, Cout) and out.is_contiguous()
-    d = _ConvDesc()
-    d.in_ = feats.data_ptr(); d.N = M; d.H = 1; d.W = 1; d.Cin = Cin; d.in_cstride = Cin; d.in_coff = 0
-    d.in_nstride = 0
-    d.weight = w.data_ptr(); d.Cout = Cout; d.KH = 1; d.KW = KW; d.stride = stride; d.pad = 0; d.dil = 1
-    d.out = out.data_ptr(); d.OH = 1; d.OW = 1; d.out_cstride = Cout; d.out_coff = 0; d.out_nstride = 0
-    d.scale = ptr(scale); d.shift = ptr(shift)
-    d.res1 = ptr(res); d.res1_cstride = 0 if res is None else res.shape[-1]
-    d.act = act; d.dtype = dtype_code(feats); d.out_dtype = dtype_code(out)
-    d.gather_idx = nbr.data_ptr(); d.m_dev = ptr(m_dev)
-    d.weight_x3 = ptr(w_x3)
-    if plan is not None:
-        d.row_perm, d.row_mask = plan[0].data_ptr(), plan[1].data_ptr()
-    if CONV_PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib().tt_conv2d_fwd(ctypes.byref(d), cur_stream(feats.device)), "tt_conv2d_fwd(gather)")
-    if CONV_PROFILE is not None:
-        e1.record()
+    d = conv_desc(x=feats.data_ptr(), x_shape=feats.shape, x_strides=None, w=w.data_ptr(), w_shape=(Cout, 1, KW, Cin),
+                  out=out.data_ptr(), out_shape=out.shape, out_strides=None, dtype=dtype_code(feats), out_dtype=dtype_code(out),
+                  stride=stride, scale=ptr(scale), shift=ptr(shift), shift_n_mod=0, act=act, res1=ptr(res),
+                  res1_shape=None if res is None else res.shape, weight_x3=ptr(w_x3), gather=(nbr.data_ptr(), ptr(m_dev), M),
+                  plan=None if plan is None else (plan[0].data_ptr(), plan[1].data_ptr()))
+    with _launch() as rec:
+        check(lib().tt_conv2d_fwd(ctypes.byref(d), _st(feats)), "tt_conv2d_fwd(gather)")
+    if rec is not None:
+        esz, osz = feats.element_size(), out.element_size()
         # FLOP accounting over the EXISTING (row, tap) pairs: per-row tap counts of the rulebook (measurement only)
-        CONV_PROFILE.append((2.0 * Cout * KW * Cin, e0, e1, f"sparse M<={M} N={Cout} K={KW * Cin}", m_dev, M,
-                             ((nbr >= 0).sum(1), 2.0 * Cout * Cin)))
-        if CONV_KERNELS is not None:
-            CONV_KERNELS.append(_last_conv_kernel())
-        if CONV_BYTES is not None:      # one input row and one output row (+ residual row) per live output row, rulebook row
-            esz, osz = feats.element_size(), out.element_size()
-            CONV_BYTES.append((Cin * esz + Cout * osz + (Cout * esz if res is not None else 0) + KW * 4,
-                               w.numel() * w.element_size()))
+        # bytes: one input row and one output row (+ residual row) per live output row, rulebook row
+        rec.log(2.0 * Cout * KW * Cin, f"sparse M<={M} N={Cout} K={KW * Cin}", m_dev, M, ((nbr >= 0).sum(1), 2.0 * Cout * Cin),
+                kernel=_last_conv_kernel,
+                nbytes=(Cin * esz + Cout * osz + (Cout * esz if res is not None else 0) + KW * 4, w.numel() * w.element_size()))
     if not _no_tape:
-        from . import autodiff
-        if autodiff.TAPE is not None:
-            autodiff.TAPE.gather_conv(feats, nbr, m_dev, w, scale, shift, act, res, out, in_rows, bn_raw)
+        _tape("gather_conv", feats, nbr, m_dev, w, scale, shift, act, res, out, in_rows, bn_raw)
     return out
 
 
@@ -174,12 +313,12 @@ def gather_conv_wgrad(feats, nbr, m_dev, dy, taps, cin_pad=None):
     cin_pad = cin_pad or Cin
     out = torch.empty(Cout, 1, taps, cin_pad, dtype=torch.float32, device=dy.device)
     L = lib()
-    nb = int(L.tt_gather_conv_wgrad_workspace_bytes(M, Cout, Cin, cin_pad, taps))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dy.device)
+    ws = _workspace(L.tt_gather_conv_wgrad_workspace_bytes(M, Cout, Cin, cin_pad, taps), dy.device)
     assert feats.is_contiguous() and dy.is_contiguous() and nbr.is_contiguous() and feats.dtype == torch.float32
+    nb = ws.numel()
     check(L.tt_gather_conv_wgrad(ptr(feats), Cin, Cin, ptr(nbr), ptr(m_dev), M, taps, ptr(dy), Cout,
                                  Cout, cin_pad, 0, ptr(out), ptr(ws), nb, _st(dy)), "tt_gather_conv_wgrad")
-    if CONV_KERNELS is not None:      # (no CONV_PROFILE record goes with it: this launch is not timed)
+    if CONV_KERNELS is not None:      # (no CONV_PROFILE record goes with it: this launch is not timed, so not under _launch())
         label = ctypes.create_string_buffer(192)
         check(L.tt_gather_conv_wgrad_plan(ptr(feats), Cin, Cin, ptr(nbr), ptr(m_dev), M, taps, ptr(dy), Cout, Cout, cin_pad, 0,
                                           ptr(out), ptr(ws), nb, 0, label, len(label)), "tt_gather_conv_wgrad_plan")
@@ -202,10 +341,8 @@ def sp_to_dense(x, coords, rows, max_rows, dims, batch_size):
     dense = torch.zeros(batch_size, H, W, C * D, dtype=x.dtype, device=x.device)
     dc = (ctypes.c_int * 3)(*dims)
     check(lib().tt_sp_to_dense(ptr(x), ptr(coords), ptr(rows), max_rows, C, dc, ptr(dense), dtype_code(x),
-                               cur_stream(x.device)), "tt_sp_to_dense")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.sp_to_dense(x, coords, rows, max_rows, dims, dense)
+                               _st(x)), "tt_sp_to_dense")
+    _tape("sp_to_dense", x, coords, rows, max_rows, dims, dense)
     return dense
 
 
@@ -214,7 +351,74 @@ def sp_from_dense(gdense, coords, rows, max_rows, dims, grows):
     D, H, W = dims
     C = grows.shape[1]
     check(lib().tt_sp_from_dense(ptr(gdense), ptr(coords), ptr(rows), max_rows, C, D, H, W,
-                                 ptr(grows), cur_stream(grows.device)), "tt_sp_from_dense")
+                                 ptr(grows), _st(grows)), "tt_sp_from_dense")
+
+
+# conv2d options that exist for inference layouts and fusions only, and why the tape refuses each
+_INFERENCE_ONLY = (
+    ("w_h2", "conv2d: half-storage (h2) layers have no backward; train in dtype torch.float32 or 'f32x3'"),
+    ("in_pair / out_pair", "conv2d: pair-format activations are an inference-path layout (the tape reads f32 tensors)"),
+    ("in_up2", "conv2d: in_up2 is an inference-path fusion (the tape records bilinear_up2 and the convolution apart)"),
+    ("nxt", "conv2d: a joined stage is an inference-path fusion (the tape records the two convolutions apart)"),
+)
+
+
+def _refuse_on_tape(*used):
+    """`used`: whether the call uses each option of _INFERENCE_ONLY, in its order.  Raises the first one's message under a tape."""
+    if any(used) and _active_tape() is not None:
+        raise TTError(next(msg for u, (_, msg) in zip(used, _INFERENCE_ONLY) if u))
+
+
+def _in_training_step(no_tape):
+    """Whether this conv2d call belongs to a training step: the forward under the tape, or one of the backward's recomputations and
+    input-gradient convolutions, which run after the tape has closed and pass _no_tape instead."""
+    return _active_tape() is not None or no_tape
+
+
+def _training_x3(w_x3, cout, training):
+    """The bf16x3 operand a layer runs with: (for a plain launch, for a split-K launch).  Inference uses w_x3 for both.  The gradient
+    goldens were taken with the exact-f32 kernels on two kinds of layer, so a training step keeps those there: the layers with fewer
+    than 64 output channels (inference runs them on the 256 x 32 bf16x3 tile) drop the operand altogether, and the few-row long-K
+    layers drop it for split-K -- the split-K query must not see it, or it answers for the bf16x3 split-K tile."""
+    if w_x3 is None or (training and cout < 64):
+        return None, None
+    return w_x3, (None if training else w_x3)
+
+
+def auto_splitk_asks(rows, k, splitk_ws=False, pair=False, in_up2=False, h2=False, res1_up=False):
+    """Whether conv2d asks the library for a split-K workspace of its own: few rows, very long K, none of the operand modes that
+    have no split-K form, and no workspace from the caller.  TT_CONV_AUTO_SPLITK=0 disables."""
+    return _AUTO_SPLITK and not splitk_ws and not (pair or in_up2) and not h2 and not res1_up and rows <= 4096 and k >= 2048
+
+
+def _auto_splitk(d, device):
+    """The f32 workspace of a launch auto_splitk_asks about, if the library wants it split (d.splitk_slices is then set), else None.
+    Few rows, very long K (BEV-update conv K=18720, flatten MLPs): cross-workgroup split-K with an f32 workspace
+    beats conv_small.hip's in-workgroup split there (277 vs 416 us on the BEV-update conv: the direct 32 B/row
+    operand loads of the small kernel waste L2 sectors on a 10 MB weight matrix).
+    Ordered form (no atomics, no zero fill): one [M][Cout] slice per K split, added in index order by the finalize kernel.
+    With a bf16x3 operand the layer runs the 64-wide bf16x3 tile with the K tiles dealt over workgroups
+    (conv_igemm_glds.hip, x3_splitk_plan) instead of the exact-f32 register-staged kernel."""
+    slices = int(lib().tt_conv2d_splitk_slices(ctypes.byref(d)))
+    if slices <= 0:
+        return None
+    d.splitk_slices = slices
+    return torch.empty(slices, d.N * d.OH * d.OW, d.Cout, dtype=torch.float32, device=device)
+
+
+def _joined_stage(nxt, nxt_out, nxt_out_coff, out_shape, device):
+    """The tt_conv_next of conv2d(nxt=...) and the tensor it writes: the 1 x 1 convolution over the rows of `out_shape`."""
+    nw, nw_x3, nscale, nshift, nact = nxt
+    N, OH, OW, Cout = out_shape
+    assert nw_x3 is not None and nw.is_contiguous() and nw_x3.is_contiguous() and tuple(nw.shape[1:]) == (1, 1, Cout) \
+        and nw_x3.shape == nw.shape
+    nout = nxt_out if nxt_out is not None else torch.empty(N, OH, OW, nw.shape[0], dtype=torch.float32, device=device)
+    assert nout.dtype == torch.float32 and nout.is_contiguous() and tuple(nout.shape[:3]) == (N, OH, OW)
+    dn = _ConvNext()
+    dn.next_weight = nw.data_ptr(); dn.next_weight_x3 = nw_x3.data_ptr(); dn.next_cout = nw.shape[0]
+    dn.next_scale = ptr(nscale); dn.next_shift = ptr(nshift); dn.next_act = nact
+    dn.next_out = nout.data_ptr(); dn.next_out_cstride = nout.shape[-1]; dn.next_out_coff = nxt_out_coff; dn.next_out_pair = 1
+    return dn, nout
 
 
 def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=None, res1_coff=0,
@@ -249,130 +453,73 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
     assert w.is_contiguous() and x.dim() == 4 and w.dim() == 4
     N, H, W, Cs = x.shape
     # inner (H, W, C) block must be dense; the image (batch) stride may be anything
-    assert x.stride(3) == 1 and (W == 1 or x.stride(2) == Cs) and (H == 1 or x.stride(1) == W * Cs), x.stride()
-    src_px = N * H * W
-    if in_up2:          # the geometry below is that of the upsampled, logical input
-        assert x.dtype == torch.float32 and x.is_contiguous() and w_x3 is not None and not in_pair and splitk_ws is None
-        H, W = 2 * H, 2 * W
+    xst = x.stride()
+    assert xst[3] == 1 and (W == 1 or xst[2] == Cs) and (H == 1 or xst[1] == W * Cs), xst
     Cout, KH, KW, Cin = w.shape
     if cin is None:
         cin = Cin
     assert cin == Cin, (cin, Cin)
-    OH = (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1
-    OW = (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1
-    if out_hw is not None:
-        OH, OW = out_hw
-    cr = Cout // 4 if pixel_shuffle2 else Cout
     if out is None:
-        odt = out_dtype or x.dtype
-        oh, ow = (2 * OH, 2 * OW) if pixel_shuffle2 else (OH, OW)
-        out = torch.empty(N, oh, ow, cr, dtype=odt, device=x.device)
-    d = _ConvDesc()
-    d.in_ = x.data_ptr(); d.N = N; d.H = H; d.W = W; d.Cin = Cin; d.in_cstride = in_cstride or Cs; d.in_coff = in_coff
-    d.in_nstride = x.stride(0) if N > 1 else 0
-    d.weight = w.data_ptr(); d.Cout = Cout; d.KH = KH; d.KW = KW; d.stride = stride; d.pad = pad; d.dil = dil
-    d.out = out.data_ptr(); d.OH = OH; d.OW = OW
-    d.out_cstride = out.shape[-1]; d.out_coff = out_coff
-    d.out_nstride = out_nstride or (out.stride(0) if (out.dim() == 4 and N > 1) else 0)
-    d.pixel_shuffle2 = 1 if pixel_shuffle2 else 0
-    d.scale = ptr(scale); d.shift = ptr(shift); d.shift_n = ptr(shift_n); d.shift_n_mod = shift_n_mod
-    d.res1 = ptr(res1); d.res1_cstride = 0 if res1 is None else res1.shape[-1]; d.res1_coff = res1_coff
-    if res1 is not None and res1.dtype == torch.float32 and x.dtype != torch.float32:
-        d.res1_f32 = 1                  # an f32 sum chain beside half conv inputs (mixed mode's PAFPN)
+        out_shape = conv_geometry(x.shape, w.shape, stride, pad, dil, out_hw, pixel_shuffle2, in_up2)[4]
+        out = torch.empty(out_shape, dtype=out_dtype or x.dtype, device=x.device)
+    x3, x3_splitk = _training_x3(w_x3, Cout, _in_training_step(_no_tape))
+    # 1. the descriptor (a split-K query sees the bf16x3 operand only where a split-K launch would run with it)
+    r1, r2, o2 = res1 is not None, res2 is not None, out2 is not None
+    d = conv_desc(x.data_ptr(), x.shape, xst, w.data_ptr(), w.shape, out.data_ptr(), out.shape, out.stride(), dtype_code(x), dtype_code(out),
+                  stride, pad, dil, out_hw, pixel_shuffle2, in_up2,
+                  in_coff, in_cstride, out_coff, out_nstride,
+                  ptr(scale), ptr(shift), ptr(shift_n), shift_n_mod, act,
+                  ptr(res1), r1 and res1.shape, r1 and dtype_code(res1), res1_coff, res1_up, ptr(res2), r2 and res2.shape, res2_coff,
+                  ptr(x3_splitk), ptr(w_h2), in_pair, out_pair, ptr(out2), o2 and out2.shape, out2_coff)
+    OH, OW = d.OH, d.OW
+    rows = N * OH * OW
+    # 2. the operand modes: what each asks of the tensors, and the inference-only ones refused under a tape
+    _refuse_on_tape(w_h2 is not None, in_pair or out_pair, in_up2, nxt is not None)
+    if in_up2:
+        assert x.dtype == torch.float32 and x.is_contiguous() and w_x3 is not None and not in_pair and splitk_ws is None
     if res1_up:
         assert res1 is not None and res1.dim() == 4 and res1.is_contiguous() and res1.shape[0] == N and splitk_ws is None
-        d.res1_up_h, d.res1_up_w = res1.shape[1], res1.shape[2]
-    d.res2 = ptr(res2); d.res2_cstride = 0 if res2 is None else res2.shape[-1]; d.res2_coff = res2_coff
-    d.act = act; d.dtype = dtype_code(x); d.out_dtype = dtype_code(out)
-    from . import autodiff
     if w_h2 is not None:
         assert x.dtype == torch.float16 and w.dtype == torch.float16 and w_h2.dtype == torch.float16 and w_h2.is_contiguous() \
             and w_h2.numel() == 2 * w.numel() and w_x3 is None and splitk_ws is None
-        if autodiff.TAPE is not None:
-            raise _lib.TTError("conv2d: half-storage (h2) layers have no backward; train in dtype torch.float32 or 'f32x3'")
-        d.weight_h2 = w_h2.data_ptr()
     if out2 is not None:
-        assert out2.dtype == torch.float32 and out2.numel() // out2.shape[-1] == N * OH * OW and out2.stride(-1) == 1
-        d.out2 = out2.data_ptr(); d.out2_cstride = out2.shape[-1]; d.out2_coff = out2_coff
-    if in_pair or out_pair:
+        assert out2.dtype == torch.float32 and out2.numel() // out2.shape[-1] == rows and out2.stride(-1) == 1
+    if in_pair or out_pair or nxt is not None:
         assert w_x3 is not None and x.dtype == torch.float32 and out.dtype == torch.float32 and splitk_ws is None
-        if autodiff.TAPE is not None:
-            raise _lib.TTError("conv2d: pair-format activations are an inference-path layout (the tape reads f32 tensors)")
-        d.in_pair, d.out_pair = int(bool(in_pair)), int(bool(out_pair))
-    if in_up2:
-        if autodiff.TAPE is not None:
-            raise _lib.TTError("conv2d: in_up2 is an inference-path fusion (the tape records bilinear_up2 and the convolution apart)")
-        d.in_up2 = 1
-    nout, dn = None, None
-    if nxt is not None:
-        if autodiff.TAPE is not None:
-            raise _lib.TTError("conv2d: a joined stage is an inference-path fusion (the tape records the two convolutions apart)")
-        nw, nw_x3, nscale, nshift, nact = nxt
-        assert w_x3 is not None and nw_x3 is not None and x.dtype == torch.float32 and out.dtype == torch.float32 and splitk_ws is None
-        assert nw.is_contiguous() and nw_x3.is_contiguous() and tuple(nw.shape[1:]) == (1, 1, Cout) and nw_x3.shape == nw.shape
-        nout = nxt_out if nxt_out is not None else torch.empty(N, OH, OW, nw.shape[0], dtype=torch.float32, device=x.device)
-        assert nout.dtype == torch.float32 and nout.is_contiguous() and tuple(nout.shape[:3]) == (N, OH, OW)
-        dn = _ConvNext()
-        dn.next_weight = nw.data_ptr(); dn.next_weight_x3 = nw_x3.data_ptr(); dn.next_cout = nw.shape[0]
-        dn.next_scale = ptr(nscale); dn.next_shift = ptr(nshift); dn.next_act = nact
-        dn.next_out = nout.data_ptr(); dn.next_out_cstride = nout.shape[-1]; dn.next_out_coff = nxt_out_coff; dn.next_out_pair = 1
-    if w_x3 is not None and Cout < 64 and (autodiff.TAPE is not None or _no_tape):
-        # training step (taped forward, recomputations, input-gradient convolutions): the layers with fewer than 64 output channels
-        # keep the exact-f32 kernels the gradient goldens were taken with (inference runs them on the 256 x 32 bf16x3 tile)
-        w_x3 = None
-    if w_x3 is not None:       # (before the split-K query: with a bf16x3 operand the query answers for the bf16x3 split-K tile)
-        assert x.dtype == torch.float32 and w_x3.shape == w.shape and w_x3.is_contiguous()
-        # the training step (forward under the tape, and the backward's recomputations / input-gradient convolutions, which
-        # pass _no_tape) keeps the exact-f32 split-K kernel for the few-row long-K layers -- the gradient goldens were taken
-        # with it: the query must not see the bf16x3 operand there
-        x3_splitk = autodiff.TAPE is None and not _no_tape
-        if x3_splitk:
-            d.weight_x3 = w_x3.data_ptr()
-    if _AUTO_SPLITK and splitk_ws is None and not (in_pair or out_pair or in_up2) and w_h2 is None and not res1_up and N * OH * OW <= 4096 and KH * KW * Cin >= 2048:
-        # few rows, very long K (BEV-update conv K=18720, flatten MLPs): cross-workgroup split-K with an f32 workspace
-        # beats conv_small.hip's in-workgroup split there (277 vs 416 us on the BEV-update conv: the direct 32 B/row
-        # operand loads of the small kernel waste L2 sectors on a 10 MB weight matrix).  TT_CONV_AUTO_SPLITK=0 disables.
-        # ordered form (no atomics, no zero fill): one [M][Cout] slice per K split, added in index order by the finalize kernel.
-        # With a bf16x3 operand the layer runs the 64-wide bf16x3 tile with the K tiles dealt over workgroups
-        # (conv_igemm_glds.hip, x3_splitk_plan) instead of the exact-f32 register-staged kernel
-        slices = int(lib().tt_conv2d_splitk_slices(ctypes.byref(d)))
-        if slices > 0:
-            splitk_ws = torch.empty(slices, N * OH * OW, Cout, dtype=torch.float32, device=x.device)
-            d.splitk_slices = slices
+    if x3 is not None:
+        assert x.dtype == torch.float32 and x3.shape == w.shape and x3.is_contiguous()
+    # 3. the joined stage
+    dn, nout = (None, None) if nxt is None else _joined_stage(nxt, nxt_out, nxt_out_coff, (N, OH, OW, Cout), x.device)
+    # 4. the split-K workspace: the caller's, or one the library asks for; a launch without one runs with the bf16x3 operand
+    if auto_splitk_asks(rows, KH * KW * Cin, splitk_ws is not None, in_pair or out_pair, in_up2, w_h2 is not None, res1_up):
+        splitk_ws = _auto_splitk(d, x.device)
     if splitk_ws is not None:
         d.splitk_ws = splitk_ws.data_ptr()
-    elif w_x3 is not None:
-        d.weight_x3 = w_x3.data_ptr()
-    if CONV_PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if dn is not None:
-        rc = lib().tt_conv2d_fwd_next(ctypes.byref(d), ctypes.byref(dn), cur_stream(x.device))
-    else:
-        rc = lib().tt_conv2d_fwd(ctypes.byref(d), cur_stream(x.device))
-    check(rc, "tt_conv2d_fwd")
-    if CONV_PROFILE is not None:
-        e1.record()
+    elif x3 is not None:
+        d.weight_x3 = x3.data_ptr()
+    # 5. the launch
+    with _launch() as rec:
+        if dn is not None:
+            rc = lib().tt_conv2d_fwd_next(ctypes.byref(d), ctypes.byref(dn), _st(x))
+        else:
+            rc = lib().tt_conv2d_fwd(ctypes.byref(d), _st(x))
+        check(rc, "tt_conv2d_fwd")
+    if rec is not None:
         n2 = 0 if nout is None else nxt[0].shape[0]
-        CONV_PROFILE.append((2.0 * N * OH * OW * Cout * (KH * KW * Cin + n2), e0, e1,
-                             f"M={N * OH * OW} N={Cout}->{n2} K={Cin} join k1x1s1" if n2 else
-                             f"M={N * OH * OW} N={Cout} K={KH * KW * Cin} k{KH}x{KW}s{stride}"))
-        if CONV_KERNELS is not None:
-            CONV_KERNELS.append(_last_conv_kernel())
-        if CONV_BYTES is not None:
-            esz, osz = x.element_size(), out.element_size()
-            m_out = N * OH * OW
-            in_px = min(src_px, m_out * KH * KW)              # a strided 1x1 layer only touches the pixels it samples
-            wsz = w.numel() * w.element_size() * (2 if w_h2 is not None else 1)
-            CONV_BYTES.append(in_px * (in_cstride or Cin) * esz + m_out * Cout * osz + wsz +
-                              m_out * Cout * esz * ((res1 is not None) + (res2 is not None)) +
-                              (m_out * Cout * 4 if out2 is not None else 0) +
-                              (m_out * n2 * 4 + nxt[0].numel() * 4 if n2 else 0))     # a joined stage: its output and weights
+        esz, osz = x.element_size(), out.element_size()
+        in_px = min(N * H * W, rows * KH * KW)               # (source pixels) a strided 1x1 layer only touches the pixels it samples
+        wsz = w.numel() * w.element_size() * (2 if w_h2 is not None else 1)
+        rec.log(2.0 * rows * Cout * (KH * KW * Cin + n2),
+                f"M={rows} N={Cout}->{n2} K={Cin} join k1x1s1" if n2 else f"M={rows} N={Cout} K={KH * KW * Cin} k{KH}x{KW}s{stride}",
+                kernel=_last_conv_kernel,
+                nbytes=(in_px * (in_cstride or Cin) * esz + rows * Cout * osz + wsz +
+                        rows * Cout * esz * ((res1 is not None) + (res2 is not None)) +
+                        (rows * Cout * 4 if out2 is not None else 0) +
+                        (rows * n2 * 4 + nxt[0].numel() * 4 if n2 else 0)))     # a joined stage: its output and weights
+    # 6. the tape
     if not _no_tape:
-        from . import autodiff
-        if autodiff.TAPE is not None:
-            autodiff.TAPE.conv(x, w, out, stride, pad, dil, scale, shift, act, in_coff, cin, out_coff, res1, res1_coff,
-                               res2, res2_coff, pixel_shuffle2, in_cstride, shift_n, shift_n_mod, stop_grad, bn_raw)
+        _tape("conv", x, w, out, stride, pad, dil, scale, shift, act, in_coff, cin, out_coff, res1, res1_coff,
+              res2, res2_coff, pixel_shuffle2, in_cstride, shift_n, shift_n_mod, stop_grad, bn_raw)
     return out if nout is None else (out, nout)
 
 
@@ -395,25 +542,14 @@ def seg_feedback_chain(x, cv1, cv2, out=None, out_coff=0):
         out = torch.empty(N, H, W, n2, dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() // out.shape[-1] == N * H * W
     R = N * H * W
-    if CONV_PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib().tt_seg_feedback_chain(ptr(x), R, Cs, k1, ptr(cv1.w), ptr(cv1.scale), ptr(cv1.shift), cv1.act, ptr(cv2.w),
-                                      ptr(cv2.w_x3), n2, ptr(cv2.scale), ptr(cv2.shift), cv2.act, ptr(out), out.shape[-1],
-                                      out_coff, cur_stream(x.device)), "tt_seg_feedback_chain")
-    if CONV_PROFILE is not None:
-        e1.record()
-        CONV_PROFILE.append((2.0 * R * (k1 * n1 + k2 * n2), e0, e1, f"M={R} N={n1}->{n2} K={k1} chain k1x1s1"))
-        if CONV_KERNELS is not None:
-            CONV_KERNELS.append("seg_chain_kernel")
-        if CONV_BYTES is not None:
-            CONV_BYTES.append(R * (Cs + n2) * 4 + (cv1.w.numel() + cv2.w.numel()) * 4)
+    with _launch() as rec:
+        check(lib().tt_seg_feedback_chain(ptr(x), R, Cs, k1, ptr(cv1.w), ptr(cv1.scale), ptr(cv1.shift), cv1.act, ptr(cv2.w),
+                                          ptr(cv2.w_x3), n2, ptr(cv2.scale), ptr(cv2.shift), cv2.act, ptr(out), out.shape[-1],
+                                          out_coff, _st(x)), "tt_seg_feedback_chain")
+    if rec is not None:
+        rec.log(2.0 * R * (k1 * n1 + k2 * n2), f"M={R} N={n1}->{n2} K={k1} chain k1x1s1", kernel="seg_chain_kernel",
+                nbytes=R * (Cs + n2) * 4 + (cv1.w.numel() + cv2.w.numel()) * 4)
     return out
-
-
-# ----------------------------------------------------------------------------- glue kernels
-def _st(t):
-    return cur_stream(t.device)
 
 
 # ----------------------------------------------------------------------------- train-mode BatchNorm / dropout
@@ -445,12 +581,6 @@ class BNSpec:
         self.eps, self.momentum = float(eps), float(momentum)
 
 
-def _bn_ws(C, groups, dev):
-    L = lib()
-    nb = int(L.tt_bn_workspace_bytes(C, groups))
-    return torch.empty(nb, dtype=torch.uint8, device=dev), nb
-
-
 def batchnorm_train(z, spec, act=0, res1=None, res1_coff=0, res2=None, res2_coff=0, out=None, out_coff=0, m_dev=None,
                     groups=1, update_running=True):
     """y = act(BN_batch(z) + res1 + res2): z [..., C] dense f32 rows (the raw conv output, bias included); out: row-linear
@@ -467,9 +597,9 @@ def batchnorm_train(z, spec, act=0, res1=None, res1_coff=0, res2=None, res2_coff
     for r in (res1, res2):
         assert r is None or (r.is_contiguous() and r.dtype == torch.float32 and r.numel() // r.shape[-1] == M)
     stats = torch.empty(groups, 2 * C + 2, dtype=torch.float64, device=dev)
-    ws, nb = _bn_ws(C, groups, dev)
-    st = _st(z)
     L = lib()
+    ws = _workspace(L.tt_bn_workspace_bytes(C, groups), dev)
+    nb, st = ws.numel(), _st(z)
     check(L.tt_bn_stats(ptr(z), M, C, C, 0, ptr(m_dev), groups, ptr(stats), ptr(ws), nb, st), "tt_bn_stats")
     _all_reduce_sum_(stats)
     scale, shift, mean, invstd = (torch.empty(groups, C, dtype=torch.float32, device=dev) for _ in range(4))
@@ -477,15 +607,9 @@ def batchnorm_train(z, spec, act=0, res1=None, res1_coff=0, res2=None, res2_coff
                            ptr(spec.running_mean if update_running else None),
                            ptr(spec.running_var if update_running else None), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
                            st), "tt_bn_finalize")
-
-    def cs(t):
-        return 0 if t is None else t.shape[-1]
-    check(L.tt_bn_apply(ptr(z), M, C, C, 0, ptr(m_dev), groups, ptr(scale), ptr(shift), ptr(mean), ptr(res1), cs(res1),
-                        res1_coff, ptr(res2), cs(res2), res2_coff, act, ptr(out), out.shape[-1], out_coff, st), "tt_bn_apply")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.bn_train(z, out, out_coff, spec, act, res1, res1_coff, res2, res2_coff, m_dev, groups, stats, scale,
-                               mean, invstd)
+    check(L.tt_bn_apply(ptr(z), M, C, C, 0, ptr(m_dev), groups, ptr(scale), ptr(shift), ptr(mean), ptr(res1), _cs(res1),
+                        res1_coff, ptr(res2), _cs(res2), res2_coff, act, ptr(out), out.shape[-1], out_coff, st), "tt_bn_apply")
+    _tape("bn_train", z, out, out_coff, spec, act, res1, res1_coff, res2, res2_coff, m_dev, groups, stats, scale, mean, invstd)
     return out
 
 
@@ -497,15 +621,12 @@ def batchnorm_train_bwd(dy, dy_coff, y, y_coff, z, mean, invstd, scale, stats, a
     M = z.numel() // C
     dev = z.device
     sums = torch.empty(groups, 2 * C, dtype=torch.float64, device=dev)
-    ws, nb = _bn_ws(C, groups, dev)
-    st = _st(z)
     L = lib()
-
-    def cs(t):
-        return 0 if t is None else t.shape[-1]
+    ws = _workspace(L.tt_bn_workspace_bytes(C, groups), dev)
+    nb, st = ws.numel(), _st(z)
     check(L.tt_bn_bwd_reduce(ptr(dy), dy.shape[-1], dy_coff, ptr(y), y.shape[-1], y_coff, ptr(z), C, 0,
-                             M, C, ptr(m_dev), groups, ptr(mean), ptr(invstd), act, ptr(dres1), cs(dres1),
-                             dres1_coff, ptr(dres2), cs(dres2), dres2_coff, ptr(sums), ptr(ws), nb, st), "tt_bn_bwd_reduce")
+                             M, C, ptr(m_dev), groups, ptr(mean), ptr(invstd), act, ptr(dres1), _cs(dres1),
+                             dres1_coff, ptr(dres2), _cs(dres2), dres2_coff, ptr(sums), ptr(ws), nb, st), "tt_bn_bwd_reduce")
     local = sums.sum(0).to(torch.float32)
     _all_reduce_sum_(sums)
     check(L.tt_bn_bwd_apply(ptr(dy), dy.shape[-1], dy_coff, ptr(z), C, 0, M, C, ptr(m_dev), groups,
@@ -528,9 +649,7 @@ def dropout(x, p=0.5):
     DROPOUT_SEED[1] += 1
     seed = (DROPOUT_SEED[0] * 0x100000001B3 + DROPOUT_SEED[1] * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
     check(lib().tt_dropout_fwd(ptr(x), ptr(out), x.numel(), p, seed, ptr(mask_in), ptr(mask), _st(x)), "tt_dropout_fwd")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.dropout(x, out, mask, p)
+    _tape("dropout", x, out, mask, p)
     return out
 
 
@@ -574,9 +693,7 @@ def maxpool3x3s2(x):
     N, H, W, C = x.shape
     out = torch.empty(N, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, C, dtype=x.dtype, device=x.device)
     check(lib().tt_maxpool3x3s2(ptr(x), ptr(out), N, H, W, C, dtype_code(x), _st(x)), "tt_maxpool3x3s2")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.maxpool3x3s2(x, out)
+    _tape("maxpool3x3s2", x, out)
     return out
 
 
@@ -584,9 +701,7 @@ def upsample_nearest_add_(dst, src):
     N, H, W, C = dst.shape
     check(lib().tt_upsample_nearest_add(ptr(dst), ptr(src), N, H, W, C, src.shape[1],
                                         src.shape[2], dtype_code(dst), _st(dst)), "tt_upsample_nearest_add")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.upsample_nearest_add_(dst, src)
+    _tape("upsample_nearest_add_", dst, src)
     return dst
 
 
@@ -598,8 +713,7 @@ def pair_ok(rows, cin=32, cout=64, taps=9):
     pair-format input (tt_conv_desc.in_pair: the LDS-DMA kernel's contract, K = taps * cin of at least two 32-channel tiles; up to
     4096 rows a layer runs the exact-f32 latency kernel, which a pair-format layer could not take).  Producer and consumer of a
     tensor ask with the CONSUMER's numbers.  tests/test_conv_choice.py pins this to the library's rule."""
-    from . import autodiff
-    return (PAIR and autodiff.TAPE is None and rows > 4096 and cin % 32 == 0 and taps * cin >= 64 and
+    return (PAIR and _active_tape() is None and rows > 4096 and cin % 32 == 0 and taps * cin >= 64 and
             (8 <= cout <= 32 or cout >= 64))
 
 
@@ -614,8 +728,7 @@ def join_ok(rows, k1, cout, next_cout):
     """Whether a bf16x3 1 x 1 / stride 1 convolution k1 -> cout over this many rows also produces the next 1 x 1 layer's cout ->
     next_cout output in its own launch (conv2d(nxt=...), tt_conv2d_fwd_next): the library's contract (csrc/conv_choose.cpp,
     choose_join) restricted to the routed forms.  tests/test_conv_join_choice.py pins this to the library's rule."""
-    from . import autodiff
-    return BNECK_JOIN and autodiff.TAPE is None and rows >= JOIN_MIN_ROWS and (k1, cout, next_cout) in JOIN_ROUTED
+    return BNECK_JOIN and _active_tape() is None and rows >= JOIN_MIN_ROWS and (k1, cout, next_cout) in JOIN_ROUTED
 
 
 SEG_UP2 = os.environ.get("TT_SEG_UP2", "1") != "0"      # A/B knob and test hook: 0 = unet_layer0's upsample and its 3 x 3 conv stay two launches
@@ -624,8 +737,7 @@ SEG_UP2 = os.environ.get("TT_SEG_UP2", "1") != "0"      # A/B knob and test hook
 def up2_ok(rows, cin, cout):
     """Whether a bf16x3 3 x 3 / stride 1 / pad 1 convolution with this many OUTPUT rows reads its input through the bilinear x2
     upsampling in the kernel (conv2d(in_up2=True), tt_conv_desc.in_up2).  tests/test_conv_up2_choice.py pins this to the library's rule."""
-    from . import autodiff
-    return autodiff.TAPE is None and rows > 4096 and cin % 32 == 0 and cout == 64
+    return _active_tape() is None and rows > 4096 and cin % 32 == 0 and cout == 64
 
 
 def bilinear_up2(x, out_pair=False):
@@ -636,9 +748,7 @@ def bilinear_up2(x, out_pair=False):
         check(lib().tt_bilinear_up2_pair(ptr(x), ptr(out), N, H, W, C, _st(x)), "tt_bilinear_up2_pair")
         return out
     check(lib().tt_bilinear_up2(ptr(x), ptr(out), N, H, W, C, dtype_code(x), _st(x)), "tt_bilinear_up2")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.bilinear_up2(x, out)
+    _tape("bilinear_up2", x, out)
     return out
 
 
@@ -648,9 +758,7 @@ def spatial_pool(x, mode, C=None, coff=0):
     C = C or Cs
     out = torch.empty(N, C, dtype=torch.float32, device=x.device)
     check(lib().tt_spatial_pool(ptr(x), ptr(out), N, H * W, C, Cs, coff, mode, dtype_code(x), _st(x)), "tt_spatial_pool")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.spatial_pool(x, out, mode, C, coff)
+    _tape("spatial_pool", x, out, mode, C, coff)
     return out
 
 
@@ -660,9 +768,7 @@ def channel_gate(x, gate, res=None, gate_act=_lib.ACT_SIGMOID, out_act=_lib.ACT_
     out = torch.empty_like(x) if out is None else out
     check(lib().tt_channel_gate(ptr(x), ptr(gate), ptr(res), ptr(out), N, H * W, C, gate_act,
                                 out_act, dtype_code(x), _st(x)), "tt_channel_gate")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.channel_gate(x, gate, res, out, gate_act, out_act)
+    _tape("channel_gate", x, gate, res, out, gate_act, out_act)
     return out
 
 
@@ -672,9 +778,7 @@ def affine_rows(x, scale, shift, act=0, out=None):
     out = torch.empty(R, C, dtype=x.dtype, device=x.device) if out is None else out
     check(lib().tt_affine_rows(ptr(x), ptr(scale), ptr(shift), ptr(out), R, C, x.stride(0),
                                out.stride(0), act, dtype_code(x), _st(x)), "tt_affine_rows")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.affine_rows(x, scale, shift, act, out)
+    _tape("affine_rows", x, scale, shift, act, out)
     return out
 
 
@@ -685,9 +789,7 @@ def layernorm_rows(x, gamma, beta, eps=1e-5, out=None, D=None):
     out = torch.zeros(R, x.shape[1], dtype=x.dtype, device=x.device) if out is None else out
     check(lib().tt_layernorm_rows(ptr(x), ptr(gamma), ptr(beta), ptr(out), R, D, x.stride(0),
                                   out.stride(0), eps, dtype_code(x), _st(x)), "tt_layernorm_rows")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.layernorm_rows(x, gamma, beta, out, D, eps)
+    _tape("layernorm_rows", x, gamma, beta, out, D, eps)
     return out
 
 
@@ -695,10 +797,9 @@ def layernorm_rows_bwd(x, gamma, dout, dx, dgamma, dbeta, D, eps=1e-5):
     """dx[:, :D] += , dgamma += , dbeta += backward of layernorm_rows (2-D row-strided f32 views)."""
     R = x.shape[0]
     L = lib()
-    nb = int(L.tt_layernorm_rows_bwd_workspace_bytes(R, D))
-    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    ws = _workspace(L.tt_layernorm_rows_bwd_workspace_bytes(R, D), x.device)
     check(L.tt_layernorm_rows_bwd(ptr(x), ptr(gamma), ptr(dout), ptr(dx), ptr(dgamma), ptr(dbeta), R, D,
-                                  x.stride(0), dout.stride(0), dx.stride(0), eps, ptr(ws), nb, _st(x)), "tt_layernorm_rows_bwd")
+                                  x.stride(0), dout.stride(0), dx.stride(0), eps, ptr(ws), ws.numel(), _st(x)), "tt_layernorm_rows_bwd")
 
 
 def concat_piece_bwd(dout, coff, C, div, mod, dsrc):
@@ -713,9 +814,7 @@ def copy_nhwc(x, out, C=None, in_coff=0, out_coff=0, rot_flip=False):
     C = C or Cs
     check(lib().tt_copy_nhwc(ptr(x), ptr(out), N, H, W, C, Cs, in_coff, out.shape[-1], out_coff, 1 if rot_flip else 0,
                              dtype_code(x), dtype_code(out), _st(x)), "tt_copy_nhwc")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.copy_nhwc(x, out, C, in_coff, out_coff, rot_flip)
+    _tape("copy_nhwc", x, out, C, in_coff, out_coff, rot_flip)
     return out
 
 
@@ -725,9 +824,7 @@ def broadcast_rows(v, out, out_coff=0):
     _, H, W, Ct = out.shape
     check(lib().tt_broadcast_rows(ptr(v), ptr(out), N, H * W, C, v.stride(0), Ct,
                                   out_coff, dtype_code(out), _st(out)), "tt_broadcast_rows")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.broadcast_rows(v, out, out_coff)
+    _tape("broadcast_rows", v, out, out_coff)
     return out
 
 
@@ -745,9 +842,7 @@ def ew(op, a, b=None, g=None, out=None, C=None, a_coff=0, b_coff=0, g_coff=0, ou
     check(lib().tt_ew(ptr(a2), ptr(b2), ptr(g2), ptr(o2), R, C, a2.stride(0), a_coff,
                       0 if b2 is None else b2.stride(0), b_coff, 0 if g2 is None else g2.stride(0),
                       g_coff, o2.stride(0), out_coff, op, act, dtype_code(a), _st(a)), "tt_ew")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.ew(op, act, R, C, a2, a_coff, b2, b_coff, g2, g_coff, o2, out_coff)
+    _tape("ew", op, act, R, C, a2, a_coff, b2, b_coff, g2, g_coff, o2, out_coff)
     return out
 
 
@@ -783,9 +878,7 @@ def concat_rows(out, pieces, coff=0):
         c += C
     check(lib().tt_concat_rows(ptr(o2), o2.shape[0], o2.stride(0), n, srcs, strides, widths, coffs, divs,
                                mods, _st(out)), "tt_concat_rows")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.concat_rows(o2, pieces, coff)
+    _tape("concat_rows", o2, pieces, coff)
     return out
 
 
@@ -796,9 +889,7 @@ def deform_im2col3x3(x, offsets, pad=1):
     cols = torch.empty(N * H * W, 1, 9, C, dtype=x.dtype, device=x.device)
     check(lib().tt_deform_im2col3x3(ptr(x), ptr(offsets), ptr(cols), N, H, W, C,
                                     offsets.shape[-1], pad, dtype_code(x), _st(x)), "tt_deform_im2col3x3")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.deform_im2col3x3(x, offsets, cols, pad)
+    _tape("deform_im2col3x3", x, offsets, cols, pad)
     return cols
 
 
@@ -810,9 +901,7 @@ def repeat_rows(t, times):
     nb = t.numel() * t.element_size()
     for k in range(times):          # `times` contiguous block copies (tt_copy_bytes): no torch kernel in the forward
         check(lib().tt_copy_bytes(out.data_ptr() + k * nb, ptr(t), nb, _st(t)), "tt_copy_bytes")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.repeat_rows(t, out, times)
+    _tape("repeat_rows", t, out, times)
     return out
 
 
@@ -831,8 +920,7 @@ def look_project_pack(wp, lidar2img, ida_mat, img_hw):
 
 def _level_args(maps):
     arr = (ctypes.c_void_p * 4)(*[m.data_ptr() for m in maps])
-    hw = (ctypes.c_int * 8)(*[v for m in maps for v in (m.shape[1], m.shape[2])])
-    return arr, hw
+    return arr, _level_hw((m.shape[1], m.shape[2]) for m in maps)
 
 
 def look_gather_query(qos, ref, wp, ctrl_sp, temporal, static, meas, flat, maps, row_stride=1544):
@@ -842,9 +930,7 @@ def look_gather_query(qos, ref, wp, ctrl_sp, temporal, static, meas, flat, maps,
     check(lib().tt_look_gather_query(B, ptr(qos), ptr(ref), ptr(wp), ptr(ctrl_sp), ptr(temporal), ptr(static),
                                      ptr(meas), ptr(flat), arr, hw, dtype_code(maps[0]), ptr(out),
                                      row_stride, _st(wp)), "tt_look_gather_query")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.look_gather_query(qos, ref, out, temporal, static, meas, flat, maps, row_stride)
+    _tape("look_gather_query", qos, ref, out, temporal, static, meas, flat, maps, row_stride)
     return out
 
 
@@ -855,7 +941,7 @@ def look_gather_query_bwd(B, qos, ref, dout, row_stride, dtemporal, dstatic, dme
 
 
 def msda_sample_bwd(B, value, coff, offsets, logits, ref, level_hw, dout, dvalue, doffsets, dlogits):
-    hw = (ctypes.c_int * 8)(*[v for pair in level_hw for v in pair])
+    hw = _level_hw(level_hw)
     assert value.dtype == torch.float32
     check(lib().tt_msda_sample_bwd(B, ptr(value), value.shape[-1], coff, ptr(offsets), ptr(logits), ptr(ref), hw,
                                    ptr(dout), ptr(dvalue), ptr(doffsets), ptr(dlogits), _st(dout)), "tt_msda_sample_bwd")
@@ -868,21 +954,17 @@ def sca_reduce_bwd(B, dout, max_len, dx):
 def msda_sample(value, offsets, logits, ref, level_hw, B, coff=0):
     """value (B*4, S, Cv) with Cv >= 256: samples channels [coff, coff+256)."""
     out = torch.empty(B * 4 * 120, 256, dtype=torch.float32, device=value.device)
-    hw = (ctypes.c_int * 8)(*[v for pair in level_hw for v in pair])
+    hw = _level_hw(level_hw)
     check(lib().tt_msda_sample_strided(B, ptr(value), dtype_code(value), value.shape[-1], coff,
                                        ptr(offsets), ptr(logits), ptr(ref), hw, ptr(out), _st(value)), "tt_msda_sample_strided")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.msda_sample(value, offsets, logits, ref, level_hw, B, coff, out)
+    _tape("msda_sample", value, offsets, logits, ref, level_hw, B, coff, out)
     return out
 
 
 def sca_reduce(x, max_len, B):
     out = torch.empty(B, 1024, dtype=torch.float32, device=x.device)
     check(lib().tt_sca_reduce(B, ptr(x), ptr(max_len), ptr(out), _st(x)), "tt_sca_reduce")
-    from . import autodiff
-    if autodiff.TAPE is not None:
-        autodiff.TAPE.sca_reduce(x, max_len, B, out)
+    _tape("sca_reduce", x, max_len, B, out)
     return out
 
 
@@ -985,9 +1067,8 @@ def mlp_chain(x, stages, n_split=1, groups=None, wide=None):
         if groups is None:
             groups = min(16, max((st["lin"].N + 31) // 32 for st in stages))
         groups = max(1, min(groups, cap // row_groups, 64))
-        nbytes = int(L.tt_mlp_chain_wide_workspace_bytes(R, n, arr))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        rc = L.tt_mlp_chain_wide(ptr(x), R, x.stride(0), n, arr, groups, ptr(ws), nbytes, _st(x))
+        ws = _workspace(L.tt_mlp_chain_wide_workspace_bytes(R, n, arr), x.device)
+        rc = L.tt_mlp_chain_wide(ptr(x), R, x.stride(0), n, arr, groups, ptr(ws), ws.numel(), _st(x))
         if rc != -4 or wide:
             check(rc, "tt_mlp_chain_wide")
             return
@@ -1014,26 +1095,21 @@ def conv2d_wgrad(x, dy, kh, kw, stride=1, pad=0, dil=1, cin=None, in_coff=0, cou
         out = torch.empty(cout, kh, kw, cin_pad, dtype=torch.float32, device=x.device)
     assert tuple(out.shape) == (cout, kh, kw, cin_pad) and out.is_contiguous()
     L = lib()
-    nb = int(L.tt_conv2d_wgrad_workspace_bytes(N, OH, cout, cin, cin_pad, kh, kw))
-    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
-    if CONV_PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ws = _workspace(L.tt_conv2d_wgrad_workspace_bytes(N, OH, cout, cin, cin_pad, kh, kw), x.device)
+    nb = ws.numel()
     name = "tt_conv2d_wgrad_x3" if x3 else "tt_conv2d_wgrad"   # x3: the forward's bf16x3 arithmetic (csrc/wgrad_choose.cpp: which layers)
-    check(getattr(L, name)(ptr(x), N, H, W, cin, Cs, in_coff, ptr(dy), OH, OW, cout, Cd, dy_coff, kh, kw, stride, pad, dil,
-                           cin_pad, 1 if accumulate else 0, ptr(out), ptr(ws), nb, _st(x)), name)
-    if CONV_PROFILE is not None:
-        e1.record()
-        CONV_PROFILE.append((2.0 * N * OH * OW * cout * kh * kw * cin, e0, e1,
-                             f"wgrad M={N * OH * OW} N={cout} K={kh * kw * cin} k{kh}x{kw}s{stride}"))
-        if CONV_KERNELS is not None:
+    with _launch() as rec:
+        check(getattr(L, name)(ptr(x), N, H, W, cin, Cs, in_coff, ptr(dy), OH, OW, cout, Cd, dy_coff, kh, kw, stride, pad, dil,
+                               cin_pad, 1 if accumulate else 0, ptr(out), ptr(ws), nb, _st(x)), name)
+    if rec is not None:
+        def plan_label():
             label = ctypes.create_string_buffer(192)
             check(L.tt_conv2d_wgrad_plan(ptr(x), N, H, W, cin, Cs, in_coff, ptr(dy), OH, OW, cout, Cd, dy_coff, kh, kw, stride, pad,
                                          dil, cin_pad, 1 if accumulate else 0, ptr(out), ptr(ws), nb, int(x3), label, len(label)),
                   "tt_conv2d_wgrad_plan")
-            CONV_KERNELS.append(label.value.decode())
-        if CONV_BYTES is not None:
-            CONV_BYTES.append((x.numel() + dy.numel() + out.numel()) * 4)
+            return label.value.decode()
+        rec.log(2.0 * N * OH * OW * cout * kh * kw * cin, f"wgrad M={N * OH * OW} N={cout} K={kh * kw * cin} k{kh}x{kw}s{stride}",
+                kernel=plan_label, nbytes=(x.numel() + dy.numel() + out.numel()) * 4)
     return out
 
 
@@ -1099,16 +1175,12 @@ def conv_epilogue_bwd(dy, y, scale=None, shift=None, act=0, res1=None, res2=None
         dshift = torch.empty(C, dtype=torch.float32, device=dev)
         accumulate = False
     L = lib()
-    nb = int(L.tt_conv_epilogue_bwd_workspace_bytes(C))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-
-    def cs(t):
-        return 0 if t is None else t.shape[-1]
-    check(L.tt_conv_epilogue_bwd(ptr(dy), dy.shape[-1], dy_coff, ptr(y), y.shape[-1], y_coff, ptr(res1), cs(res1), res1_coff,
-                                 ptr(res2), cs(res2), res2_coff, ptr(scale), ptr(shift), M, C, act, ptr(dconv), C, 0,
-                                 ptr(dres1), cs(dres1), dres1_coff, ptr(dres2), cs(dres2), dres2_coff,
+    ws = _workspace(L.tt_conv_epilogue_bwd_workspace_bytes(C), dev)
+    check(L.tt_conv_epilogue_bwd(ptr(dy), dy.shape[-1], dy_coff, ptr(y), y.shape[-1], y_coff, ptr(res1), _cs(res1), res1_coff,
+                                 ptr(res2), _cs(res2), res2_coff, ptr(scale), ptr(shift), M, C, act, ptr(dconv), C, 0,
+                                 ptr(dres1), _cs(dres1), dres1_coff, ptr(dres2), _cs(dres2), dres2_coff,
                                  1 if dres_accumulate else 0, ptr(dscale if scale is not None else None), ptr(dshift),
-                                 1 if accumulate else 0, ptr(m_dev), ptr(pre), ptr(conv_raw), ptr(ws), nb, _st(y)),
+                                 1 if accumulate else 0, ptr(m_dev), ptr(pre), ptr(conv_raw), ptr(ws), ws.numel(), _st(y)),
           "tt_conv_epilogue_bwd")
     return dconv, dres, (dscale if scale is not None else None), dshift
 
@@ -1209,7 +1281,7 @@ def msda_sample_ln(value, offsets, logits, ref, level_hw, B, coff, gamma, beta, 
     R = B * 4 * 120
     out = torch.empty(R, 256, dtype=torch.float32, device=value.device)
     out_ln = torch.empty(R, 256, dtype=torch.float32, device=value.device)
-    hw = (ctypes.c_int * 8)(*[v for pair in level_hw for v in pair])
+    hw = _level_hw(level_hw)
     check(lib().tt_msda_sample_ln(B, ptr(value), dtype_code(value), value.shape[-1], coff, ptr(offsets),
                                   ptr(logits), ptr(ref), hw, ptr(gamma), ptr(beta), eps, ptr(out), ptr(out_ln),
                                   ptr(max_len), _st(value)), "tt_msda_sample_ln")

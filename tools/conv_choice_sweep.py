@@ -240,31 +240,36 @@ def plan_label(L, d):
     return buf.value.decode() if rc == 0 else "ERROR: " + L.tt_last_error().decode()
 
 
+def _strides(shape):
+    """Element strides of a contiguous tensor of this shape."""
+    st = [1]
+    for n in reversed(shape[1:]):
+        st.insert(0, st[0] * n)
+    return tuple(st)
+
+
 def describe(c, L):
     """The descriptor ops.conv2d / ops.gather_conv build for a case (pointers 1 / 0), and the split-K query's answer where they ask."""
-    row = {n: 0 for n, _ in _fields()}
-    row.update(in_=1, weight=1, out=1, Cin=c["Cin"], Cout=c["Cout"], dil=1, act=0, dtype=DT[c["dt"]], out_dtype=DT[c["dt"]],
-               stride=c["stride"], shift_n_mod=1, weight_x3=int(c["x3"]))
+    from thinktwice_amd import ops
+    here = lambda flag: 1 if flag else None       # the "address" of an operand the case has
+    operands = dict(x=1, w=1, out=1, dtype=DT[c["dt"]], out_dtype=DT[c["dt"]], weight_x3=here(c["x3"]))
     if c["kind"] == "sparse":
-        row.update(N=c["M"], H=1, W=1, OH=1, OW=1, KH=1, KW=27, in_cstride=c["Cin"], out_cstride=c["Cout"], gather_idx=1, m_dev=1,
-                   row_perm=int(c["plan"]), row_mask=int(c["plan"]), shift_n_mod=0)
-        return row, None
-    N, H, W, KH, KW, s, p = c["N"], c["H"], c["W"], c["KH"], c["KW"], c["stride"], c["pad"]
-    OH, OW = c["out_hw"] or ((H + 2 * p - KH) // s + 1, (W + 2 * p - KW) // s + 1)
-    cr = c["Cout"] // 4 if c["ps2"] else c["Cout"]
-    row.update(N=N, H=H, W=W, KH=KH, KW=KW, pad=p, OH=OH, OW=OW, in_cstride=c["in_cstride"] or c["cs"], in_coff=c["in_coff"],
-               in_nstride=H * W * c["cs"] if N > 1 else 0, out_cstride=cr,
-               out_nstride=(4 if c["ps2"] else 1) * OH * OW * cr if N > 1 else 0, pixel_shuffle2=int(c["ps2"]),
-               weight_h2=int(c["h2"]), in_pair=int(c["in_pair"]), out_pair=int(c["out_pair"]))
-    if c["out2"]:
-        row.update(out2=1, out2_cstride=c["Cout"])
-    if c["res"] >= 1:
-        row.update(res1=1, res1_cstride=c["Cout"])
-    if c["res"] >= 2:
-        row.update(res2=1, res2_cstride=c["Cout"])
+        d = ops.conv_desc(x_shape=(GRID[0] * GRID[1] * GRID[2] * GRID[3], c["Cin"]), x_strides=None, w_shape=(c["Cout"], 1, 27, c["Cin"]),
+                          out_shape=(c["M"], c["Cout"]), out_strides=None, stride=c["stride"], shift_n_mod=0, gather=(1, 1, c["M"]),
+                          plan=(1, 1) if c["plan"] else None, **operands)
+        return desc_to_dict(d), None
+    x_shape, w_shape = (c["N"], c["H"], c["W"], c["cs"]), (c["Cout"], c["KH"], c["KW"], c["Cin"])
+    geometry = dict(stride=c["stride"], pad=c["pad"], out_hw=c["out_hw"], pixel_shuffle2=c["ps2"])
+    _, _, OH, OW, out_shape = ops.conv_geometry(x_shape, w_shape, **geometry)
+    full = (c["N"], OH, OW, c["Cout"])       # the shape of a residual and of the second output
+    d = ops.conv_desc(x_shape=x_shape, x_strides=_strides(x_shape), w_shape=w_shape, out_shape=out_shape, out_strides=_strides(out_shape),
+                      in_coff=c["in_coff"], in_cstride=c["in_cstride"], res1=here(c["res"] >= 1), res1_shape=full, res1_dtype=DT[c["dt"]],
+                      res2=here(c["res"] >= 2), res2_shape=full, weight_h2=here(c["h2"]), in_pair=c["in_pair"], out_pair=c["out_pair"],
+                      out2=here(c["out2"]), out2_shape=full, **geometry, **operands)
+    row = desc_to_dict(d)
     query = None
-    if c.get("ask") or (not c["ws"] and not (c["in_pair"] or c["out_pair"] or c["h2"]) and N * OH * OW <= 4096 and
-                        KH * KW * c["Cin"] >= 2048):
+    if c.get("ask") or ops.auto_splitk_asks(c["N"] * OH * OW, c["KH"] * c["KW"] * c["Cin"], splitk_ws=c["ws"],
+                                            pair=c["in_pair"] or c["out_pair"], h2=c["h2"]):
         query = int(L.tt_conv2d_splitk_slices(ctypes.byref(dict_to_desc(row))))
     if c["ws"] or query:
         row.update(splitk_ws=1, splitk_slices=query or 0)
