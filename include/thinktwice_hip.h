@@ -394,6 +394,22 @@ int tt_nhwc_to_nchw(const void* in, float* out, int N, int C, int H, int W, int 
                     int in_dtype, void* stream);
 /* F.max_pool2d(x,3,2,1): mmdet ResNet stem (lss.py:401 -> [3P]) */
 int tt_maxpool3x3s2(const void* in, void* out, int N, int H, int W, int C, int dtype, void* stream);
+/* The ResNet stem of the bf16x3 modes in ONE launch, from the NCHW image to the pooled map (csrc/conv_x3_stem.hip):
+ *   out = F.max_pool2d(relu(scale * conv7x7s2p3(img) + shift), 3, 2, 1)   f32 (B*T*N, ceil(H/4), ceil(W/4), 64), channel-last, contiguous
+ * bit for bit what tt_nchw_to_nhwc_border (4 channels, border 3 / 3 / 3 / 5), tt_conv2d_fwd of the row-run stem (7 x 1, stride 2,
+ * in_cstride 4, ReLU) and tt_maxpool3x3s2 produce over the same image.  Inference only.
+ *   img          f32 (B, T, N, 3, H, W): element (b, t, n, c, y, x) at img[b*stride_b + t*stride_t + n*stride_n + c*stride_c +
+ *                y*stride_h + x*stride_w]; the inner (3, H, W) block must be contiguous (stride_c = H*W, stride_h = W, stride_w = 1),
+ *                H and W even.  Output image (s*B + b)*N + n is img[b, T-1-s, n] (sweep-major, key sweep first).  img_dtype: TT_F32.
+ *   weight_x3    the row-run stem weights f32 [w_cout = 64][w_kh = 7][1][w_k = 32] (8 pixels x 4 channels per filter row, the 4th
+ *                channel and the 8th pixel zero) in pair format (tt_conv_desc.weight_x3), 16-byte aligned;
+ *   scale/shift  folded BN, 64 floats each;  out: 16-byte aligned, out_floats = the floats it may hold;
+ *   max_workgroups  0, or a bound on the persistent grid (tests).
+ * Anything else is refused with an error naming the field; nothing here runs as three launches. */
+int tt_stem_pool_x3(const float* img, long long stride_b, long long stride_t, long long stride_n, long long stride_c,
+                    long long stride_h, long long stride_w, int B, int T, int N, int H, int W, int img_dtype,
+                    const void* weight_x3, int w_cout, int w_kh, int w_k, const float* scale, const float* shift,
+                    float* out, long long out_floats, int max_workgroups, void* stream);
 /* dst += F.interpolate(src, size=dst.shape, mode='nearest'): PAFPN top-down (lss.py:301-305) */
 int tt_upsample_nearest_add(void* dst, const void* src, int N, int H, int W, int C, int h, int w,
                             int dtype, void* stream);

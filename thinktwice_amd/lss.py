@@ -64,8 +64,14 @@ class _ResNet50:
         """(top, left, bottom, right) zero border the row-run stem needs around the image, or None."""
         return (3, 3, 3, 5) if self.stem_rr is not None else None
 
-    def __call__(self, x, bordered=False):
-        if bordered:      # x: (NI, H+6, W+8, 8) with the image at (3, 3)
+    def stem_pool_ok(self, img):
+        """Whether `img` (B, T, N, 3, H, W) takes the one-launch stem (ops.stem_pool): bf16x3 inference with the row-run weights."""
+        return self.stem_rr_x3 is not None and ops.stem_pool_ok(img, self.stem_rr_x3)
+
+    def __call__(self, x, bordered=False, image=False):
+        if image:         # x: the NCHW image (B, T, N, 3, H, W); stem and max pool in one launch (stem_pool_ok is the caller's rule)
+            x = ops.stem_pool(x, self.stem_rr_x3, self.stem.scale, self.stem.shift)
+        elif bordered:    # x: (NI, H+6, W+8, 8) with the image at (3, 3)
             NI, Hp, Wp, _ = x.shape
             if layers.BN_TRAIN:       # model.train(): raw row-run convolution, then the stem's batch-statistics BatchNorm
                 z = ops.conv2d(x, self.stem_rr, stride=2, pad=0, act=0, in_cstride=self.cin_pad,
@@ -77,7 +83,8 @@ class _ResNet50:
                                w_x3=self.stem_rr_x3)
         else:
             y = self.stem(x, stop_grad=True)      # (training tape: the image is a leaf without a gradient)
-        x = ops.maxpool3x3s2(y)
+        if not image:
+            x = ops.maxpool3x3s2(y)
         outs = []
 
         def pair_c1(blk, shape):
@@ -373,11 +380,11 @@ class LSS:
         return self
 
     # ------------------------------------------------------------------ forward pieces
-    def _trunk(self, x, bordered=False):
-        """ResNet-50 + PAFPN + neck_conv on NI channel-last images.  FPN maps are produced directly
-        inside the UNet concat buffers (torch.cat of lss.py:256 becomes a channel offset)."""
-        NI = x.shape[0]
-        c = self.backbone(x, bordered=bordered)
+    def _trunk(self, x, bordered=False, image=False):
+        """ResNet-50 + PAFPN + neck_conv on NI channel-last images (`image`: on the NCHW image (B, T, N, 3, H, W) itself).  FPN maps
+        are produced directly inside the UNet concat buffers (torch.cat of lss.py:256 becomes a channel offset)."""
+        NI = x.shape[0] * x.shape[1] * x.shape[2] if image else x.shape[0]
+        c = self.backbone(x, bordered=bordered, image=image)
         H0, W0 = c[0].shape[1:3]
         dt, dev = self.dtype, x.device
         cat2 = torch.empty(NI, H0, W0, 384, dtype=dt, device=dev)            # [up(d3) 128 | e1 256]
@@ -519,7 +526,12 @@ class LSS:
         from . import autodiff
         # (the row-run stem has no backward yet: a taped forward uses the plain 7x7 form)
         border = self.backbone.stem_border() if (H % 2 == 0 and W % 2 == 0 and autodiff.TAPE is None) else None
-        if border is not None:
+        # bf16x3 inference: the stem reads the NCHW image itself and does the sweep-major reordering (ops.stem_pool) -- no bordered
+        # copy, no conversion launches
+        fused_stem = border is not None and self.backbone.stem_pool_ok(img)
+        if fused_stem:
+            x = img
+        elif border is not None:
             # zero-bordered image buffer for the row-run stem; the border is written once, the interior every call
             # (one per stream: with batches pipelined on alternating streams the next forward's image upload must not overwrite
             # a buffer the previous forward's stem may still be reading)
@@ -531,7 +543,7 @@ class LSS:
                 self._xpad[key] = x      # every bordered buffer stays alive: captured HIP graphs hold raw pointers
         else:
             x = torch.empty(NI, H, W, self.backbone.cin_pad, dtype=self.dtype, device=img.device)
-        for s in range(T):
+        for s in range(0 if fused_stem else T):
             for b in range(B):
                 src = img[b, T - 1 - s].contiguous()
                 o = (s * B + b) * N
@@ -544,7 +556,7 @@ class LSS:
         # train mode: the T sweeps are T equal image groups; every BatchNorm below normalises each with its own batch
         # statistics, like the reference's one-pass-per-sweep loop (lss.py:690-717)
         with layers.bn_groups(T):
-            bufs = self._trunk(x, bordered=border is not None)
+            bufs = self._trunk(x, bordered=border is not None, image=fused_stem)
             fpn2_buf, fpn2_off, _ = self._fpn_views(bufs)[2]
             src = self.neck_conv(fpn2_buf, in_coff=fpn2_off, cin=256)
             mlp_in = consts["mlp_in"]

@@ -697,6 +697,42 @@ def maxpool3x3s2(x):
     return out
 
 
+STEM_POOL = os.environ.get("TT_STEM_POOL", "1") != "0"     # A/B knob and test hook: 0 = border copy, row-run stem and max pool stay three launches
+
+
+def stem_pool_ok(img, w_x3):
+    """Whether the bf16x3 stem runs from the NCHW image to the pooled map in one launch (stem_pool, tt_stem_pool_x3): inference
+    on f32 storage with the row-run weights, even H and W, a contiguous (3, H, W) block per image, and more than 4,096 stem
+    pixels in all: up to there the three launches run the stem on the exact-f32 latency kernel (csrc/conv_choose.cpp,
+    choose_small), whose sums the one launch does not reproduce.  tests/test_stem_pool_choice.py pins the rule."""
+    from . import layers
+    if not (STEM_POOL and _active_tape() is None and not layers.BN_TRAIN and w_x3 is not None and img.dtype == torch.float32 and
+            img.dim() == 6 and img.shape[3] == 3 and img.shape[4] % 2 == 0 and img.shape[5] % 2 == 0):
+        return False
+    B, T, N, _, H, W = img.shape
+    return tuple(img.stride()[3:]) == (H * W, W, 1) and B * T * N * (H // 2) * (W // 2) > 4096
+
+
+def stem_pool(img, w_x3, scale, shift, max_workgroups=0):
+    """img (B, T, N, 3, H, W) f32 (any b / t / n strides) -> max_pool2d(relu(scale * conv7x7s2p3(img) + shift), 3, 2, 1) as f32
+    (T*B*N, ceil(H/4), ceil(W/4), 64) channel-last, images sweep-major ((s*B + b)*N + n = img[b, T-1-s, n]).  w_x3: the row-run
+    stem weights [64][7][1][32] in pair format.  Bit-equal to nchw_to_nhwc_border + conv2d(row-run) + maxpool3x3s2."""
+    require_cuda(img, w_x3, scale, shift)
+    B, T, N, C, H, W = img.shape
+    NI, PH, PW = B * T * N, (H // 2 + 1) // 2, (W // 2 + 1) // 2
+    out = torch.empty(NI, PH, PW, 64, dtype=torch.float32, device=img.device)
+    sb, st, sn, sc, sh, sw = img.stride()
+    with _launch() as rec:
+        check(lib().tt_stem_pool_x3(ptr(img), sb, st, sn, sc, sh, sw, B, T, N, H, W, dtype_code(img), ptr(w_x3), w_x3.shape[0],
+                                    w_x3.shape[1], w_x3.shape[-1], ptr(scale), ptr(shift), ptr(out), out.numel(), max_workgroups,
+                                    _st(img)), "tt_stem_pool_x3")
+    if rec is not None:
+        M = NI * (H // 2) * (W // 2)
+        rec.log(2.0 * M * 64 * 224, f"M={M} N=64 K=224 stem+pool k7x7s2", kernel="conv_x3_stem_pool_kernel",
+                nbytes=NI * 3 * H * W * 4 + out.numel() * 4 + w_x3.numel() * 4)
+    return out
+
+
 def upsample_nearest_add_(dst, src):
     N, H, W, C = dst.shape
     check(lib().tt_upsample_nearest_add(ptr(dst), ptr(src), N, H, W, C, src.shape[1],
