@@ -95,9 +95,26 @@ __device__ __forceinline__ void split8(const V& r0, const V& r1, uint4& hi, uint
                         frag_f32(r1.x), frag_f32(r1.y), frag_f32(r1.z), frag_f32(r1.w)};
     split8(x, hi, lo);
 }
+// The same fragment through split_hi / split_lo, pair by pair: the prologue of the hand-pipelined kernels (conv_x3_pipe.hip), whose
+// loop places these halves between MFMAs one at a time.  V: a 16-byte vector of four uint32 (u32x4, uint4).
+template <typename V>
+__device__ __forceinline__ void split8_halves(const V& r0, const V& r1, V& hi, V& lo) {
+    static_assert(sizeof(V) == 16, "a 16-byte fragment of four f32");
+    const float x[8] = {frag_f32(r0.x), frag_f32(r0.y), frag_f32(r0.z), frag_f32(r0.w),
+                        frag_f32(r1.x), frag_f32(r1.y), frag_f32(r1.z), frag_f32(r1.w)};
+    uint32_t h[4], l[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t0, t1;
+        split_hi(x[2 * e], x[2 * e + 1], h[e], t0, t1);
+        l[e] = split_lo(x[2 * e], x[2 * e + 1], t0, t1);
+    }
+    hi = V{h[0], h[1], h[2], h[3]};
+    lo = V{l[0], l[1], l[2], l[3]};
+}
 
 // ---- pair format
-constexpr int kPairGroup = 16;         // channels of a group
+constexpr int kPairGroup = 16;        // channels of a group
 constexpr int kPairGroupBytes = 64;    // [hi 0-7 | hi 8-15 | lo 0-7 | lo 8-15]
 constexpr int kPairLo = 32;            // a lo half lies this many bytes after its hi half
 static_assert(kPairGroupBytes == kPairGroup * 2 * (int)sizeof(uint16_t), "a group holds a bf16 hi and a bf16 lo per channel");

@@ -240,8 +240,8 @@ __global__ __launch_bounds__(256, 1) void conv_h2_pipe_kernel(const ConvArgs p, 
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const unsigned ldsA = lds_base, ldsB = lds_base + 3u * A_BYTES;
 
-    // ---- the two DMA walkers (wave-uniform, branch-free; the same as conv_x3_pipe_kernel's, which explains them, over rows of
-    // 2 Cin halves -- see there why they stay lambdas of the kernel).  K order: channel chunk outer, filter tap inner
+    // ---- the two DMA walkers (wave-uniform, branch-free; the same as conv_x3_pipe_kernel's in conv_x3_pipe.hip, which explains
+    // them, over rows of 2 Cin halves -- see there why they stay lambdas of the kernel).  K order: channel chunk outer, filter tap inner
     const int ntaps = p.KH * p.KW;
     const long long a_d1 = (long long)p.dil * p.in_cstride;
     const long long a_d2 = ((long long)p.dil * p.W - (long long)(p.KW - 1) * p.dil) * p.in_cstride;

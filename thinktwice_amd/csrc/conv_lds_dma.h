@@ -22,6 +22,13 @@ __device__ __forceinline__ u32x4 lds_read(unsigned addr) {
     asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
     return v;
 }
+// ... with a compile-time byte offset
+template <int OFF>
+__device__ __forceinline__ u32x4 lds_read_at(unsigned addr) {
+    u32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+    return v;
+}
 
 // The counted wait: at most N of this wave's loads (LDS-DMA pieces, in issue order) are still outstanding.
 template <int N>

@@ -33,12 +33,6 @@ namespace {
 __device__ __forceinline__ void lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void pin(u32x4& v) { asm volatile("" : "+v"(v)); }
 template <int OFF>
-__device__ __forceinline__ u32x4 lds_read_at(unsigned addr) {
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-template <int OFF>
 __device__ __forceinline__ void lds_write_f32_at(unsigned addr, float v) {
     asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
 }

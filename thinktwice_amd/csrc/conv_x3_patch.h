@@ -54,14 +54,6 @@ __device__ __forceinline__ Tile tile_of(int tiles, int tiles_x, int tiles_y) {
 }
 }  // namespace patch
 
-// ds_read_b128 with a compile-time byte offset (inline asm for the reason conv_lds_dma.h gives for lds_read)
-template <int OFF>
-__device__ __forceinline__ u32x4 lds_read_at(unsigned addr) {
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-
 // The K loop of a tile: for every chunk, produce(first channel of the chunk) and the nine taps.  `wgt`: the pre-split weights
 // [Cout][9 C]; `C` = Cin.  TAP0_VM: the loads of this wave that may still be in flight when tap 0 of a chunk reads the patch -- 1 (the
 // next tap's weight piece) where the production has consumed its own loads, 0 where the production IS loads (LDS-DMA pieces, issued

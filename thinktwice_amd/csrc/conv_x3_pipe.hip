@@ -1,4 +1,4 @@
-// bf16x3 implicit-GEMM convolution, 256 x 256 tile, FOUR waves of 128 x 128: one wave per SIMD, hand-pipelined K loop.
+// bf16x3 implicit-GEMM convolution, 256 x 256 or 256 x 128 tile, FOUR waves of 64 x BN (4 x 1): one wave per SIMD, hand-pipelined K loop.
 //
 // Same arithmetic, operand formats, LDS image (the pipeline of conv_lds_dma.h) and epilogue as the X3 body of
 // conv_igemm_glds.hip (f32 activations split into bf16 (hi, lo) in registers, pre-split pair-format weights, three
@@ -20,13 +20,29 @@
 // MFMAs, fragment reads and waits are inline asm (program order = issue order; hipcc does not model them, so the
 // hazards it would pad are spaced by construction or by explicit s_nop); the split and the address arithmetic are
 // plain C++ pinned into their gap by empty asm statements on their inputs / outputs.
-// Contract (dispatcher in conv_igemm_glds.hip): dense conv, f32 storage, Cin % 32 == 0, Cout % 256 == 0, KH*KW <= 31.
+// Contract (conv_choose.cpp): dense conv, f32 storage, Cin % 32 == 0, Cout % BN == 0, KH*KW <= 31.
+//
+// Two kernels run this schedule, and the K step itself -- the groups of MFMAs and what stands in the gaps behind them -- is stated
+// once, in conv_x3_pipe_kstep.h, which both include as text.  conv_x3_pipe_kernel is the form described above: one 256-row activation
+// tile per (channel chunk, tap), padded at DMA time from the zero page, three stages.  What the run-staged form
+// (conv_x3_run3_kernel, below) replaces is the activation side only: slots and masks, walker, LDS map, fragment address, the
+// distribution of the DMA pieces over the groups and the stage rotation.  Each kernel keeps its own set-up and prologue: the pieces
+// tried as one shared body (a force-inlined function over both forms, or one text with `if constexpr` arms) moved the instruction
+// stream of one form or the other (profiles/x3_pipe_one_body.txt), which on these kernels has to be measured, not assumed harmless.
 #include "conv_lds_dma.h"
 
 namespace tt {
 
 #ifndef TT_PIPE_DEBUG
 #define TT_PIPE_DEBUG 0
+#endif
+// Timing ablations (tools/build_pipe_debug.sh; results are wrong by design): TT_PIPE_DEBUG bit 0 no DMA in the loop, bit 1 no
+// operand split, bit 2 no MFMA, bit 3 no fragment reads in the loop, bit 4 no tile barrier.
+// They act in both kernels: in conv_x3_pipe_kstep.h and in the dma lambdas.
+#if TT_PIPE_DEBUG & 4
+#define TT_MFMA(c, a, b) asm volatile("" : "+a"(c) : "v"(a), "v"(b))
+#else
+#define TT_MFMA(c, a, b) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b))
 #endif
 
 // APAIR: pre-split (pair-format) activations, tt_conv_desc.in_pair -- the fragment reads fetch the bf16 hi and lo halves directly
@@ -39,8 +55,8 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
     constexpr int NW = WAVES_M * WAVES_N;
     constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
     constexpr int TM = WTM / 32, TN = WTN / 32;
-    static_assert(NW == 4 && (TM * TN == 16 || TM * TN == 8) && TN % TM == 0,
-                  "four waves of 128 x 128 (2 x 2) or 64 x 256 (4 x 1) on a 256 x 256 tile; of 64 x 128 (4 x 1) on a 256 x 128 tile");
+    static_assert(WAVES_M == 4 && WAVES_N == 1 && (BN == 256 || BN == 128) && TM == 2,
+                  "four waves of 64 x BN (4 x 1) on a 256 x 256 or 256 x 128 tile: the one form conv_x3_pipe_kstep.h is written for");
     constexpr int A_BYTES = BM * BKB, B_BYTES = BN * BKB;
     constexpr int NIA = BM * 8 / 64 / NW, NIB = BN * 8 / 64 / NW;      // 1 KiB DMA pieces per wave per tile (8 + 8)
     constexpr int MG = 3 * TM;            // MFMAs per group (one 32-wide column block x TM row blocks x 3 terms)
@@ -102,7 +118,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
     int a_kw = 0, a_tap = 0, a_rem = nk;          // a_rem: tiles not yet issued, this one included
     long long a_off = 0;
     unsigned a_st = ldsA;
-    int b_tap = 0, b_rem = nk, b_w = 0;
+    int b_tap = 0, b_rem = nk, b_w = 0;           // (b_w: a local of b_walk1 in the run-staged kernel; either kernel moves with the other's form)
     long long b_off = 0;
     unsigned b_st = ldsB;
     long long a_d = 0;
@@ -159,13 +175,6 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
 #pragma unroll
         for (int j = 0; j < TN; ++j) fb_pre[kc][j] = frag_off<BKB>(wn * WTN + j * 32 + (lane & 31), 4u * kc + hi);
     }
-// Timing ablations (tools/build_pipe_debug.sh; results are wrong by design): TT_PIPE_DEBUG bit 0 no DMA in the loop, bit 1 no
-// operand split, bit 2 no MFMA, bit 3 no fragment reads in the loop, bit 4 no tile barrier
-#if TT_PIPE_DEBUG & 4
-#define TT_MFMA(c, a, b) asm volatile("" : "+a"(c) : "v"(a), "v"(b))
-#else
-#define TT_MFMA(c, a, b) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b))
-#endif
     // (the split of one element pair comes in two 3-VALU halves, cvt_pk, shift, and | sub, sub, cvt_pk: split_hi / split_lo of bf16x3.h)
 
     u32x4 ah[2][TM], al[2][TM];       // [K step parity][row block]: split activation fragments
@@ -199,17 +208,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
             ra1 = lds_read(ldsA + (fa_pre[0][i] ^ 16u));
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             asm volatile("" : "+v"(ra0), "+v"(ra1));
-            const float x[8] = {__uint_as_float(ra0.x), __uint_as_float(ra0.y), __uint_as_float(ra0.z), __uint_as_float(ra0.w),
-                                __uint_as_float(ra1.x), __uint_as_float(ra1.y), __uint_as_float(ra1.z), __uint_as_float(ra1.w)};
-            uint32_t h[4], l[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t0, t1;
-                split_hi(x[2 * e], x[2 * e + 1], h[e], t0, t1);
-                l[e] = split_lo(x[2 * e], x[2 * e + 1], t0, t1);
-            }
-            ah[0][i] = u32x4{h[0], h[1], h[2], h[3]};
-            al[0][i] = u32x4{l[0], l[1], l[2], l[3]};
+            split8_halves(ra0, ra1, ah[0][i], al[0][i]);
         }
 #pragma unroll
         for (int j = 0; j < TN - 1; ++j) {        // column TN-1's hi half is read in the first gap of the K step itself
@@ -239,146 +238,9 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
                 else b_emit(q);
                 asm volatile("" ::: "memory");
             };
-            uint32_t sh[4], sl[4];
-            float st0 = 0.f, st1 = 0.f;
-            // split stage s = 2 * pair + half of the fragment in ra0 / ra1
-            auto split_stage = [&](int s) {
-                // pinned on both sides: the stage's 3 VALU cannot start before this point (input pin) nor end after it
-                const int e = s >> 1;
-                asm volatile("" : "+v"(ra0), "+v"(ra1));
-                const float x0 = __uint_as_float(e == 0 ? ra0.x : e == 1 ? ra0.z : e == 2 ? ra1.x : ra1.z);
-                const float x1 = __uint_as_float(e == 0 ? ra0.y : e == 1 ? ra0.w : e == 2 ? ra1.y : ra1.w);
-                if (TT_PIPE_DEBUG & 2) {
-                    if ((s & 1) == 0) sh[e] = __float_as_uint(x0);
-                    else sl[e] = __float_as_uint(x1);
-                    return;
-                }
-                if ((s & 1) == 0) {
-                    split_hi(x0, x1, sh[e], st0, st1);
-                    asm volatile("" : "+v"(sh[e]), "+v"(st0), "+v"(st1));
-                } else {
-                    asm volatile("" : "+v"(st0), "+v"(st1));
-                    sl[e] = split_lo(x0, x1, st0, st1);
-                    asm volatile("" : "+v"(sl[e]));
-                }
-            };
-#pragma unroll
-            for (int g = 0; g < TN; ++g) {
-                const int rb = g / NGR;                             // row block whose next fragment this group works on
-                const bool barw = (kc == 1 && rb == 0);             // window that carries the tile barrier
-                const bool bar = barw && (g % NGR) == 0;            // ... and the group inside it
-                const bool last = g == TN - 1;
-                // window slots: reads @1, wait @4, eight split stages from @4 on; barrier window: barrier @3, reads @4, wait @7
-                constexpr int R0 = 1, W0 = 4, RB = 4, WB = 7;
-#pragma unroll
-                for (int m = 0; m < MG; ++m) {
-                    const int t = m / TM, i = m % TM;
-                    if (t == 0) TT_MFMA(acc[i][g], al[kc][i], bh[g]);
-                    else if (t == 1) TT_MFMA(acc[i][g], ah[kc][i], bl[g]);
-                    else TT_MFMA(acc[i][g], ah[kc][i], bh[g]);
-                    // ---- the gap behind MFMA m
-                    const int ws = (g % NGR) * MG + m;              // slot inside the row-block window
-                    if (m == 0 && !(TT_PIPE_DEBUG & 8)) {
-                        // hi half of the column block the previous group finished with.  g = 0: column TN-1 of THIS K step
-                        // (its registers were busy until the previous K step's last MFMA); else column g-1 of the next one
-                        if (g == 0) bh[TN - 1] = lds_read(sB_cur + fb_pre[kc][TN - 1]);
-                        else bh[g - 1] = lds_read(srcB + fb_pre[kn][g - 1]);
-                    }
-                    if (bar && m == 3) {
-                        // tile kt + 1 has landed for this wave (the NIA youngest loads = activations of tile kt + 2 stay in
-                        // flight); every fragment read of tile kt is complete: publish tile kt + 1, free tile kt's stages
-                        if (TT_PIPE_DEBUG & 16) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-                        else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                    }
-                    if (ws == (barw ? RB : R0) && !(TT_PIPE_DEBUG & 8)) {
-                        if constexpr (APAIR) {      // (the registers' last readers, the previous K step's MFMAs, were issued long ago)
-                            ah[kn][rb] = lds_read(srcA + fa_pre[kn][rb]);
-                            al[kn][rb] = lds_read(srcA + (fa_pre[kn][rb] ^ 32u));
-                        } else {
-                            ra0 = lds_read(srcA + fa_pre[kn][rb]);
-                            ra1 = lds_read(srcA + (fa_pre[kn][rb] ^ 16u));
-                        }
-                    }
-                    // DMA: behind the fragment reads; in the barrier group after the barrier (the weight stage it frees)
-                    {
-                        constexpr int DPG = 2;                      // slots per group (a weight step may use one)
-                        const int npieces = kc == 0 ? DPA : DPB;
-                        const int s0 = bar ? (MG >= 8 ? 5 : 4) : 2; // barrier group: after the barrier at gap 3
-                        if (m == s0) dma(npieces * g);
-                        if (m == s0 + 1 && npieces == DPG) dma(npieces * g + 1);
-                    }
-                    if (ws == (barw ? WB : W0)) {
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        if constexpr (APAIR) asm volatile("" : "+v"(ah[kn][rb]), "+v"(al[kn][rb]));
-                        else asm volatile("" : "+v"(ra0), "+v"(ra1));
-                        if (g == 0) asm volatile("" : "+v"(bh[TN - 1]));     // the gap-0 read of this K step has landed too
-                    }
-                    if (m == 2 * TM - 1 && !(TT_PIPE_DEBUG & 8)) bl[g] = lds_read(srcB + (fb_pre[kn][g] ^ 32u));   // lo half: free now
-                    if constexpr (!APAIR) {
-                        // the eight 3-VALU split stages, spread over what is left of the window
-                        const int first = barw ? WB : W0;
-                        const int avail = WIN - first;
-                        int lastslot;
-                        if (avail >= 16) {                           // every other gap
-                            if (ws >= first && ((ws - first) & 1) == 0 && (ws - first) / 2 < 8) split_stage((ws - first) / 2);
-                            lastslot = first + 14;
-                        } else if (avail >= 8) {                     // every gap
-                            if (ws >= first && ws - first < 8) split_stage(ws - first);
-                            lastslot = first + 7;
-                        } else {                                     // two stages per gap
-                            if (ws >= first && ws - first < 4) {
-                                split_stage(2 * (ws - first));
-                                split_stage(2 * (ws - first) + 1);
-                            }
-                            lastslot = first + 3;
-                        }
-                        if (ws == lastslot) {
-                            ah[kn][rb] = u32x4{sh[0], sh[1], sh[2], sh[3]};
-                            al[kn][rb] = u32x4{sl[0], sl[1], sl[2], sl[3]};
-                            asm volatile("" : "+v"(ah[kn][rb]), "+v"(al[kn][rb]));
-                        }
-                    }
-                    // the walker of the DMA stream this K step has just finished issuing, and the tile's stage rotation
-                    if (last && kc == 0) {
-                        if (m == MG - 3) {
-                            asm volatile("" : "+s"(a_kw));
-                            a_walk1();
-                            asm volatile("" : "+s"(a_kw), "+s"(a_d));
-                        }
-                        if (m == MG - 2) {
-                            asm volatile("" : "+s"(a_tap), "+s"(a_d), "+s"(a_off));
-                            a_walk2();
-                            asm volatile("" : "+s"(a_tap), "+s"(a_off));
-                        }
-                        if (m == MG - 1) {
-                            asm volatile("" : "+s"(a_rem), "+s"(a_st));
-                            a_walk3();
-                            asm volatile("" : "+s"(a_rem), "+s"(a_st));
-                        }
-                    }
-                    if (last && kc == 1) {
-                        if (m == MG - 3) {
-                            asm volatile("" : "+s"(b_tap), "+s"(b_off));
-                            b_walk1();
-                            asm volatile("" : "+s"(b_tap), "+s"(b_off));
-                        }
-                        if (m == MG - 2) {
-                            asm volatile("" : "+s"(b_rem), "+s"(b_st));
-                            b_walk2();
-                            asm volatile("" : "+s"(b_rem), "+s"(b_st));
-                        }
-                        if (m == MG - 1) {
-                            asm volatile("" : "+s"(sA_cur), "+s"(sA_nxt), "+s"(sB_cur), "+s"(sB_nxt));
-                            sA_cur = sA_nxt;
-                            sA_nxt = sA_nxt == ldsA + 2u * A_BYTES ? ldsA : sA_nxt + A_BYTES;
-                            const unsigned tb = sB_cur;
-                            sB_cur = sB_nxt;
-                            sB_nxt = tb;
-                            asm volatile("" : "+s"(sA_cur), "+s"(sA_nxt), "+s"(sB_cur), "+s"(sB_nxt));
-                        }
-                    }
-                }
-            }
+#define TT_X3_RUN3 0
+#include "conv_x3_pipe_kstep.h"
+#undef TT_X3_RUN3
         }
     }
     // MFMA results -> any other reader: the hazard hipcc would pad for a builtin (8-pass XDL: 12+ states)
@@ -389,10 +251,6 @@ __global__ __launch_bounds__(256, 1) void conv_x3_pipe_kernel(const ConvArgs p, 
     // row-block loop anywhere in it would pin all 256 accumulator registers to scratch for the whole kernel)
     conv_epilogue<float, 1, TN, 32, WTN>(p, *reinterpret_cast<f32x16(*)[1][TN]>(&acc[0]), smem, wave, lane, wm * TM + 0, wn, m0, n0, Mlim);
     conv_epilogue<float, 1, TN, 32, WTN>(p, *reinterpret_cast<f32x16(*)[1][TN]>(&acc[1]), smem, wave, lane, wm * TM + 1, wn, m0, n0, Mlim);
-    if constexpr (TM == 4) {
-        conv_epilogue<float, 1, TN, 32, WTN>(p, *reinterpret_cast<f32x16(*)[1][TN]>(&acc[2]), smem, wave, lane, wm * TM + 2, wn, m0, n0, Mlim);
-        conv_epilogue<float, 1, TN, 32, WTN>(p, *reinterpret_cast<f32x16(*)[1][TN]>(&acc[3]), smem, wave, lane, wm * TM + 3, wn, m0, n0, Mlim);
-    }
 #endif
 }
 
@@ -572,17 +430,7 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
             ra1 = lds_read(a0 ^ 16u);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             asm volatile("" : "+v"(ra0), "+v"(ra1));
-            const float x[8] = {__uint_as_float(ra0.x), __uint_as_float(ra0.y), __uint_as_float(ra0.z), __uint_as_float(ra0.w),
-                                __uint_as_float(ra1.x), __uint_as_float(ra1.y), __uint_as_float(ra1.z), __uint_as_float(ra1.w)};
-            uint32_t h[4], l[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t0, t1;
-                split_hi(x[2 * e], x[2 * e + 1], h[e], t0, t1);
-                l[e] = split_lo(x[2 * e], x[2 * e + 1], t0, t1);
-            }
-            ah[0][i] = u32x4{h[0], h[1], h[2], h[3]};
-            al[0][i] = u32x4{l[0], l[1], l[2], l[3]};
+            split8_halves(ra0, ra1, ah[0][i], al[0][i]);
         }
 #pragma unroll
         for (int j = 0; j < TN - 1; ++j) {
@@ -620,124 +468,9 @@ __global__ __launch_bounds__(256, 1) void conv_x3_run3_kernel(const ConvArgs p, 
                     else b_emit(q);
                     asm volatile("" ::: "memory");
                 };
-                uint32_t sh[4], sl[4];
-                float st0 = 0.f, st1 = 0.f;
-                auto split_stage = [&](int s) {
-                    const int e = s >> 1;
-                    asm volatile("" : "+v"(ra0), "+v"(ra1));
-                    const float x0 = __uint_as_float(e == 0 ? ra0.x : e == 1 ? ra0.z : e == 2 ? ra1.x : ra1.z);
-                    const float x1 = __uint_as_float(e == 0 ? ra0.y : e == 1 ? ra0.w : e == 2 ? ra1.y : ra1.w);
-                    if ((s & 1) == 0) {
-                        split_hi(x0, x1, sh[e], st0, st1);
-                        asm volatile("" : "+v"(sh[e]), "+v"(st0), "+v"(st1));
-                    } else {
-                        asm volatile("" : "+v"(st0), "+v"(st1));
-                        sl[e] = split_lo(x0, x1, st0, st1);
-                        asm volatile("" : "+v"(sl[e]));
-                    }
-                };
-#pragma unroll
-                for (int g = 0; g < TN; ++g) {
-                    const int rb = g / NGR;
-                    const bool barw = (kc == 1 && rb == 0);
-                    const bool bar = barw && (g % NGR) == 0;
-                    const bool last = g == TN - 1;
-                    constexpr int R0 = 1, W0 = 4, RB = 4, WB = 7;
-#pragma unroll
-                    for (int m = 0; m < MG; ++m) {
-                        const int tt = m / TM, i = m % TM;
-                        if (tt == 0) TT_MFMA(acc[i][g], al[kc][i], bh[g]);
-                        else if (tt == 1) TT_MFMA(acc[i][g], ah[kc][i], bl[g]);
-                        else TT_MFMA(acc[i][g], ah[kc][i], bh[g]);
-                        const int ws = (g % NGR) * MG + m;
-                        if (m == 0) {
-                            if (g == 0) bh[TN - 1] = lds_read(sB_cur + fb_pre[kc][TN - 1]);
-                            else bh[g - 1] = lds_read(srcB + fb_pre[kn][g - 1]);
-                        }
-                        if (bar && m == 3) {
-                            // the next tile's operands have landed for this wave: its weights, and -- third tile of a run --
-                            // the next run (issued with the first two tiles).  Younger loads = this tile's share of the run
-                            if (t == 0) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                            else if (t == 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                        }
-                        if (ws == (barw ? RB : R0)) {
-                            // padding: a lane whose (row, tap) is outside the image reads the zero row
-                            const unsigned a0 = ((f_mask[rb] >> ntap) & 1u) ? srcA + fa_run[nkw][kn][rb] : zaddr;
-                            if constexpr (APAIR) {
-                                ah[kn][rb] = lds_read(a0);
-                                al[kn][rb] = lds_read(a0 ^ 32u);
-                            } else {
-                                ra0 = lds_read(a0);
-                                ra1 = lds_read(a0 ^ 16u);
-                            }
-                        }
-                        {
-                            // DMA slots: gaps 2 and 3 of a group (4 and 5 behind the barrier).  Weights: one piece per group;
-                            // run pieces: spread from group 0 on, two per group only where the count needs it (TN = 4)
-                            const int s0 = bar ? (MG >= 8 ? 5 : 4) : 2;
-                            if (kc == 1) {
-                                if (m == s0) dma(g);
-                            } else if (a_count > 0) {
-                                const int per = (a_count + TN - 1) / TN;                    // 1 (TN = 8) or 2 (TN = 4, five pieces)
-                                const int q0 = g * per;
-                                if (m == s0 && q0 < a_count) dma(q0);
-                                if (per == 2 && m == s0 + 1 && q0 + 1 < a_count) dma(q0 + 1);
-                            }
-                        }
-                        if (ws == (barw ? WB : W0)) {
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                            if constexpr (APAIR) asm volatile("" : "+v"(ah[kn][rb]), "+v"(al[kn][rb]));
-                            else asm volatile("" : "+v"(ra0), "+v"(ra1));
-                            if (g == 0) asm volatile("" : "+v"(bh[TN - 1]));
-                        }
-                        if (m == 2 * TM - 1) bl[g] = lds_read(srcB + (fb_pre[kn][g] ^ 32u));
-                        if constexpr (!APAIR) {
-                            const int first = barw ? WB : W0;
-                            const int avail = WIN - first;
-                            int lastslot;
-                            if (avail >= 16) {
-                                if (ws >= first && ((ws - first) & 1) == 0 && (ws - first) / 2 < 8) split_stage((ws - first) / 2);
-                                lastslot = first + 14;
-                            } else if (avail >= 8) {
-                                if (ws >= first && ws - first < 8) split_stage(ws - first);
-                                lastslot = first + 7;
-                            } else {
-                                if (ws >= first && ws - first < 4) {
-                                    split_stage(2 * (ws - first));
-                                    split_stage(2 * (ws - first) + 1);
-                                }
-                                lastslot = first + 3;
-                            }
-                            if (ws == lastslot) {
-                                ah[kn][rb] = u32x4{sh[0], sh[1], sh[2], sh[3]};
-                                al[kn][rb] = u32x4{sl[0], sl[1], sl[2], sl[3]};
-                                asm volatile("" : "+v"(ah[kn][rb]), "+v"(al[kn][rb]));
-                            }
-                        }
-                        // walkers: the run walker after the run's last piece went out (second tile), the weight walker every tile
-                        if (last && kc == 0 && t == 1 && m == MG - 2) run_walk();     // (a dozen SALU once per run: not pinned)
-                        if (last && kc == 1) {
-                            if (m == MG - 3) {
-                                asm volatile("" : "+s"(b_tap), "+s"(b_off));
-                                b_walk1();
-                                asm volatile("" : "+s"(b_tap), "+s"(b_off));
-                            }
-                            if (m == MG - 2) {
-                                asm volatile("" : "+s"(b_rem), "+s"(b_st));
-                                b_walk2();
-                                asm volatile("" : "+s"(b_rem), "+s"(b_st));
-                            }
-                            if (m == MG - 1) {
-                                asm volatile("" : "+s"(sB_cur), "+s"(sB_nxt));
-                                const unsigned tb = sB_cur;
-                                sB_cur = sB_nxt;
-                                sB_nxt = tb;
-                                asm volatile("" : "+s"(sB_cur), "+s"(sB_nxt));
-                            }
-                        }
-                    }
-                }
+#define TT_X3_RUN3 1
+#include "conv_x3_pipe_kstep.h"
+#undef TT_X3_RUN3
             }
         }
         const unsigned tr = sR_cur;
@@ -762,13 +495,15 @@ int launch_conv_x3_pipe(const ConvChoice& c, ConvArgs& a, hipStream_t st) {
     if (c.main_rows > 0 && c.main_rows < tiles_m) tiles_m = c.main_rows;
     const int tiles_n = a.Cout / bn;
     if (c.family == CONV_X3_RUN3) {
+        // the kernel's map: 2 run buffers (RUN_BYTES = 288 rows x 128 B) + 2 weight stages (B_BYTES = bn x 128 B) + the zero row at Z_OFF
         const size_t smem_r = (size_t)2 * 288 * 128 + (size_t)2 * bn * 128 + 256;
         auto kr = bn == 128 ? (c.apair ? conv_x3_run3_kernel<128, true> : conv_x3_run3_kernel<128>)
                             : (c.apair ? conv_x3_run3_kernel<256, true> : conv_x3_run3_kernel<256>);
         return launch_lds_dma(kr, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), smem_r, smem_r, "conv_x3_run3_kernel", a, st,
                               tiles_m, tiles_n, 1);
     }
-    // activation ring 3 x 32 KiB + weight ring 2 x (bn x 128 B); the epilogue stages 4 x 32 x (WTN + 4) floats
+    // the kernel's map: activation ring 3 x A_BYTES (32 KiB) + weight ring 2 x B_BYTES (bn x 128 B); the epilogue stages
+    // 4 x 32 x (WTN + 4) floats
     size_t smem = (size_t)(3 * 256 + 2 * bn) * 128;
     const size_t epi = (size_t)4 * 32 * ((bn == 128 ? 128 : 256) + 4) * 4;
     if (smem < epi) smem = epi;
