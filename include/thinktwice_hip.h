@@ -779,12 +779,13 @@ enum tt_png_status {
     TT_PNG_OK = 0,
     TT_PNG_TRUNCATED = 1,                /* the stream ends inside a header, a code, extra bits, stored bytes or the Adler-32 */
     TT_PNG_BAD_ZLIB_HEADER = 2,          /* CM != 8, window > 32 KiB, FCHECK, or a preset dictionary */
-    TT_PNG_BAD_BLOCK_TYPE = 3,           /* BTYPE 3 */
+    TT_PNG_BAD_BLOCK_TYPE = 3,           /* BTYPE 3; inside a segment (tt_png_decode_u8_segmented), a block with BFINAL set */
     TT_PNG_BAD_STORED_LEN = 4,           /* LEN != ~NLEN */
     TT_PNG_BAD_CODE_LENGTHS = 5,         /* over-subscribed or unacceptably incomplete code, a repeat with no previous length,
                                             a run past the last code, HLIT > 286, HDIST > 30, no end-of-block code */
     TT_PNG_BAD_SYMBOL = 6,               /* a bit pattern no code has; length symbol 286 / 287, distance symbol 30 / 31 */
-    TT_PNG_BAD_DISTANCE = 7,             /* a distance before the first output byte or beyond the stream's window */
+    TT_PNG_BAD_DISTANCE = 7,             /* a distance before the first output byte (of a segment: ITS first byte) or beyond the
+                                            stream's window */
     TT_PNG_OUTPUT_OVERRUN = 8,           /* more than H * (1 + W * C) bytes */
     TT_PNG_OUTPUT_SHORT = 9,             /* fewer */
     TT_PNG_BAD_FILTER = 10               /* a row's filter type above 4 */
@@ -879,6 +880,67 @@ int tt_png_decode_u8_verified(const uint8_t* packed_dev, long long packed_bytes,
                               const tt_png_image* images_dev, int num_images, const tt_png_chunk* chunks_host,
                               const tt_png_chunk* chunks_dev, int num_chunks, int verify_flags, void* workspace,
                               long long workspace_bytes, uint8_t* out_base, long long out_bytes, int32_t* status_dev, void* stream);
+
+/* ------------------------------------------------------------------------
+ * tt_png_decode_u8_verified for files whose zlib stream has restart points, every SEGMENT of a stream inflated by a wave of
+ * its own.  A stream written with a full flush (Z_FULL_FLUSH) after every R rows is one valid zlib stream; at each flush point
+ * it is byte-aligned, the block before it is an empty stored block (00 00 FF FF) and no later match reaches back across it.
+ * thinktwice_amd/png.py::segment_png writes such files and records the cut points in a private ancillary chunk (`ttSG`);
+ * read_segments reads them back.  This entry takes them as a table:
+ *   segment  bytes [offset, offset + bytes) of packed_dev, inside its image's stream and past its two header bytes: whole
+ *            non-final deflate blocks, the last of them an empty stored block, that inflate to the image's scanlines
+ *            [first_row, first_row + rows).  An image's segments stand together in the table, in row order, tile [0, H) and
+ *            follow each other in the stream without a gap; the images of the table are in increasing order.
+ *   tail     what follows an image's last segment, to the end of its stream: one final block without output (03 00, or
+ *            01 00 00 FF FF), then the four Adler-32 bytes, which are the trailer TT_PNGV_ADLER32 compares.
+ * An image WITHOUT an entry in the table is decoded by one wave over its whole stream, as by tt_png_decode_u8_verified, in the
+ * same launch; num_segments = 0 (the segment tables may then be null) gives that entry's bytes and statuses.  The window of a segmented image is read from its
+ * stream's CMF byte on the device and the header is checked as for a whole stream (TT_PNG_BAD_ZLIB_HEADER).
+ * Launches: (the tile plan,) the inflate: one 64-lane workgroup per segment and one per image (its tail, or its whole
+ * stream); the statuses' fold, one lane per image; then as tt_png_decode_u8_verified: checksum tiles, fold + compare, the
+ * unfilter, all unchanged: they read the same workspace layout.  No workgroup waits for another.
+ * A segment's scanlines start at first_row * (1 + W * C) of the image's slot, in general not 16-byte aligned; a wave stores
+ * 16 bytes at a time only where the whole aligned group is its segment's, bytes at the two ends.
+ * Status of an image, first match: the error of its LOWEST-NUMBERED failing segment (whatever the order the waves ran in);
+ * its tail's error; then as tt_png_decode_u8_verified.  Inside a segment a block with BFINAL set is TT_PNG_BAD_BLOCK_TYPE, a
+ * match that reaches before the segment's first byte TT_PNG_BAD_DISTANCE (so a stream cut at a sync flush, or an index that
+ * does not fit its stream, ends in a status: no wave reads what another writes), rows that come out long or short
+ * TT_PNG_OUTPUT_OVERRUN / TT_PNG_OUTPUT_SHORT, input that ends before the closing stored block TT_PNG_TRUNCATED.  A failed
+ * image leaves its destination untouched and does not affect the others.
+ * workspace: tt_png_segmented_workspace_bytes(...) bytes, 256-byte aligned; it begins with tt_png_decode_u8_verified's.
+ * Returns an error before any launch for everything tt_png_decode_u8_verified refuses, and for: num_segments < 0 or
+ * > TT_PNG_MAX_SEGMENTS; a null or misaligned segment table with num_segments > 0; an image index out of range or below the
+ * previous entry's; an image's segments out of row order, with rows < 1, or not tiling [0, H); a segment that is empty,
+ * does not start at its image's stream_offset + 2 or at the previous segment's end, or leaves fewer than 6 bytes of the
+ * stream for the tail; a segmented image with more than 2^31 - 17 scanline bytes.
+ * ---------------------------------------------------------------------- */
+#define TT_PNG_MAX_SEGMENTS 1048576
+typedef struct tt_png_segment {
+    long long offset;                    /* of the segment's first byte in packed_dev */
+    long long bytes;                     /* >= 1; a well-formed one has at least 5 and ends in 00 00 FF FF */
+    int image;                           /* index into the image table */
+    int first_row;
+    int rows;                            /* >= 1 */
+    int reserved;                        /* not read */
+} tt_png_segment;                        /* 32 bytes */
+/* Host arithmetic only; 0 where the entry would refuse the tables. */
+long long tt_png_segmented_workspace_bytes(const tt_png_image* images_host, int num_images, const tt_png_chunk* chunks_host,
+                                           int num_chunks, int verify_flags, const tt_png_segment* segments_host,
+                                           int num_segments);
+int tt_png_decode_u8_segmented(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
+                               const tt_png_image* images_dev, int num_images, const tt_png_chunk* chunks_host,
+                               const tt_png_chunk* chunks_dev, int num_chunks, int verify_flags,
+                               const tt_png_segment* segments_host, const tt_png_segment* segments_dev, int num_segments,
+                               void* workspace, long long workspace_bytes, uint8_t* out_base, long long out_bytes,
+                               int32_t* status_dev, void* stream);
+/* Measurement only (thinktwice_amd/bench_png.py): the same call up to and including the inflate launch and the statuses' fold
+ * (phases = 1), or all of it (2). */
+int tt_png_decode_u8_segmented_phases(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
+                                      const tt_png_image* images_dev, int num_images, const tt_png_chunk* chunks_host,
+                                      const tt_png_chunk* chunks_dev, int num_chunks, int verify_flags,
+                                      const tt_png_segment* segments_host, const tt_png_segment* segments_dev, int num_segments,
+                                      void* workspace, long long workspace_bytes, uint8_t* out_base, long long out_bytes,
+                                      int32_t* status_dev, int phases, void* stream);
 
 /* ------------------------------------------------------------------------
  * SURVEY 8f-4 (training step), optimizer half: the reference's `optimizer_config = dict(grad_clip=dict(max_norm=100,

@@ -18,7 +18,16 @@ commit on the same machine, which the whole call is set against.
 CRC-32 of every IDAT chunk, on the device): the whole decode_sample_batch call with verification off, off again (A/A), with
 ("adler32",) and with ("adler32", "crc32"), and the inflate launch alone, alternating in one process; then the checksum
 kernels on their own (png.device_adler32 / device_crc32 over the same number of bytes).  The cost of verification is the
-verify-on median minus the verify-off median, to be read against the A/A spread.  Without the switch the output is as before."""
+verify-on median minus the verify-off median, to be read against the A/A spread.  Without the switch the output is as before.
+
+    python -m thinktwice_amd.bench_png --segment-rows 8,16,32,64 [--batch 8] [--repeats 5] [--train-step-ms 735]
+                                       [--out profiles/train_png_segmented.txt]
+
+--segment-rows measures instead the segmented decode (png.segment_png, tt_png_decode_u8_segmented: one wave per segment) for
+every R of the list: the batch is segmented on the host first (16 processes, not counted: it is done once per dataset), the
+file-size ratio is reported per image kind, and then, alternating in one process, the whole decode_sample_batch call on the
+unsegmented files twice (A/A; that path is the parent's) and on the files of every R, twice each, and the inflate launch
+alone for each (tt_png_decode_u8_phases, tt_png_decode_u8_segmented_phases)."""
 import argparse
 import io
 import multiprocessing
@@ -239,6 +248,111 @@ def main_verify(B, repeats, emit):
          f"adler32 + crc32 - off {med['adler32 + crc32'] - med['off']:+.2f} ms; inflate launch {med['inflate']:.2f} ms")
 
 
+def _segment_one(job):
+    from . import png
+    i, rows = job
+    return png.segment_png(_FILES[i], rows)
+
+
+def _nest_like(nest, flat):
+    """`flat` (an iterator) poured into the shape of the nested lists `nest`."""
+    return [_nest_like(x, flat) if isinstance(x, list) else next(flat) for x in nest]
+
+
+def main_segments(B, repeats, rows_list, train_step_ms, emit):
+    write, writer = _writer()
+    t0 = time.perf_counter()
+    (rgb_f, ramp_f, _, seg_f), (rgb_a, ramp_a, _, seg_a) = make_batch(B, write)
+    kinds = (("camera frames", rgb_f), ("depth ramps", ramp_f), ("tags", seg_f))
+    flat = [f for s in rgb_f for t in s for f in t] + [f for s in ramp_f for f in s] + [f for s in seg_f for f in s]
+    n_rgb, n_dep = B * T * N, B * N
+    decoded = B * (T + 1) * N * H * W * 3 + B * N * H * W
+    emit(f"B = {B}: {len(flat)} files of {H} x {W} ({n_rgb} camera frames, {n_dep} depth maps, {n_dep} segmentation maps) written by "
+         f"{writer}; made in {time.perf_counter() - t0:.0f} s; {sum(map(len, flat))} file bytes, {decoded} decoded bytes")
+    _FILES[:] = flat
+    nests = {}
+    with multiprocessing.get_context("fork").Pool(16) as pool:       # before this process touches the device
+        for rows in rows_list:
+            t0 = time.perf_counter()
+            out = pool.map(_segment_one, [(i, rows) for i in range(len(flat))], chunksize=1)
+            took = time.perf_counter() - t0
+            it = iter(out)
+            nests[rows] = tuple(_nest_like(nest, it) for _, nest in kinds)
+            sizes = [sum(len(f) for f in out[a:b]) for a, b in ((0, n_rgb), (n_rgb, n_rgb + n_dep), (n_rgb + n_dep, len(out)))]
+            before = [sum(len(f) for f in flat[a:b]) for a, b in ((0, n_rgb), (n_rgb, n_rgb + n_dep), (n_rgb + n_dep, len(out)))]
+            emit(f"  R = {rows:3d}: segmented at zlib level 6 by 16 host processes in {took:.1f} s (not counted below); "
+                 f"{-(-H // rows)} segments per image, {len(flat) * -(-H // rows)} per batch; file bytes / unsegmented: "
+                 + ", ".join(f"{k} {a / b:.3f}" for (k, _), a, b in zip(kinds, sizes, before)) + f", all {sum(sizes) / sum(before):.3f}")
+
+    import torch
+    from . import png
+    from .ops import check, cur_stream, lib, ptr
+    emit(f"build {build.source_fingerprint()} device {torch.cuda.get_device_name(0)}")
+    want = [torch.from_numpy(np.array(a)) for a in (rgb_a, ramp_a, seg_a)]
+    plain = png.PngDecoder()
+    fns = {"plain": lambda: plain.decode_sample_batch(rgb_f, ramp_f, seg_f), "plain'": lambda: plain.decode_sample_batch(rgb_f, ramp_f, seg_f)}
+    labels = {"plain": "unsegmented files: decode_sample_batch (parse, pack, copy, 2 launches, status read-back)",
+              "plain'": "the same again (A/A)"}
+    keep = []                                                          # the buffers of the launch-only variants
+
+    def launch_only(files, label):
+        dec = png.PngDecoder()
+        infos = dec._parse(files)
+        offsets, pos = [], 0
+        for i in infos:
+            offsets.append(pos)
+            pos += i.width * i.height * i.channels
+        out = torch.empty(pos, dtype=torch.uint8, device="cuda")
+        table, total = dec._pack(infos, offsets)
+        packed = dec._stage[:total].clone().cuda()
+        segs, segs_at = dec._segs or (None, 0)
+        need = int(lib().tt_png_segmented_workspace_bytes(table, len(infos), None, 0, 0, segs, len(segs) if segs else 0))
+        work = torch.empty(need, dtype=torch.uint8, device="cuda")
+        status = torch.zeros(len(infos), dtype=torch.int32, device="cuda")
+        stream = cur_stream(out.device)
+        keep.append((dec, table, segs, packed, work, out, status))
+
+        def run():
+            if segs:
+                check(lib().tt_png_decode_u8_segmented_phases(ptr(packed), total, table, ptr(packed), len(infos), None, None, 0, 0, segs,
+                                                              ptr(packed) + segs_at, len(segs), ptr(work), need, ptr(out), pos, ptr(status),
+                                                              1, stream), "tt_png_decode_u8_segmented_phases")
+            else:
+                check(lib().tt_png_decode_u8_phases(ptr(packed), total, table, ptr(packed), len(infos), ptr(work), need, ptr(out), pos,
+                                                    ptr(status), 1, stream), "tt_png_decode_u8_phases")
+        fns[label] = run
+
+    launch_only(flat, "plain inflate")
+    labels["plain inflate"] = f"unsegmented files: inflate launch alone ({len(flat)} workgroups)"
+    for rows in rows_list:
+        r, d, s = nests[rows]
+        dec = png.PngDecoder(segments="require")
+        raw, depth, seg = dec.decode_sample_batch(r, d, s)
+        bad = sum(int((got.cpu() != w).sum()) for got, w in zip((raw, depth, seg), want))
+        emit(f"  [R = {rows}] every status TT_PNG_OK; device against the source arrays: {bad} of {decoded} bytes differ")
+        del raw, depth, seg
+        fns[f"R{rows}"] = lambda dec=dec, r=r, d=d, s=s: dec.decode_sample_batch(r, d, s)
+        labels[f"R{rows}"] = f"R = {rows}: decode_sample_batch (parse, pack, copy, 4 launches, status read-back)"
+        fns[f"R{rows}'"] = fns[f"R{rows}"]
+        labels[f"R{rows}'"] = f"R = {rows}: the same again (A/A)"
+        seg_flat = [f for x in r for t in x for f in t] + [f for x in d for f in x] + [f for x in s for f in x]
+        launch_only(seg_flat, f"R{rows} inflate")
+        labels[f"R{rows} inflate"] = (f"R = {rows}: inflate launch and the statuses' fold alone "
+                                      f"({len(flat) * -(-H // rows)} + {len(flat)} workgroups)")
+    ms = _events(fns, repeats)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    emit(f"  device events around each call, {repeats} rounds after 1 warm-up round, the variants alternating in one process")
+    for k, label in labels.items():
+        emit(f"    {label:100s} median {med[k]:9.2f} ms (min {min(ms[k]):.2f}, max {max(ms[k]):.2f})")
+    spreads = [("unsegmented", med["plain'"] - med["plain"])] + [(f"R = {r}", med[f"R{r}'"] - med[f"R{r}"]) for r in rows_list]
+    emit("    A/A spread: " + ", ".join(f"{k} {v:+.2f} ms" for k, v in spreads))
+    for rows in rows_list:
+        emit(f"    R = {rows:3d}: whole call {med[f'R{rows}']:8.2f} ms = {med[f'R{rows}'] / train_step_ms * 100:5.1f} % of a {train_step_ms:.0f} ms "
+             f"train_step at B = {B}, {med['plain'] / med[f'R{rows}']:.1f} x the unsegmented call; inflate launch "
+             f"{med[f'R{rows} inflate']:8.2f} ms, {med['plain inflate'] / med[f'R{rows} inflate']:.1f} x, "
+             f"{decoded / med[f'R{rows} inflate'] / 1e6:.2f} GB/s of scanlines")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -246,6 +360,7 @@ if __name__ == "__main__":
     ap.add_argument("--train-step-ms", type=float, default=750.0)
     ap.add_argument("--out", default=None, help="also write the report to this file")
     ap.add_argument("--verify", action="store_true", help="measure what PngDecoder(verify=...) adds instead")
+    ap.add_argument("--segment-rows", default=None, help="R[,R...]: measure the segmented decode at these rows per segment instead")
     a = ap.parse_args()
     lines = []
 
@@ -253,7 +368,9 @@ if __name__ == "__main__":
         print(s, flush=True)
         lines.append(s)
 
-    if a.verify:
+    if a.segment_rows:
+        main_segments(a.batch, a.repeats, [int(r) for r in a.segment_rows.split(",")], a.train_step_ms, emit)
+    elif a.verify:
         main_verify(a.batch, a.repeats, emit)
     else:
         main(a.batch, a.repeats, a.train_step_ms, emit)

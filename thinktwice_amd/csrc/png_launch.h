@@ -35,4 +35,25 @@ int png_check_args(const uint8_t* packed_dev, long long packed_bytes, const tt_p
 void png_launch_unverified(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_dev, int num_images,
                            uint8_t* workspace, uint8_t* out_base, int32_t* status_dev, bool inflate, hipStream_t st);
 
+// The segment table of tt_png_decode_u8_segmented, host and device copy, after png_segments.hip has checked it.
+struct PngSegments {
+    const tt_png_segment* host;
+    const tt_png_segment* dev;
+    int count;
+};
+// tt_png_verify_workspace_bytes plus one int32 per segment, which starts at *segment_status_at; 0 for refused tables
+// (png_verify.hip)
+long long png_verified_workspace_bytes(const tt_png_image* images_host, int num_images, const tt_png_chunk* chunks_host, int num_chunks,
+                                       int verify_flags, int num_segments, long long* segment_status_at);
+// tt_png_decode_u8_verified; with `seg` its inflate launch is png_launch_segmented_inflate (png_verify.hip)
+int png_decode_verified(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host, const tt_png_image* images_dev,
+                        int num_images, const tt_png_chunk* chunks_host, const tt_png_chunk* chunks_dev, int num_chunks, int verify_flags,
+                        const PngSegments* seg, void* workspace, long long workspace_bytes, uint8_t* out_base, long long out_bytes,
+                        int32_t* status_dev, int phases, void* stream);
+// one workgroup per segment and one per image (its tail or its whole stream), then the statuses' fold; trailer may be null
+// (png_segments.hip)
+void png_launch_segmented_inflate(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_dev, int num_images,
+                                  const PngSegments& seg, uint8_t* workspace, int32_t* segment_status, int32_t* status_dev,
+                                  uint32_t* trailer, hipStream_t st);
+
 }  // namespace tt

@@ -134,17 +134,27 @@ static int png_verify_layout(const tt_png_image* images_host, int num_images, co
 
 using namespace tt;
 
-extern "C" long long tt_png_verify_workspace_bytes(const tt_png_image* images_host, int num_images, const tt_png_chunk* chunks_host,
-                                                   int num_chunks, int verify_flags) {
+// what both entries ask of the workspace: the verified layout, then one int32 per segment (png_segments.hip)
+long long tt::png_verified_workspace_bytes(const tt_png_image* images_host, int num_images, const tt_png_chunk* chunks_host,
+                                           int num_chunks, int verify_flags, int num_segments, long long* segment_status_at) {
     PngVerifyLayout L;
-    return png_verify_layout(images_host, num_images, chunks_host, num_chunks, verify_flags, L) ? 0 : L.total;
+    if (png_verify_layout(images_host, num_images, chunks_host, num_chunks, verify_flags, L)) return 0;
+    if (segment_status_at) *segment_status_at = L.total;
+    return L.total + (4LL * num_segments + kPngSlotAlign - 1) / kPngSlotAlign * kPngSlotAlign;
 }
 
-extern "C" int tt_png_decode_u8_verified(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
-                                         const tt_png_image* images_dev, int num_images, const tt_png_chunk* chunks_host,
-                                         const tt_png_chunk* chunks_dev, int num_chunks, int verify_flags, void* workspace,
-                                         long long workspace_bytes, uint8_t* out_base, long long out_bytes, int32_t* status_dev,
-                                         void* stream) {
+extern "C" long long tt_png_verify_workspace_bytes(const tt_png_image* images_host, int num_images, const tt_png_chunk* chunks_host,
+                                                   int num_chunks, int verify_flags) {
+    return png_verified_workspace_bytes(images_host, num_images, chunks_host, num_chunks, verify_flags, 0, nullptr);
+}
+
+// tt_png_decode_u8_verified, and with `seg` tt_png_decode_u8_segmented (png_segments.hip, which has checked the table): the
+// inflate launch is then the segmented one, everything after it is the same.  phases 1: stop after the inflate.
+int tt::png_decode_verified(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
+                            const tt_png_image* images_dev, int num_images, const tt_png_chunk* chunks_host,
+                            const tt_png_chunk* chunks_dev, int num_chunks, int verify_flags, const PngSegments* seg, void* workspace,
+                            long long workspace_bytes, uint8_t* out_base, long long out_bytes, int32_t* status_dev, int phases,
+                            void* stream) {
     if (png_check_args(packed_dev, packed_bytes, images_host, images_dev, num_images, workspace, out_base, out_bytes, status_dev))
         return -1;
     PngVerifyLayout L;
@@ -155,10 +165,12 @@ extern "C" int tt_png_decode_u8_verified(const uint8_t* packed_dev, long long pa
     for (int j = 0; crc && j < num_chunks; ++j)                  // (inside its image's stream, which is inside packed_bytes)
         TT_REQUIRE(chunks_host[j].offset >= 0 && chunks_host[j].offset <= packed_bytes - chunks_host[j].bytes,
                    "tt_png_decode_u8_verified: chunk %d outside the %lld packed bytes", j, packed_bytes);
-    TT_REQUIRE(workspace_bytes >= L.total, "tt_png_decode_u8: need %lld bytes of workspace, got %lld", L.total, workspace_bytes);
+    const long long total = L.total + (seg ? (4LL * seg->count + kPngSlotAlign - 1) / kPngSlotAlign * kPngSlotAlign : 0);
+    TT_REQUIRE(workspace_bytes >= total, "tt_png_decode_u8: need %lld bytes of workspace, got %lld", total, workspace_bytes);
 
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = (uint8_t*)workspace;
+    int32_t* segment_status = (int32_t*)(ws + L.total);
     if (verify_flags != 0) {
         uint32_t* trailer = (uint32_t*)(ws + L.trailer);
         int* first_tile = (int*)(ws + L.first_tile);
@@ -168,13 +180,29 @@ extern "C" int tt_png_decode_u8_verified(const uint8_t* packed_dev, long long pa
         static const uint32_t crc_start = png_crc_of_idat();
         hipLaunchKernelGGL(checksum_plan_kernel<PngRanges>, dim3(1), dim3(tt_cksum::kLanes), 0, st, src, L.num_ranges, first_tile, tiles,
                            L.tiles);
-        hipLaunchKernelGGL(png_inflate_trailer_kernel, dim3((unsigned)num_images), dim3(kWave), 0, st, packed_dev, packed_bytes,
-                           images_dev, ws, status_dev, trailer);
+        if (seg)
+            png_launch_segmented_inflate(packed_dev, packed_bytes, images_dev, num_images, *seg, ws, segment_status, status_dev, trailer, st);
+        else
+            hipLaunchKernelGGL(png_inflate_trailer_kernel, dim3((unsigned)num_images), dim3(kWave), 0, st, packed_dev, packed_bytes,
+                               images_dev, ws, status_dev, trailer);
+        if (phases < 2) return check_launch("tt_png_decode_u8");
         checksum_launch_tiles(ws, L.scanlines, packed_dev, packed_bytes, L.num_adler, tiles, L.tiles, parts, st);
         hipLaunchKernelGGL(png_verify_fold_kernel, dim3((unsigned)div_up(L.num_ranges, tt_cksum::kLanes)), dim3(tt_cksum::kLanes), 0, st,
                            src, L.num_ranges, num_images, first_tile, parts, L.tiles, trailer, crc_start, status_dev,
                            checksum_pow_table());
+    } else if (seg) {
+        png_launch_segmented_inflate(packed_dev, packed_bytes, images_dev, num_images, *seg, ws, segment_status, status_dev, nullptr, st);
+        if (phases < 2) return check_launch("tt_png_decode_u8");
     }
-    png_launch_unverified(packed_dev, packed_bytes, images_dev, num_images, ws, out_base, status_dev, verify_flags == 0, st);
+    png_launch_unverified(packed_dev, packed_bytes, images_dev, num_images, ws, out_base, status_dev, verify_flags == 0 && !seg, st);
     return check_launch("tt_png_decode_u8");
+}
+
+extern "C" int tt_png_decode_u8_verified(const uint8_t* packed_dev, long long packed_bytes, const tt_png_image* images_host,
+                                         const tt_png_image* images_dev, int num_images, const tt_png_chunk* chunks_host,
+                                         const tt_png_chunk* chunks_dev, int num_chunks, int verify_flags, void* workspace,
+                                         long long workspace_bytes, uint8_t* out_base, long long out_bytes, int32_t* status_dev,
+                                         void* stream) {
+    return png_decode_verified(packed_dev, packed_bytes, images_host, images_dev, num_images, chunks_host, chunks_dev, num_chunks,
+                               verify_flags, nullptr, workspace, workspace_bytes, out_base, out_bytes, status_dev, 2, stream);
 }
