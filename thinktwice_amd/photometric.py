@@ -335,12 +335,16 @@ def scratch_bytes(num_images, H, W):
     return num_images * H * W * 4
 
 
-def device_programs(programs, num_images, H, W, device):
+def device_programs(programs, num_images, H, W, device, pinned=False):
     """(host tensor, device tensor, scratch tensor or None, scratch bytes) of a call over `num_images` images: the scratch
-    comes from torch's caching allocator, and only when a program has a blur."""
+    comes from torch's caching allocator, and only when a program has a blur.  pinned: the host copy is page-locked and goes
+    up without the host waiting for the stream (loader.py queues it behind a decode it must not wait for); the default, a
+    pageable copy, synchronises the current stream."""
     import torch
     host = pack_programs(programs)
-    dev = host.to(device)
+    if pinned:
+        host = host.pin_memory()
+    dev = host.to(device, non_blocking=pinned)
     scratch, nbytes = None, 0
     if any(p.blur_index >= 0 for p in programs):
         nbytes = scratch_bytes(num_images, H, W)

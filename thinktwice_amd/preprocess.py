@@ -132,14 +132,17 @@ class TrainImagePipeline(ImagePreprocessor):
         flat = [p for per_cam in params for p in per_cam]
         return (IdaSet * len(flat))(*[IdaSet(p.resized_h, p.resized_w, p.crop_y, p.crop_x, int(bool(p.flip))) for p in flat])
 
-    def __call__(self, raw, depth=None, seg=None, params=None, sampler=None, channel_last_dtype=None, c_pad=None, augment=None):
+    def __call__(self, raw, depth=None, seg=None, params=None, sampler=None, channel_last_dtype=None, c_pad=None, augment=None,
+                 pinned_programs=False):
         """raw uint8 [B, T, N, H, W, 3] on the device; depth / seg f32 [B, N, H, W] (key sweep) or None.  `params`
         ([B][N] IdaParams) override `sampler` (an IdaSampler).  Returns dict(img [B, T, N, 3, fh, fw] f32 -- or, with
         `channel_last_dtype`, the channel-last padded [B*T*N, fh, fw, c_pad] tensor the LSS trunk consumes --, depth / seg
         [B, N, fh, fw] where given, ida_mats [B, T, N, 4, 4] f32 on the host, params).
         `augment` (a photometric.PhotometricSampler, or a list of B compiled photometric.Program) adds
         ImageTransformMulti(aug=True): the frames are truncated to uint8 grey levels and every frame of sample b goes through
-        program b before the normalisation; the labels and ida_mats are untouched, and the result gains `programs`."""
+        program b before the normalisation; the labels and ida_mats are untouched, and the result gains `programs`.
+        `pinned_programs`: upload the programs from page-locked memory without waiting for the stream (see
+        photometric.device_programs); the result is the same."""
         if raw.dim() != 6 or raw.dtype != torch.uint8 or raw.shape[-1] != 3 or not raw.is_contiguous():
             raise ValueError("raw must be a contiguous uint8 [B, T, N, H, W, 3] tensor")
         B, T, N, H, W, _ = raw.shape
@@ -172,7 +175,7 @@ class TrainImagePipeline(ImagePreprocessor):
             check(lib().tt_preprocess_images_ida(ptr(raw), B, T, N, H, W, ptr(self.mapx), ptr(self.mapy), table, fh, fw, self.mean,
                                                  self.std, ptr(nhwc), cp, code, ptr(nchw), stream), "tt_preprocess_images_ida")
         else:
-            host, dev, scratch, nbytes = photometric.device_programs(programs, B * T * N, fh, fw, raw.device)
+            host, dev, scratch, nbytes = photometric.device_programs(programs, B * T * N, fh, fw, raw.device, pinned_programs)
             check(lib().tt_preprocess_images_ida_aug(ptr(raw), B, T, N, H, W, ptr(self.mapx), ptr(self.mapy), table, fh, fw,
                                                      self.mean, self.std, ptr(nhwc), cp, code, ptr(nchw), host.data_ptr(), ptr(dev),
                                                      ptr(scratch), nbytes, stream), "tt_preprocess_images_ida_aug")
