@@ -965,6 +965,37 @@ int tt_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* ex
 int tt_adamw_advance(int* good_steps_dev, const float* grad_scale_or_null, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Device log windows (thinktwice_amd/logvars.py): the logged values of a training job stay on the device from the loss terms to
+ * the closed window, so the loop around Trainer.step never waits for them.
+ *
+ * tt_logvars_pack restates EncoderDecoder._parse_losses (encoder_decoder_framework.py:409-439) for one-element f32 terms, one
+ * launch: packed[s] for every slot s (log name, dict order), packed[n_slots] = the total loss.  A slot is the sequential f32 sum
+ * of its terms, in table order, starting from +0.0f: a plain entry has one term (`value.mean()` of one element is torch's
+ * reduction from +0.0f, so -0.0 comes out as +0.0), a list entry several (`sum(v.mean() for v in value)`: Python's sum starts at
+ * int 0).  The total is the sequential f32 sum, from +0.0f, in slot order, of the slots with in_loss[s] != 0 (the names containing
+ * 'loss').  One thread does every sum, so the results are the bits of the torch expression, zeros' signs and NaN included.  The
+ * table travels BY VALUE as the kernel argument: `terms` is a HOST pointer read during the call, nothing is uploaded.
+ * ---------------------------------------------------------------------- */
+#define TT_LOGVARS_MAX_TERMS 64
+typedef struct tt_logvars_terms {
+    const float* term[TT_LOGVARS_MAX_TERMS];         /* device f32 scalars, table order = dict order, list entries in list order */
+    unsigned char slot[TT_LOGVARS_MAX_TERMS];        /* slot of term i, non-decreasing, every slot 0..n_slots-1 has >= 1 term */
+    unsigned char in_loss[TT_LOGVARS_MAX_TERMS];     /* per slot */
+} tt_logvars_terms;                                  /* 640 bytes */
+/* 1 <= n_slots <= n_terms <= TT_LOGVARS_MAX_TERMS; packed: n_slots + 1 device floats */
+int tt_logvars_pack(const tt_logvars_terms* terms, int n_terms, int n_slots, float* packed, void* stream);
+/* One iteration into a window (eval_tool.py:96-109 `results[k] += v * batch_size`; mmcv LogBuffer.update).  `window`: n + n_tail
+ * + 3 device doubles: the sums of packed[0..n) then tail[0..n_tail), then [total weight, iterations, skipped].  gate non-null and
+ * gate[0] not finite: skipped += 1 and nothing else.  Otherwise sum[i] += (double)v[i] * weight, total weight += weight,
+ * iterations += 1.  `tail` (nullable with n_tail == 0): a second f32 source vector.  0 < weight < 2^29; n >= 1; n + n_tail <= 1024.
+ * Calls on one stream add in call order, in f64. */
+int tt_logvars_accumulate(const float* packed, int n, const float* tail, int n_tail, int weight, const float* gate,
+                          double* window, void* stream);
+/* out[0..n_all) = window[0..n_all), then window[0..n_all) = 0, one launch (mmcv LogBuffer.average + clear_output: the division by
+ * the total weight is the reader's).  `out` is DEVICE memory that does not overlap `window`; 1 <= n_all <= 1027. */
+int tt_logvars_flush(double* window, int n_all, double* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * SURVEY 8f-4, the torch-autograd route of the training step (thinktwice_amd/autograd_route.py): what mmcv's OptimizerHook gets
  * from `outputs['loss'].backward()` depositing into every parameter's `.grad` (apis/mmdet_train.py:70-97) -- here the reverse
  * sweep leaves one separately allocated f32 tensor per parameter, and ONE launch gathers `nseg` of them into one flat f32 buffer
@@ -1123,7 +1154,7 @@ int tt_ew_bwd(int op, int act, long long R, int C, const float* a, int a_stride,
               int b_coff, const float* g, int g_stride, int g_coff, const float* out, int o_stride, int o_coff,
               const float* dout, int d_stride, int d_coff, float* da, int da_stride, int da_coff, float* db, int db_stride,
               int db_coff, float* dg, int dg_stride, int dg_coff, void* stream);
-/* Backward of the look module's kernels (f32; scatters with atomics).  The waypoint / control inputs of a refinement layer
+/* Backward of the look module's kernels (f32; the scatters add in a fixed order without atomics: bit-reproducible).  The waypoint / control inputs of a refinement layer
  * are detached in the reference (thinktwice_decoder.py:429-430), so there is no gradient for them or the reference points.
  * tt_look_gather_query_bwd: dout = gradient of the query rows; adds into the embeddings, the per-sample vectors and the four
  * FPN-side maps.  tt_msda_sample_bwd: adds into the value tensor's channel window, the offsets [R][512] and the attention
@@ -1152,7 +1183,7 @@ int tt_lift_splat_bwd(int batch_size, int num_cams, int D, int fH, int fW, int C
                       int num_voxel_z, const float* depth_logits, const float* context, const int32_t* geom_xyz,
                       const float* grad_out, int out_cstride, int out_coff, float* grad_depth_logits, float* grad_context,
                       void* stream);
-/* backward of tt_deform_im2col3x3: gx += (f32 atomics), goffsets[pix][2 tap (+1)] += the sampling-position gradients */
+/* backward of tt_deform_im2col3x3: gx += (no atomics: each channel's addends in (pixel, tap) order, bit-reproducible), goffsets[pix][2 tap (+1)] += the sampling-position gradients */
 int tt_deform_im2col3x3_bwd(const float* x, const float* offsets, const float* gcols, float* gx, float* goffsets, int N,
                             int H, int W, int C, int off_cstride, int pad, void* stream);
 

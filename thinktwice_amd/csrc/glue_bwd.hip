@@ -225,11 +225,11 @@ __global__ __launch_bounds__(256) void spatial_mean_bwd_kernel(const float* __re
 
 // Deformable im2col (mmcv DCN v1, 3x3, deform_groups = 1) backward.  Forward (csrc/dcn.hip): cols[pix][tap][c] = bilinear
 // sample of x[n] at (y + tap/3 - pad + off[2 tap], x + tap%3 - pad + off[2 tap + 1]), zero outside.  From gcols:
-//   gx   += corner weight * gcols  (scattered with f32 atomics: a sample point can land anywhere)
+//   gx   += corner weight * gcols  (a sample point can land anywhere: deform_im2col_bwd_gx_kernel below adds them in a fixed order)
 //   goff[pix][2 tap] = sum_c gcols * d(sample)/d(py),  goff[pix][2 tap + 1] = ... d(px)
-// One wave per (pixel, tap): lanes stride the channels, the two offset gradients are wave reductions.
+// This kernel: goff.  One wave per (pixel, tap): lanes stride the channels, the two offset gradients are wave reductions.
 __global__ __launch_bounds__(256) void deform_im2col_bwd_kernel(const float* __restrict__ x, const float* __restrict__ off,
-                                                                const float* __restrict__ gcols, float* __restrict__ gx,
+                                                                const float* __restrict__ gcols,
                                                                 float* __restrict__ goff, int N, int H, int W, int C,
                                                                 int off_cstride, int pad) {
     const int lane = threadIdx.x & 63;
@@ -257,10 +257,6 @@ __global__ __launch_bounds__(256) void deform_im2col_bwd_kernel(const float* __r
                 const float a11 = v11 ? x[(b + (long long)(y0 + 1) * W + x0 + 1) * C + c] : 0.f;
                 gy_ += gv * (hx * (a10 - a00) + lx * (a11 - a01));
                 gx_ += gv * (hy * (a01 - a00) + ly * (a11 - a10));
-                if (v00) unsafeAtomicAdd(gx + (b + (long long)y0 * W + x0) * C + c, gv * hy * hx);
-                if (v01) unsafeAtomicAdd(gx + (b + (long long)y0 * W + x0 + 1) * C + c, gv * hy * lx);
-                if (v10) unsafeAtomicAdd(gx + (b + (long long)(y0 + 1) * W + x0) * C + c, gv * ly * hx);
-                if (v11) unsafeAtomicAdd(gx + (b + (long long)(y0 + 1) * W + x0 + 1) * C + c, gv * ly * lx);
             }
         }
 #pragma unroll
@@ -273,6 +269,35 @@ __global__ __launch_bounds__(256) void deform_im2col_bwd_kernel(const float* __r
             goff[pix * off_cstride + 2 * tap + 1] += gx_;
         }
     }
+}
+
+// gx of the deformable im2col: no atomics, a fixed order.  One workgroup per (image, block of 256 channels), thread = channel: it is
+// the only writer of its channel of the image's gx and walks the image's (pixel, tap) pairs in index order, so two runs give the
+// same bits.  The positions are workgroup-uniform.
+__global__ __launch_bounds__(256) void deform_im2col_bwd_gx_kernel(const float* __restrict__ off, const float* __restrict__ gcols,
+                                                                   float* __restrict__ gx, int H, int W, int C, int off_cstride,
+                                                                   int pad) {
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= C) return;
+    const long long b = (long long)blockIdx.x * H * W;
+    for (int yh = 0; yh < H; ++yh)
+        for (int xw = 0; xw < W; ++xw) {
+            const long long pix = b + (long long)yh * W + xw;
+            for (int tap = 0; tap < 9; ++tap) {
+                const float py = (float)(yh + tap / 3 - pad) + off[pix * off_cstride + 2 * tap];
+                const float px = (float)(xw + tap % 3 - pad) + off[pix * off_cstride + 2 * tap + 1];
+                if (!(py > -1.f && py < (float)H && px > -1.f && px < (float)W)) continue;
+                const int y0 = (int)floorf(py), x0 = (int)floorf(px);
+                const float ly = py - (float)y0, lx = px - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+                const bool v00 = y0 >= 0 && x0 >= 0, v01 = y0 >= 0 && x0 + 1 <= W - 1;
+                const bool v10 = y0 + 1 <= H - 1 && x0 >= 0, v11 = y0 + 1 <= H - 1 && x0 + 1 <= W - 1;
+                const float gv = gcols[(pix * 9 + tap) * C + c];
+                if (v00) gx[(b + (long long)y0 * W + x0) * C + c] += gv * hy * hx;
+                if (v01) gx[(b + (long long)y0 * W + x0 + 1) * C + c] += gv * hy * lx;
+                if (v10) gx[(b + (long long)(y0 + 1) * W + x0) * C + c] += gv * ly * hx;
+                if (v11) gx[(b + (long long)(y0 + 1) * W + x0 + 1) * C + c] += gv * ly * lx;
+            }
+        }
 }
 
 // tt_ew backward: out = act(v), v = a + b | (1 - b) a | (1 - g) a + g b | a  (ops 0..3).  gv = dout * act'(.) from the saved
@@ -539,7 +564,9 @@ extern "C" int tt_deform_im2col3x3_bwd(const float* x, const float* offsets, con
     TT_REQUIRE(x && offsets && gcols && gx && goffsets && N > 0 && H > 0 && W > 0 && C > 0 && off_cstride >= 18,
                "tt_deform_im2col3x3_bwd: bad argument");
     hipLaunchKernelGGL(deform_im2col_bwd_kernel, dim3(bwd_grid((long long)N * H * W * 9 * 64)), dim3(256), 0,
-                       (hipStream_t)stream, x, offsets, gcols, gx, goffsets, N, H, W, C, off_cstride, pad);
+                       (hipStream_t)stream, x, offsets, gcols, goffsets, N, H, W, C, off_cstride, pad);
+    hipLaunchKernelGGL(deform_im2col_bwd_gx_kernel, dim3((unsigned)N, (unsigned)((C + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, offsets, gcols, gx, H, W, C, off_cstride, pad);
     return check_launch("tt_deform_im2col3x3_bwd");
 }
 

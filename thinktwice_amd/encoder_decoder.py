@@ -413,9 +413,9 @@ class EncoderDecoder(torch.nn.Module):
                     red.depth_bce_bwd(dep, batch["depth"], self.d_bound, self.downsample_factor)))
         return out
 
-    def _parse_losses(self, losses):
+    def _parse_losses(self, losses, device_log=False):
         from . import losses as LS
-        loss, log_vars = LS.parse_losses(losses)
+        loss, log_vars = LS.parse_losses(losses, device_log=device_log)
         tape = getattr(losses, "tape", None)
         if tape is not None:
             from .autograd_route import attach
@@ -423,18 +423,19 @@ class EncoderDecoder(torch.nn.Module):
             loss = attach(self, self._masters, tape, loss)
         return loss, log_vars
 
-    def train_step(self, data, optimizer=None):
+    def train_step(self, data, optimizer=None, device_log=False):
         """encoder_decoder_framework.py:140-145: dict(loss, log_vars, num_samples).  `optimizer` is unused, as in the
         reference (the mmcv OptimizerHook calls loss.backward() and steps it); the backward + all-reduce + AdamW half of
         the iteration is trainer.Trainer.step, which calls this inside its tape -- or, on a `trainable=True` model with
         autograd enabled, torch's own: `loss` then carries the autograd node whose backward sweeps this forward's tape
-        (autograd_route.TapedLoss)."""
-        loss, log_vars = self._parse_losses(self.forward_train(data))
+        (autograd_route.TapedLoss).  `device_log=True`: `log_vars` is a logvars.DeviceLogVars and `loss` an element of its
+        vector -- nothing here waits for the device (losses.parse_losses)."""
+        loss, log_vars = self._parse_losses(self.forward_train(data), device_log=device_log)
         return dict(loss=loss, log_vars=log_vars, num_samples=data["img"].shape[0])
 
-    def forward(self, is_eval=True, **kwargs):
+    def forward(self, is_eval=True, device_log=False, **kwargs):
         """EncoderDecoder.forward (encoder_decoder_framework.py:393-407): the training entry of the mmcv runner."""
-        return self.train_step(kwargs, None)
+        return self.train_step(kwargs, None, device_log=device_log)
 
 
 class PrevSweepCache:

@@ -88,6 +88,35 @@ def read_sample(folder, route_path, frame, history, cameras, pred_len, read=data
     return out
 
 
+def _rng_state(rng):
+    name, keys, pos, has_gauss, cached = rng.get_state()
+    return {"name": name, "keys": [int(k) for k in keys], "pos": int(pos), "has_gauss": int(has_gauss), "cached": float(cached)}
+
+
+def _load_rng(rng, s):
+    rng.set_state((s["name"], np.asarray(s["keys"], dtype=np.uint32), s["pos"], s["has_gauss"], s["cached"]))
+
+
+def sampler_state(ida_sampler, photometric_sampler):
+    """The random streams of a training loader as plain Python data (a checkpoint's meta): the IdaSampler's RandomState, the
+    PhotometricSampler's RandomState and its `reads` (the sample count its schedule runs on).  None for a sampler that is off."""
+    return {"ida": None if ida_sampler is None else _rng_state(ida_sampler.rng),
+            "photometric": None if photometric_sampler is None else {"rng": _rng_state(photometric_sampler.rng),
+                                                                     "reads": int(photometric_sampler.reads)}}
+
+
+def load_sampler_state(ida_sampler, photometric_sampler, s):
+    for name, have, saved in (("ida", ida_sampler, s["ida"]), ("photometric", photometric_sampler, s["photometric"])):
+        if (have is None) != (saved is None):
+            raise ValueError(f"load_sampler_state: the {name} sampler is {'off' if have is None else 'on'} here and "
+                             f"{'off' if saved is None else 'on'} in the saved state")
+    if ida_sampler is not None:
+        _load_rng(ida_sampler.rng, s["ida"])
+    if photometric_sampler is not None:
+        _load_rng(photometric_sampler.rng, s["photometric"]["rng"])
+        photometric_sampler.reads = int(s["photometric"]["reads"])
+
+
 class _Slot:
     """What one in-flight batch owns: its decoder and pipeline objects, its pinned target blob and the event behind the
     blob's last copy."""
@@ -150,6 +179,19 @@ class DeviceBatchLoader:
 
     def __len__(self):
         return -(-len(self.sampler) // self.batch_size)
+
+    def state(self):
+        """What a bit-identical resume needs of this loader BETWEEN epochs (sampler_state: the augmentation streams; the
+        sample order is a function of seed and epoch).  RuntimeError while an epoch is being iterated: the draws of the
+        prefetched batches are already taken."""
+        if self._pool is not None:
+            raise RuntimeError("DeviceBatchLoader.state(): an epoch is being iterated; the state is defined between epochs")
+        return sampler_state(self.ida_sampler, self.augment)
+
+    def load_state(self, s):
+        if self._pool is not None:
+            raise RuntimeError("DeviceBatchLoader.load_state(): an epoch is being iterated; the state is defined between epochs")
+        load_sampler_state(self.ida_sampler, self.augment, s)
 
     def __enter__(self):
         return self

@@ -4,7 +4,7 @@
 order; `seg_loss` / `depth_loss` mirror encoder_decoder_framework.py:172-190 (+ utils.py:31-47, :441-489);
 `parse_losses` is EncoderDecoder._parse_losses (encoder_decoder_framework.py:409-439).  Every term is ONE launch of a
 tt_loss_* reduction writing a device float; nothing here synchronises with the host except `parse_losses`' `.item()`
-calls, which the reference makes too.
+calls, which the reference makes too (`parse_losses(device_log=True)` makes none: thinktwice_amd/logvars.py).
 """
 from collections import OrderedDict
 
@@ -198,13 +198,26 @@ def decoder_loss(red, c, batch, pred, mid_bev, channel_last=False):
     return L
 
 
-def parse_losses(losses):
+def parse_losses(losses, device_log=False):
     """EncoderDecoder._parse_losses EDF:409-439: log_vars = mean of every entry, loss = sum of the entries whose name
     contains 'loss'; under torch.distributed the logged values are averaged over the ranks -- the returned `loss` tensor
     stays local.  The reference issues one all-reduce and one `.item()` per logged value (~24 latency-bound collectives
     and host syncs per iteration); here the values are packed into ONE vector: one all-reduce over xGMI, one
-    device-to-host copy."""
+    device-to-host copy.
+    `device_log=True`: no copy at all -- `log_vars` is a logvars.DeviceLogVars over the packed device vector (ONE launch of
+    tt_logvars_pack builds it from one-element terms, logvars.pack) and `loss` its last element; the all-reduce stays where it
+    is, on a copy, so `loss` stays local.  Nothing on that path synchronises with the host."""
     import torch.distributed as dist
+    if device_log:
+        from . import logvars
+        names, packed, loss = logvars.pack(losses)
+        if dist.is_available() and dist.is_initialized():
+            local, packed = packed, packed / dist.get_world_size()
+            if dist.get_backend() == "gloo":                              # test rigs without RCCL
+                packed = packed.cpu()
+            dist.all_reduce(packed)
+            packed = packed.to(local.device)
+        return loss, logvars.DeviceLogVars(names, packed)
     log_vars = OrderedDict()
     for name, value in losses.items():
         if torch.is_tensor(value):

@@ -1266,7 +1266,7 @@ def spatial_mean_bwd(dpool, dx, C, coff=0):
 
 
 def deform_im2col3x3_bwd(x, offsets, gcols, gx, goff, pad=1):
-    """gx += , goff += backward of deform_im2col3x3 (f32; gx through atomics)."""
+    """gx += , goff += backward of deform_im2col3x3 (f32; gx in a fixed order, no atomics)."""
     require_cuda(x, offsets, gcols, gx, goff)
     N, H, W, C = x.shape
     assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (x, offsets, gcols, gx, goff))

@@ -1,0 +1,259 @@
+"""A whole training job around `trainer.Trainer`: epochs, windowed logging, validation, checkpoints, resume -- what the
+reference gets from train.py -> mmcv's EpochBasedRunner with its LoggerHook, CheckpointHook and the DistEvalHook of
+core/evaluation/eval_hooks.py:116-152.  There is no hook system: `EpochRunner.run()` is one loop, and inside an epoch it adds no
+host synchronisation of its own -- the logged values stay on the device (logvars.LogWindow) and a closed window is written when
+its copy has arrived.
+
+    runner = EpochRunner(trainer, train_loader, val_loader, work_dir="work", max_epochs=60)
+    runner.resume("auto")               # continues from work/latest.pth if there is one
+    runner.run()
+
+Unpinned conventions (mmcv is not installed; these are owned by this module): `ignore_last=True` drops an epoch's incomplete
+last window (mmcv LoggerHook's default, from memory), and the line format of log.json / the text line (`EpochRunner._write`).
+"""
+import collections
+import contextlib
+import json
+import os
+import shutil
+import time
+import warnings
+from collections import OrderedDict
+
+import torch
+
+
+def log_schedule(iters_per_epoch, log_interval, ignore_last=True):
+    """The 1-based inner iterations of an epoch after which a log window is closed AND written: every `log_interval`-th, and
+    the last one too unless `ignore_last` (then an incomplete last window is dropped)."""
+    out = [i for i in range(1, iters_per_epoch + 1) if i % log_interval == 0]
+    if not ignore_last and iters_per_epoch > 0 and iters_per_epoch % log_interval != 0:
+        out.append(iters_per_epoch)
+    return out
+
+
+def merge_ranks(parts):
+    """collect_results_cpu's merge (eval_tool.py:146-160) over `parts` = [(means of rank r, samples of rank r)] in rank
+    order: per name sum_r mean_r * n_r / sum_r n_r, Python floats.  A rank that saw no sample contributes nothing."""
+    results, counts = OrderedDict(), {}
+    for means, n in parts:
+        if not n:
+            continue
+        for key, mean in means.items():
+            if key not in results:
+                results[key], counts[key] = 0.0, 0.0
+            results[key] += mean * n
+            counts[key] += n
+    for key in results:
+        results[key] /= counts[key]
+    return results
+
+
+def _dist(dist):
+    if dist is None:
+        import torch.distributed as td
+        dist = td if (td.is_available() and td.is_initialized()) else None
+    return dist
+
+
+def validate(target, loader, dist=None, window=None):
+    """custom_multi_gpu_test (eval_tool.py:71-116) restated: the model under eval() and no_grad, `train_step` -- losses
+    included, the reference evaluates forward_train too -- on every batch of `loader`, each batch's
+    `log_vars` weighted by its size; ONE read at the end.  `target`: a Trainer (validated through `Trainer.evaluating()`) or a
+    model.  Per rank the device window holds the reference's `results[k] += float(v) * batch_size` in f64, divided by the
+    sample count when read; across ranks `merge_ranks` over one all_gather of (means, n) -- every rank returns the merged
+    result.  Before a distributed validation rank 0's BatchNorm running statistics are broadcast (eval_hooks.py:123-129).
+    -> OrderedDict: a mean per name, then `num_samples` and `eval_iter_num` (this rank's batches)."""
+    from . import logvars
+    dist = _dist(dist)
+    is_trainer = hasattr(target, "evaluating")
+    model = target.model if is_trainer else target
+    if dist is not None and dist.get_world_size() > 1 and is_trainer:
+        for k in sorted(target.buffers):
+            dist.broadcast(target.buffers[k], 0)
+    if window is None:
+        window = logvars.LogWindow(model.device)
+    iters = 0
+    with (target.evaluating() if is_trainer else _eval_mode(model)), torch.no_grad():
+        for batch in loader:
+            out = model.train_step(batch, None, device_log=True)
+            window.add(out["log_vars"], out["num_samples"])
+            iters += 1
+    if iters == 0:
+        raise ValueError("validate: the loader gave no batch")
+    res = window.close().result()
+    n = res["num_samples"]
+    means = OrderedDict((k, v) for k, v in res.items() if k not in logvars.COUNTERS)
+    if dist is not None and dist.get_world_size() > 1:
+        mine = torch.tensor(list(means.values()) + [float(n)], dtype=torch.float64,
+                            device=model.device if dist.get_backend() != "gloo" else "cpu")
+        parts = [torch.empty_like(mine) for _ in range(dist.get_world_size())]
+        dist.all_gather(parts, mine)
+        parts = [p.tolist() for p in parts]
+        means = merge_ranks([(OrderedDict(zip(means, p[:-1])), p[-1]) for p in parts])
+        n = int(sum(p[-1] for p in parts))
+    means["num_samples"], means["eval_iter_num"] = n, iters
+    return means
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    was = model.training
+    model.eval()
+    try:
+        yield model
+    finally:
+        model.train(was)
+
+
+class EpochRunner:
+    """See the module text.  `trainer`: a trainer.Trainer; the loaders: loader.DeviceBatchLoader (train=True / False) -- anything
+    with __len__, __iter__, set_epoch and, for a bit-identical resume, state() / load_state().  `save_best`: a logged name;
+    the checkpoint of the epoch with the LOWEST validation mean of it is kept as best_{name}.pth.  `make_window`: the factory of
+    the log windows (default: logvars.LogWindow on the model's device)."""
+
+    def __init__(self, trainer, train_loader, val_loader=None, work_dir="work_dir", max_epochs=1, log_interval=100,
+                 ckpt_interval=1, eval_interval=1, ignore_last=True, save_best=None, dist=None, make_window=None, verbose=True):
+        if min(int(max_epochs), int(log_interval), int(ckpt_interval), int(eval_interval)) < 1:
+            raise ValueError("EpochRunner: max_epochs and the intervals are >= 1")
+        self.trainer, self.train_loader, self.val_loader = trainer, train_loader, val_loader
+        self.work_dir, self.max_epochs, self.log_interval = str(work_dir), int(max_epochs), int(log_interval)
+        self.ckpt_interval, self.eval_interval, self.ignore_last = int(ckpt_interval), int(eval_interval), bool(ignore_last)
+        self.save_best, self.verbose = save_best, verbose
+        self.dist = _dist(dist)
+        self.rank = self.dist.get_rank() if self.dist is not None else 0
+        self.world = self.dist.get_world_size() if self.dist is not None else 1
+        if make_window is None:
+            from . import logvars
+            make_window = lambda: logvars.LogWindow(trainer.model.device)      # noqa: E731
+        self.make_window = make_window
+        self.window = None
+        self.epoch = 0                   # epochs completed
+        self.best = None                 # lowest validation mean of `save_best` so far
+        self.logs = []                   # every line written, as dicts (all ranks)
+        os.makedirs(self.work_dir, exist_ok=True)
+
+    # ------------------------------------------------------------------------------------------------------- logging
+    def _write(self, line):
+        """One log: a JSON line in work_dir/log.json and a text line, both by rank 0.  The format is this function's."""
+        self.logs.append(line)
+        if self.rank != 0:
+            return
+        with open(os.path.join(self.work_dir, "log.json"), "a") as f:
+            f.write(json.dumps(line) + "\n")
+        if self.verbose:
+            skip = ("mode", "epoch", "iter")
+            body = ", ".join(f"{k}: {v:.4e}" if isinstance(v, float) else f"{k}: {v}" for k, v in line.items() if k not in skip)
+            print(f"Epoch({line['mode']}) [{line['epoch']}][{line['iter']}/{len(self.train_loader)}]  {body}", flush=True)
+
+    def _write_window(self, pending, head):
+        from .logvars import COUNTERS
+        res = pending.result()
+        if res["iterations"] == 0:
+            raise FloatingPointError(f"EpochRunner: every step of the log window ending at epoch {head['epoch']}, iteration "
+                                     f"{head['iter']} had a non-finite gradient norm ({res['skipped']} skipped updates)")
+        line = OrderedDict(head)
+        line.update((k, v) for k, v in res.items() if k not in COUNTERS)
+        line["num_samples"], line["iterations"], line["skipped"] = res["num_samples"], res["iterations"], res["skipped"]
+        line["time"] = line.pop("time")
+        self._write(line)
+
+    # ----------------------------------------------------------------------------------------------------- one epoch
+    def _train_epoch(self, e):
+        trainer, loader = self.trainer, self.train_loader
+        n = len(loader)
+        closes = set(log_schedule(n, self.log_interval, self.ignore_last))
+        if self.window is None:
+            self.window = self.make_window()
+        window, pending = self.window, collections.deque()
+        loader.set_epoch(e)
+        t_last, i_last = time.perf_counter(), 0
+        for i, batch in enumerate(loader, 1):
+            while pending and pending[0][0].ready():                  # non-blocking: written when the copy has arrived
+                self._write_window(*pending.popleft())
+            lr = trainer.current_lr()
+            out = trainer.step(batch, check_finite=False, device_log=True)
+            window.add(out["log_vars"], out["num_samples"], gate=out["grad_norm"], extra={"grad_norm": out["grad_norm"]})
+            if i in closes:
+                now = time.perf_counter()
+                head = OrderedDict(mode="train", epoch=e + 1, iter=i, lr=lr, time=(now - t_last) / (i - i_last))
+                pending.append((window.close(), head))
+                t_last, i_last = now, i
+        if window.adds:
+            window.close()                                            # ignore_last: the incomplete window is dropped
+        while pending:
+            self._write_window(*pending.popleft())
+
+    # ---------------------------------------------------------------------------------------------------- checkpoints
+    def _runner_meta(self):
+        from . import ops
+        state = self.train_loader.state() if hasattr(self.train_loader, "state") else None
+        states = [state]
+        if self.world > 1:                                            # every rank draws its own augmentation stream
+            states = [None] * self.world
+            self.dist.all_gather_object(states, state)
+        return {"loader": states, "dropout_seed": list(ops.DROPOUT_SEED), "best": self.best}
+
+    def _save(self, ckpt, name):
+        path = os.path.join(self.work_dir, name)
+        torch.save(ckpt, path + ".tmp")
+        os.replace(path + ".tmp", path)
+        return path
+
+    def run(self):
+        trainer, n = self.trainer, len(self.train_loader)
+        trainer.set_schedule(self.max_epochs * n, n)
+        for e in range(self.epoch, self.max_epochs):
+            self._train_epoch(e)
+            trainer.reconcile()
+            val = None
+            if self.val_loader is not None and (e + 1) % self.eval_interval == 0:
+                lr = trainer.current_lr()
+                val = validate(trainer, self.val_loader, dist=self.dist, window=self.make_window())
+                line = OrderedDict(mode="val", epoch=e + 1, iter=n, lr=lr)
+                line.update(val)
+                self._write(line)
+            better = (val is not None and self.save_best is not None and self.save_best in val
+                      and (self.best is None or val[self.save_best] < self.best))
+            if better:
+                self.best = val[self.save_best]
+            if (e + 1) % self.ckpt_interval == 0 or better:
+                meta = self._runner_meta()                            # (collective: every rank)
+                if self.rank == 0:
+                    ckpt = trainer.checkpoint(e + 1)
+                    ckpt["meta"]["runner"] = meta
+                    if (e + 1) % self.ckpt_interval == 0:
+                        path = self._save(ckpt, f"epoch_{e + 1}.pth")
+                        shutil.copyfile(path, os.path.join(self.work_dir, "latest.pth.tmp"))
+                        os.replace(os.path.join(self.work_dir, "latest.pth.tmp"), os.path.join(self.work_dir, "latest.pth"))
+                    if better:
+                        self._save(ckpt, f"best_{self.save_best}.pth")
+            self.epoch = e + 1
+        return self.logs
+
+    def resume(self, path="auto"):
+        """Continue from a checkpoint: `auto` is work_dir/latest.pth (none there: returns None, the run starts fresh), else
+        a file.  The trainer loads weights, optimizer state and counters; meta['runner'] brings back the loader's augmentation
+        streams, the dropout generator's counter and the best validation value, so that the continued run is the
+        uninterrupted one bit for bit.  A reference (mmcv) checkpoint has no meta['runner']: it resumes too, with a warning
+        that the augmentation streams start over.  -> the epoch the run continues with (0-based)."""
+        from . import ops
+        if path == "auto":
+            path = os.path.join(self.work_dir, "latest.pth")
+            if not os.path.exists(path):
+                return None
+        ckpt = torch.load(path, map_location="cpu", weights_only=False)
+        self.trainer.load_checkpoint(ckpt)
+        meta = ckpt.get("meta") or {}
+        state = meta.get("runner")
+        if state is None:
+            warnings.warn(f"{path} has no meta['runner'] (a reference checkpoint?): weights, optimizer state and counters are "
+                          f"resumed, the augmentation and dropout streams restart from their seeds")
+        else:
+            mine = state["loader"][self.rank] if self.rank < len(state["loader"]) else None
+            if mine is not None and hasattr(self.train_loader, "load_state"):
+                self.train_loader.load_state(mine)
+            ops.DROPOUT_SEED[:] = list(state["dropout_seed"])
+            self.best = state.get("best")
+        self.epoch = int(meta.get("epoch", 0) or 0)
+        return self.epoch

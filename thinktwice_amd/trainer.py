@@ -11,6 +11,7 @@ kernels' operand formats all stay resident).  BatchNorm runs on its running stat
 F13 pin); its affine parameters train, its statistics are not updated.  Parameters the loss never reaches (the reference's 90
 dead ones) keep zero gradients, as under DDP's find_unused_parameters.
 """
+import contextlib
 import os
 import sys
 
@@ -81,15 +82,15 @@ class Trainer:
         with torch.no_grad():
             self.model.load_state_dict({k: (v.detach().cpu() if k in self._trainable else v) for k, v in self.sd.items()})
 
-    def backward(self, batch):
+    def backward(self, batch, device_log=False):
         """Forward + losses + reverse sweep: fills the flat gradient buffer (no collective, no update).  Returns
-        dict(loss, log_vars, num_samples) of train_step."""
+        dict(loss, log_vars, num_samples) of train_step (`device_log`: its device-resident form)."""
         self.grads.zero_()
         was_training = self.model.training
         self.model.train(not self.frozen_bn)
         try:
             with autodiff.Tape(x3=self.x3, release=True) as tape:
-                out = self.model.train_step(batch, None)
+                out = self.model.train_step(batch, None, device_log=True) if device_log else self.model.train_step(batch, None)
                 tape.backward()
         finally:
             self.model.train(was_training)
@@ -143,15 +144,17 @@ class Trainer:
                 self.epoch = self.iteration // self.schedule["iters_per_epoch"]
         return max(k, 0)
 
-    def step(self, batch, lr=None, check_finite=True):
+    def step(self, batch, lr=None, check_finite=True, device_log=False):
         """One iteration; adds `grad_norm` (device tensor [norm, clip factor]) to train_step's dict.  A non-finite gradient
         norm never reaches the weights: tt_grad_norm_clip hands the update a NaN factor and tt_adamw_step_dev skips (p, m, v
         and the device-side step count untouched).  `check_finite` (one host sync per iteration) additionally raises here;
-        pass False to stay asynchronous and look at `grad_norm` whenever convenient (reconcile() squares the host counters
-        with what the device applied).  Without `lr`, the rate of set_schedule() (else the constructor's)."""
+        pass False to look at `grad_norm` whenever convenient (reconcile() squares the host counters with what the device
+        applied).  That alone does not make the step asynchronous: the float `log_vars` are read from the device every
+        iteration.  With `device_log=True` as well they stay there (a logvars.DeviceLogVars, for a logvars.LogWindow) and the
+        step issues no host synchronisation of its own.  Without `lr`, the rate of set_schedule() (else the constructor's)."""
         if lr is None and self.schedule is not None:
             lr = self.current_lr()
-        out = self.backward(batch)
+        out = self.backward(batch, device_log=device_log)
         self.grads.all_reduce_mean()
         out["grad_norm"] = self.opt.step(lr, live_ranges=self.live_ranges)
         if check_finite and not bool(torch.isfinite(out["grad_norm"][0])):
@@ -166,6 +169,26 @@ class Trainer:
             self.epoch = self.iteration // self.schedule["iters_per_epoch"]
         self._prepare()
         return out
+
+    @contextlib.contextmanager
+    def evaluating(self):
+        """`with trainer.evaluating():` -- the model as `model.eval()` sees it, for a validation pass between steps
+        (runner.validate; eval_hooks.py:116-152).  The operands are re-prepared for running-statistics BatchNorm from the
+        masters and buffers as they stand (a frozen_bn=False trainer prepares for batch statistics after every step), the model
+        is put in eval mode; on exit the training preparation and the mode come back.  Parameters, moments, running statistics
+        and the counters are not touched."""
+        was_training = self.model.training
+        if not self._prepare_on_device:
+            self._prepare()
+        else:
+            masters.prepare_on_device(self.model, {k: (v.detach() if k in self._trainable else self._dev_buffers.get(k, v))
+                                                   for k, v in self.sd.items()}, True)
+        self.model.eval()
+        try:
+            yield self.model
+        finally:
+            self.model.train(was_training)
+            self._prepare()
 
     # ---- checkpoints (mmcv CheckpointHook / torch.save layout: meta + state_dict + optimizer)
     def _num_batches_tracked(self, key, value):
