@@ -307,6 +307,8 @@ int tt_seg_feedback_chain(const float* x, long long R, int x_stride, int K1, con
  * w: pair-format weights [N rounded up to 32][Kp] (weights.py::split_pairs_x3 of the zero-padded f32 matrix),
  * Kp % 16 == 0.  `out` (nullable): f32 rows in global memory.  Outputs that a later stage reads stay in LDS
  * (<= 160 KiB in total per 32 rows, checked).
+ * Two forms, tt_mlp_chain and tt_mlp_chain_wide below; both entries are FORCED forms (what a launch plan records).  Which one a
+ * chain should take, with which grid, and every argument check of both: csrc/chain_choose.cpp, asked through tt_mlp_chain_plan.
  * ---------------------------------------------------------------------- */
 typedef struct tt_chain_stage {
     const void* w; const float* bias;
@@ -326,10 +328,11 @@ int tt_mlp_chain(const float* x, long long R, int x_stride, int nstages, const t
  * sum is taken in eight interleaved slices added in a fixed order.
  * Co-residency: the barrier needs every workgroup of the launch running.  The library bounds a launch to
  * tt_mlp_chain_wide_max_workgroups() = (hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs) / 2 workgroups (two launches at a
- * time: the decoder's main and branch streams) and returns -1 beyond it (callers take tt_mlp_chain instead).  A barrier wait is
- * bounded; a wait that gives up is LOUD: the workgroup writes NaN from there on, the device's fault word (pinned host memory,
- * written by the kernel) is set, and from then on tt_mlp_chain_wide, tt_plan_run, tt_encoder_fwd and tt_decoder_fwd return -3
- * until tt_clear_device_faults().  tt_device_faults(): non-blocking read of that word for the current device (check it after any
+ * time: the decoder's main and branch streams) and returns -1 beyond it (tt_mlp_chain_plan never chooses such a grid).  A wait
+ * is bounded; a wait that gives up is LOUD: the workgroup writes NaN from there on, the device's fault word (pinned host memory,
+ * written by the kernel; tt_dec_gru's hand-over shares it) is set, and from then on tt_mlp_chain_wide, tt_dec_gru, tt_plan_run,
+ * tt_encoder_fwd and tt_decoder_fwd return -3 until tt_clear_device_faults().
+ * tt_device_faults(): non-blocking read of that word for the current device (check it after any
  * synchronisation with the forward's streams -- thinktwice_amd does after the D2H copy of tt_action_post's result and at the
  * start of every forward); tt_mlp_chain_wide_faults(): the same after a hipDeviceSynchronize().  Ticket counters are per
  * device; launches recorded into a HIP graph claim theirs permanently (a replay reuses the recorded counter); when those
@@ -338,6 +341,21 @@ long long tt_mlp_chain_wide_workspace_bytes(long long R, int nstages, const tt_c
 int tt_mlp_chain_wide(const float* x, long long R, int x_stride, int nstages, const tt_chain_stage* stages, int n_groups,
                       void* workspace, long long workspace_bytes, void* stream);
 int tt_mlp_chain_wide_max_workgroups(void);
+/* What a chain of these rows and stages runs as.  Host arithmetic only: touches no device and dereferences no data pointer (the
+ * stages' pointers are tested for null-ness and alignment), takes no stream (a launch plan does not record it), and returns the
+ * code and error text the launch would return before launching.  force: 0 by the rows (the wide form up to 512 rows, unless
+ * TT_CHAIN_WIDE=0 or the device cannot hold a workgroup per row group), 1 tt_mlp_chain, 2 tt_mlp_chain_wide with `groups` clamped to
+ * what can be co-resident, 3 tt_mlp_chain_wide with exactly `groups` (refused beyond the bounds, as the entry does).  groups: column
+ * groups wanted, 0 = the widest stage's 32-column blocks, at most 16.  n_split: tt_mlp_chain's.  max_workgroups: what
+ * tt_mlp_chain_wide_max_workgroups() answered on the device the chain will run on.
+ * Answer: wide (0: call tt_mlp_chain with n_split; 1: tt_mlp_chain_wide with n_groups and a workspace of workspace_bytes), the
+ * launch's grid row_groups x (n_groups | n_split) and its dynamic LDS. */
+typedef struct tt_chain_choice {
+    long long row_groups, workspace_bytes, dynamic_lds;
+    int wide, n_groups, n_split;
+} tt_chain_choice;
+int tt_mlp_chain_plan(long long R, int x_stride, int nstages, const tt_chain_stage* stages, int n_split, int groups, int force,
+                      int max_workgroups, tt_chain_choice* out);
 int tt_mlp_chain_wide_faults(void);
 int tt_device_faults(void);
 int tt_clear_device_faults(void);

@@ -44,6 +44,35 @@ def test_look_query_chain_matches_torch(R, wide):
     assert torch.isnan(aw[:, :44]).all()
 
 
+def test_the_unforced_chain_is_the_form_the_plan_names():
+    """The look-query chain at 5, 33 and 513 rows (one and two row blocks per workgroup of the wide form; past its 512 rows): without
+    wide= ops.mlp_chain runs what tt_mlp_chain_plan answers for the device's capacity, bit for bit the forced form of that name."""
+    import ctypes
+    from thinktwice_amd import _lib, ops
+    g = torch.Generator().manual_seed(11)
+    lins = [ops.ChainLinear(*_lin(g, 512, 1544), act=3), ops.ChainLinear(*_lin(g, 256, 512), act=3),
+            ops.ChainLinear(*_lin(g, 512, 256)), ops.ChainLinear(*_lin(g, 256, 256))]
+    arr = (ops._ChainStage * 4)()
+    for d, lin, src in zip(arr, lins, (-1, 0, 1, 1)):
+        d.w, d.K, d.Kp, d.N, d.in_sel = lin.w.data_ptr(), lin.K, lin.Kp, lin.N, src
+    cap = ops.chain_wide_max_workgroups(torch.device("cuda", torch.cuda.current_device()))
+    for R in (5, 33, 513):
+        x = torch.randn(R, 1552, generator=g).cuda()
+        c = ops._ChainChoice()
+        _lib.check(_lib.lib().tt_mlp_chain_plan(R, 1552, 4, arr, 1, 0, 0, cap, ctypes.byref(c)), "tt_mlp_chain_plan")
+        assert bool(c.wide) == (R <= 512) == ops.chain_is_wide(R)
+        outs = []
+        for wide in (None, bool(c.wide)):
+            off = torch.full((R, 512), float("nan"), device="cuda")
+            aw = torch.full((R, 256), float("nan"), device="cuda")
+            ops.mlp_chain(x, [{"lin": lins[0], "src": -1}, {"lin": lins[1], "src": 0}, {"lin": lins[2], "src": 1, "out": (off, 0)},
+                              {"lin": lins[3], "src": 1, "out": (aw, 0)}], wide=wide)
+            outs.append((off, aw))
+        assert ops.chain_faults() == 0
+        for a, b in zip(*outs):
+            assert torch.isfinite(a).all() and torch.equal(a, b)
+
+
 @pytest.mark.parametrize("wide", [False, True], ids=["rows", "wide"])
 def test_residual_side_input_and_narrow_heads(wide):
     """ffn-style residual (out = W2 gelu(W1 x) + x), a side input of 2 leading columns (cat([wp, h]) @ W^T), a 2-wide

@@ -1,9 +1,10 @@
-// Error reporting, per-device launch state and version for libthinktwice_hip.so.
+// Error reporting, per-device launch state, the per-device fault word and version for libthinktwice_hip.so.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <mutex>
 #include <unordered_map>
 
@@ -84,7 +85,76 @@ int lds_opt_in(const void* kernel, size_t bytes, const char* name) {
         set_error("%s: device %d refuses %zu bytes of dynamic LDS: %s", name, dev, bytes, hipGetErrorString(g.refusal));
     return -1;
 }
+
+// ---- The fault word: one int in pinned, host-mapped memory per device (64 B apart).  A cross-workgroup wait that gives up
+// (bounded_wait.h) sets it from the device with a system-scope store; the host reads it without a copy or a synchronisation of its
+// own (tt_device_faults), and once it is set tt_mlp_chain_wide / tt_dec_gru / tt_encoder_fwd / tt_decoder_fwd / tt_plan_run refuse
+// to run until tt_clear_device_faults().  Allocated under g_launch_mutex, which is taken last (tt_mlp_chain_wide comes here holding
+// its pool's mutex; nothing under g_launch_mutex calls out of this file).
+namespace {
+int* g_fault_words = nullptr;
+std::atomic<int> g_max_spin{kWaitMaxSpin};
+}  // namespace
+
+int* device_fault_word() {
+    const int dev = current_device(nullptr);
+    if (dev < 0) return nullptr;
+    std::lock_guard<std::mutex> lock(g_launch_mutex);
+    if (!g_fault_words) {
+        void* p = nullptr;
+        if (hipHostMalloc(&p, (size_t)kMaxDevices * 64, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) {
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        memset(p, 0, (size_t)kMaxDevices * 64);
+        g_fault_words = static_cast<int*>(p);
+    }
+    return g_fault_words + (size_t)dev * 16;
+}
+
+int pair_wait_max_spin() { return g_max_spin.load(); }
+
+// The check every forward entry point makes first: a wait's time-out is sticky (like a device fault), because whatever ran
+// after it consumed poisoned data.
+int refuse_after_fault(const char* what) {
+    const int f = tt_device_faults();
+    if (f > 0) {
+        set_error("%s: refused -- an earlier tt_mlp_chain_wide launch on this device gave up waiting at its barrier (its "
+                  "outputs are NaN); results since then are invalid.  tt_clear_device_faults() re-arms the device", what);
+        return -3;
+    }
+    return 0;
+}
 }  // namespace tt
+
+// Non-blocking: the fault word of the CURRENT device (0 = no wait has timed out since the last clear).  Meaningful for the
+// work the caller has already synchronised with; any entry point that synchronises anyway (the D2H copy of tt_action_post's
+// result, the end of a plan run in tools/plan_host.cpp) checks it there.
+extern "C" int tt_device_faults(void) {
+    const int dev = tt::current_device(nullptr);
+    if (dev < 0) return -2;
+    if (!tt::g_fault_words) return 0;
+    return __atomic_load_n(tt::g_fault_words + (size_t)dev * 16, __ATOMIC_ACQUIRE);
+}
+
+extern "C" int tt_clear_device_faults(void) {
+    const int dev = tt::current_device(nullptr);
+    if (dev < 0) return -2;
+    if (tt::g_fault_words) __atomic_store_n(tt::g_fault_words + (size_t)dev * 16, 0, __ATOMIC_RELEASE);
+    return 0;
+}
+
+// Blocking form (tests): waits for the device, then reads the fault word.
+extern "C" int tt_mlp_chain_wide_faults(void) {
+    if (hipDeviceSynchronize() != hipSuccess) return -2;
+    return tt_device_faults();
+}
+
+// (named after the first kernel that waited; the bound is every bounded_wait's)
+extern "C" int tt_mlp_chain_wide_set_max_spin(int polls) {
+    tt::g_max_spin.store(polls < 0 ? tt::kWaitMaxSpin : polls);
+    return 0;
+}
 
 extern "C" const char* tt_last_error(void) { return tt::g_err; }
 

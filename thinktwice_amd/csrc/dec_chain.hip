@@ -19,33 +19,17 @@
 // blocks of N round-robin, up to 4 accumulator blocks per wave at a time, so one A fragment feeds up to 12 MFMAs.
 // Weights stream from L2 straight into the B operand registers (each element is used once per workgroup: staging
 // them through LDS would only add a round trip), double-buffered one K step ahead.
-#include <atomic>
+//
+// Which of the two forms below a chain runs in, its grid and where its intermediates go: chain_choose.cpp.
 #include <mutex>
-#include <string.h>
 
+#include "bounded_wait.h"
+#include "chain_choose.h"
 #include "conv_common.h"
 
 namespace tt {
 
-constexpr int kChainMaxStages = 12;
-constexpr int kChainWaves = 8;
-constexpr int kChainNBW = 2;      // accumulator blocks per wave per pass
 constexpr int kChainPF = 4;       // weight K-steps in flight per wave
-
-struct ChainStage {
-    const void* w;        // fragment-major pair-format weights of the [N padded to 32][Kp] matrix
-    const float* bias;    // [N] or null
-    const float* res;     // optional residual rows (global f32): v += res[m * res_stride + res_coff + n]
-    const float* side;    // optional extra input columns (global f32 [R][side_stride]): v += sum_j side[m][j] * side_w[n][j]
-    const float* side_w;  // [N][side_k] f32
-    float* out;           // optional global f32 output: out[m * out_stride + out_coff + n]
-    int K, Kp, N, act;
-    int in_sel;           // -1: the chain input x; s >= 0: the LDS output of stage s
-    int res_stride, res_coff, side_stride, side_k;
-    int out_stride, out_coff;
-    int lds_off;          // byte offset of this stage's LDS output (pair format); -1: not kept
-    int lds_stride;       // bytes per row of that buffer (Kp_next * 4 + 16: an odd number of 16 B slots, conflict-free)
-};
 
 struct ChainArgs {
     const float* x;
@@ -210,7 +194,6 @@ __global__ __launch_bounds__(kChainWaves * 64) void mlp_chain_kernel(const Chain
 // coherent with each other for ordinary stores).  The ticket counters live in a library-owned pool, are claimed round-robin per
 // launch and reset themselves with the launch's last arrival.
 constexpr int kWidePF = 8;               // K steps in flight per wave (8 x 4 KiB: weights + activation fragments)
-constexpr int kWideMaxSpin = 1 << 21;    // default bail-out of a ticket wait (~1 s): a wrong count must not hang the device
 
 struct WideStage {
     ChainStage s;
@@ -229,7 +212,7 @@ struct WideArgs {
     unsigned* tickets;    // one counter (64 B apart) per row group
     int* fault;           // HOST-mapped (pinned) word of this device, set with a system-scope store if a ticket wait gave up:
                           // the host reads it without a copy (tt_device_faults) and every later entry point refuses to run
-    int max_spin;         // polls before a wait gives up (kWideMaxSpin; tests force a time-out with 0)
+    int max_spin;         // polls before a wait gives up (pair_wait_max_spin; tests force a time-out with 0)
     long long* trace;     // debug (tt_mlp_chain_wide_set_trace): 64 wall-clock stamps (10 ns ticks) per workgroup, or null
     WideStage st[kChainMaxStages];
 };
@@ -242,25 +225,14 @@ __device__ __forceinline__ void lds_barrier() {
 #endif
 }
 
-// Returns true if the wait GAVE UP (the launch's workgroups were not all running within max_spin polls: the chip was
-// oversubscribed beyond what the host-side occupancy check allows for, or a count is wrong).  A time-out is made LOUD, never
-// silent: the device's host-mapped fault word is set (system scope), and the caller poisons every value the workgroup writes
-// from here on with NaN, so the launch's outputs cannot be mistaken for results.  The workgroup still arrives at every later
-// barrier, so the counter reaches its total and resets itself for the slot's next launch.
+// Arrive + wait (bounded_wait.h).  Returns true if the wait GAVE UP: the caller poisons every value the workgroup writes from here
+// on.  The workgroup still arrives at every later barrier, so the counter reaches its total and resets itself for the slot's next
+// launch.
 __device__ __forceinline__ bool ticket_barrier(unsigned* ctr, unsigned target, int* fault, int max_spin, int* gave_up) {
     __syncthreads();
     if (threadIdx.x == 0) {
         __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        int spin = 0;
-        while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            if (++spin > max_spin) {
-                __hip_atomic_store(fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                *gave_up = 1;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // one cache invalidate after the wait, not one per poll
+        bounded_wait(ctr, target, fault, max_spin, gave_up);
     }
     __syncthreads();
     return *gave_up != 0;
@@ -479,84 +451,19 @@ using namespace tt;
 
 extern "C" int tt_mlp_chain(const float* x, long long R, int x_stride, int nstages, const tt_chain_stage* st,
                             int n_split, void* stream) {
-    TT_REQUIRE(x && st && R > 0 && nstages >= 1 && nstages <= kChainMaxStages, "tt_mlp_chain: bad arguments");
-    TT_REQUIRE(n_split >= 1 && (n_split == 1 || nstages == 1), "tt_mlp_chain: n_split > 1 needs a single stage");
-    TT_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && x_stride % 4 == 0, "tt_mlp_chain: x must be 16 B aligned rows");
+    if (int rc = chain_validate("tt_mlp_chain", x, R, x_stride, nstages, st)) return rc;
+    ChainChoice c;
+    if (int rc = chain_choose(R, nstages, st, n_split, 0, CHAIN_ROWS, -1, &c)) return rc;
     ChainArgs a;
     a.x = x; a.R = R; a.x_stride = x_stride; a.nstages = nstages;
-    a.nbw = n_split > 1 ? 1 : kChainNBW;
-    // LDS plan: an output is kept while a LATER stage reads it; buffers are placed first-fit over the live ranges
-    int last_use[kChainMaxStages];
-    for (int s = 0; s < nstages; ++s) last_use[s] = -1;
+    a.nbw = c.nbw;
     for (int s = 0; s < nstages; ++s) {
-        TT_REQUIRE(st[s].in_sel < s, "tt_mlp_chain: stage %d reads stage %d", s, st[s].in_sel);
-        if (st[s].in_sel >= 0) last_use[st[s].in_sel] = s;
+        a.st[s] = chain_stage(st[s]);
+        a.st[s].lds_off = c.lds_off[s];
+        a.st[s].lds_stride = c.lds_stride[s];
     }
-    size_t off[kChainMaxStages], len[kChainMaxStages];
-    size_t total = 0;
-    for (int s = 0; s < nstages; ++s) {
-        const tt_chain_stage& d = st[s];
-        TT_REQUIRE(d.w && d.K > 0 && d.N > 0 && d.Kp % 16 == 0 && d.Kp >= d.K && d.K % 4 == 0,
-                   "tt_mlp_chain: stage %d: K=%d Kp=%d N=%d", s, d.K, d.Kp, d.N);
-        TT_REQUIRE((reinterpret_cast<uintptr_t>(d.w) & 15) == 0, "tt_mlp_chain: stage %d weights unaligned", s);
-        TT_REQUIRE(d.side_k >= 0 && d.side_k <= 8 && (!d.side || d.side_w), "tt_mlp_chain: stage %d side input", s);
-        TT_REQUIRE(d.in_sel >= 0 || x_stride >= d.Kp,
-                   "tt_mlp_chain: stage %d: x rows (stride %d) must cover the padded K = %d (finite padding)", s, x_stride,
-                   d.Kp);
-        TT_REQUIRE(d.in_sel < 0 || st[d.in_sel].N == d.K, "tt_mlp_chain: stage %d: K=%d but stage %d has N=%d", s, d.K,
-                   d.in_sel, d.in_sel >= 0 ? st[d.in_sel].N : 0);
-        ChainStage& S = a.st[s];
-        S.w = d.w; S.bias = d.bias; S.res = d.res; S.side = d.side; S.side_w = d.side_w; S.out = d.out;
-        S.K = d.K; S.Kp = d.Kp; S.N = d.N; S.act = d.act; S.in_sel = d.in_sel;
-        S.res_stride = d.res_stride; S.res_coff = d.res_coff; S.side_stride = d.side_stride; S.side_k = d.side_k;
-        S.out_stride = d.out_stride; S.out_coff = d.out_coff;
-        S.lds_off = -1; S.lds_stride = 0;
-        off[s] = 0; len[s] = 0;
-        if (last_use[s] >= 0) {
-            const int np = (d.N + 15) / 16 * 16;          // the consumer's Kp
-            S.lds_stride = np * 4 + 16;
-            len[s] = (size_t)32 * S.lds_stride;
-            // Two-ended placement against the buffers still live at stage s (those read at or after s): a buffer goes
-            // to the END of the 160 KiB window when its input sits in the lower half, else to the start -- a chain then
-            // ping-pongs between the two ends and a long-lived buffer in the middle never splits the free space.
-            constexpr size_t kBudget = 160 * 1024;
-            auto clashes = [&](size_t pos) -> int {
-                for (int t = 0; t < s; ++t)
-                    if (len[t] != 0 && last_use[t] >= s && pos < off[t] + len[t] && off[t] < pos + len[s]) return t;
-                return -1;
-            };
-            const bool in_low = d.in_sel < 0 || off[d.in_sel] + len[d.in_sel] / 2 < kBudget / 2;
-            bool placed = false;
-            size_t pos = 0;
-            for (int attempt = 0; attempt < 2 && !placed; ++attempt) {
-                const bool top = (attempt == 0) ? (d.in_sel >= 0 && in_low) : !(d.in_sel >= 0 && in_low);
-                if (top) {
-                    if (len[s] > kBudget) break;
-                    long long p = (long long)((kBudget - len[s]) / 16 * 16);
-                    int t;
-                    while (p >= 0 && (t = clashes((size_t)p)) >= 0) p = ((long long)off[t] - (long long)len[s]) / 16 * 16;
-                    if (p >= 0 && clashes((size_t)p) < 0) { pos = (size_t)p; placed = true; }
-                } else {
-                    size_t p = 0;
-                    int t;
-                    while ((t = clashes(p)) >= 0) p = (off[t] + len[t] + 15) / 16 * 16;
-                    if (p + len[s] <= kBudget) { pos = p; placed = true; }
-                }
-            }
-            TT_REQUIRE(placed, "tt_mlp_chain: intermediates of stage %d do not fit in 160 KiB of LDS", s);
-            off[s] = pos;
-            S.lds_off = (int)pos;
-            if (pos + len[s] > total) total = pos + len[s];
-        }
-    }
-    for (int s = 0; s < nstages; ++s)
-        if (a.st[s].in_sel >= 0)
-            TT_REQUIRE(a.st[a.st[s].in_sel].lds_stride == a.st[s].Kp * 4 + 16, "tt_mlp_chain: stage %d Kp mismatch", s);
-    TT_REQUIRE(total <= 160 * 1024, "tt_mlp_chain: intermediates need %zu B of LDS (> 160 KiB)", total);
-    if (total < 16) total = 16;
     if (lds_opt_in(reinterpret_cast<const void*>(mlp_chain_kernel), 160 * 1024, "mlp_chain_kernel")) return -1;
-    const unsigned blocks = (unsigned)((R + 31) / 32);
-    hipLaunchKernelGGL(mlp_chain_kernel, dim3(blocks, (unsigned)n_split), dim3(kChainWaves * 64), total,
+    hipLaunchKernelGGL(mlp_chain_kernel, dim3((unsigned)c.row_groups, (unsigned)c.n_split), dim3(kChainWaves * 64), c.lds_total,
                        (hipStream_t)stream, a);
     return check_launch("tt_mlp_chain");
 }
@@ -566,15 +473,13 @@ extern "C" int tt_mlp_chain(const float* x, long long R, int x_stride, int nstag
 //  * the ticket pool: kEagerSlots counters claimed round-robin by plain launches (a collision needs > kEagerSlots row groups in
 //    flight at once), and kCapturedSlots claimed PERMANENTLY by launches recorded into a HIP graph (a captured launch replays
 //    with the slot baked into its arguments, so no later launch may be handed the same counter);
-//  * the fault word: one int in pinned, host-mapped memory per device.  A barrier that gives up sets it from the device with a
-//    system-scope store; the host reads it without a copy or a synchronisation of its own (tt_device_faults), and once it is
-//    set tt_mlp_chain_wide / tt_encoder_fwd / tt_decoder_fwd / tt_plan_run refuse to run until tt_clear_device_faults();
 //  * the co-residency capacity: hipOccupancyMaxActiveBlocksPerMultiprocessor x the device's CU count.  A launch may use at most
 //    capacity / kWideConcurrent workgroups (the decoder runs two chains at a time, on its main and its branch stream), so the
 //    spinning workgroups of concurrent launches can never fill the chip and keep their own peers out.  hipLaunchCooperativeKernel
 //    would give the same guarantee per launch, but it goes through the device's single cooperative queue (the two streams'
 //    chains would serialise) and is not recordable into a HIP graph; the occupancy bound + bounded spin + loud fault is the
 //    form that keeps both.
+// (The fault word a barrier that gives up sets, and the bound on its wait: common.cpp.)
 namespace {
 constexpr int kEagerSlots = 4096;        // 64 B each; a launch claims one per row group
 constexpr int kCapturedSlots = 12288;
@@ -585,29 +490,14 @@ struct WidePool {
     int capacity = 0;                    // co-resident workgroups of mlp_chain_wide_kernel on this device
 };
 WidePool g_pools[kMaxDevices];
-int* g_fault_words = nullptr;            // pinned host-mapped: one int (64 B apart) per device
 std::mutex g_wide_mutex;
-std::atomic<int> g_wide_max_spin{kWideMaxSpin};
 long long* g_trace = nullptr;            // tt_mlp_chain_wide_set_trace
-
-int* fault_word(int dev) {               // (g_wide_mutex held, or after the first successful call)
-    if (!g_fault_words) {
-        void* p = nullptr;
-        if (hipHostMalloc(&p, (size_t)kMaxDevices * 64, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        memset(p, 0, (size_t)kMaxDevices * 64);
-        g_fault_words = static_cast<int*>(p);
-    }
-    return g_fault_words + (size_t)dev * 16;
-}
 
 // (g_wide_mutex held)
 WidePool* wide_pool(int dev) {
     WidePool& P = g_pools[dev];
     if (P.tickets) return &P;
-    if (!fault_word(dev)) {
+    if (!tt::device_fault_word()) {
         tt::set_error("tt_mlp_chain_wide: cannot allocate the host-mapped fault word");
         return nullptr;
     }
@@ -631,49 +521,6 @@ WidePool* wide_pool(int dev) {
 }
 }  // namespace
 
-// Non-blocking: the fault word of the CURRENT device (0 = no barrier has timed out since the last clear).  Meaningful for the
-// work the caller has already synchronised with; any entry point that synchronises anyway (the D2H copy of tt_action_post's
-// result, the end of a plan run in tools/plan_host.cpp) checks it there.
-extern "C" int tt_device_faults(void) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return -2;
-    if (!g_fault_words) return 0;
-    return __atomic_load_n(g_fault_words + (size_t)dev * 16, __ATOMIC_ACQUIRE);
-}
-
-extern "C" int tt_clear_device_faults(void) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return -2;
-    if (g_fault_words) __atomic_store_n(g_fault_words + (size_t)dev * 16, 0, __ATOMIC_RELEASE);
-    return 0;
-}
-
-int* tt::device_fault_word() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
-    std::lock_guard<std::mutex> lock(g_wide_mutex);
-    return fault_word(dev);
-}
-
-int tt::pair_wait_max_spin() { return g_wide_max_spin.load(); }
-
-// The check every forward entry point makes first: a barrier time-out is sticky (like a device fault), because whatever ran
-// after it consumed poisoned data.
-int tt::refuse_after_fault(const char* what) {
-    const int f = tt_device_faults();
-    if (f > 0) {
-        tt::set_error("%s: refused -- an earlier tt_mlp_chain_wide launch on this device gave up waiting at its barrier (its "
-                      "outputs are NaN); results since then are invalid.  tt_clear_device_faults() re-arms the device", what);
-        return -3;
-    }
-    return 0;
-}
-
-extern "C" int tt_mlp_chain_wide_set_max_spin(int polls) {
-    g_wide_max_spin.store(polls < 0 ? kWideMaxSpin : polls);
-    return 0;
-}
-
 // Workgroups one launch may use on the current device (co-resident capacity / kWideConcurrent), or < 0 on error.
 extern "C" int tt_mlp_chain_wide_max_workgroups(void) {
     int dev = 0;
@@ -683,111 +530,47 @@ extern "C" int tt_mlp_chain_wide_max_workgroups(void) {
     return P ? P->capacity / kWideConcurrent : -2;
 }
 
-static inline long long wide_keep_stride(int N) { return (N + 31) / 32 * 32; }
-// 32-row blocks per workgroup: with several row blocks the waves of a workgroup share the weight stream (same K slice, different
-// rows) instead of every row block streaming all the weights through its own workgroup
-static inline int wide_rb(long long row_blocks) { return row_blocks <= 1 ? 1 : (row_blocks == 2 ? 2 : 4); }
-static inline long long wide_rows(long long R) {
-    const long long row_blocks = (R + 31) / 32;
-    const int rb = wide_rb(row_blocks);
-    return (row_blocks + rb - 1) / rb * rb * 32;
-}
-
-extern "C" long long tt_mlp_chain_wide_workspace_bytes(long long R, int nstages, const tt_chain_stage* st) {
-    if (!st || R <= 0 || nstages < 1 || nstages > kChainMaxStages) return -1;
-    const long long rows = wide_rows(R);
-    long long total = 0;
-    for (int s = 0; s < nstages; ++s) {
-        bool kept = false;
-        for (int t = s + 1; t < nstages; ++t) kept = kept || st[t].in_sel == s;
-        if (kept) total += (rows * wide_keep_stride(st[s].N) * 4 + 255) / 256 * 256;
-    }
-    return total < 256 ? 256 : total;
-}
-
 extern "C" int tt_mlp_chain_wide_set_trace(void* stamps_or_null) {
     g_trace = static_cast<long long*>(stamps_or_null);
     return 0;
 }
 
-// Blocking form (tests): waits for the device, then reads the fault word.
-extern "C" int tt_mlp_chain_wide_faults(void) {
-    if (hipDeviceSynchronize() != hipSuccess) return -2;
-    return tt_device_faults();
-}
-
 extern "C" int tt_mlp_chain_wide(const float* x, long long R, int x_stride, int nstages, const tt_chain_stage* st,
                                  int n_groups, void* workspace, long long workspace_bytes, void* stream) {
-    TT_REQUIRE(x && st && R > 0 && nstages >= 1 && nstages <= kChainMaxStages, "tt_mlp_chain_wide: bad arguments");
-    TT_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && x_stride % 4 == 0, "tt_mlp_chain_wide: x must be 16 B aligned rows");
-    const long long row_blocks = (R + 31) / 32;
-    const int rb = wide_rb(row_blocks);
-    const long long row_groups = (row_blocks + rb - 1) / rb;
     // host-side argument checks first (no device is touched until they pass)
-    TT_REQUIRE(n_groups >= 1 && n_groups <= 64, "tt_mlp_chain_wide: %d column groups: 1 - 64 workgroups per row group can be "
-               "co-resident", n_groups);
-    const long long need = tt_mlp_chain_wide_workspace_bytes(R, nstages, st);
-    TT_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-               "tt_mlp_chain_wide: workspace of %lld B needed (%lld given)", need, workspace_bytes);
+    if (int rc = chain_validate("tt_mlp_chain_wide", x, R, x_stride, nstages, st)) return rc;
+    ChainChoice c;
+    if (int rc = chain_choose(R, nstages, st, 1, n_groups, CHAIN_WIDE_AS_GIVEN, -1, &c)) return rc;
+    TT_REQUIRE(workspace && workspace_bytes >= c.workspace_bytes && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+               "tt_mlp_chain_wide: workspace of %lld B needed (%lld given)", c.workspace_bytes, workspace_bytes);
     if (int rc = tt::refuse_after_fault("tt_mlp_chain_wide")) return rc;
     int dev = 0;
     TT_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices, "tt_mlp_chain_wide: no current device");
     std::lock_guard<std::mutex> lock(g_wide_mutex);     // pool creation + slot claim (+ the launch: slots stay in claim order)
     WidePool* P = wide_pool(dev);
     if (!P) return -2;
-    TT_REQUIRE(n_groups >= 1 && n_groups <= 64 && row_groups * n_groups * kWideConcurrent <= P->capacity,
-               "tt_mlp_chain_wide: %lld row groups x %d column groups: at most %d workgroups per launch can be guaranteed "
-               "co-resident on this device (%d resident, %d launches at a time)", row_groups, n_groups,
-               P->capacity / kWideConcurrent, P->capacity, kWideConcurrent);
+    if (int rc = chain_wide_fits(c, P->capacity / kWideConcurrent)) return rc;
     WideArgs a;
-    a.R = R; a.nstages = nstages; a.nsync = 0; a.rb = rb;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    int synced_upto = -1;                 // stages <= this index are complete on every workgroup of the row block
+    a.R = R; a.nstages = nstages; a.nsync = c.nsync; a.rb = c.rb;
     for (int s = 0; s < nstages; ++s) {
-        const tt_chain_stage& d = st[s];
-        TT_REQUIRE(d.in_sel < s, "tt_mlp_chain_wide: stage %d reads stage %d", s, d.in_sel);
-        TT_REQUIRE(d.w && d.K > 0 && d.N > 0 && d.Kp % 16 == 0 && d.Kp >= d.K && d.K % 4 == 0,
-                   "tt_mlp_chain_wide: stage %d: K=%d Kp=%d N=%d", s, d.K, d.Kp, d.N);
-        TT_REQUIRE((reinterpret_cast<uintptr_t>(d.w) & 15) == 0, "tt_mlp_chain_wide: stage %d weights unaligned", s);
-        TT_REQUIRE(d.side_k >= 0 && d.side_k <= 8 && (!d.side || d.side_w), "tt_mlp_chain_wide: stage %d side input", s);
-        TT_REQUIRE(d.in_sel >= 0 || x_stride >= d.Kp,
-                   "tt_mlp_chain_wide: stage %d: x rows (stride %d) must cover the padded K = %d (finite padding)", s, x_stride,
-                   d.Kp);
-        TT_REQUIRE(d.in_sel < 0 || st[d.in_sel].N == d.K, "tt_mlp_chain_wide: stage %d: K=%d but stage %d has N=%d", s, d.K,
-                   d.in_sel, d.in_sel >= 0 ? st[d.in_sel].N : 0);
         WideStage& W = a.st[s];
-        ChainStage& S = W.s;
-        S.w = d.w; S.bias = d.bias; S.res = d.res; S.side = d.side; S.side_w = d.side_w; S.out = d.out;
-        S.K = d.K; S.Kp = d.Kp; S.N = d.N; S.act = d.act; S.in_sel = d.in_sel;
-        S.res_stride = d.res_stride; S.res_coff = d.res_coff; S.side_stride = d.side_stride; S.side_k = d.side_k;
-        S.out_stride = d.out_stride; S.out_coff = d.out_coff;
-        S.lds_off = -1; S.lds_stride = 0;
-        bool kept = false;
-        for (int t = s + 1; t < nstages; ++t) kept = kept || st[t].in_sel == s;
-        W.keep = nullptr; W.keep_stride = 0;
-        if (kept) {
-            W.keep = reinterpret_cast<float*>(ws);
-            W.keep_stride = (int)wide_keep_stride(d.N) / 16;
-            ws += (wide_rows(R) * wide_keep_stride(d.N) * 4 + 255) / 256 * 256;
-        }
-        if (d.in_sel < 0) {
-            W.in = x; W.in_stride = x_stride; W.in_frag = 0; W.sync_before = 0;
+        W.s = chain_stage(st[s]);
+        W.keep = c.keep_off[s] < 0 ? nullptr : reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + c.keep_off[s]);
+        W.keep_stride = c.keep_stride[s];
+        W.sync_before = c.sync_before[s];
+        const int in = st[s].in_sel;
+        if (in < 0) {
+            W.in = x; W.in_stride = x_stride; W.in_frag = 0;
         } else {
-            W.in = a.st[d.in_sel].keep; W.in_stride = a.st[d.in_sel].keep_stride; W.in_frag = 1;
-            // the consumer's padded K (a multiple of 16) lies inside the producer's 32-column blocks: finite (zero) padding
-            W.sync_before = d.in_sel > synced_upto ? 1 : 0;
-            if (W.sync_before) { synced_upto = s - 1; ++a.nsync; }
+            W.in = a.st[in].keep; W.in_stride = a.st[in].keep_stride; W.in_frag = 1;
         }
-    }
-    if (n_groups == 1) {                   // one workgroup per row block: nobody to wait for
-        for (int s = 0; s < nstages; ++s) a.st[s].sync_before = 0;
-        a.nsync = 0;
     }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (stream && hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) {
         (void)hipGetLastError();
         cap = hipStreamCaptureStatusNone;
     }
+    const unsigned row_groups = (unsigned)c.row_groups;
     if (cap == hipStreamCaptureStatusActive) {          // replayed with these arguments: the slots are this launch's for good
         if (P->next_captured + row_groups > (unsigned)kCapturedSlots) {
             // a process that keeps re-capturing graphs: captured launches own their slots for good.  Distinct code: the caller
@@ -796,16 +579,16 @@ extern "C" int tt_mlp_chain_wide(const float* x, long long R, int x_stride, int 
             return -4;
         }
         a.tickets = P->tickets + (size_t)(kEagerSlots + P->next_captured) * 16;
-        P->next_captured += (unsigned)row_groups;
+        P->next_captured += row_groups;
     } else {
         if (P->next_eager + row_groups > (unsigned)kEagerSlots) P->next_eager = 0;
         a.tickets = P->tickets + (size_t)P->next_eager * 16;
-        P->next_eager += (unsigned)row_groups;
+        P->next_eager += row_groups;
     }
-    a.fault = fault_word(dev);
-    a.max_spin = g_wide_max_spin.load();
+    a.fault = tt::device_fault_word();
+    a.max_spin = tt::pair_wait_max_spin();
     a.trace = g_trace;
-    hipLaunchKernelGGL(mlp_chain_wide_kernel, dim3((unsigned)row_groups, (unsigned)n_groups), dim3(kChainWaves * 64), 0,
+    hipLaunchKernelGGL(mlp_chain_wide_kernel, dim3(row_groups, (unsigned)c.n_groups), dim3(kChainWaves * 64), 0,
                        (hipStream_t)stream, a);
     return check_launch("tt_mlp_chain_wide");
 }

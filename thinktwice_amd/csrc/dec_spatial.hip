@@ -18,6 +18,7 @@
 //     never enter the GEMM: their contribution is sum over the VALID taps of G[tap][n] = W[n, tap, const] . x, which
 //     depends on the pixel only through its border class (3 row classes x 3 column classes); the 9 class sums are
 //     tabulated once per conv and added in the epilogue.  The BEV update's K drops from 18,720 to 288 that way.
+#include "bounded_wait.h"
 #include "conv_common.h"
 
 namespace tt {
@@ -265,32 +266,20 @@ struct GruArgs {
     const unsigned char* wd0; const float* bd0;   // conv_decoder.0 / .2
     const unsigned char* wd2; const float* bd2;
     unsigned* flags;          // [B][2], zero at launch: [0] states published by role 0, [1] update gates published by role 1
-    int* fault;               // the device's host-mapped fault word (dec_chain.hip): set if a wait gave up
+    int* fault;               // the device's host-mapped fault word (common.cpp): set if a wait gave up
     int max_spin;
     long long* trace;         // debug (tt_dec_set_trace): wall-clock stamps of workgroup 0 after every phase, or null
 };
 
 // Flag hand-over between the two workgroups of a sample (agent scope: they may sit on different XCDs, whose L2s are not
 // coherent for plain stores).  post: every thread's stores of the phase, then thread 0 releases and bumps the flag.  wait:
-// thread 0 polls (bounded: a partner that is not running within max_spin polls makes the wait give up LOUDLY -- the device's
-// fault word is set and the caller poisons everything it writes from then on, as in tt_mlp_chain_wide), then acquires.
+// thread 0 polls and acquires (bounded_wait.h: a partner that is not running in time makes the wait give up loudly); true = gave up.
 __device__ __forceinline__ void flag_post(unsigned* f, unsigned value) {
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(f, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ bool flag_wait(const unsigned* f, unsigned target, int* fault, int max_spin, int* gave_up) {
-    if (threadIdx.x == 0) {
-        int spin = 0;
-        while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            if (++spin > max_spin) {
-                __hip_atomic_store(fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                *gave_up = 1;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
+    if (threadIdx.x == 0) bounded_wait(f, target, fault, max_spin, gave_up);
     __syncthreads();
     return *gave_up != 0;
 }
@@ -898,7 +887,7 @@ extern "C" int tt_dec_gru(int B, const float* inp6, const float* state, float* f
     a.wd0 = (const unsigned char*)wd0; a.bd0 = bd0; a.wd2 = (const unsigned char*)wd2; a.bd2 = bd2;
     a.trace = g_dec_trace;
     // the two workgroups of a sample hand the state / the update gate over through flags behind the scratch maps (zeroed here,
-    // on the stream: recordable into a HIP graph); a wait that gives up sets the device's fault word (dec_chain.hip)
+    // on the stream: recordable into a HIP graph); a wait that gives up sets the device's fault word (common.cpp)
     a.flags = reinterpret_cast<unsigned*>(scratch + (size_t)B * 3 * kMapPixPad * kMapC);
     a.fault = device_fault_word();
     TT_REQUIRE(a.fault, "tt_dec_gru: cannot allocate the host-mapped fault word");

@@ -10,13 +10,16 @@
 namespace tt {
 
 void set_error(const char* fmt, ...);
-// Non-zero (and the error text set) if a tt_mlp_chain_wide barrier has timed out on the current device since the last
-// tt_clear_device_faults(): forward entry points return it first (csrc/dec_chain.hip).
+// Kernels whose workgroups wait for each other (tt_mlp_chain_wide, tt_dec_gru; the wait itself: bounded_wait.h) share one
+// host-mapped fault word per device and one poll bound (common.cpp).
+//  * refuse_after_fault: non-zero (and the error text set) if a wait has given up on the current device since the last
+//    tt_clear_device_faults(): forward entry points return it first.
+//  * device_fault_word: the current device's word (allocated on first use; null on failure).
+//  * pair_wait_max_spin: polls before a wait gives up (tt_mlp_chain_wide_set_max_spin; tests force a time-out with 0).
 int refuse_after_fault(const char* what);
-// The current device's host-mapped fault word (allocated on first use; null on failure) and the poll bound of a cross-workgroup
-// wait (tt_mlp_chain_wide_set_max_spin): for kernels whose workgroups wait for each other (tt_mlp_chain_wide, tt_dec_gru).
 int* device_fault_word();
 int pair_wait_max_spin();
+constexpr int kWaitMaxSpin = 1 << 21;    // its default (~1 s): a wrong count must not hang the device
 
 constexpr int kMaxDevices = 64;    // size of every per-device host table
 

@@ -1006,6 +1006,7 @@ def sca_reduce(x, max_len, B):
 
 # ----------------------------------------------------------------------------- decoder row chains (tt_mlp_chain)
 _ChainStage = _lib.structs()["tt_chain_stage"]
+_ChainChoice = _lib.structs()["tt_chain_choice"]
 
 
 class ChainLinear:
@@ -1028,13 +1029,18 @@ class ChainLinear:
         self.act = act
 
 
-CHAIN_WIDE = os.environ.get("TT_CHAIN_WIDE", "1") != "0"   # A/B knob: 0 = always the one-workgroup-per-32-rows kernel
-CHAIN_WIDE_MAX_ROW_BLOCKS = 16                               # beyond this the rows alone fill enough workgroups
+_chain_form = {}
 
 
 def chain_is_wide(R):
-    """Whether mlp_chain runs R rows on tt_mlp_chain_wide (callers order their stages for the form that runs)."""
-    return CHAIN_WIDE and (R + 31) // 32 <= CHAIN_WIDE_MAX_ROW_BLOCKS
+    """Whether mlp_chain runs R rows on tt_mlp_chain_wide on the current device (callers order their stages for the form that
+    runs): the form depends on the rows alone, so the library is asked, once, about the smallest chain there is."""
+    key = (R, torch.cuda.current_device())
+    if key not in _chain_form:
+        one = (_ChainStage * 1)()
+        one[0].w, one[0].K, one[0].Kp, one[0].N, one[0].in_sel = 16, 16, 16, 1, -1
+        _chain_form[key] = bool(_chain_plan(R, 16, one, 1, None, None, torch.device("cuda", key[1])).wide)
+    return _chain_form[key]
 
 
 def chain_faults():
@@ -1058,12 +1064,21 @@ def chain_wide_max_workgroups(device):
     return _wide_cap[idx]
 
 
+def _chain_plan(R, x_stride, arr, n_split, groups, wide, device):
+    """tt_mlp_chain_plan: the library's choice (csrc/chain_choose.cpp) for these rows, stages and hints on `device`."""
+    c = _ChainChoice()
+    check(lib().tt_mlp_chain_plan(R, x_stride, len(arr), arr, n_split, 0 if groups is None else max(1, groups),
+                                  0 if wide is None else 2 if wide else 1, chain_wide_max_workgroups(device), ctypes.byref(c)),
+          "tt_mlp_chain_plan")
+    return c
+
+
 def mlp_chain(x, stages, n_split=1, groups=None, wide=None):
     """x (R, >= K0) f32 rows (row-strided ok).  stages: list of dicts {lin: ChainLinear, src: -1 | earlier stage index,
     res: (tensor (R, *), coff) | None, side: tensor (R, >= side_k) | None, out: (tensor (R, *), coff) | None}.
-    Few rows (<= 512) run tt_mlp_chain_wide: the columns of every stage over `groups` workgroups per 32 rows (default: the
-    widest stage's 32-column blocks, at most 16; capped so that all workgroups are co-resident); otherwise tt_mlp_chain
-    (`n_split`: the single-stage column split of that kernel).  `wide`: force one form (tests)."""
+    The library chooses the form (tt_mlp_chain_plan): few rows (<= 512) run tt_mlp_chain_wide, the columns of every stage over
+    `groups` workgroups per row group (default: the widest stage's 32-column blocks, at most 16; capped so that all workgroups are
+    co-resident); otherwise tt_mlp_chain (`n_split`: the single-stage column split of that kernel).  `wide`: force one form."""
     require_cuda(x)
     assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
     R = x.shape[0]
@@ -1089,22 +1104,10 @@ def mlp_chain(x, stages, n_split=1, groups=None, wide=None):
             t, coff = out
             assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= R and t.shape[1] >= coff + lin.N
             d.out, d.out_stride, d.out_coff = t.data_ptr(), t.stride(0), coff
-    row_blocks = (R + 31) // 32
-    use_wide = chain_is_wide(R) if wide is None else wide
-    if use_wide:
-        row_groups = 1 if row_blocks <= 2 else (row_blocks + 3) // 4       # workgroups take 1, 2 or 4 row blocks
-        cap = min(128, chain_wide_max_workgroups(x.device))     # co-resident with room to spare (the library enforces cap)
-        if cap < row_groups:
-            if wide:
-                raise TTError(f"tt_mlp_chain_wide: {row_groups} row groups cannot be co-resident on this device ({cap})")
-            use_wide = False                                       # a small / partitioned device: the per-row-block kernel
-    if use_wide:
-        L = lib()
-        if groups is None:
-            groups = min(16, max((st["lin"].N + 31) // 32 for st in stages))
-        groups = max(1, min(groups, cap // row_groups, 64))
-        ws = _workspace(L.tt_mlp_chain_wide_workspace_bytes(R, n, arr), x.device)
-        rc = L.tt_mlp_chain_wide(ptr(x), R, x.stride(0), n, arr, groups, ptr(ws), ws.numel(), _st(x))
+    c = _chain_plan(R, x.stride(0), arr, n_split, groups, wide, x.device)
+    if c.wide:
+        ws = _workspace(c.workspace_bytes, x.device)
+        rc = lib().tt_mlp_chain_wide(ptr(x), R, x.stride(0), n, arr, c.n_groups, ptr(ws), ws.numel(), _st(x))
         if rc != -4 or wide:
             check(rc, "tt_mlp_chain_wide")
             return
