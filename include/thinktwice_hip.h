@@ -981,6 +981,11 @@ int tt_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* ex
                       float beta1, float beta2, float eps, float weight_decay, const int* good_steps_dev,
                       const float* grad_scale_or_null, void* stream);
 int tt_adamw_advance(int* good_steps_dev, const float* grad_scale_or_null, void* stream);
+/* tt_adamw_advance for the close of a gradient-accumulation window of `window_len` >= 1 micro-iterations (Trainer.step(window=)):
+ * the count advances unless the clip factor is NaN; then *skipped_iters_dev += window_len instead, so that the host can take a
+ * skipped window's micro-iterations back out of its counters whatever the window's length was (Trainer.reconcile). */
+int tt_adamw_advance_window(int* good_steps_dev, int* skipped_iters_dev, int window_len, const float* grad_scale_or_null,
+                            void* stream);
 
 /* ------------------------------------------------------------------------
  * Device log windows (thinktwice_amd/logvars.py): the logged values of a training job stay on the device from the loss terms to

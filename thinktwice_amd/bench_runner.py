@@ -10,7 +10,14 @@ synchronises on the host clock:
 Per round the order is x, x', y: (x) against (x') is the A/A spread.  Reported per iteration: the whole epoch / 12 (this is
 what the condition is about: (y) not slower than (x) by more than the A/A spread), and the steady-state hand-over interval
 (iterations 3..10 of the epoch, from the loader's hand-over times).  Then the three logvars kernels from device events, and
-the number of torch operators parse_losses dispatches with and without device_log on a dict of the real one's shapes."""
+the number of torch operators parse_losses dispatches with and without device_log on a dict of the real one's shapes.
+
+    python -m thinktwice_amd.bench_runner --cumulative-iters 1 2 4 [--out profiles/train_accumulate.txt]
+
+measures gradient accumulation instead (profiles/train_accumulate.txt): EpochRunner's epoch under every given cumulative_iters,
+one runner per k over the same loader and trainer, per round the legs [k = 1, k = 1 again, then the other k]; ms per
+micro-iteration (the epoch / 12), and k = 1 against its repeat as the A/A spread.  With `--cumulative-iters 1` alone it uses
+nothing a build without accumulation lacks, which is how the parent commit's leg is measured beside it."""
 import argparse
 import os
 import shutil
@@ -157,12 +164,73 @@ def _measure(root, metadata, B, rounds, emit):
          "by the arithmetic tests only (tests/test_runner_cpu.py)")
 
 
-def main(B, rounds, emit):
+def _measure_accumulate(root, metadata, B, rounds, ks, emit):
+    import torch
+    from . import dataset, model as tm, params
+    from .loader import DeviceBatchLoader
+    from .runner import EpochRunner
+    from .trainer import Trainer
+    if not torch.cuda.is_available():
+        raise SystemExit("needs a GPU: nothing here is measured on the host alone")
+    emit(f"build {build.source_fingerprint()} device {torch.cuda.get_device_name(0)}")
+    sync, med = torch.cuda.synchronize, statistics.median
+    index = dataset.DatasetIndex(metadata, ["town01_00"], bench_loader.CFG, root=root)
+    n = bench_loader.LINKS
+    loader = DeviceBatchLoader(index, bench_loader.CFG, calib.IDA_AUG_CONF, batch_size=B, seed=1, prefetch=2, threads=8,
+                               png=dict(verify=("adler32",), segments="require"))
+    model, cfg = tm.build_thinktwice(dtype="f32x3", device="cuda")
+    trainer = Trainer(model, params.init_params(cfg, seed=0), frozen_bn=False)
+    trainer.set_schedule(10 ** 6 * n, n)
+    works, runners = [], {}
+    for k in ks:
+        works.append(tempfile.mkdtemp(prefix="tt_bench_runner_"))
+        runners[k] = EpochRunner(trainer, loader, work_dir=works[-1], max_epochs=10 ** 6, log_interval=4, verbose=False,
+                                 **({"cumulative_iters": k} if k > 1 else {}))
+    legs = [(1, "a"), (1, "b")] + [(k, "a") for k in ks if k != 1]          # per round: k = 1, its repeat, the others
+    times = {leg: [] for leg in legs}
+    e = 0
+    for k in ks:                                                           # warm-up: allocator, first launches, every path
+        runners[k]._train_epoch(e)
+        e += 1
+    sync()
+    for _ in range(rounds):
+        for leg in legs:
+            sync()
+            t0 = time.perf_counter()
+            runners[leg[0]]._train_epoch(e)
+            sync()
+            times[leg].append((time.perf_counter() - t0) * 1e3 / n)
+            e += 1
+    trainer.reconcile()
+    loader.close()
+    for w in works:
+        shutil.rmtree(w, ignore_errors=True)
+    a, b = times[1, "a"], times[1, "b"]
+    base, spread = med(a + b), abs(med(a) - med(b))
+    emit(f"B = {B}, thinktwice.py size, f32x3, frozen_bn=False, prefetch = 2, {n} iterations per epoch, log_interval = 4, {rounds} "
+         f"rounds of [{', '.join(f'k = {k}' + chr(39) * (tag == 'b') for k, tag in legs)}], one epoch of EpochRunner per leg; host "
+         f"clock, a device synchronise before and after every leg; medians, ms per MICRO-iteration over the epoch")
+    emit(f"  cumulative_iters = 1 (plain steps):   {base:8.1f} ms (k = 1 {med(a):.1f}, k = 1' {med(b):.1f}: A/A spread {spread:.1f} ms; "
+         f"min {min(a + b):.1f}, max {max(a + b):.1f}, n = {len(a + b)})")
+    for k in ks:
+        if k == 1:
+            continue
+        t = times[k, "a"]
+        emit(f"  cumulative_iters = {k} ({n // k} updates per epoch): {med(t):8.1f} ms (min {min(t):.1f}, max {max(t):.1f}, n = {len(t)}); "
+             f"{med(t) - base:+.1f} ms against k = 1 beside it")
+    emit(f"  skipped updates found by reconcile() over the whole run: {trainer.opt.skipped()}")
+    return base, spread, {k: med(times[k, "a"]) for k in ks if k != 1}
+
+
+def main(B, rounds, emit, cumulative_iters=None):
     tmp = tempfile.mkdtemp(prefix="tt_bench_runner_data_")
     try:
         root, metadata, _, _, writer = bench_loader.write_dataset(tmp, B)
         emit(f"dataset: bench_loader's (one route of {B + 5} frames under {bench_loader.LINKS} names, PNG files written by {writer}, "
              f"segmented at R = {bench_loader.ROWS})")
+        if cumulative_iters:
+            _measure_accumulate(root, metadata, B, rounds, sorted(set([1] + list(cumulative_iters))), emit)
+            return
         _measure(root, metadata, B, rounds, emit)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
@@ -173,6 +241,8 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the report to this file")
+    ap.add_argument("--cumulative-iters", type=int, nargs="+", default=None, metavar="K", help="measure EpochRunner under these "
+                    "cumulative_iters instead (k = 1 is always measured, twice per round)")
     args = ap.parse_args()
     lines = []
 
@@ -180,7 +250,7 @@ if __name__ == "__main__":
         print(s, flush=True)
         lines.append(s)
 
-    main(args.batch, args.rounds, emit)
+    main(args.batch, args.rounds, emit, args.cumulative_iters)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

@@ -103,6 +103,16 @@ __global__ void adamw_advance_kernel(int* good_steps, const float* __restrict__ 
     if (gs == gs) *good_steps += 1;
 }
 
+// The same for the close of a gradient-accumulation window of `window_len` micro-iterations (Trainer.step(window=...)): a skipped
+// window additionally leaves its length in `*skipped_iters`, because windows differ in length (an epoch's remainder window) and
+// the host, running ahead, has counted every micro-iteration.
+__global__ void adamw_advance_window_kernel(int* good_steps, int* skipped_iters, int window_len,
+                                            const float* __restrict__ grad_scale) {
+    const float gs = grad_scale ? *grad_scale : 1.f;
+    if (gs == gs) *good_steps += 1;
+    else *skipped_iters += window_len;
+}
+
 }  // namespace tt
 
 using namespace tt;
@@ -152,4 +162,12 @@ extern "C" int tt_adamw_advance(int* good_steps_dev, const float* grad_scale_or_
     TT_REQUIRE(good_steps_dev, "tt_adamw_advance: null");
     hipLaunchKernelGGL(adamw_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, good_steps_dev, grad_scale_or_null);
     return check_launch("tt_adamw_advance");
+}
+
+extern "C" int tt_adamw_advance_window(int* good_steps_dev, int* skipped_iters_dev, int window_len,
+                                       const float* grad_scale_or_null, void* stream) {
+    TT_REQUIRE(good_steps_dev && skipped_iters_dev && window_len >= 1, "tt_adamw_advance_window: bad args");
+    hipLaunchKernelGGL(adamw_advance_window_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, good_steps_dev, skipped_iters_dev,
+                       window_len, grad_scale_or_null);
+    return check_launch("tt_adamw_advance_window");
 }

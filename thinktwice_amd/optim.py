@@ -19,6 +19,8 @@ class FlatAdamW:
         # is skipped there, and the bias corrections / the checkpointed `step` must stay with the untouched moments
         self.steps_dev = torch.zeros(1, dtype=torch.int32, device=flat_param.device)
         self.issued, self._base = 0, 0   # optimizer steps issued by the host since the count was set (>= the applied ones)
+        # micro-iterations of the accumulation windows the device skipped (tt_adamw_advance_window) since the count was set
+        self.skipped_iters_dev = torch.zeros(1, dtype=torch.int32, device=flat_param.device)
         self._ws = torch.empty(1024, dtype=torch.float32, device=flat_param.device)
         self.norm_scale = torch.zeros(2, dtype=torch.float32, device=flat_param.device)   # [||g||, clip factor]
 
@@ -30,11 +32,16 @@ class FlatAdamW:
     @steps.setter
     def steps(self, n):
         self.steps_dev.fill_(int(n))
+        self.skipped_iters_dev.zero_()
         self._base, self.issued = int(n), 0
 
     def skipped(self):
         """Issued optimizer steps the device did NOT apply (non-finite gradient norm) since the count was last set.  Blocking."""
         return self.issued - (self.steps - self._base)
+
+    def skipped_iters(self):
+        """Micro-iterations of the accumulation windows (`step(window_len=...)`) the device did not apply.  Blocking."""
+        return int(self.skipped_iters_dev.item())
 
     def state_dict(self):
         """Adam moments + step count (what an mmcv checkpoint's `optimizer` entry carries for a resume)."""
@@ -46,10 +53,12 @@ class FlatAdamW:
         self.v.copy_(sd["exp_avg_sq"].to(self.v.device))
         self.steps = int(sd["step"])
 
-    def step(self, lr=None, live_ranges=None):
+    def step(self, lr=None, live_ranges=None, window_len=None):
         """One optimizer step; returns the (device) tensor [grad norm, clip factor] of this step.  `live_ranges`: [(offset,
         count)] element ranges to update -- torch's AdamW skips parameters whose .grad is None (the reference's 90 dead
-        ones: no weight decay, no moment update); the ranges of the others, merged, are what this step touches."""
+        ones: no weight decay, no moment update); the ranges of the others, merged, are what this step touches.
+        `window_len`: the step closes a gradient-accumulation window of that many micro-iterations; if the device skips it,
+        `skipped_iters()` grows by the window's length."""
         st = cur_stream(self.p.device)
         scale = None
         if self.max_norm is not None:
@@ -62,7 +71,11 @@ class FlatAdamW:
             check(lib().tt_adamw_step_dev(at(self.p), at(self.g), at(self.m), at(self.v), cnt,
                                           self.lr if lr is None else lr, self.betas[0], self.betas[1],
                                           self.eps, self.wd, ptr(self.steps_dev), scale, st), "tt_adamw_step_dev")
-        check(lib().tt_adamw_advance(ptr(self.steps_dev), scale, st), "tt_adamw_advance")
+        if window_len is None:
+            check(lib().tt_adamw_advance(ptr(self.steps_dev), scale, st), "tt_adamw_advance")
+        else:
+            check(lib().tt_adamw_advance_window(ptr(self.steps_dev), ptr(self.skipped_iters_dev), int(window_len), scale, st),
+                  "tt_adamw_advance_window")
         return self.norm_scale
 
 

@@ -32,6 +32,20 @@ def log_schedule(iters_per_epoch, log_interval, ignore_last=True):
     return out
 
 
+def accumulation_plan(n_iters, k):
+    """[(j, k_eff)] for the `n_iters` iterations of one epoch under gradient accumulation over `k`: iteration i is micro-step j
+    of a window of k_eff, which updates at j == k_eff - 1.  mmcv's GradientCumulativeOptimizerHook restated (mmcv is not
+    installed where this is built, so the rule is owned here): divisible_iters = n // k * k iterations form full windows with
+    loss factor k; the n % k iterations after them form ONE short window whose loss factor is its own length, closed by the
+    last iteration.  EpochRunner applies the plan per epoch (n = len(train_loader)): a window never spans an epoch boundary,
+    where mmcv counts over the run's global iteration -- the two coincide when len(loader) % k == 0."""
+    n_iters, k = int(n_iters), int(k)
+    if n_iters < 0 or k < 1:
+        raise ValueError(f"accumulation_plan: n_iters {n_iters} >= 0 and k {k} >= 1")
+    divisible = n_iters // k * k
+    return [(i % k, k) if i < divisible else (i - divisible, n_iters - divisible) for i in range(n_iters)]
+
+
 def merge_ranks(parts):
     """collect_results_cpu's merge (eval_tool.py:146-160) over `parts` = [(means of rank r, samples of rank r)] in rank
     order: per name sum_r mean_r * n_r / sum_r n_r, Python floats.  A rank that saw no sample contributes nothing."""
@@ -110,12 +124,19 @@ class EpochRunner:
     """See the module text.  `trainer`: a trainer.Trainer; the loaders: loader.DeviceBatchLoader (train=True / False) -- anything
     with __len__, __iter__, set_epoch and, for a bit-identical resume, state() / load_state().  `save_best`: a logged name;
     the checkpoint of the epoch with the LOWEST validation mean of it is kept as best_{name}.pth.  `make_window`: the factory of
-    the log windows (default: logvars.LogWindow on the model's device)."""
+    the log windows (default: logvars.LogWindow on the model's device).  `cumulative_iters` = k > 1: gradient accumulation, one
+    optimizer update per window of k iterations (`accumulation_plan`, per epoch; the trainer's step(window=...)); 1: plain
+    steps, the trainer's step() without a window.  The logged values of a window's micro-steps are held back (on the device) and
+    added at its close, all gated by that close's gradient norm: a skipped window adds nothing to the means and counts its
+    length as skipped.  `log_interval` and a line's `iter` count micro-iterations; a log window whose turn comes inside an
+    accumulation window closes once that window's adds are issued, and its `iterations` says what it holds."""
 
     def __init__(self, trainer, train_loader, val_loader=None, work_dir="work_dir", max_epochs=1, log_interval=100,
-                 ckpt_interval=1, eval_interval=1, ignore_last=True, save_best=None, dist=None, make_window=None, verbose=True):
-        if min(int(max_epochs), int(log_interval), int(ckpt_interval), int(eval_interval)) < 1:
-            raise ValueError("EpochRunner: max_epochs and the intervals are >= 1")
+                 ckpt_interval=1, eval_interval=1, ignore_last=True, save_best=None, dist=None, make_window=None, verbose=True,
+                 cumulative_iters=1):
+        if min(int(max_epochs), int(log_interval), int(ckpt_interval), int(eval_interval), int(cumulative_iters)) < 1:
+            raise ValueError("EpochRunner: max_epochs, the intervals and cumulative_iters are >= 1")
+        self.cumulative_iters = int(cumulative_iters)
         self.trainer, self.train_loader, self.val_loader = trainer, train_loader, val_loader
         self.work_dir, self.max_epochs, self.log_interval = str(work_dir), int(max_epochs), int(log_interval)
         self.ckpt_interval, self.eval_interval, self.ignore_last = int(ckpt_interval), int(eval_interval), bool(ignore_last)
@@ -168,17 +189,30 @@ class EpochRunner:
         window, pending = self.window, collections.deque()
         loader.set_epoch(e)
         t_last, i_last = time.perf_counter(), 0
+        plan = accumulation_plan(n, self.cumulative_iters) if self.cumulative_iters > 1 else None
+        held, due = [], None         # an open accumulation window's logged values; the log close whose turn has come: (iter, lr)
         for i, batch in enumerate(loader, 1):
             while pending and pending[0][0].ready():                  # non-blocking: written when the copy has arrived
                 self._write_window(*pending.popleft())
             lr = trainer.current_lr()
-            out = trainer.step(batch, check_finite=False, device_log=True)
-            window.add(out["log_vars"], out["num_samples"], gate=out["grad_norm"], extra={"grad_norm": out["grad_norm"]})
             if i in closes:
+                due = (i, lr)
+            if plan is None:
+                out = trainer.step(batch, check_finite=False, device_log=True)
+            else:
+                out = trainer.step(batch, check_finite=False, device_log=True, window=plan[i - 1])
+                if not out["updated"]:
+                    held.append((out["log_vars"], out["num_samples"]))
+                    continue
+                for log_vars, num in held:                            # the window's earlier micro-steps, under ITS gate
+                    window.add(log_vars, num, gate=out["grad_norm"], extra={"grad_norm": out["grad_norm"]})
+                held = []
+            window.add(out["log_vars"], out["num_samples"], gate=out["grad_norm"], extra={"grad_norm": out["grad_norm"]})
+            if due is not None:
                 now = time.perf_counter()
-                head = OrderedDict(mode="train", epoch=e + 1, iter=i, lr=lr, time=(now - t_last) / (i - i_last))
+                head = OrderedDict(mode="train", epoch=e + 1, iter=due[0], lr=due[1], time=(now - t_last) / (i - i_last))
                 pending.append((window.close(), head))
-                t_last, i_last = now, i
+                t_last, i_last, due = now, i, None
         if window.adds:
             window.close()                                            # ignore_last: the incomplete window is dropped
         while pending:
@@ -192,7 +226,10 @@ class EpochRunner:
         if self.world > 1:                                            # every rank draws its own augmentation stream
             states = [None] * self.world
             self.dist.all_gather_object(states, state)
-        return {"loader": states, "dropout_seed": list(ops.DROPOUT_SEED), "best": self.best}
+        meta = {"loader": states, "dropout_seed": list(ops.DROPOUT_SEED), "best": self.best}
+        if self.cumulative_iters > 1:                                 # (absent: 1, what every earlier checkpoint is)
+            meta["cumulative_iters"] = self.cumulative_iters
+        return meta
 
     def _save(self, ckpt, name):
         path = os.path.join(self.work_dir, name)
@@ -255,5 +292,10 @@ class EpochRunner:
                 self.train_loader.load_state(mine)
             ops.DROPOUT_SEED[:] = list(state["dropout_seed"])
             self.best = state.get("best")
+            k = int(state.get("cumulative_iters", 1))
+            if k != self.cumulative_iters:
+                warnings.warn(f"{path} was written with cumulative_iters={k}, this run uses {self.cumulative_iters}: accepted, "
+                              f"accumulation windows never cross an epoch boundary and checkpoints are written at epoch ends "
+                              f"(the effective batch, and with it the suitable rate, changes)")
         self.epoch = int(meta.get("epoch", 0) or 0)
         return self.epoch

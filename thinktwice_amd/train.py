@@ -1,7 +1,7 @@
 """Train from a dataset directory (the reference's open_loop_training/train.py with configs/thinktwice.py):
 
     python -m thinktwice_amd.train --data-root <dir the route paths are relative to> --metadata <dataset_metadata.pkl> \\
-        --work-dir work --epochs 60 --batch-size 8 [--resume auto] [--load-from weights.pth]
+        --work-dir work --epochs 60 --batch-size 8 [--cumulative-iters 2] [--resume auto] [--load-from weights.pth]
     python -m torch.distributed.run --nproc_per_node 8 -m thinktwice_amd.train ...          # one rank per GPU
 
 It builds the model, a trainer.Trainer, the train and validation dataset.DatasetIndex and loader.DeviceBatchLoader and hands
@@ -24,6 +24,9 @@ def parse_args(argv=None):
     ap.add_argument("--epochs", type=int, default=dc.TOTAL_EPOCHS)
     ap.add_argument("--batch-size", type=int, default=dc.BATCH_SIZE_PER_GPU, help="per GPU")
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--cumulative-iters", type=int, default=1, metavar="K", help="accumulate gradients over K iterations per "
+                    "optimizer update (mmcv GradientCumulativeOptimizerHook): the effective global batch is world x batch-size x K; "
+                    "the reference's recipe, lr 1e-4, is a global batch of 128")
     ap.add_argument("--dtype", choices=DTYPES, default="f32x3", help="convolution arithmetic: exact f32 or the bf16x3 split")
     ap.add_argument("--final-dim", type=int, nargs=2, default=None, metavar=("H", "W"), help="reduced image size (default 448 896)")
     ap.add_argument("--dev", action="store_true", help="the reference's is_dev split: town01_00, 10 samples")
@@ -50,7 +53,7 @@ def assemble(args):
     final_dim = tuple(args.final_dim) if args.final_dim else None
     metadata = args.metadata or os.path.join(args.data_root, "..", "dataset", "dataset_metadata.pkl")
     return {"cfg": cfg, "ida_aug_conf": dc.ida_aug_conf(final_dim), "overrides": {} if final_dim is None else {"final_dim": final_dim},
-            "metadata": metadata, "root": args.data_root,
+            "metadata": metadata, "root": args.data_root, "cumulative_iters": args.cumulative_iters,
             "trainer": dict(lr=args.lr, frozen_bn=bool(args.frozen_bn)),
             "loader": dict(batch_size=args.batch_size, seed=args.seed, augment=not args.no_augment),
             "runner": dict(work_dir=args.work_dir, max_epochs=args.epochs, log_interval=args.log_interval,
@@ -94,7 +97,11 @@ def main(argv=None):
         if len(val_index):
             val_loader = DeviceBatchLoader(val_index, cfg, conf["ida_aug_conf"], device=device, train=False, rank=rank, world=world,
                                            batch_size=args.batch_size, seed=args.seed)
-        runner = EpochRunner(trainer, train_loader, val_loader, verbose=rank == 0, **conf["runner"])
+        runner = EpochRunner(trainer, train_loader, val_loader, verbose=rank == 0, cumulative_iters=conf["cumulative_iters"],
+                             **conf["runner"])
+        if rank == 0:
+            print(f"effective global batch: {world} x {args.batch_size} x {conf['cumulative_iters']} = "
+                  f"{world * args.batch_size * conf['cumulative_iters']} (world x batch-size x cumulative-iters)", flush=True)
         try:
             if args.resume:
                 runner.resume(args.resume)

@@ -52,6 +52,10 @@ class Trainer:
         self._stepped = set()          # names of the parameters the optimizer has updated at least once (torch: those with state)
         self.iteration, self.epoch, self._bn_steps = 0, 0, 0
         self._skips_accounted = 0      # device-skipped updates already taken out of iteration / _bn_steps (reconcile())
+        # gradient accumulation (step(window=(j, k))): the open window as (next j, k), the names its micro-steps reached, the
+        # closes issued and the skipped windows' micro-iterations accounted since the last reconcile()
+        self._window, self._window_names, self._window_closes, self._skipped_iters_accounted = None, set(), 0, 0
+        self._seg_table, self._window_scales, self._issued_seen = None, {}, 0
         self.schedule = None           # set_schedule(): the reference's lr_config
         self._prepare_on_device = os.environ.get("TT_TRAIN_PREPARE", "device") != "host"
         # BatchNorm running statistics: device copies the prepared layers alias (train mode updates them in place)
@@ -133,8 +137,24 @@ class Trainer:
         gradient norm is not finite (p, m, v and the applied-step count untouched; non-finite batch statistics never reach
         the BatchNorm running buffers either, tt_bn_finalize).  This takes those skipped iterations back out of the host's
         counters (`iteration`, the BatchNorm call count) so that checkpoints agree with the device; called by state_dict() /
-        optimizer_state_dict() / checkpoint().  Returns the number of skipped updates found."""
+        optimizer_state_dict() / checkpoint().  Returns the number of skipped updates found.
+
+        Accumulation windows: a skipped update is a skipped WINDOW, and `iteration` goes back by the window's length, which
+        the device recorded (tt_adamw_advance_window: remainder windows are shorter than k).  `_bn_steps` does NOT go back for
+        a skipped window: its micro-steps' forwards ran, their batch statistics went into the running buffers when they ran,
+        and torch's num_batches_tracked counts train-mode forwards, not optimizer updates -- the counter stays with what the
+        device holds.  Between two reconciles the steps are either all plain or all window closes (step() reconciles where the
+        form changes), so one applied-step count tells both cases apart."""
         k = self.opt.skipped() - self._skips_accounted
+        windows, self._window_closes, self._issued_seen = self._window_closes, 0, self.opt.issued
+        if windows:
+            lost = self.opt.skipped_iters() - self._skipped_iters_accounted
+            self._skipped_iters_accounted += lost
+            self.iteration -= lost
+            self._skips_accounted += max(k, 0)
+            if self.schedule is not None:
+                self.epoch = self.iteration // self.schedule["iters_per_epoch"]
+            return max(k, 0)
         if k > 0:
             self.iteration -= k
             if not self.frozen_bn:
@@ -144,14 +164,125 @@ class Trainer:
                 self.epoch = self.iteration // self.schedule["iters_per_epoch"]
         return max(k, 0)
 
-    def step(self, batch, lr=None, check_finite=True, device_log=False):
+    # ---- gradient accumulation (mmcv GradientCumulativeOptimizerHook(cumulative_iters=k); the window policy is the caller's:
+    # runner.accumulation_plan)
+    @property
+    def window_open(self):
+        """An accumulation window has taken a micro-step and is not closed yet."""
+        return self._window is not None
+
+    def abandon_window(self):
+        """Drop an open window (after an exception inside one of its micro-steps): the next window=(0, k) starts clean.  The
+        counters keep the micro-steps taken."""
+        self._window = None
+
+    def _no_open_window(self, what):
+        if self._window is not None:
+            raise TTError(f"Trainer.{what}: accumulation window open at micro-step {self._window[0]} of {self._window[1]}; a "
+                          f"half-summed gradient is not something a checkpoint holds -- close the window first")
+
+    def _window_step(self, batch, lr, check_finite, device_log, window):
+        """step(window=(j, k)): micro-step j (0-based) of a window of k.  Every micro-step runs forward + reverse sweep and
+        DEPOSITS the tape's parameter gradients into the flat buffer scaled by 1/k (mmcv: loss / k before backward), one
+        launch of tt_grad_gather: j == 0 zeroes the buffer and writes scale * g (never 0 * old + scale * g: a NaN left by a
+        skipped window does not survive), j > 0 adds.  `iteration`, the BatchNorm call count, the running statistics and the
+        dropout counter move on every micro-step.  j < k - 1 does nothing else (no collective, no clip, no AdamW, no operand
+        preparation, no host synchronisation; `grad_norm` None, `updated` False, `check_finite` has nothing to look at).
+        j == k - 1 closes: one all-reduce, clip + AdamW over the union of the micro-steps' live ranges at the closing
+        iteration's rate, operands re-prepared; `updated` True.  A non-finite norm skips the update on the device as in step();
+        reconcile() takes the whole window's micro-iterations back out of `iteration` (see there for `_bn_steps`)."""
+        from . import ops
+        if window is None:
+            if self._window is not None:
+                raise ValueError(f"Trainer.step: window=None while an accumulation window is open (next: micro-step "
+                                 f"{self._window[0]} of {self._window[1]})")
+            self.reconcile()       # plain steps after window closes: one blocking read where the form changes, none after it
+            return self.step(batch, lr=lr, check_finite=check_finite, device_log=device_log)
+        j, k = (int(v) for v in window)
+        if not (k >= 1 and 0 <= j < k):
+            raise ValueError(f"Trainer.step: window=({j}, {k}) is not a micro-step j of k with 0 <= j < k")
+        if self._window is None and j != 0:
+            raise ValueError(f"Trainer.step: window=({j}, {k}) with no window open; a window starts at micro-step 0")
+        if self._window is not None and (j, k) != self._window:
+            raise ValueError(f"Trainer.step: window=({j}, {k}) does not continue the open window, whose next micro-step is "
+                             f"{self._window[0]} of {self._window[1]}")
+        if j == 0:
+            if self.opt.issued - self._issued_seen > self._window_closes:
+                self.reconcile()   # window closes after plain steps: the same single read
+            self._window_names = set()
+        if j == k - 1 and lr is None and self.schedule is not None:
+            lr = self.current_lr()
+        was_training = self.model.training
+        self.model.train(not self.frozen_bn)
+        try:
+            with autodiff.Tape(x3=self.x3, release=True) as tape:
+                out = self.model.train_step(batch, None, device_log=True) if device_log else self.model.train_step(batch, None)
+                tape.backward()
+        finally:
+            self.model.train(was_training)
+        grads = tape.param_grads
+        if self._seg_table is None:
+            # two tables in turn: uploading one waits for ITS previous upload only, two micro-steps back
+            self._seg_table = [ops.GradSegTable(self.flat_param.device) for _ in range(2)]
+            self._offsets = dict(zip(self.names, self.grads.offsets))
+        unknown = [n for n in grads if n not in self._offsets]
+        assert not unknown, f"gradients for names outside the state_dict: {unknown[:5]}"
+        srcs, offs = [], []
+        for name, g in grads.items():
+            assert g.numel() == self.sd[name].numel() and g.dtype == torch.float32, name
+            srcs.append(g.reshape(-1) if g.is_contiguous() else g.contiguous().view(-1))
+            offs.append(self._offsets[name])
+        if k not in self._window_scales:
+            self._window_scales[k] = torch.full((1,), 1.0 / k, dtype=torch.float32, device=self.flat_param.device)
+        if j == 0:
+            self.grads.zero_()
+        table = self._seg_table[self.iteration & 1].upload(srcs, offs, self.grads.numel)
+        ops.grad_gather(table, self.grads.flat, self._window_scales[k], accumulate=j > 0)
+        self._window = (j + 1, k) if j < k - 1 else None
+        self.param_grads = grads
+        self._window_names.update(grads)
+        self.iteration += 1
+        if not self.frozen_bn:
+            self._bn_steps += 1
+        if self.schedule is not None:
+            self.epoch = self.iteration // self.schedule["iters_per_epoch"]
+        if j < k - 1:
+            out["grad_norm"], out["updated"] = None, False
+            return out
+        runs, off = [], 0
+        for name in self.names:
+            n = self.sd[name].numel()
+            if name in self._window_names:
+                if runs and runs[-1][0] + runs[-1][1] == off:
+                    runs[-1][1] += n
+                else:
+                    runs.append([off, n])
+            off += n
+        self.live_ranges = [tuple(r) for r in runs]
+        self.grads.all_reduce_mean()
+        out["grad_norm"], out["updated"] = self.opt.step(lr, live_ranges=self.live_ranges, window_len=k), True
+        self._window_closes += 1
+        if check_finite and not bool(torch.isfinite(out["grad_norm"][0])):
+            self.reconcile()                        # takes the window's k micro-iterations back out of `iteration`
+            raise FloatingPointError("Trainer.step: non-finite gradient norm at the close of an accumulation window; the update "
+                                     "was skipped on the device (weights, Adam moments and the step count are those of the last "
+                                     "good update)")
+        self._stepped.update(self._window_names)
+        self._prepare()
+        return out
+
+    def step(self, batch, lr=None, check_finite=True, device_log=False, window=None):
         """One iteration; adds `grad_norm` (device tensor [norm, clip factor]) to train_step's dict.  A non-finite gradient
         norm never reaches the weights: tt_grad_norm_clip hands the update a NaN factor and tt_adamw_step_dev skips (p, m, v
         and the device-side step count untouched).  `check_finite` (one host sync per iteration) additionally raises here;
         pass False to look at `grad_norm` whenever convenient (reconcile() squares the host counters with what the device
         applied).  That alone does not make the step asynchronous: the float `log_vars` are read from the device every
         iteration.  With `device_log=True` as well they stay there (a logvars.DeviceLogVars, for a logvars.LogWindow) and the
-        step issues no host synchronisation of its own.  Without `lr`, the rate of set_schedule() (else the constructor's)."""
+        step issues no host synchronisation of its own.  Without `lr`, the rate of set_schedule() (else the constructor's).
+        `window=(j, k)`: this call is micro-step j of a gradient-accumulation window of k (_window_step; the dict then also
+        carries `updated`).  `window=None` is the plain iteration below."""
+        if window is not None or self._window is not None or self._window_closes:
+            return self._window_step(batch, lr, check_finite, device_log, window)
         if lr is None and self.schedule is not None:
             lr = self.current_lr()
         out = self.backward(batch, device_log=device_log)
@@ -200,6 +331,7 @@ class Trainer:
     def state_dict(self):
         """Reference-format weights (own copies: the master tensors are views of one flat buffer), BatchNorm running
         statistics and `num_batches_tracked` as they stand now."""
+        self._no_open_window("state_dict")
         self.reconcile()
         out = {}
         for k, v in self.sd.items():
@@ -218,6 +350,7 @@ class Trainer:
         resume, train.py:238 / EpochBasedRunner.resume): per-parameter state keyed by the parameter's index in
         model.parameters() order (= state_dict order without the buffers), plus one param_group.  Parameters that never
         received a gradient carry no state, exactly like torch's `grad is None` ones (the reference's 90 dead parameters)."""
+        self._no_open_window("optimizer_state_dict")
         self.reconcile()
         o = self.opt
         steps = o.steps
@@ -240,6 +373,7 @@ class Trainer:
     def load_optimizer_state_dict(self, osd):
         o = self.opt
         self._skips_accounted = 0                  # (setting the step count restarts the issued / applied bookkeeping)
+        self._window_closes = self._skipped_iters_accounted = self._issued_seen = 0
         if "exp_avg" in osd:                       # round-3 flat layout (whole-buffer moments)
             o.load_state_dict(osd)
             self._stepped = set(self.names)
@@ -268,11 +402,13 @@ class Trainer:
     def checkpoint(self, epoch=None):
         """What an mmcv checkpoint holds for a resume (configs/thinktwice.py:292 checkpoint_config, mmcv save_checkpoint):
         `meta` (epoch / iter), `state_dict` (reference key names), `optimizer` (torch AdamW layout)."""
+        self._no_open_window("checkpoint")
         self.reconcile()
         return {"meta": {"epoch": self.epoch if epoch is None else epoch, "iter": self.iteration},
                 "state_dict": self.state_dict(), "optimizer": self.optimizer_state_dict()}
 
     def load_checkpoint(self, ckpt):
+        self._window = None                        # (a half-summed window does not outlive the weights it was computed on)
         sd = ckpt["state_dict"]
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
         with torch.no_grad():
@@ -293,4 +429,5 @@ class Trainer:
             # this load are not taken out of the freshly loaded iteration count by the next reconcile()
             self.opt.steps = self.opt.steps
             self._skips_accounted = 0
+            self._window_closes = self._skipped_iters_accounted = self._issued_seen = 0
         self._prepare()
