@@ -237,6 +237,13 @@ typedef struct tt_conv_desc {
     int in_up2;
 } tt_conv_desc;
 
+/* The two row counts callers route by (csrc/conv_choose.h derives its bounds from them; thinktwice_amd/ops.py reads them here).
+ * TT_CONV_SMALL_ROWS: up to this many output rows a plain dense layer runs the exact-f32 latency kernel (conv_small.hip), whose
+ * sums no bf16x3 form reproduces, so "N*OH*OW > 4096" in the contracts above and below is "more than TT_CONV_SMALL_ROWS".
+ * TT_CONV_JOIN_MIN_ROWS: fewest rows from which every routed form of a joined stage (tt_conv_next) beats its two launches. */
+#define TT_CONV_SMALL_ROWS 4096
+#define TT_CONV_JOIN_MIN_ROWS 32768
+
 /* A JOINED STAGE for tt_conv2d_fwd_next (bf16x3 layers: dtype TT_F32, weight_x3 given): the 1 x 1 / stride 1 convolution that reads the
  * layer's output runs in the SAME launch, on each row tile of `out` while it is still on chip,
  *   next_out = next_act(next_scale * (next_weight . out) + next_shift),

@@ -5,18 +5,16 @@ and both sides of every threshold; the chooser must reproduce it, and the label 
 hold, row for row.  Its last rows were never launched: they are that commit's tt_conv2d_splitk_slices (host only) on layers beyond
 the bounds at which ops.conv2d asks, with the workspace the answer sizes attached."""
 import ctypes
-import importlib.util
 import json
 import os
 
 import pytest
 import torch
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-_spec = importlib.util.spec_from_file_location("conv_choice_sweep", os.path.join(ROOT, "tools", "conv_choice_sweep.py"))
-sweep = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(sweep)
-ROWS = json.load(open(os.path.join(ROOT, "tests", "conv_choice_cases.json")))["cases"]
+from thinktwice_amd import ops
+from tools import conv_choice_sweep as sweep
+
+ROWS = json.load(open(os.path.join(os.path.dirname(__file__), "conv_choice_cases.json")))["cases"]
 
 X3_SPLITK = "conv_igemm_glds_kernel<float, 64, 8, 1, 128, 2, false, true> split-K"
 
@@ -28,9 +26,7 @@ def _lib():
 
 def _plan(case):
     """Label (or "ERROR: text") tt_conv2d_plan gives the descriptor ops.conv2d / ops.gather_conv build for a sweep-style case."""
-    L = _lib()
-    row, _ = sweep.describe(case, L)
-    return sweep.plan_label(L, sweep.dict_to_desc(row))
+    return ops.plan_label(sweep.dict_to_desc(sweep.describe(case, _lib())[0]))
 
 
 def test_the_recorded_choices_are_reproduced():
@@ -38,7 +34,7 @@ def test_the_recorded_choices_are_reproduced():
     assert len(ROWS) > 100
     bad = []
     for r in ROWS:
-        got = sweep.plan_label(L, sweep.dict_to_desc(r["desc"]))
+        got = ops.plan_label(sweep.dict_to_desc(r["desc"]))
         if "label" not in r:      # a query-only row: with the slices it asked for the layer splits K, with none it does not
             if got.startswith("ERROR") or ("split-K" in got) != (r["query"] > 0):
                 bad.append((r["name"], got, r["query"]))
@@ -51,7 +47,7 @@ def test_the_recorded_choices_are_reproduced():
                 bad.append((r["name"], n, r["query"]))
     assert not bad, bad
     # the far bounds of the bf16x3 split-K tile, on both sides: counts of the commit before the chooser
-    asked = {r["name"]: (r["query"], sweep.plan_label(L, sweep.dict_to_desc(r["desc"]))) for r in ROWS if "label" not in r}
+    asked = {r["name"]: (r["query"], ops.plan_label(sweep.dict_to_desc(r["desc"]))) for r in ROWS if "label" not in r}
     for name, n in (("query x3 M=8192", 2), ("query x3 K=1024", 4), ("query x3 255 tiles", 2), ("query x3 32 taps", 4)):
         assert asked[name] == (n, X3_SPLITK), (name, asked[name])
     for name in ("query x3 M=8193", "query x3 K=992", "query x3 256 tiles", "query x3 33 taps", "query x3 pixel shuffle"):
@@ -100,16 +96,18 @@ def test_the_label_tables_of_the_gpu_tests_hold():
     assert got == T.LAUNCH_STATE_LABELS, got
 
 
-def test_pair_ok_is_pinned_to_the_chooser():
-    """ops.pair_ok restates part of the bf16x3 LDS-DMA kernels' contract on the Python side (deliberately stricter in rows: up to
-    4096 the non-pair consumer would be the exact-f32 small kernel).  Wherever it says yes, the library takes the pair-format layer."""
-    from thinktwice_amd import ops
+def test_pair_ok_over_the_grid():
+    """ops.pair_ok from plain numbers: more than 4096 rows (up to there the non-pair consumer would be the exact-f32 small kernel, so
+    the caller is stricter than the library, which takes pair format from 2048 rows) and a layer the library takes.  Wherever it says
+    yes, the library plans the pair-format layer the sweep tool describes; the answers themselves are stated here."""
     yes = 0
     for rows in (2048, 4096, 4097, 65536):
         for cin in (16, 32, 48, 64, 96):
             for cout in (4, 8, 12, 32, 48, 64, 96, 256):
                 for k in (1, 3):
-                    if ops.pair_ok(rows, cin, cout, k * k):
+                    ok = ops.pair_ok(rows, cin, cout, k * k)
+                    assert ok == (rows > 4096 and cin % 32 == 0 and k * k * cin >= 64 and cout not in (4, 48)), (rows, cin, cout, k)
+                    if ok:
                         yes += 1
                         label = _plan(sweep.D("pair", 1, 1, rows, cin, cout, k=k, pad=k // 2, x3=True, in_pair=True))
                         assert "pre-split A" in label, (rows, cin, cout, k, label)
@@ -137,7 +135,6 @@ def _family(label):
 def test_a_launch_runs_the_kernel_the_plan_names():
     """One real launch per kernel family -- the smallest recorded case of each -- reports the label tt_conv2d_plan gives its
     descriptor."""
-    L = _lib()
     by_name = {c["name"]: c for c in sweep.CASES}
     pick = {}
     for r in ROWS:
@@ -150,4 +147,4 @@ def test_a_launch_runs_the_kernel_the_plan_names():
             pick[fam] = (work, r["name"])
     assert len(pick) >= 10, sorted(pick)
     for rec in sweep.run_launch([by_name[name] for _, name in sorted(pick.values())]):
-        assert rec["label"] == sweep.plan_label(L, sweep.dict_to_desc(rec["desc"])), rec["name"]
+        assert rec["label"] == ops.plan_label(sweep.dict_to_desc(rec["desc"])), rec["name"]

@@ -1,40 +1,25 @@
 """tt_conv2d_plan_next (host only, no device) answers for a 1 x 1 bf16x3 layer with a joined stage (tt_conv2d_fwd_next, tt_conv_next;
 csrc/conv_choose.cpp choose_join): the label of every form at and just below kJoinMinRows and at the contract's floor, the refusals, and
-ops.join_ok against the library's answer."""
+ops.join_ok, which routes by that label."""
 import ctypes
 
-P = 0x10000       # a stand-in for every pointer: tt_conv2d_plan looks at null-ness and alignment only
+from thinktwice_amd import _lib, ops
 
 FORMS = [(64, 256, 64), (64, 256, 128), (128, 512, 128), (128, 512, 256), (256, 1024, 256)]
+P = ops.canonical_desc("join", 4551, 64, 256, 64)[0].weight       # the stand-in for every pointer of a canonical descriptor
 
 
 def _desc(rows, k1, cout, n2, in_pair=1, **change):
-    """(tt_conv_desc, tt_conv_next); a change goes to whichever of the two has the field"""
-    from thinktwice_amd import _lib, ops
-    d, n = ops._ConvDesc(), ops._ConvNext()
-    d.in_ = P; d.N = 1; d.H = 1; d.W = rows; d.Cin = k1; d.in_cstride = k1
-    d.weight = P; d.Cout = cout; d.KH = d.KW = d.stride = d.dil = 1
-    d.out = P; d.OH = 1; d.OW = rows; d.out_cstride = cout
-    d.scale = d.shift = P
-    d.res1 = P; d.res1_cstride = cout
-    d.act = 1; d.dtype = d.out_dtype = _lib.TT_F32
-    d.weight_x3 = P; d.in_pair = in_pair
-    n.next_weight = n.next_weight_x3 = P; n.next_cout = n2
-    n.next_scale = n.next_shift = P; n.next_act = 1
-    n.next_out = P; n.next_out_cstride = n2; n.next_out_pair = 1
-    for f, v in change.items():
+    """ops.canonical_desc's (tt_conv_desc, tt_conv_next) of the joined form; a change goes to whichever of the two has the field"""
+    d, n = ops.canonical_desc("join", rows, k1, cout, n2)
+    for f, v in dict(change, in_pair=in_pair).items():
         setattr(n if f.startswith("next_") else d, f, v)
     return d, n
 
 
 def _plan(dn):
     """the label of tt_conv2d_plan_next, or "ERROR: " + tt_last_error"""
-    from thinktwice_amd import _lib
-    L = _lib.lib()
-    label = ctypes.create_string_buffer(192)
-    if L.tt_conv2d_plan_next(ctypes.byref(dn[0]), ctypes.byref(dn[1]), label, len(label)) != 0:
-        return "ERROR: " + L.tt_last_error().decode()
-    return label.value.decode()
+    return ops.plan_label(*dn)
 
 
 def _label(k1, n2, pair=True):
@@ -43,8 +28,7 @@ def _label(k1, n2, pair=True):
 
 def test_label_of_every_form_at_and_just_below_the_threshold_and_the_floor():
     """From kJoinMinRows on the plain label; below it the same kernel, marked; at 4,096 rows (the pair format's floor) a refusal."""
-    from thinktwice_amd import ops
-    m = ops.JOIN_MIN_ROWS
+    m = _lib.TT_CONV_JOIN_MIN_ROWS
     assert m == 32768
     for k1, cout, n2 in FORMS:
         for rows in (m, m + 1, 50176, 100352, 200704, 401408, 1605632):
@@ -57,7 +41,6 @@ def test_label_of_every_form_at_and_just_below_the_threshold_and_the_floor():
 
 
 def test_the_descriptor_alone_keeps_its_kernel_and_a_null_next_is_refused():
-    from thinktwice_amd import _lib
     L = _lib.lib()
     d, _ = _desc(1605632, 64, 256, 64)
     label = ctypes.create_string_buffer(192)
@@ -86,13 +69,13 @@ def test_refusals_without_a_device():
     assert "next_cout" in _plan(_desc(4551, 256, 1024, 512))      # layer 3 -> 4: no 512-wide form
 
 
-def test_join_ok_agrees_with_the_library():
-    """join_ok = the library takes the descriptor, at or above kJoinMinRows (an unmarked label), AND the form is one the model
-    routes (ops.JOIN_ROUTED)."""
-    from thinktwice_amd import autodiff, ops
+def test_join_ok_over_the_grid():
+    """join_ok from plain numbers: yes for the forms the model routes (ops.JOIN_ROUTED) from 32,768 rows on, and every yes is a
+    descriptor the library takes with an unmarked label."""
+    from thinktwice_amd import autodiff
     assert ops.BNECK_JOIN and autodiff.TAPE is None
     yes = 0
-    for rows in (2048, 4096, 4097, 4551, 16384, ops.JOIN_MIN_ROWS - 1, ops.JOIN_MIN_ROWS, 50176, 100352, 1605632):
+    for rows in (2048, 4096, 4097, 4551, 16384, 32767, 32768, 50176, 100352, 1605632):
         for k1 in (32, 64, 128, 256, 512):
             for cout in (2 * k1, 4 * k1):
                 for n2 in (32, 64, 128, 256, 512):
@@ -101,6 +84,7 @@ def test_join_ok_agrees_with_the_library():
                     assert taken or label.startswith("ERROR: tt_conv2d_fwd: next_"), label
                     ok = ops.join_ok(rows, k1, cout, n2)
                     yes += ok
+                    assert ok == (rows >= 32768 and (k1, cout, n2) in ops.JOIN_ROUTED), (rows, k1, cout, n2)
                     assert ok == (taken and not label.endswith(" below kJoinMinRows") and (k1, cout, n2) in ops.JOIN_ROUTED), \
                         (rows, k1, cout, n2, label)
                     assert (k1, cout, n2) in FORMS or not taken
@@ -109,7 +93,7 @@ def test_join_ok_agrees_with_the_library():
 
 
 def test_the_knob_and_the_tape_turn_join_ok_off(monkeypatch):
-    from thinktwice_amd import autodiff, ops
+    from thinktwice_amd import autodiff
     assert ops.join_ok(1605632, 64, 256, 64)
     monkeypatch.setattr(ops, "BNECK_JOIN", False)
     assert not ops.join_ok(1605632, 64, 256, 64)

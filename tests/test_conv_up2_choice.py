@@ -1,12 +1,7 @@
 """tt_conv2d_plan (host only, no device) answers for the convolution that reads its input through the bilinear x2 upsampling
-(tt_conv_desc.in_up2, csrc/conv_choose.cpp choose_up2), and ops.up2_ok restates the library's rule."""
-import importlib.util
-import os
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-_spec = importlib.util.spec_from_file_location("conv_choice_sweep", os.path.join(ROOT, "tools", "conv_choice_sweep.py"))
-sweep = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(sweep)
+(tt_conv_desc.in_up2, csrc/conv_choose.cpp choose_up2), and ops.up2_ok asks it."""
+from thinktwice_amd import _lib, ops
+from tools import conv_choice_sweep as sweep
 
 UP2 = "conv_x3_run3_kernel<64, up2>"
 
@@ -14,12 +9,10 @@ UP2 = "conv_x3_run3_kernel<64, up2>"
 def _plan(N, h, w, cin, cout, up2=True, **kw):
     """Label (or "ERROR: text") for the 3 x 3 / pad 1 bf16x3 layer over the [N, 2h, 2w] map; in_up2: the descriptor ops.conv2d builds
     for the [N, h, w, cin] source, else the layer over a pair-format upsampled tensor (what the two launches run)."""
-    from thinktwice_amd import _lib
-    L = _lib.lib()
-    row, _ = sweep.describe(sweep.D("up2", N, 2 * h, 2 * w, cin, cout, k=3, x3=True, in_pair=not up2, **kw), L)
+    row, _ = sweep.describe(sweep.D("up2", N, 2 * h, 2 * w, cin, cout, k=3, x3=True, in_pair=not up2, **kw), _lib.lib())
     if up2:
         row.update(in_up2=1, in_nstride=h * w * cin if N > 1 else 0)
-    return sweep.plan_label(L, sweep.dict_to_desc(row))
+    return ops.plan_label(sweep.dict_to_desc(row))
 
 
 def test_the_label_starts_with_a_prefix_the_bench_counts_three_mfmas_for():
@@ -41,8 +34,9 @@ def test_the_old_choice_when_the_field_is_zero():
         assert _plan(N, 112, 224, 128, 64, up2=False) == "conv_igemm_glds_kernel<float, 64, 8, 1, 128, 2, false, true> pre-split A"
 
 
-def test_up2_ok_agrees_with_the_library():
-    from thinktwice_amd import ops
+def test_up2_ok_over_the_grid():
+    """up2_ok from plain numbers: more than 4096 output rows, Cin a multiple of 32, 64 output channels -- exactly where the library
+    plans the in_up2 kernel; everything else it refuses by name."""
     yes = 0
     for h, w in ((32, 32), (32, 33), (16, 32), (64, 64)):       # 4096 rows, 4224, 2048, 16384
         for cin in (16, 32, 48, 64, 128):
@@ -50,6 +44,8 @@ def test_up2_ok_agrees_with_the_library():
                 label = _plan(1, h, w, cin, cout)
                 ok = ops.up2_ok(4 * h * w, cin, cout)
                 yes += ok
+                assert ok == (4 * h * w > 4096 and cin % 32 == 0 and cout == 64), (h, w, cin, cout)
+                assert ok == (ops.plan_label(*ops.canonical_desc("up2", 4 * h * w, cin, cout)) == UP2), (h, w, cin, cout)
                 assert (label == UP2) == ok, (h, w, cin, cout, label)
                 assert ok or (label.startswith("ERROR: tt_conv2d_fwd: in_up2") and len(label) > 40), label
     assert yes == 2 * 3
@@ -57,12 +53,11 @@ def test_up2_ok_agrees_with_the_library():
 
 def test_refusals_without_a_device():
     assert "residual" in _plan(1, 40, 64, 32, 64, res=1)
-    from thinktwice_amd import _lib
     L = _lib.lib()
     row, _ = sweep.describe(sweep.D("both", 1, 80, 128, 32, 64, k=3, x3=True, in_pair=True), L)
     row.update(in_up2=1)
-    msg = sweep.plan_label(L, sweep.dict_to_desc(row))
+    msg = ops.plan_label(sweep.dict_to_desc(row))
     assert msg.startswith("ERROR") and "in_up2" in msg and "in_pair" in msg, msg
     row, _ = sweep.describe(sweep.D("odd", 1, 81, 128, 32, 64, k=3, x3=True), L)
     row.update(in_up2=1)
-    assert "even" in sweep.plan_label(L, sweep.dict_to_desc(row))
+    assert "even" in ops.plan_label(sweep.dict_to_desc(row))

@@ -36,7 +36,7 @@ bool choose_h2(const ConvArgs& a, ConvChoice* c) {
 
 // ---- latency-bound small-M variant (conv_small.hip: 32 x 32 tile, intra-block split-K)
 bool choose_small(const ConvArgs& a, ConvChoice* c) {
-    if (a.gather || a.m_dev || a.M > 4096) return false;
+    if (a.gather || a.m_dev || a.M > kSmallMaxRows) return false;
     if ((long long)div_up(a.M, 32) * div_up(a.Cout, 32) > 4096) return false;
     set_tile(c, CONV_SMALL, 32, 1, 1, 32, 1);
     return true;
@@ -231,8 +231,8 @@ bool choose_x3(const ConvArgs& a, ConvChoice* c) {
 }
 
 // ---- bf16x3 3 x 3 convolution that reads its input through the bilinear x2 upsampling (conv_x3_up2.hip, tt_conv_desc.in_up2): the
-// kernel's whole contract.  a.H / a.W are the upsampled size.  More than 4096 rows, as for in_pair: up to there a layer runs the
-// latency kernel.  Measured against the two launches it replaces in profiles/seg_up2_fusion.txt.
+// kernel's whole contract.  a.H / a.W are the upsampled size.  More than kSmallMaxRows rows, as for in_pair: up to there a layer runs
+// the latency kernel.  Measured against the two launches it replaces in profiles/seg_up2_fusion.txt.
 int choose_up2(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
     TT_REQUIRE(f.dtype == TT_F32 && a.out_dtype == TT_F32 && f.weight_x3 && aligned16(f.weight_x3) && !f.weight_h2,
                "tt_conv2d_fwd: in_up2 goes with a bf16x3 layer (f32 storage, a 16-byte aligned weight_x3)");
@@ -242,7 +242,8 @@ int choose_up2(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
                    a.OW == a.W,
                "tt_conv2d_fwd: in_up2 is a 3 x 3 / stride 1 / pad 1 layer over an even H x W (got %d x %d, k %d x %d s %d p %d d %d)", a.H,
                a.W, a.KH, a.KW, a.stride, a.pad, a.dil);
-    TT_REQUIRE(a.Cin % 32 == 0 && a.Cout == 64 && a.M > 4096 && a.vec_epi,
+    static_assert(kSmallMaxRows == 4096, "the refusal below spells the number");
+    TT_REQUIRE(a.Cin % 32 == 0 && a.Cout == 64 && a.M > kSmallMaxRows && a.vec_epi,
                "tt_conv2d_fwd: in_up2 layer outside the kernel's contract (Cin %% 32 == 0, Cout == 64, more than 4096 rows, aligned "
                "output: M=%d Cin=%d Cout=%d)", a.M, a.Cin, a.Cout);
     const long long img = (long long)(a.H / 2) * (a.W / 2) * a.Cin;
@@ -272,7 +273,8 @@ int choose_up2(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
 // 128 -> 512 -> 128 lose.  The two four-wave forms (one wave per SIMD) win at 32,768 rows only and lose at the model's row counts
 // (B = 8: 819 -> 835 and 497 -> 586 us; B = 1: 125 -> 132 and 95 -> 136): callers leave them to two launches (ops.JOIN_ROUTED); the
 // kernel keeps them.  The model's routed shapes (us): B = 8 1074 -> 805, 1297 -> 961, 710 -> 501; B = 1 160 -> 137, 202 -> 158, 108 -> 72.
-// The threshold is the CALLERS' rule: a call below it is still run here (label " below kJoinMinRows"), down to kJoinFloorRows.
+// A call below the threshold is still run here, down to kJoinFloorRows, and its label says " below kJoinMinRows": callers route by
+// that label (ops.join_ok asks tt_conv2d_plan_next), so the number stands in conv_choose.h alone.
 int choose_join(const ConvArgs& a, const ConvFacts& f, ConvChoice* c) {
     const ConvArgs& n = *f.join;
     TT_REQUIRE(f.dtype == TT_F32 && a.out_dtype == TT_F32 && f.weight_x3 && aligned16(f.weight_x3) && !f.weight_h2,

@@ -71,10 +71,14 @@ constexpr int kSpL2MinRows = 16384;
 constexpr int kPatchMinRows = 16384;
 
 // Joined stage (tt_conv2d_fwd_next, tt_conv_next; conv_choose.cpp, choose_join).  kJoinFloorRows: fewest output rows the kernel's contract takes
-// (its pair-format output needs more than 4,096).  kJoinMinRows: fewest rows at which every routed form beats its two launches --
-// what callers route by (ops.join_ok); a launch below it still runs the joined kernel and its label says " below kJoinMinRows".
-constexpr int kJoinFloorRows = 4097;
-constexpr int kJoinMinRows = 32768;
+// (its pair-format output needs more than kSmallMaxRows).  kJoinMinRows: fewest rows at which every routed form beats its two
+// launches.  The rule is stated here: a launch below it still runs the joined kernel, and its label -- tt_conv2d_plan_next's too -- ends
+// in " below kJoinMinRows"; ops.join_ok routes by that label and keeps no number of its own.
+// kSmallMaxRows: most output rows of the latency kernel (choose_small), hence the floor of pair format, in_up2 and the joined stage.
+// Both numbers are the header's (include/thinktwice_hip.h), where the Python side reads them too.
+constexpr int kSmallMaxRows = TT_CONV_SMALL_ROWS;
+constexpr int kJoinFloorRows = kSmallMaxRows + 1;
+constexpr int kJoinMinRows = TT_CONV_JOIN_MIN_ROWS;
 
 // What conv2d_run knows about a layer beside its validated ConvArgs.
 struct ConvFacts {

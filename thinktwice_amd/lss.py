@@ -69,7 +69,7 @@ class _ResNet50:
         return self.stem_rr_x3 is not None and ops.stem_pool_ok(img, self.stem_rr_x3)
 
     def __call__(self, x, bordered=False, image=False):
-        if image:         # x: the NCHW image (B, T, N, 3, H, W); stem and max pool in one launch (stem_pool_ok is the caller's rule)
+        if image:         # x: the NCHW image (B, T, N, 3, H, W); stem and max pool in one launch (where stem_pool_ok says so)
             x = ops.stem_pool(x, self.stem_rr_x3, self.stem.scale, self.stem.shift)
         elif bordered:    # x: (NI, H+6, W+8, 8) with the image at (3, 3)
             NI, Hp, Wp, _ = x.shape
@@ -92,10 +92,8 @@ class _ResNet50:
             # operand split once per element in conv1's epilogue instead of nine times per column tile in conv2's K loop
             c2 = blk["c2"]
             rows2 = shape[0] * (shape[1] // c2.stride) * (shape[2] // c2.stride)
-            return (c2.w_x3 is not None and not layers.BN_TRAIN and
-                    ops.pair_ok(min(rows2, shape[0] * shape[1] * shape[2]), c2.w.shape[-1], c2.w.shape[0]))
+            return ops.pair_ok(min(rows2, shape[0] * shape[1] * shape[2]), c2.w.shape[-1], c2.w.shape[0], x3=(c2,))
 
-        from . import autodiff
         flat = [blk for stage in self.blocks for blk in stage]
         last = [len(stage) for stage in self.blocks]
         last = [sum(last[:i + 1]) - 1 for i in range(len(last))]          # index of each stage's last block
@@ -112,9 +110,8 @@ class _ResNet50:
             # and the taped / train-mode / 16-bit paths keep two launches.  TT_BNECK_JOIN=0: two launches everywhere
             c3, nb = blk["c3"], flat[i + 1] if i + 1 < len(flat) else None
             rows = y.shape[0] * y.shape[1] * y.shape[2]
-            if (nb is not None and autodiff.TAPE is None and not layers.BN_TRAIN and c3.w_x3 is not None and
-                    nb["c1"].w_x3 is not None and pair_c1(nb, y.shape) and
-                    ops.join_ok(rows, c3.w.shape[-1], c3.w.shape[0], nb["c1"].w.shape[0])):
+            if (nb is not None and pair_c1(nb, y.shape) and
+                    ops.join_ok(rows, c3.w.shape[-1], c3.w.shape[0], nb["c1"].w.shape[0], x3=(c3, nb["c1"]))):
                 x, y1 = c3(y, res1=idt, join=nb["c1"])
             else:
                 x, y1 = c3(y, res1=idt), None          # relu(bn3(conv3) + identity)
@@ -151,8 +148,8 @@ class PAFPN_fp32:
         self.down = [conv_from_sd(sd, f"{n}.downsample_convs.{i}.conv", dt, dev, stride=2, pad=1) for i in range(L - 1)]
         self.paf = [conv_from_sd(sd, f"{n}.pafpn_convs.{i}.conv", dt, dev, pad=1) for i in range(L - 1)]
         if self.half:
-            # the same 3 x 3 layers on the h2 kernel (half input copy x f16 (hi, lo) weights); a level with <= 4096 pixel rows in
-            # the batch keeps the bf16x3 forms above (the latency kernels have no half / two-output epilogue)
+            # the same 3 x 3 layers on the h2 kernel (half input copy x f16 (hi, lo) weights); a level with at most ops.SMALL_ROWS
+            # pixel rows in the batch keeps the bf16x3 forms above (the latency kernels have no half / two-output epilogue)
             assert self.out_channels % 64 == 0, "half-storage PAFPN: out_channels must be a multiple of 64"
             h2 = weights.H2
             self.fpn_h = [conv_from_sd(sd, f"{n}.fpn_convs.{i}.conv", h2, dev, pad=1) for i in range(L)]
@@ -167,11 +164,11 @@ class PAFPN_fp32:
         product).  One rounding per conv input, none accumulating along the chains (tools/precision_mix_emul.py plan `neckop`:
         waypoint L2 0.62 mm on F14, against 1.08 mm with the chains themselves in half).  The copies cost no extra launch: the
         producing epilogue writes the half tensor as its primary output and the f32 one through tt_conv_desc.out2; a level with
-        <= 4096 rows runs the plain bf16x3 layers."""
+        at most ops.SMALL_ROWS rows runs the plain bf16x3 layers."""
         L, C, f16, f32 = self.num_outs, self.out_channels, torch.float16, torch.float32
         dev = inputs[0].device
         rows = [t.shape[0] * t.shape[1] * t.shape[2] for t in inputs]
-        half = [r > 4096 for r in rows]
+        half = [r > ops.SMALL_ROWS for r in rows]
         lat32, lat16 = [None] * L, [None] * L
         for i in range(L - 1, -1, -1):
             n, h, w, _ = inputs[i].shape
@@ -226,16 +223,14 @@ class PAFPN_fp32:
         targets = list(targets) if targets is not None else [None] * L
         C = self.out_channels
         if self.half:
-            from . import autodiff
-            if autodiff.TAPE is not None or layers.BN_TRAIN:
+            if not ops.inference():
                 raise _lib.TTError("PAFPN: the half-storage mode ('f32x3h') is an inference mode; train in 'f32x3' or float32")
             return self._call_half(inputs, targets)
-        from . import autodiff
         lat = [None] * L
         lat[L - 1] = self.lat[L - 1](inputs[L - 1])
         for i in range(L - 2, -1, -1):
             n, h, w, _ = inputs[i].shape
-            if autodiff.TAPE is None and not layers.BN_TRAIN and n * h * w > 4096 and inputs[i].dtype == torch.float32:
+            if ops.res1_up_ok(n * h * w, inputs[i].dtype):
                 # top-down path inside the lateral conv's epilogue: lat[i] = conv(C_i) + nearest_up(lat[i+1]) -- the same two f32
                 # additions per element as the separate kernel (bit-identical), without re-reading and re-writing lat[i]
                 lat[i] = self.lat[i](inputs[i], res1=lat[i + 1], res1_up=True)
@@ -424,15 +419,14 @@ class LSS:
         d = ops.channel_gate(x, g_dep)
         if dbg is not None:
             dbg.update(se_depth=d)
-        x3 = self.bb[0][0].w_x3 is not None and not layers.BN_TRAIN
-        pr = x3 and ops.pair_ok(NI * h * w, d.shape[-1], d.shape[-1])    # conv1's output: one reader, conv2 (pair format)
+        pr = ops.pair_ok(NI * h * w, d.shape[-1], d.shape[-1], x3=(self.bb[0][1],))    # conv1's output: one reader, conv2 (pair format)
         for c1, c2 in self.bb:
             d = c2(c1(d, out_pair=pr), res1=d, in_pair=pr)
         if dbg is not None:
             dbg.update(blocks=d)
         mid = d.shape[-1]
         cat = torch.empty(NI, h, w, 4 * mid, dtype=dt, device=dev)
-        pr_cat = x3 and mid % 16 == 0 and ops.pair_ok(NI * h * w, 4 * mid, mid, taps=1)   # the branch concat: one reader, conv1 of the ASPP
+        pr_cat = mid % 16 == 0 and ops.pair_ok(NI * h * w, 4 * mid, mid, taps=1, x3=(self.aspp_out,))   # the branch concat: one reader, conv1 of the ASPP
         for i, br in enumerate(self.aspp):
             br(d, out=cat, out_coff=i * mid, out_pair=pr_cat)
         x5 = self.aspp_gap(rows(ops.spatial_pool(d, 0)))                 # (NI,1,1,mid) f32
@@ -463,18 +457,17 @@ class LSS:
         d3 = self.upc["unet_layer3"](cat3)
         self.up["unet_layer2"](d3, out=cat2, out_coff=0)
         d2 = self.upc["unet_layer2"](cat2)
-        from . import autodiff
         NI, h2, w2, _ = d2.shape
         H, W = 2 * h2, 2 * w2
-        fused = autodiff.TAPE is None and not layers.BN_TRAIN and self.dtype == torch.float32
+        fused = ops.inference(dtype=self.dtype)
         # the upsampled map and unet_layer0.1's output have ONE reader each, a bf16x3 convolution: they are produced pre-split
         # (pair format, tt_conv_desc.in_pair) -- same sums, the operand split once per element instead of once per tap
-        x3 = self.u0a.w_x3 is not None
-        p_up = x3 and ops.pair_ok(NI * H * W, 128, 64)
-        p_mid = fused and x3 and self.seg_fused.w_x3 is not None and ops.pair_ok(NI * H * W, 64, self.seg_fused.w.shape[0])
+        # (p_up's gate has always ignored BN_TRAIN: a train-mode forward without a tape upsamples into pair format too)
+        p_up = ops.pair_ok(NI * H * W, 128, 64, x3=(self.u0a,), bn_train=True)
+        p_mid = ops.pair_ok(NI * H * W, 64, self.seg_fused.w.shape[0], x3=(self.u0a, self.seg_fused), dtype=self.dtype)
         # ... and where the layer takes it, the upsampled map is not produced at all: unet_layer0.1 interpolates it into its operand
         # patch (tt_conv_desc.in_up2: the same bits; TT_SEG_UP2=0 keeps the two launches)
-        if (ops.SEG_UP2 and x3 and fused and d2.is_contiguous() and ops.up2_ok(NI * H * W, d2.shape[-1], self.u0a.w.shape[0])):
+        if d2.is_contiguous() and ops.up2_ok(NI * H * W, d2.shape[-1], self.u0a.w.shape[0], x3=(self.u0a,), dtype=self.dtype):
             d1 = self.u0a(d2, in_up2=True, out_pair=p_mid)
         else:
             d1 = self.u0a(ops.bilinear_up2(d2, out_pair=p_up), in_pair=p_up, out_pair=p_mid)
@@ -564,8 +557,7 @@ class LSS:
             # keep FPN maps of the key sweep before the UNet overwrites nothing of them (offset slices)
             seg = self._seg_net(bufs)
             f, first = seg, 0
-            if (ops.SEG_CHAIN and autodiff.TAPE is None and not layers.BN_TRAIN and self.dtype == torch.float32
-                    and self.seg2feat[1].w_x3 is not None):
+            if ops.seg_chain_ok(self.seg2feat[1], self.dtype):
                 # inference in the bf16x3 modes: the two full-resolution 1 x 1 layers (n_class -> 64 -> 16) as one launch, the
                 # 64-channel map between them (1.6 GB at B = 8) stays on chip; same bits as the two launches
                 f, first = ops.seg_feedback_chain(seg, self.seg2feat[0], self.seg2feat[1]), 2

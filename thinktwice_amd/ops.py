@@ -5,6 +5,8 @@ computes anything in PyTorch: allocation and stream handling only.
 """
 import contextlib
 import ctypes
+import functools
+import math
 import os
 
 import torch
@@ -120,6 +122,7 @@ def lift_splat_bwd(depth_logits, context, geom_xyz, voxel_num, batch_size, num_c
 
 # ----------------------------------------------------------------------------- conv / linear
 _AUTO_SPLITK = os.environ.get("TT_CONV_AUTO_SPLITK", "1") == "1"
+SMALL_ROWS = _lib.TT_CONV_SMALL_ROWS    # up to this many output rows a plain layer runs the exact-f32 latency kernel (conv_choose.cpp, choose_small)
 CONV_PROFILE = None   # bench.py sets this to a list to collect (flops, start, end, shape) per launch
 CONV_KERNELS = None   # same order as CONV_PROFILE: tt_conv_last_kernel() of the launch (a weight gradient: its plan label); plus one
                       # entry per gather_conv_wgrad, which has no CONV_PROFILE record -- do not zip the two over a sparse backward
@@ -388,7 +391,7 @@ def _training_x3(w_x3, cout, training):
 def auto_splitk_asks(rows, k, splitk_ws=False, pair=False, in_up2=False, h2=False, res1_up=False):
     """Whether conv2d asks the library for a split-K workspace of its own: few rows, very long K, none of the operand modes that
     have no split-K form, and no workspace from the caller.  TT_CONV_AUTO_SPLITK=0 disables."""
-    return _AUTO_SPLITK and not splitk_ws and not (pair or in_up2) and not h2 and not res1_up and rows <= 4096 and k >= 2048
+    return _AUTO_SPLITK and not splitk_ws and not (pair or in_up2) and not h2 and not res1_up and rows <= SMALL_ROWS and k >= 2048
 
 
 def _auto_splitk(d, device):
@@ -436,7 +439,7 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
     out2 / out2_coff: optional second, f32, copy of the output rows at channel offset out2_coff of a [.., Ct2] tensor
     in_pair / out_pair (bf16x3 layers only): x is / out becomes a PAIR-format tensor (an f32-typed container holding, per 16
     channels, the bf16 hi and lo halves the kernel's operand split would produce: tt_conv_desc.in_pair).  Only for tensors whose
-    every reader is a bf16x3 convolution (`pair_ok(rows)` says whether a layer of that many output rows takes one).
+    every reader is a bf16x3 convolution (`pair_ok` says whether a layer of those numbers takes one).
     in_up2 (bf16x3 3 x 3 / stride 1 / pad 1 layers with 64 output channels; `up2_ok` says which): x is the low-resolution f32 map
     [N, h, w, C] and the layer convolves bilinear_up2(x) -- nn.Upsample(scale_factor=2, bilinear, align_corners=True) -- without that
     tensor ever existing (tt_conv_desc.in_up2); bit for bit conv2d(bilinear_up2(x, out_pair=True), ..., in_pair=True).
@@ -445,6 +448,7 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
     conv2d returns (out, next_out) with next_out [N, OH, OW, w.shape[0]] in PAIR format; both are bit for bit what the two conv2d
     calls give (a ResNet bottleneck's conv3 and the next block's conv1).  nxt_out / nxt_out_coff: the tensor (and channel offset)
     next_out is written into instead of a new one.  Inference only.
+    The `*_ok` predicates (section "routes" below) are where the model chooses among these forms; they ask the library.
     in_cstride / out_hw: "row-run" form -- the kernel reads `cin` CONTIGUOUS elements starting at pixel (ih, iw) of a
     tensor whose pixels are only Cs < cin elements apart (a run of cin/Cs pixels along W), with the output size given
     explicitly; used for the 7x7/2 stem (lss.py).
@@ -521,9 +525,6 @@ def conv2d(x, w, *, stride=1, pad=0, dil=1, scale=None, shift=None, act=0, res1=
         _tape("conv", x, w, out, stride, pad, dil, scale, shift, act, in_coff, cin, out_coff, res1, res1_coff,
               res2, res2_coff, pixel_shuffle2, in_cstride, shift_n, shift_n_mod, stop_grad, bn_raw)
     return out if nout is None else (out, nout)
-
-
-SEG_CHAIN = os.environ.get("TT_SEG_CHAIN", "1") != "0"     # A/B knob and test hook: 0 = the two feedback convs stay two launches
 
 
 def seg_feedback_chain(x, cv1, cv2, out=None, out_coff=0):
@@ -697,22 +698,6 @@ def maxpool3x3s2(x):
     return out
 
 
-STEM_POOL = os.environ.get("TT_STEM_POOL", "1") != "0"     # A/B knob and test hook: 0 = border copy, row-run stem and max pool stay three launches
-
-
-def stem_pool_ok(img, w_x3):
-    """Whether the bf16x3 stem runs from the NCHW image to the pooled map in one launch (stem_pool, tt_stem_pool_x3): inference
-    on f32 storage with the row-run weights, even H and W, a contiguous (3, H, W) block per image, and more than 4,096 stem
-    pixels in all: up to there the three launches run the stem on the exact-f32 latency kernel (csrc/conv_choose.cpp,
-    choose_small), whose sums the one launch does not reproduce.  tests/test_stem_pool_choice.py pins the rule."""
-    from . import layers
-    if not (STEM_POOL and _active_tape() is None and not layers.BN_TRAIN and w_x3 is not None and img.dtype == torch.float32 and
-            img.dim() == 6 and img.shape[3] == 3 and img.shape[4] % 2 == 0 and img.shape[5] % 2 == 0):
-        return False
-    B, T, N, _, H, W = img.shape
-    return tuple(img.stride()[3:]) == (H * W, W, 1) and B * T * N * (H // 2) * (W // 2) > 4096
-
-
 def stem_pool(img, w_x3, scale, shift, max_workgroups=0):
     """img (B, T, N, 3, H, W) f32 (any b / t / n strides) -> max_pool2d(relu(scale * conv7x7s2p3(img) + shift), 3, 2, 1) as f32
     (T*B*N, ceil(H/4), ceil(W/4), 64) channel-last, images sweep-major ((s*B + b)*N + n = img[b, T-1-s, n]).  w_x3: the row-run
@@ -741,39 +726,97 @@ def upsample_nearest_add_(dst, src):
     return dst
 
 
-PAIR = os.environ.get("TT_X3_PAIR", "1") != "0"     # A/B knob: 0 = every activation tensor stays plain f32
+# ----------------------------------------------------------------------------- routes: which layer takes an inference-only form
+# The model picks a tensor's form before the tensor exists, so it asks these predicates with plain numbers.  None restates a kernel's
+# contract: the shape part of an answer is the library's (tt_conv2d_plan about the form's canonical layer), the row bound is the
+# header's SMALL_ROWS, the rest is `inference` and the route's A/B knob (an env switch and test hook, read by its one predicate).
+PAIR = os.environ.get("TT_X3_PAIR", "1") != "0"             # 0 = every activation tensor stays plain f32
+BNECK_JOIN = os.environ.get("TT_BNECK_JOIN", "1") != "0"    # 0 = a bottleneck's conv3 and the next block's conv1 stay two launches
+SEG_UP2 = os.environ.get("TT_SEG_UP2", "1") != "0"          # 0 = unet_layer0's upsample and its 3 x 3 conv stay two launches
+STEM_POOL = os.environ.get("TT_STEM_POOL", "1") != "0"      # 0 = border copy, row-run stem and max pool stay three launches
+SEG_CHAIN = os.environ.get("TT_SEG_CHAIN", "1") != "0"      # 0 = the two seg feedback convs stay two launches
 
 
-def pair_ok(rows, cin=32, cout=64, taps=9):
-    """Whether a bf16x3 convolution with this many output rows / these channel counts / `taps` = KH * KW filter taps accepts a
-    pair-format input (tt_conv_desc.in_pair: the LDS-DMA kernel's contract, K = taps * cin of at least two 32-channel tiles; up to
-    4096 rows a layer runs the exact-f32 latency kernel, which a pair-format layer could not take).  Producer and consumer of a
-    tensor ask with the CONSUMER's numbers.  tests/test_conv_choice.py pins this to the library's rule."""
-    return (PAIR and _active_tape() is None and rows > 4096 and cin % 32 == 0 and taps * cin >= 64 and
-            (8 <= cout <= 32 or cout >= 64))
+def inference(*x3, dtype=None, bn_train=False):
+    """The gate of every inference-only route: no active tape, eval-mode BatchNorm (bn_train=True: either mode), the bf16x3 operand
+    on every layers.Conv (or bare weight_x3) in `x3`, f32 storage where the site names its activations' `dtype`."""
+    from . import layers
+    return (_active_tape() is None and (bn_train or not layers.BN_TRAIN) and dtype in (None, torch.float32) and
+            all(getattr(c, "w_x3", c) is not None for c in x3))
 
 
-BNECK_JOIN = os.environ.get("TT_BNECK_JOIN", "1") != "0"      # A/B knob and test hook: 0 = a bottleneck's conv3 and the next block's conv1 stay two launches
-JOIN_MIN_ROWS = 32768                                       # csrc/conv_choose.h: kJoinMinRows
-# the (Cin, Cout, next Cout) forms of the joined kernel that are faster than their two launches at the model's row counts
+def canonical_desc(form, rows, cin, cout, arg=0):
+    """(tt_conv_desc, tt_conv_next or None) of a form's CANONICAL layer from plain numbers, every operand at one stand-in aligned
+    address (the planner looks at null-ness and alignment only): bf16x3, one image of 1 x rows pixels, a dense cout-channel output.
+    "pair": k x k / pad k // 2, arg = k * k taps, pair-format input; "up2": the 3 x 3 in_up2 layer over the 2 x rows / 2 map;
+    "join": the 1 x 1 layer (pair-format input, folded BN, residual, ReLU) with the joined stage cout -> arg."""
+    P, k, up2, n = 0x10000, {"pair": math.isqrt(arg), "up2": 3, "join": 1}[form], form == "up2", None
+    x, o = (1, 1, rows // 4 if up2 else rows, cin), ((1, 2, rows // 2, cout) if up2 else (1, 1, rows, cout))
+    epi = dict(scale=P, shift=P, act=1, res1=P, res1_shape=o) if form == "join" else {}
+    d = conv_desc(P, x, (0, 0, cin, 1), P, (cout, k, k, cin), P, o, (0, 0, cout, 1), TT_F32, TT_F32, pad=k // 2, weight_x3=P,
+                  in_up2=up2, in_pair=not up2, **epi)
+    if form == "join":
+        n = _ConvNext()
+        n.next_weight = n.next_weight_x3 = n.next_scale = n.next_shift = n.next_out = P
+        n.next_cout = n.next_out_cstride = arg; n.next_act = n.next_out_pair = 1
+    return d, n
+
+
+def plan_label(d, nxt=None):
+    """What tt_conv_last_kernel would report after launching `d` (with the joined stage `nxt`), or "ERROR: " + the refusal.  Host only."""
+    L, buf = lib(), ctypes.create_string_buffer(192)
+    rc = L.tt_conv2d_plan(ctypes.byref(d), buf, len(buf)) if nxt is None else \
+        L.tt_conv2d_plan_next(ctypes.byref(d), ctypes.byref(nxt), buf, len(buf))
+    return buf.value.decode() if rc == 0 else "ERROR: " + L.tt_last_error().decode()
+
+
+@functools.lru_cache(maxsize=None)
+def _taken(form, rows, cin, cout, arg=0):
+    """Whether the library takes the form's canonical layer, and not below a routing threshold of its own (conv_choose.h,
+    kJoinMinRows).  Asked once per set of numbers (no stream goes in, so a launch plan records none of this)."""
+    label = plan_label(*canonical_desc(form, rows, cin, cout, arg))
+    return not (label.startswith("ERROR") or label.endswith(" below kJoinMinRows"))
+
+
+def pair_ok(rows, cin=32, cout=64, taps=9, x3=(), **gate):
+    """Whether the input of the bf16x3 convolution with these numbers -- output rows, channels, KH * KW taps: the CONSUMER's, also
+    when the tensor's producer asks -- is in pair format (tt_conv_desc.in_pair).  `x3`, `gate`: see inference."""
+    return PAIR and inference(*x3, **gate) and rows > SMALL_ROWS and _taken("pair", rows, cin, cout, taps)
+
+
+def up2_ok(rows, cin, cout, x3=(), **gate):
+    """Whether the 3 x 3 bf16x3 convolution with this many OUTPUT rows reads its input through the bilinear x2 upsampling (in_up2)."""
+    return SEG_UP2 and inference(*x3, **gate) and rows > SMALL_ROWS and _taken("up2", rows, cin, cout)
+
+
+# the (Cin, Cout, next Cout) forms of the joined kernel that beat their two launches at the model's row counts
 # (profiles/bottleneck_join.txt); the library also takes (128, 512, 256) and (256, 1024, 256), which lose there
 JOIN_ROUTED = ((64, 256, 64), (64, 256, 128), (128, 512, 128))
 
 
-def join_ok(rows, k1, cout, next_cout):
-    """Whether a bf16x3 1 x 1 / stride 1 convolution k1 -> cout over this many rows also produces the next 1 x 1 layer's cout ->
-    next_cout output in its own launch (conv2d(nxt=...), tt_conv2d_fwd_next): the library's contract (csrc/conv_choose.cpp,
-    choose_join) restricted to the routed forms.  tests/test_conv_join_choice.py pins this to the library's rule."""
-    return BNECK_JOIN and _active_tape() is None and rows >= JOIN_MIN_ROWS and (k1, cout, next_cout) in JOIN_ROUTED
+def join_ok(rows, k1, cout, next_cout, x3=()):
+    """Whether the 1 x 1 bf16x3 convolution k1 -> cout over these rows also runs the next 1 x 1 layer, cout -> next_cout (nxt=...)."""
+    return BNECK_JOIN and inference(*x3) and (k1, cout, next_cout) in JOIN_ROUTED and _taken("join", rows, k1, cout, next_cout)
 
 
-SEG_UP2 = os.environ.get("TT_SEG_UP2", "1") != "0"      # A/B knob and test hook: 0 = unet_layer0's upsample and its 3 x 3 conv stay two launches
+def res1_up_ok(rows, dtype=torch.float32):
+    """Whether a conv over these rows adds a coarser map through nearest upsampling in its epilogue (res1_up; PAFPN top-down path)."""
+    return inference(dtype=dtype) and rows > SMALL_ROWS
 
 
-def up2_ok(rows, cin, cout):
-    """Whether a bf16x3 3 x 3 / stride 1 / pad 1 convolution with this many OUTPUT rows reads its input through the bilinear x2
-    upsampling in the kernel (conv2d(in_up2=True), tt_conv_desc.in_up2).  tests/test_conv_up2_choice.py pins this to the library's rule."""
-    return _active_tape() is None and rows > 4096 and cin % 32 == 0 and cout == 64
+def seg_chain_ok(cv2, dtype):
+    """Whether the two seg feedback convs run as one launch (seg_feedback_chain); cv2: the second of them."""
+    return SEG_CHAIN and inference(cv2, dtype=dtype)
+
+
+def stem_pool_ok(img, w_x3):
+    """Whether the bf16x3 stem runs from the NCHW image to the pooled map in one launch (stem_pool): even H and W, a contiguous
+    (3, H, W) block per image, and more than SMALL_ROWS stem pixels: up to there the three launches run the latency kernel."""
+    if not (STEM_POOL and inference(w_x3, dtype=img.dtype) and img.dim() == 6 and img.shape[3] == 3 and img.shape[4] % 2 == 0 and
+            img.shape[5] % 2 == 0):
+        return False
+    B, T, N, _, H, W = img.shape
+    return tuple(img.stride()[3:]) == (H * W, W, 1) and B * T * N * (H // 2) * (W // 2) > SMALL_ROWS
 
 
 def bilinear_up2(x, out_pair=False):

@@ -223,7 +223,7 @@ def desc_to_dict(d):
 
 
 def dict_to_desc(row):
-    """A descriptor with dummy 64-byte aligned addresses where the row has a pointer (tt_conv2d_plan reads none of them)."""
+    """A recorded row as a descriptor ops.plan_label takes: dummy 64-byte aligned addresses where the row has a pointer."""
     from thinktwice_amd import ops
     d = ops._ConvDesc()
     for i, (n, is_ptr) in enumerate(_fields()):
@@ -235,9 +235,9 @@ def dict_to_desc(row):
 
 
 def plan_label(L, d):
-    buf = ctypes.create_string_buffer(128)
-    rc = L.tt_conv2d_plan(ctypes.byref(d), buf, len(buf))
-    return buf.value.decode() if rc == 0 else "ERROR: " + L.tt_last_error().decode()
+    """ops.plan_label(d), under the name and signature this tool's other users call (L: the loaded library, not needed any more)."""
+    from thinktwice_amd import ops
+    return ops.plan_label(d)
 
 
 def _strides(shape):
@@ -282,12 +282,12 @@ def _lib_only():
 
 
 def run_plan(cases=None):
-    from thinktwice_amd import _lib
+    from thinktwice_amd import _lib, ops
     L = _lib.lib()
     out = []
     for c in cases or CASES + QUERIES:
         row, query = describe(c, L)
-        rec = dict(name=c["name"], desc=row, label=plan_label(L, dict_to_desc(row)))
+        rec = dict(name=c["name"], desc=row, label=ops.plan_label(dict_to_desc(row)))
         if query is not None:
             rec["query"] = query
         out.append(rec)
