@@ -1026,6 +1026,57 @@ int tt_logvars_accumulate(const float* packed, int n, const float* tail, int n_t
 int tt_logvars_flush(double* window, int n_all, double* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Open-loop task metrics on the device (thinktwice_amd/evaluate.py, csrc/eval_metrics.hip): a forward's heads against a loader
+ * batch's labels, folded into caller-owned device accumulators.  Counts are int64 and added with integer atomics (exact, the
+ * same bits every run); f64 sums are one workgroup's, in sample order; no entry waits for the host and calls on one stream
+ * accumulate in call order.  The metric definitions are this project's; what is restated from the reference is which label a
+ * cell is compared with.
+ *
+ * tt_eval_seg_confusion: logits_cl channel-last [BN][H/factor][W/factor][cstride >= num_classes], labels [BN][H][W] float class
+ * ids -- the layout of tt_loss_seg_focal.  The label of cell (y, x) is the pixel (y*factor, x*factor): get_downsampled_gt_seg
+ * (encoder_decoder_framework.py:485-491, torchvision's nearest resize).  The prediction is the argmax over channels
+ * [0, num_classes), ties to the lowest index; padding channels take no part.  conf: num_classes * num_classes + 2 int64:
+ * conf[label * num_classes + pred] += 1, then [bad_label, nonfinite].  Label 255 is skipped as in the loss; another label outside
+ * [0, num_classes) adds to bad_label only; a cell whose num_classes logits hold a NaN adds to nonfinite only.
+ * 1 <= num_classes <= 32; H and W divisible by factor.
+ *
+ * tt_eval_depth_bins: logits_cl [BN][H/factor][W/factor][cstride >= D], gt_depth [BN][H][W] metres (0 = no return) -- the layout
+ * and the cell rule of tt_loss_depth_bce, i.e. get_downsampled_gt_depth (encoder_decoder_framework.py:443-482): g = min over the
+ * factor x factor cell with 0 read as 1e5, (g - (d_lo - d_step)) / d_step in f32, outside [0, D + 1) -> 0, truncated: bin 0 is
+ * background, bin k the depth channel k - 1.  acc: 5 int64 over the foreground cells: [n_fg, n_top1 (argmax == bin - 1, ties to
+ * the lowest index), n_within1 (|argmax - (bin - 1)| <= 1), sum_abs_bins (the sum of that distance), nonfinite (a foreground
+ * cell whose D logits hold a NaN: counted here and nowhere else)].
+ *
+ * tt_eval_decoder: pred_wp [B][S][4][2], mu_branches / sigma_branches [B][S][2], pred_speed [B] (the head's speed / 12,
+ * encoder_decoder_framework.py:198) against the expert's waypoints [B][4][2], action_mu / action_sigma [B][2], speed [B] (m/s).
+ * sums: 8 S + 1 doubles, per stage s at sums[8 s ..]: [ADE (mean over the 4 steps of the L2 distance), FDE (the last step's),
+ * mean |dx| (longitudinal), mean |dy| (lateral), |mu - a_mu| columns 0 and 1, |sigma - a_sigma| columns 0 and 1], then
+ * sums[8 S] = |12 pred_speed - speed|.  Every term is computed in f64 from the f32 inputs (differences, squares, their sum, sqrt,
+ * the steps added in order, * 0.25) and every sum is ONE sequential f64 sum over the samples of all calls in order.  counts: 2
+ * int64 [samples, nonfinite]: a sample with a non-finite pred_wp / mu / sigma / pred_speed value adds to nonfinite and to nothing
+ * else.  1 <= S <= 7.
+ *
+ * tt_eval_pair_deviation: two f32 tensors of n elements (precision modes A and B of one output).  slots: 3 int64 [the bit
+ * pattern of max |a - b| as f32, that of max |a|, the number of elements where a or b is not finite (they stay out of both
+ * maxima)]; the maxima fold by integer maximum, which is exact for non-negative floats.
+ * tt_eval_pair_wp: two pred_wp tensors of `points` (x, y) pairs: per pair the f64 L2 distance (what `(a - b).norm(dim=-1)`
+ * measures).  max_sum: 2 doubles [maximum, sequential sum in index order]; counts: 2 int64 [finite points, others].
+ * tt_eval_pair_seg: two seg logit maps [cells][cstride >= num_classes]: out: 3 int64 [cells whose argmax differs, cells compared,
+ * cells with a NaN in either (not compared)].
+ * ---------------------------------------------------------------------- */
+int tt_eval_seg_confusion(const float* logits_cl, int cstride, int num_classes, const float* labels, int BN, int H, int W,
+                          int factor, long long* conf, void* stream);
+int tt_eval_depth_bins(const float* logits_cl, int cstride, int D, const float* gt_depth, int BN, int H, int W, int factor,
+                       float d_lo, float d_step, long long* acc, void* stream);
+int tt_eval_decoder(const float* pred_wp, const float* mu_branches, const float* sigma_branches, const float* pred_speed,
+                    const float* waypoints, const float* action_mu, const float* action_sigma, const float* speed, int B, int S,
+                    double* sums, long long* counts, void* stream);
+int tt_eval_pair_deviation(const float* a, const float* b, long long n, long long* slots, void* stream);
+int tt_eval_pair_wp(const float* a, const float* b, int points, double* max_sum, long long* counts, void* stream);
+int tt_eval_pair_seg(const float* a_cl, const float* b_cl, int cstride, int num_classes, long long cells, long long* out,
+                     void* stream);
+
+/* ------------------------------------------------------------------------
  * SURVEY 8f-4, the torch-autograd route of the training step (thinktwice_amd/autograd_route.py): what mmcv's OptimizerHook gets
  * from `outputs['loss'].backward()` depositing into every parameter's `.grad` (apis/mmdet_train.py:70-97) -- here the reverse
  * sweep leaves one separately allocated f32 tensor per parameter, and ONE launch gathers `nseg` of them into one flat f32 buffer

@@ -33,6 +33,10 @@ class EncoderDecoder(torch.nn.Module):
     `parameters_changed()` after one.  `.to(other_gpu)` rebuilds the model there: the parameters are NEW objects afterwards
     (build optimizers after placing the model, as the reference does)."""
 
+    # optional callable (batch, pred): `_forward_train` hands it the forward's outputs before the loss terms read them
+    # (evaluate.MetricWindow.add under runner.validate(metrics=...)).  None: nothing is called.
+    pred_observer = None
+
     def __init__(self, img_encoder, decoder, lidar_encoder=None, num_cams=4, use_depth=False, use_seg=False,
                  downsample_factor=16, seg_downsample_factor=2, train_cfg=None, test_cfg=None,
                  dtype=torch.float32, device="cuda", cfg=None, lidar_dtype=None, trainable=False):
@@ -392,6 +396,8 @@ class EncoderDecoder(torch.nn.Module):
         # Under the training tape (thinktwice_amd/trainer.py) every term reads the forward's own channel-last tensors and
         # records the gradient of its mean w.r.t. them; the terms are elementwise means, so the values do not change.
         pred = self.forward_inference(batch, teacher=teacher, channel_last_out=tape is not None)
+        if self.pred_observer is not None:            # (runner.validate(metrics=...): the task metrics of this very forward)
+            self.pred_observer(batch, pred)
         if tape is None:
             mids = [None if m is None else ops.nhwc_to_nchw(m) for m in pred["_mid_bev_cl"]]
             out = LS.decoder_loss(red, self.config, batch, pred, mids)

@@ -70,14 +70,33 @@ def _dist(dist):
     return dist
 
 
-def validate(target, loader, dist=None, window=None):
+def is_better(value, best, rule="less"):
+    """The `save_best` rule: `less` keeps the lowest value (a loss, an error in metres), `greater` the highest (seg_miou, an
+    accuracy).  The first value is the best so far; a NaN never beats a value."""
+    if rule not in ("less", "greater"):
+        raise ValueError(f"save_best_rule is 'less' or 'greater', not {rule!r}")
+    return best is None or (value < best if rule == "less" else value > best)
+
+
+def parse_save_best(spec):
+    """`NAME[:greater|:less]` of train.py's --save-best -> (name, rule)."""
+    name, _, rule = str(spec).partition(":")
+    rule = rule or "less"
+    if not name or rule not in ("less", "greater"):
+        raise ValueError(f"--save-best takes NAME[:greater|:less], not {spec!r}")
+    return name, rule
+
+
+def validate(target, loader, dist=None, window=None, metrics=None):
     """custom_multi_gpu_test (eval_tool.py:71-116) restated: the model under eval() and no_grad, `train_step` -- losses
     included, the reference evaluates forward_train too -- on every batch of `loader`, each batch's
     `log_vars` weighted by its size; ONE read at the end.  `target`: a Trainer (validated through `Trainer.evaluating()`) or a
     model.  Per rank the device window holds the reference's `results[k] += float(v) * batch_size` in f64, divided by the
     sample count when read; across ranks `merge_ranks` over one all_gather of (means, n) -- every rank returns the merged
     result.  Before a distributed validation rank 0's BatchNorm running statistics are broadcast (eval_hooks.py:123-129).
-    -> OrderedDict: a mean per name, then `num_samples` and `eval_iter_num` (this rank's batches)."""
+    `metrics`: an evaluate.MetricWindow filled from the SAME forwards through the model's `pred_observer` (no second pass, no
+    host synchronisation per batch); its scalar metrics (evaluate.scalar_metrics, merged over the ranks) follow the loss means.
+    -> OrderedDict: a mean per name, the metrics if asked for, then `num_samples` and `eval_iter_num` (this rank's batches)."""
     from . import logvars
     dist = _dist(dist)
     is_trainer = hasattr(target, "evaluating")
@@ -88,11 +107,17 @@ def validate(target, loader, dist=None, window=None):
     if window is None:
         window = logvars.LogWindow(model.device)
     iters = 0
-    with (target.evaluating() if is_trainer else _eval_mode(model)), torch.no_grad():
-        for batch in loader:
-            out = model.train_step(batch, None, device_log=True)
-            window.add(out["log_vars"], out["num_samples"])
-            iters += 1
+    if metrics is not None:
+        model.pred_observer = metrics.add
+    try:
+        with (target.evaluating() if is_trainer else _eval_mode(model)), torch.no_grad():
+            for batch in loader:
+                out = model.train_step(batch, None, device_log=True)
+                window.add(out["log_vars"], out["num_samples"])
+                iters += 1
+    finally:
+        if metrics is not None:
+            model.pred_observer = None
     if iters == 0:
         raise ValueError("validate: the loader gave no batch")
     res = window.close().result()
@@ -106,6 +131,9 @@ def validate(target, loader, dist=None, window=None):
         parts = [p.tolist() for p in parts]
         means = merge_ranks([(OrderedDict(zip(means, p[:-1])), p[-1]) for p in parts])
         n = int(sum(p[-1] for p in parts))
+    if metrics is not None:
+        from . import evaluate
+        means.update(evaluate.scalar_metrics(metrics.summarize(metrics.merge_ranks(metrics.close().result(), dist))))
     means["num_samples"], means["eval_iter_num"] = n, iters
     return means
 
@@ -123,7 +151,9 @@ def _eval_mode(model):
 class EpochRunner:
     """See the module text.  `trainer`: a trainer.Trainer; the loaders: loader.DeviceBatchLoader (train=True / False) -- anything
     with __len__, __iter__, set_epoch and, for a bit-identical resume, state() / load_state().  `save_best`: a logged name;
-    the checkpoint of the epoch with the LOWEST validation mean of it is kept as best_{name}.pth.  `make_window`: the factory of
+    the checkpoint of the epoch with the LOWEST validation mean of it is kept as best_{name}.pth (`save_best_rule="greater"`: the
+    highest, for seg_miou and the like).  `metrics=True`: the validation pass also fills an evaluate.MetricWindow from the same
+    forwards; the task metrics join the validation line after the loss means and `save_best` may name one.  `make_window`: the factory of
     the log windows (default: logvars.LogWindow on the model's device).  `cumulative_iters` = k > 1: gradient accumulation, one
     optimizer update per window of k iterations (`accumulation_plan`, per epoch; the trainer's step(window=...)); 1: plain
     steps, the trainer's step() without a window.  The logged values of a window's micro-steps are held back (on the device) and
@@ -133,7 +163,10 @@ class EpochRunner:
 
     def __init__(self, trainer, train_loader, val_loader=None, work_dir="work_dir", max_epochs=1, log_interval=100,
                  ckpt_interval=1, eval_interval=1, ignore_last=True, save_best=None, dist=None, make_window=None, verbose=True,
-                 cumulative_iters=1):
+                 cumulative_iters=1, metrics=False, save_best_rule="less"):
+        if save_best_rule not in ("less", "greater"):
+            raise ValueError(f"EpochRunner: save_best_rule is 'less' or 'greater', not {save_best_rule!r}")
+        self.metrics, self.save_best_rule = bool(metrics), save_best_rule
         if min(int(max_epochs), int(log_interval), int(ckpt_interval), int(eval_interval), int(cumulative_iters)) < 1:
             raise ValueError("EpochRunner: max_epochs, the intervals and cumulative_iters are >= 1")
         self.cumulative_iters = int(cumulative_iters)
@@ -150,7 +183,7 @@ class EpochRunner:
         self.make_window = make_window
         self.window = None
         self.epoch = 0                   # epochs completed
-        self.best = None                 # lowest validation mean of `save_best` so far
+        self.best = None                 # best validation value of `save_best` so far (lowest, or highest under "greater")
         self.logs = []                   # every line written, as dicts (all ranks)
         os.makedirs(self.work_dir, exist_ok=True)
 
@@ -246,12 +279,16 @@ class EpochRunner:
             val = None
             if self.val_loader is not None and (e + 1) % self.eval_interval == 0:
                 lr = trainer.current_lr()
-                val = validate(trainer, self.val_loader, dist=self.dist, window=self.make_window())
+                mwin = None
+                if self.metrics:
+                    from . import evaluate
+                    mwin = evaluate.window_for(trainer.model)
+                val = validate(trainer, self.val_loader, dist=self.dist, window=self.make_window(), metrics=mwin)
                 line = OrderedDict(mode="val", epoch=e + 1, iter=n, lr=lr)
                 line.update(val)
                 self._write(line)
             better = (val is not None and self.save_best is not None and self.save_best in val
-                      and (self.best is None or val[self.save_best] < self.best))
+                      and is_better(val[self.save_best], self.best, self.save_best_rule))
             if better:
                 self.best = val[self.save_best]
             if (e + 1) % self.ckpt_interval == 0 or better:

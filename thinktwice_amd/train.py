@@ -1,7 +1,8 @@
 """Train from a dataset directory (the reference's open_loop_training/train.py with configs/thinktwice.py):
 
     python -m thinktwice_amd.train --data-root <dir the route paths are relative to> --metadata <dataset_metadata.pkl> \\
-        --work-dir work --epochs 60 --batch-size 8 [--cumulative-iters 2] [--resume auto] [--load-from weights.pth]
+        --work-dir work --epochs 60 --batch-size 8 [--cumulative-iters 2] [--resume auto] [--load-from weights.pth] \\
+        [--metrics] [--save-best wp_ade_5 | --save-best seg_miou:greater]
     python -m torch.distributed.run --nproc_per_node 8 -m thinktwice_amd.train ...          # one rank per GPU
 
 It builds the model, a trainer.Trainer, the train and validation dataset.DatasetIndex and loader.DeviceBatchLoader and hands
@@ -38,7 +39,18 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--train-towns", nargs="+", default=None, help="override the split's training towns")
     ap.add_argument("--val-towns", nargs="+", default=None, help="override the split's validation towns")
-    return ap.parse_args(argv)
+    ap.add_argument("--metrics", action="store_true", help="the validation pass also reports the open-loop task metrics "
+                    "(evaluate.MetricWindow: waypoint errors in metres, seg IoU, depth-bin accuracy), from the same forwards")
+    ap.add_argument("--save-best", default=None, metavar="NAME[:greater]", help="keep the checkpoint with the best validation "
+                    "value of a logged name as best_NAME.pth: the lowest, or with :greater the highest (seg_miou)")
+    args = ap.parse_args(argv)
+    if args.save_best is not None:
+        from .runner import parse_save_best
+        try:
+            parse_save_best(args.save_best)
+        except ValueError as e:
+            ap.error(str(e))
+    return args
 
 
 def assemble(args):
@@ -52,12 +64,18 @@ def assemble(args):
         cfg["val_town"] = list(args.val_towns)
     final_dim = tuple(args.final_dim) if args.final_dim else None
     metadata = args.metadata or os.path.join(args.data_root, "..", "dataset", "dataset_metadata.pkl")
+    runner_extra = {}
+    if getattr(args, "metrics", False):
+        runner_extra["metrics"] = True
+    if getattr(args, "save_best", None):
+        from .runner import parse_save_best
+        runner_extra["save_best"], runner_extra["save_best_rule"] = parse_save_best(args.save_best)
     return {"cfg": cfg, "ida_aug_conf": dc.ida_aug_conf(final_dim), "overrides": {} if final_dim is None else {"final_dim": final_dim},
             "metadata": metadata, "root": args.data_root, "cumulative_iters": args.cumulative_iters,
             "trainer": dict(lr=args.lr, frozen_bn=bool(args.frozen_bn)),
             "loader": dict(batch_size=args.batch_size, seed=args.seed, augment=not args.no_augment),
             "runner": dict(work_dir=args.work_dir, max_epochs=args.epochs, log_interval=args.log_interval,
-                           ckpt_interval=dc.CKPT_INTERVAL, eval_interval=dc.EVAL_INTERVAL)}
+                           ckpt_interval=dc.CKPT_INTERVAL, eval_interval=dc.EVAL_INTERVAL, **runner_extra)}
 
 
 def main(argv=None):
