@@ -82,6 +82,34 @@ def test_a_window_of_one_is_the_plain_step(rig):
     assert rig.main.live_ranges == rig.twin.live_ranges
 
 
+def test_backward_hands_over_the_tape_gradients_bit_for_bit(rig):
+    """Trainer.backward over a buffer full of NaN: the flat gradient is, bit for bit, a zeroed buffer into which every
+    `param_grads` entry is copied at its parameter's offset with torch; nothing outside `live_ranges` is written after the
+    zeroing, and `live_ranges` are the merged runs of the reached parameters."""
+    _reset(rig.main, ck=rig.ck0)
+    t = rig.main
+    t.grads.flat.fill_(float("nan"))
+    t.backward(rig.A)
+    got = t.grads.flat.clone()
+    want, runs = torch.zeros_like(got), []
+    for name, off in zip(t.names, t.grads.offsets):
+        g = t.param_grads.get(name)
+        if g is None:
+            continue
+        n = t.sd[name].numel()
+        want[off:off + n].copy_(g.reshape(-1))
+        if runs and runs[-1][1] == off:
+            runs[-1][1] = off + n
+        else:
+            runs.append([off, off + n])
+    assert set(t.param_grads) <= set(t.names) and 0 < len(t.param_grads) < len(t.names)
+    assert not torch.isnan(got).any()
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    assert t.live_ranges == [(a, b - a) for a, b in runs]
+    dead = ~_live_mask(t, t.live_ranges)
+    assert int(dead.sum()) > 0 and not got[dead].any()
+
+
 def test_two_micro_steps_are_the_update_on_the_scaled_sum(rig, grads):
     """k = 2 on two different batches: after micro-step 0 the buffer is f32(0.5 * gA) and nothing else has happened; the close is
     clip + AdamW + re-preparation on f32(0.5 * gA) + f32(0.5 * gB), which the twin is handed directly."""
@@ -229,6 +257,33 @@ def test_train_mode_counters_move_on_every_micro_step():
     osd = tr.optimizer_state_dict()
     assert osd["state"] and all(float(s["step"]) == 1.0 for s in osd["state"].values())
     assert tr.iteration == 2 and tr._bn_steps == 2 and tr.opt.steps == 1
+
+
+def test_a_skipped_plain_step_and_a_skipped_window_are_counted_by_their_own_rules():
+    """frozen_bn=False, a batch whose gradient norm is not finite (a NaN in the Beta target action_mu, as test_runner.Poisoned
+    makes one), check_finite=False: the device skips the update, reconcile() finds one skip and takes the iteration back.
+    `_bn_steps` goes back with a plain step and stays with a window (its forward ran and moved the running statistics).
+    check_finite=True on the plain step raises before the counters move, and reconcile() has nothing left to find."""
+    from thinktwice_amd import model as tm, params
+    from thinktwice_amd.trainer import Trainer
+    m, cfg = tm.build_thinktwice(final_dim=HW, dtype="f32x3")
+    tr = Trainer(m, params.init_params(cfg, seed=0), lr=1e-4, frozen_bn=False)
+    ck0, p0 = tr.checkpoint(), tr.flat_param.clone()
+    bad = dict(_batch(2, 3))
+    bad["action_mu"] = bad["action_mu"].clone()
+    bad["action_mu"].view(-1)[0] = float("nan")
+    for window, bn_steps in ((None, 0), ((0, 1), 1)):
+        tr.load_checkpoint(ck0)
+        out = tr.step(bad, check_finite=False, window=window)
+        assert not torch.isfinite(out["grad_norm"][0]) and ("updated" in out) is (window is not None)
+        assert tr.reconcile() == 1
+        assert (tr.iteration, tr.opt.steps, tr._bn_steps) == (0, 0, bn_steps), window
+        assert torch.equal(tr.flat_param, p0)
+    tr.load_checkpoint(ck0)
+    with pytest.raises(FloatingPointError, match="non-finite"):
+        tr.step(bad)
+    assert tr.iteration == 0 and tr.reconcile() == 0 and tr.iteration == 0 and tr._bn_steps == 0
+    assert tr.opt.steps == 0 and torch.equal(tr.flat_param, p0)
 
 
 def test_the_autograd_route_accumulates_the_same_bits(rig):

@@ -178,6 +178,68 @@ def test_prepared_weight_gradients_return_in_the_reference_layouts():
     assert torch.equal(tape.param_grads["a.dcn.weight"], dcn)
 
 
+@pytest.mark.parametrize("has_bn,has_bias", [(True, False), (True, True), (False, True)])
+def test_folded_affine_parameter_gradients_match_torch_autograd(has_bn, has_bias):
+    """Tape._affine_param_grads against torch autograd in float64: y = scale * z + shift with scale = gamma / sigma and
+    shift = beta + (bias - mean) * scale (bias only: y = z + bias), fed dscale = sum g * z and dshift = sum g.  rtol 1e-12:
+    float64 and a handful of operations per element."""
+    gen = torch.Generator().manual_seed(5)
+    R, C = 7, 5
+    r = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64)           # noqa: E731
+    gamma, beta, bias = (r(C).requires_grad_(True) for _ in range(3))
+    mean, sigma, z, g = r(C), r(C).abs() + 0.5, r(R, C), r(R, C)
+    if has_bn:
+        scale = gamma / sigma
+        shift = beta + ((bias if has_bias else 0.0) - mean) * scale
+    else:
+        scale, shift = None, bias
+    y = z * (1.0 if scale is None else scale) + shift
+    (y * g).sum().backward()
+    meta = autodiff.ConvMeta("a.conv", C, bn="a.bn" if has_bn else None, mean=mean, sigma=sigma,
+                             bias=bias.detach() if has_bias else None)
+    det = lambda t: None if t is None else t.detach()                             # noqa: E731
+    tape = autodiff.Tape()
+    tape._affine_param_grads(meta, (g * z).sum(0), g.sum(0), det(scale), det(shift))
+    want = {}
+    if has_bn:
+        want.update({"a.bn.weight": gamma.grad, "a.bn.bias": beta.grad})
+    if has_bias:
+        want["a.conv.bias"] = bias.grad
+    assert list(tape.param_grads) == list(want)
+    for k, w in want.items():
+        torch.testing.assert_close(tape.param_grads[k], w, rtol=1e-12, atol=0.0)
+    if has_bn and not has_bias:               # a BatchNorm on its own (affine_rows) hands AFFINE_META's tuple: the same tensors
+        alone = autodiff.Tape()
+        alone._affine_param_grads(("a.bn", mean, sigma), (g * z).sum(0), g.sum(0), det(scale), det(shift))
+        assert list(alone.param_grads) == list(want) and all(torch.equal(alone.param_grads[k], tape.param_grads[k]) for k in want)
+    # bn_raw (the train-mode form: the launch wrote z + bias, ops.batchnorm_train owns gamma / beta): the bias alone
+    raw = autodiff.Tape()
+    raw._affine_param_grads(meta, None, g.sum(0), None, det(bias) if has_bias else None, bn_raw=True)
+    assert list(raw.param_grads) == (["a.conv.bias"] if has_bias else [])
+    if has_bias:
+        assert torch.equal(raw.param_grads["a.conv.bias"], g.sum(0))
+
+
+def test_recorders_refuse_the_bias_and_batchnorm_forms_they_never_differentiated():
+    """A transposed convolution and a sparse convolution with both a bias and a folded BatchNorm (no layer of the model is
+    one): the recorders raise instead of filing the narrower rule they used to state."""
+    both = autodiff.ConvMeta("a.up", 4, bn="a.bn", mean=torch.zeros(2), sigma=torch.ones(2), bias=torch.zeros(2))
+    x, w, y = torch.zeros(1, 2, 2, 4), torch.zeros(8, 1, 1, 4), torch.zeros(1, 4, 4, 2)
+    tape = autodiff.Tape()
+    with pytest.raises(NotImplementedError, match="tape: transposed convolution with both a bias and a folded BatchNorm"):
+        tape._deconv2x2(both, x, w, y, torch.zeros(2), 0, 0, 4, 0, torch.ones(2), None, None)
+    ws = torch.zeros(2, 1, 27, 4)
+    owner = object()
+    with autodiff.owned_by(owner):
+        autodiff.CONV_META[ws] = both
+    try:
+        with pytest.raises(NotImplementedError, match="tape: sparse convolution with a bias"):
+            tape.gather_conv(torch.zeros(3, 4), None, None, ws, torch.ones(2), torch.zeros(2), 1, None, torch.zeros(3, 2), None)
+    finally:
+        autodiff.CONV_META.clear(owner)
+    assert not tape.nodes and not tape.param_grads
+
+
 def test_trainable_split_matches_the_reference_gradient_golden():
     """trainer._trainable keeps exactly the reference's nn.Parameters: the 878 live + 90 dead names of golden F13 (whose
     backward ran on the instantiated reference modules), none of the registered buffers."""

@@ -278,6 +278,29 @@ class Tape:
         else:
             self.param_grads[name] = g
 
+    def _affine_param_grads(self, meta, dscale, dshift, scale, shift, bn_raw=False):
+        """File the parameter gradients behind a layer's epilogue y = scale * z + shift from d(loss)/d(scale), d(loss)/d(shift).
+        `meta` names the parameters: a ConvMeta, or AFFINE_META's (BatchNorm name, mean, sigma) of a BatchNorm on its own.
+        Folded BatchNorm: scale = gamma / sigma, shift = beta + (bias - mean) * scale, so with off = mean [- bias]:
+        dgamma = (dscale - off * dshift) / sigma, dbeta = dshift, dbias = dshift * scale.  Without one, shift is the bias:
+        dbias = dshift.  `bn_raw` (ops.batchnorm_train owns the BatchNorm parameters): the same, if the launch added a bias."""
+        if isinstance(meta, tuple):
+            conv, bias, (bn, mean, sigma) = None, None, meta
+        else:
+            conv, bias, bn, mean, sigma = meta.name, meta.bias, meta.bn, meta.mean, meta.sigma
+        if bn_raw:
+            if bias is not None and shift is not None:
+                self.add_param_grad(conv + ".bias", dshift)
+        elif bn is not None:
+            off = mean if bias is None else mean - bias
+            self.add_param_grad(bn + ".weight", (dscale - off * dshift) / sigma)
+            self.add_param_grad(bn + ".bias", dshift)
+            if bias is not None:
+                self.add_param_grad(conv + ".bias", dshift * scale)
+        elif bias is not None:
+            assert shift is not None, f"tape: {conv} has a bias its launch did not add"
+            self.add_param_grad(conv + ".bias", dshift)
+
     def backward(self):
         global TAPE
         active, TAPE = TAPE, None          # the backward closures call forward ops too: nothing of that is recorded
@@ -372,18 +395,7 @@ class Tape:
             # parameters
             dw = ops.conv2d_wgrad(xd, dconv, KH, KW, stride, pad, dil, cin=cin, in_coff=in_coff, cin_pad=cin_p, x3=self.x3)
             meta.place_weight_grad(self, dw)
-            if bn_raw:
-                if meta.bias is not None and shift is not None:
-                    self.add_param_grad(meta.name + ".bias", dshift)
-            elif meta.bn is not None:
-                # scale = gamma / sigma, shift = beta + (bias - mean) * gamma / sigma
-                off = meta.mean if meta.bias is None else meta.mean - meta.bias
-                self.add_param_grad(meta.bn + ".weight", (dscale - off * dshift) / meta.sigma)
-                self.add_param_grad(meta.bn + ".bias", dshift)
-                if meta.bias is not None:
-                    self.add_param_grad(meta.name + ".bias", dshift * scale)
-            elif meta.bias is not None:
-                self.add_param_grad(meta.name + ".bias", dshift)
+            self._affine_param_grads(meta, dscale, dshift, scale, shift, bn_raw)
             # input: conv of dconv with the rotated weights, accumulated into x's gradient window
             if stop_grad:           # the reference detaches this input (lss.py:589 seg_output.detach())
                 return
@@ -407,6 +419,8 @@ class Tape:
         gradient is un-shuffled (a layout copy) and the layer is differentiated as the 1x1 convolution it is."""
         if res1 is not None or res2 is not None:
             raise NotImplementedError("tape: transposed convolution with a residual input")
+        if meta.bn is not None and meta.bias is not None and not bn_raw:
+            raise NotImplementedError("tape: transposed convolution with both a bias and a folded BatchNorm")
         C4 = w.shape[0]
         Cout = C4 // 4
         self._keep += [x, y]
@@ -421,14 +435,7 @@ class Tape:
             # prepared rows are (dh*2+dw)*Cout + co; the reference weight is [Cin, Cout, 2, 2]
             self.add_param_grad(meta.name + ".weight",
                                 dw[:, 0, 0, :meta.cin].reshape(2, 2, Cout, meta.cin).permute(3, 2, 0, 1).contiguous())
-            if bn_raw:
-                if meta.bias is not None and shift is not None:
-                    self.add_param_grad(meta.name + ".bias", dshift)
-            elif meta.bn is not None:
-                self.add_param_grad(meta.bn + ".weight", (dscale - meta.mean * dshift) / meta.sigma)
-                self.add_param_grad(meta.bn + ".bias", dshift)
-            elif meta.bias is not None:
-                self.add_param_grad(meta.name + ".bias", dshift)
+            self._affine_param_grads(meta, dscale, dshift, scale, shift, bn_raw)
             ops.conv2d_dgrad(dconv, w, (H, W_), 1, 0, 1, x3=self.x3, out=self.grad(x), out_coff=in_coff)
 
         self.nodes.append(bwd)
@@ -549,7 +556,6 @@ class Tape:
             return      # a constant rescaling of a model input (speed / 12): nothing to differentiate
         if meta is None or act != 0:
             raise NotImplementedError("tape: affine_rows without a registered BatchNorm / with an activation")
-        name, mean, sigma = meta
         self._keep += [x, out]
 
         def bwd():
@@ -557,8 +563,7 @@ class Tape:
             go = self.grad(out)
             # y = scale * x + shift on the first C columns: the conv-epilogue backward with conv := x
             dconv, _, dscale, dshift = ops.conv_epilogue_bwd(go, out, scale, shift, 0, C=C)
-            self.add_param_grad(name + ".weight", (dscale - mean * dshift) / sigma)
-            self.add_param_grad(name + ".bias", dshift)
+            self._affine_param_grads(meta, dscale, dshift, scale, shift)
             self.grad(x).add_(dconv)
 
         self.nodes.append(bwd)
@@ -600,6 +605,8 @@ class Tape:
         meta = CONV_META.get(w)
         if meta is None:
             raise NotImplementedError("tape: sparse convolution with an unregistered weight")
+        if meta.bias is not None or (meta.bn is None and not bn_raw):
+            raise NotImplementedError("tape: sparse convolution with a bias / without a BatchNorm")
         Cout, _, taps, cin_p = w.shape
         self._keep += [feats, nbr, m_dev, res, out]
 
@@ -610,9 +617,7 @@ class Tape:
                                                              m_dev=m_dev)
             dw = ops.gather_conv_wgrad(feats, nbr, m_dev, dconv, taps, cin_pad=cin_p)
             meta.place_weight_grad(self, dw)
-            if not bn_raw:
-                self.add_param_grad(meta.bn + ".weight", (dscale - meta.mean * dshift) / meta.sigma)
-                self.add_param_grad(meta.bn + ".bias", dshift)
+            self._affine_param_grads(meta, dscale, dshift, scale, shift, bn_raw)
             # input rows: the same gathered GEMM on the transposed rulebook, accumulated into the input's gradient -- in bf16x3
             # like the dense input gradients when the tape runs in that mode (a submanifold layer's transposed rulebook is a
             # submanifold rulebook again: the run-staged kernel takes it; was the exact-f32 register-staged gather kernel,

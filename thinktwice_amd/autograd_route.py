@@ -29,13 +29,9 @@ class MasterState:
 
     def __init__(self, model, sd):
         dev = model.device
-        self.names, self.flat, views = masters.flat_masters(sd, dev)
-        self.keys = list(sd)
-        self.params, self.buffers, self.layout = {}, {}, {}
-        off = 0
-        for k in self.names:
-            self.layout[k] = (off, views[k].numel(), tuple(views[k].shape))
-            off += views[k].numel()
+        self.layout, self.flat, views = masters.flat_masters(sd, dev)
+        self.names, self.keys = self.layout.names, list(sd)
+        self.params, self.buffers = {}, {}
         # BatchNorm running statistics: views of one flat buffer (the prepared layers alias them and update them in place under
         # model.train(); one version counter tells when somebody else wrote them), call counters: views of one int64 buffer
         stat_keys = [k for k, v in sd.items() if torch.is_tensor(v) and k.endswith(("running_mean", "running_var"))]
@@ -101,7 +97,7 @@ class MasterState:
         return (self.flat._version, self.stats._version)
 
     def operand_tensors(self):
-        return {k: (self.params[k].detach() if k in self.params else self.buffers[k]) for k in self.keys}
+        return masters.operand_tensors(self.keys, self.params, self.buffers)
 
 
 class TapedLosses(dict):
@@ -131,18 +127,9 @@ class TapedLoss(torch.autograd.Function):
         route.tape = None
         tape.backward()
         grads, tape.param_grads = tape.param_grads, {}
-        unknown = [k for k in grads if k not in st.layout]
-        assert not unknown, f"gradients for names outside the state_dict: {unknown[:5]}"
-        flat = torch.empty(st.flat.numel(), dtype=torch.float32, device=st.flat.device)       # (a buffer of its own per
-        srcs, offs = [], []                                      # backward: AccumulateGrad may keep the views as `.grad`)
-        for k, g in grads.items():
-            off, n, _ = st.layout[k]
-            assert g.numel() == n and g.dtype == torch.float32, k
-            srcs.append(g.reshape(-1) if g.is_contiguous() else g.contiguous().view(-1))
-            offs.append(off)
-        st.table.upload(srcs, offs, flat.numel())
-        scale = grad_output.detach().to(torch.float32).reshape(1)
-        ops.grad_gather(st.table, flat, scale)
+        # (a buffer of its own per backward: AccumulateGrad may keep the views as `.grad`)
+        flat = torch.empty(st.flat.numel(), dtype=torch.float32, device=st.flat.device)
+        st.layout.deposit(st.table, grads, flat, grad_output.detach().to(torch.float32).reshape(1))
         out = []
         for i, k in enumerate(st.names):
             if k in grads and ctx.needs_input_grad[2 + i]:

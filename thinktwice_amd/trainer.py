@@ -3,8 +3,13 @@
 under MMDistributedDataParallel (apis/mmdet_train.py:67-74)).
 
     forward_train on the HIP forward  ->  reverse sweep of the tape (thinktwice_amd/autodiff.py: hand-written backward kernels,
-    gradients under the reference's state_dict names)  ->  ONE all-reduce of the flat gradient buffer (grad_sync.py, RCCL)
-    ->  global-norm clip + AdamW on the flat buffers (optim.py, two launches)  ->  operands re-prepared from the master weights.
+    gradients under the reference's state_dict names)  ->  ONE launch that gathers them into the flat gradient buffer
+    (masters.FlatLayout.deposit: the hand-over the torch-autograd route uses too)  ->  ONE all-reduce of that buffer
+    (grad_sync.py, RCCL)  ->  global-norm clip + AdamW on the flat buffers (optim.py, two launches)  ->  operands re-prepared
+    from the master weights.
+
+`Trainer.step` is one body: a plain iteration is an accumulation window of one with the unscaled gradient; where the two forms
+differ (when the counters move, what reconcile() takes back, the `updated` key) the body asks `plain`.
 
 The master parameters are f32 views of one flat buffer (288 GB of HBM: master weights, Adam moments, the flat gradient and the
 kernels' operand formats all stay resident).  BatchNorm runs on its running statistics (frozen-BN fine-tuning, what golden F10 /
@@ -17,7 +22,7 @@ import sys
 
 import torch
 
-from . import autodiff, masters
+from . import autodiff, masters, ops
 from ._lib import TTError
 from .grad_sync import FlatGradBuffer
 from .masters import BUFFERS as _BUFFERS, trainable as _trainable  # noqa: F401  (the layout rule, shared with the autograd route)
@@ -41,10 +46,11 @@ class Trainer:
         self.frozen_bn = bool(frozen_bn)
         self.x3 = (model.dtype != torch.float32) if x3 is None else x3
         sd = masters.strip(state_dict)
-        self.names, self.flat_param, views = masters.flat_masters(sd, dev)
-        self._trainable = set(self.names)
+        self.layout, self.flat_param, views = masters.flat_masters(sd, dev)
+        self.names = self.layout.names
         # (a master view is a leaf whose .grad FlatGradBuffer points into its buffer)
-        self.sd = {k: (views[k].requires_grad_(True) if k in views else v) for k, v in sd.items()}
+        self._trainable = {k: v.requires_grad_(True) for k, v in views.items()}
+        self.sd = {k: self._trainable.get(k, v) for k, v in sd.items()}
         self.grads = FlatGradBuffer([self.sd[k] for k in self.names])
         self.opt = FlatAdamW(self.flat_param, self.grads.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                              max_grad_norm=max_grad_norm)
@@ -75,8 +81,7 @@ class Trainer:
         a host-only operation on a device tensor."""
         if self._prepare_on_device:
             try:
-                masters.prepare_on_device(self.model, {k: (v.detach() if k in self._trainable else self._dev_buffers.get(k, v))
-                                                       for k, v in self.sd.items()}, self.frozen_bn)
+                masters.prepare_on_device(self.model, self._operand_tensors(), self.frozen_bn)
                 return
             except (RuntimeError, TypeError) as e:
                 print(f"[trainer] device-side operand preparation failed ({type(e).__name__}: {e}); "
@@ -86,10 +91,11 @@ class Trainer:
         with torch.no_grad():
             self.model.load_state_dict({k: (v.detach().cpu() if k in self._trainable else v) for k, v in self.sd.items()})
 
-    def backward(self, batch, device_log=False):
-        """Forward + losses + reverse sweep: fills the flat gradient buffer (no collective, no update).  Returns
-        dict(loss, log_vars, num_samples) of train_step (`device_log`: its device-resident form)."""
-        self.grads.zero_()
+    def _operand_tensors(self):
+        return masters.operand_tensors(self.sd, self._trainable, self._dev_buffers, other=self.sd)
+
+    def _sweep(self, batch, device_log):
+        """Forward + losses + reverse sweep under this trainer's BatchNorm mode -> (train_step's dict, the swept tape)."""
         was_training = self.model.training
         self.model.train(not self.frozen_bn)
         try:
@@ -98,23 +104,29 @@ class Trainer:
                 tape.backward()
         finally:
             self.model.train(was_training)
+        return out, tape
+
+    def _gradients(self, batch, device_log, scale=None, accumulate=False):
+        """Forward + losses + reverse sweep, then the tape's parameter gradients into the flat buffer (masters.FlatLayout.deposit,
+        one launch): flat (=|+=) scale * g, `param_grads` = the tape's.  Not accumulating, the buffer is zeroed first and the
+        deposit WRITES (never 0 * old + scale * g: a NaN left by a skipped update does not survive)."""
+        if not accumulate:
+            self.grads.zero_()
+        out, tape = self._sweep(batch, device_log)
+        if self._seg_table is None:
+            # two tables in turn: uploading one waits for ITS previous upload only, two deposits back
+            self._seg_table = [ops.GradSegTable(self.flat_param.device) for _ in range(2)]
+        self._seg_table.reverse()
+        self.layout.deposit(self._seg_table[0], tape.param_grads, self.grads.flat, scale, accumulate)
         self.param_grads = tape.param_grads
-        # element ranges of the parameters that received a gradient (the others are skipped by the optimizer like torch's
-        # grad-is-None parameters): merged runs in flat-buffer order
-        runs, off = [], 0
-        for k in self.names:
-            n = self.sd[k].numel()
-            if k in tape.param_grads:
-                if runs and runs[-1][0] + runs[-1][1] == off:
-                    runs[-1][1] += n
-                else:
-                    runs.append([off, n])
-            off += n
-        self.live_ranges = [tuple(r) for r in runs]
-        unknown = [k for k in tape.param_grads if k not in self.sd]
-        assert not unknown, f"gradients for names outside the state_dict: {unknown[:5]}"
-        for k, g in tape.param_grads.items():
-            self.sd[k].grad.copy_(g.reshape(self.sd[k].shape))
+        return out
+
+    def backward(self, batch, device_log=False):
+        """Forward + losses + reverse sweep: fills the flat gradient buffer with the unscaled gradients and sets `param_grads`
+        and `live_ranges` (no collective, no update).  Returns dict(loss, log_vars, num_samples) of train_step (`device_log`:
+        its device-resident form)."""
+        out = self._gradients(batch, device_log)
+        self.live_ranges = self.layout.live_ranges(self.param_grads)
         return out
 
     def set_schedule(self, total_iters, iters_per_epoch, warmup_iters=1000, warmup_ratio=1.0 / 3, min_lr_ratio=1e-3):
@@ -181,95 +193,12 @@ class Trainer:
             raise TTError(f"Trainer.{what}: accumulation window open at micro-step {self._window[0]} of {self._window[1]}; a "
                           f"half-summed gradient is not something a checkpoint holds -- close the window first")
 
-    def _window_step(self, batch, lr, check_finite, device_log, window):
-        """step(window=(j, k)): micro-step j (0-based) of a window of k.  Every micro-step runs forward + reverse sweep and
-        DEPOSITS the tape's parameter gradients into the flat buffer scaled by 1/k (mmcv: loss / k before backward), one
-        launch of tt_grad_gather: j == 0 zeroes the buffer and writes scale * g (never 0 * old + scale * g: a NaN left by a
-        skipped window does not survive), j > 0 adds.  `iteration`, the BatchNorm call count, the running statistics and the
-        dropout counter move on every micro-step.  j < k - 1 does nothing else (no collective, no clip, no AdamW, no operand
-        preparation, no host synchronisation; `grad_norm` None, `updated` False, `check_finite` has nothing to look at).
-        j == k - 1 closes: one all-reduce, clip + AdamW over the union of the micro-steps' live ranges at the closing
-        iteration's rate, operands re-prepared; `updated` True.  A non-finite norm skips the update on the device as in step();
-        reconcile() takes the whole window's micro-iterations back out of `iteration` (see there for `_bn_steps`)."""
-        from . import ops
-        if window is None:
-            if self._window is not None:
-                raise ValueError(f"Trainer.step: window=None while an accumulation window is open (next: micro-step "
-                                 f"{self._window[0]} of {self._window[1]})")
-            self.reconcile()       # plain steps after window closes: one blocking read where the form changes, none after it
-            return self.step(batch, lr=lr, check_finite=check_finite, device_log=device_log)
-        j, k = (int(v) for v in window)
-        if not (k >= 1 and 0 <= j < k):
-            raise ValueError(f"Trainer.step: window=({j}, {k}) is not a micro-step j of k with 0 <= j < k")
-        if self._window is None and j != 0:
-            raise ValueError(f"Trainer.step: window=({j}, {k}) with no window open; a window starts at micro-step 0")
-        if self._window is not None and (j, k) != self._window:
-            raise ValueError(f"Trainer.step: window=({j}, {k}) does not continue the open window, whose next micro-step is "
-                             f"{self._window[0]} of {self._window[1]}")
-        if j == 0:
-            if self.opt.issued - self._issued_seen > self._window_closes:
-                self.reconcile()   # window closes after plain steps: the same single read
-            self._window_names = set()
-        if j == k - 1 and lr is None and self.schedule is not None:
-            lr = self.current_lr()
-        was_training = self.model.training
-        self.model.train(not self.frozen_bn)
-        try:
-            with autodiff.Tape(x3=self.x3, release=True) as tape:
-                out = self.model.train_step(batch, None, device_log=True) if device_log else self.model.train_step(batch, None)
-                tape.backward()
-        finally:
-            self.model.train(was_training)
-        grads = tape.param_grads
-        if self._seg_table is None:
-            # two tables in turn: uploading one waits for ITS previous upload only, two micro-steps back
-            self._seg_table = [ops.GradSegTable(self.flat_param.device) for _ in range(2)]
-            self._offsets = dict(zip(self.names, self.grads.offsets))
-        unknown = [n for n in grads if n not in self._offsets]
-        assert not unknown, f"gradients for names outside the state_dict: {unknown[:5]}"
-        srcs, offs = [], []
-        for name, g in grads.items():
-            assert g.numel() == self.sd[name].numel() and g.dtype == torch.float32, name
-            srcs.append(g.reshape(-1) if g.is_contiguous() else g.contiguous().view(-1))
-            offs.append(self._offsets[name])
-        if k not in self._window_scales:
-            self._window_scales[k] = torch.full((1,), 1.0 / k, dtype=torch.float32, device=self.flat_param.device)
-        if j == 0:
-            self.grads.zero_()
-        table = self._seg_table[self.iteration & 1].upload(srcs, offs, self.grads.numel)
-        ops.grad_gather(table, self.grads.flat, self._window_scales[k], accumulate=j > 0)
-        self._window = (j + 1, k) if j < k - 1 else None
-        self.param_grads = grads
-        self._window_names.update(grads)
+    def _count_iteration(self):
         self.iteration += 1
         if not self.frozen_bn:
             self._bn_steps += 1
         if self.schedule is not None:
             self.epoch = self.iteration // self.schedule["iters_per_epoch"]
-        if j < k - 1:
-            out["grad_norm"], out["updated"] = None, False
-            return out
-        runs, off = [], 0
-        for name in self.names:
-            n = self.sd[name].numel()
-            if name in self._window_names:
-                if runs and runs[-1][0] + runs[-1][1] == off:
-                    runs[-1][1] += n
-                else:
-                    runs.append([off, n])
-            off += n
-        self.live_ranges = [tuple(r) for r in runs]
-        self.grads.all_reduce_mean()
-        out["grad_norm"], out["updated"] = self.opt.step(lr, live_ranges=self.live_ranges, window_len=k), True
-        self._window_closes += 1
-        if check_finite and not bool(torch.isfinite(out["grad_norm"][0])):
-            self.reconcile()                        # takes the window's k micro-iterations back out of `iteration`
-            raise FloatingPointError("Trainer.step: non-finite gradient norm at the close of an accumulation window; the update "
-                                     "was skipped on the device (weights, Adam moments and the step count are those of the last "
-                                     "good update)")
-        self._stepped.update(self._window_names)
-        self._prepare()
-        return out
 
     def step(self, batch, lr=None, check_finite=True, device_log=False, window=None):
         """One iteration; adds `grad_norm` (device tensor [norm, clip factor]) to train_step's dict.  A non-finite gradient
@@ -279,25 +208,70 @@ class Trainer:
         applied).  That alone does not make the step asynchronous: the float `log_vars` are read from the device every
         iteration.  With `device_log=True` as well they stay there (a logvars.DeviceLogVars, for a logvars.LogWindow) and the
         step issues no host synchronisation of its own.  Without `lr`, the rate of set_schedule() (else the constructor's).
-        `window=(j, k)`: this call is micro-step j of a gradient-accumulation window of k (_window_step; the dict then also
-        carries `updated`).  `window=None` is the plain iteration below."""
-        if window is not None or self._window is not None or self._window_closes:
-            return self._window_step(batch, lr, check_finite, device_log, window)
-        if lr is None and self.schedule is not None:
+
+        `window=(j, k)`: micro-step j (0-based) of a gradient-accumulation window of k; the dict then also carries `updated`.
+        Every micro-step runs forward + reverse sweep and deposits the gradients scaled by 1/k (mmcv: loss / k before
+        backward): j == 0 writes, j > 0 adds.  j < k - 1 does nothing else (no collective, no clip, no AdamW, no operand
+        preparation, no host synchronisation; `grad_norm` None, `updated` False, `check_finite` has nothing to look at).
+        j == k - 1 closes: one all-reduce, clip + AdamW over the union of the micro-steps' live ranges at the closing
+        iteration's rate, operands re-prepared; `updated` True.  `window=None`, the plain iteration, is the window (0, 1)
+        with the unscaled gradient, except where `plain` is asked below."""
+        plain = window is None
+        if plain:
+            j, k = 0, 1
+            if self._window is not None:
+                raise ValueError(f"Trainer.step: window=None while an accumulation window is open (next: micro-step "
+                                 f"{self._window[0]} of {self._window[1]})")
+            if self._window_closes:
+                self.reconcile()   # plain steps after window closes: one blocking read where the form changes, none after it
+        else:
+            j, k = (int(v) for v in window)
+            if not (k >= 1 and 0 <= j < k):
+                raise ValueError(f"Trainer.step: window=({j}, {k}) is not a micro-step j of k with 0 <= j < k")
+            if self._window is None and j != 0:
+                raise ValueError(f"Trainer.step: window=({j}, {k}) with no window open; a window starts at micro-step 0")
+            if self._window is not None and (j, k) != self._window:
+                raise ValueError(f"Trainer.step: window=({j}, {k}) does not continue the open window, whose next micro-step is "
+                                 f"{self._window[0]} of {self._window[1]}")
+            if j == 0 and self.opt.issued - self._issued_seen > self._window_closes:
+                self.reconcile()   # window closes after plain steps: the same single read
+            if k not in self._window_scales:
+                self._window_scales[k] = torch.full((1,), 1.0 / k, dtype=torch.float32, device=self.flat_param.device)
+        closes = j == k - 1
+        if closes and lr is None and self.schedule is not None:
             lr = self.current_lr()
-        out = self.backward(batch, device_log=device_log)
+        if j == 0:
+            self._window_names = set()
+        out = self._gradients(batch, device_log, None if plain else self._window_scales[k], accumulate=j > 0)
+        self._window = None if closes else (j + 1, k)
+        self._window_names.update(self.param_grads)
+        if not plain:
+            # a window's counters (and the running statistics, the dropout counter) move on every micro-step: a skipped close
+            # is taken back by reconcile() through the device's skipped_iters (see there for `_bn_steps`, which stays)
+            self._count_iteration()
+        if not closes:
+            out["grad_norm"], out["updated"] = None, False
+            return out
+        self.live_ranges = self.layout.live_ranges(self._window_names)
         self.grads.all_reduce_mean()
-        out["grad_norm"] = self.opt.step(lr, live_ranges=self.live_ranges)
+        out["grad_norm"] = self.opt.step(lr, live_ranges=self.live_ranges, window_len=None if plain else k)
+        if not plain:
+            out["updated"] = True
+            self._window_closes += 1
         if check_finite and not bool(torch.isfinite(out["grad_norm"][0])):
-            self._skips_accounted += 1              # nothing below runs: iteration / BatchNorm counters never saw this step
-            raise FloatingPointError("Trainer.step: non-finite gradient norm; the update was skipped on the device (weights, "
-                                     "Adam moments and running statistics of the optimizer are those of the last good step)")
-        self._stepped.update(self.param_grads.keys())
-        self.iteration += 1
-        if not self.frozen_bn:
-            self._bn_steps += 1
-        if self.schedule is not None:
-            self.epoch = self.iteration // self.schedule["iters_per_epoch"]
+            if plain:
+                self._skips_accounted += 1          # nothing below runs: iteration / BatchNorm counters never saw this step
+                raise FloatingPointError("Trainer.step: non-finite gradient norm; the update was skipped on the device (weights, "
+                                         "Adam moments and running statistics of the optimizer are those of the last good step)")
+            self.reconcile()                        # takes the window's k micro-iterations back out of `iteration`
+            raise FloatingPointError("Trainer.step: non-finite gradient norm at the close of an accumulation window; the update "
+                                     "was skipped on the device (weights, Adam moments and the step count are those of the last "
+                                     "good update)")
+        self._stepped.update(self._window_names)
+        if plain:
+            # a plain step counts itself once the update is known to be issued for good; one the device skips unseen
+            # (check_finite=False) is taken back by reconcile(), `_bn_steps` included
+            self._count_iteration()
         self._prepare()
         return out
 
@@ -312,8 +286,7 @@ class Trainer:
         if not self._prepare_on_device:
             self._prepare()
         else:
-            masters.prepare_on_device(self.model, {k: (v.detach() if k in self._trainable else self._dev_buffers.get(k, v))
-                                                   for k, v in self.sd.items()}, True)
+            masters.prepare_on_device(self.model, self._operand_tensors(), True)
         self.model.eval()
         try:
             yield self.model

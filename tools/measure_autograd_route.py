@@ -1,7 +1,8 @@
 """Numbers behind profiles/autograd_route.txt (one MI355X, the thinktwice.py size, f32x3):
 
-  loop    the per-parameter `copy_` loop of Trainer.backward (trainer.py: `self.sd[k].grad.copy_(g.reshape(...))`, one torch launch
-          per gradient tensor) on the real gradient tensors of one backward -- runs on any commit that has trainer.Trainer
+  loop    a per-parameter `copy_` loop written here (`tr.sd[k].grad.copy_(g.reshape(...))`, one torch launch per gradient
+          tensor: how Trainer.backward filled its flat buffer before it took the gather) on the real gradient tensors of one
+          backward -- runs on any commit that has trainer.Trainer
   gather  tt_grad_gather on the same tensors' segment table: upload + one launch, and the launch alone; achieved bytes/s
   iter    one iteration of the torch-autograd route (trainable model, torch AdamW(foreach=True) + clip_grad_norm_) next to
           Trainer.step on the same batch, alternating, model.train() semantics on both sides
@@ -58,7 +59,7 @@ def loop_and_gather(args, what):
             for k, g in grads.items():
                 tr.sd[k].grad.copy_(g.reshape(tr.sd[k].shape))
         med, lo, hi = _events(loop, args.repeats)
-        print(f"copy_ loop ({len(grads)} launches): median {med:.3f} ms (min {lo:.3f}, max {hi:.3f}) over {args.repeats} repeats; "
+        print(f"this tool's own copy_ loop ({len(grads)} launches): median {med:.3f} ms (min {lo:.3f}, max {hi:.3f}) over {args.repeats} repeats; "
               f"{8 * n / med / 1e6:.1f} GB/s of read + write")
     if "gather" in what:
         from thinktwice_amd import ops
