@@ -968,6 +968,62 @@ int tt_png_decode_u8_segmented_phases(const uint8_t* packed_dev, long long packe
                                       int32_t* status_dev, int phases, void* stream);
 
 /* ------------------------------------------------------------------------
+ * PNG files WRITTEN on the device: uint8 [H, W, C] images (C = 1 grey, 3 RGB) -> complete files, born segmented: signature,
+ * IHDR, the `ttSG` index exactly as thinktwice_amd/png.py lays it out (version 1, rows_per_segment, ceil(H / R), n + 1
+ * big-endian offsets into the IDAT payload, offsets[0] = 2), ONE IDAT chunk with the whole zlib stream (78 01; per R rows one
+ * segment of non-final deflate blocks that ends in the empty stored block 00 00 FF FF and inflates alone; 03 00; the Adler-32
+ * of the filtered scanlines), IEND; every chunk with its CRC-32.  tt_png_decode_u8_segmented reads them one wave per segment,
+ * any PNG reader reads them as ordinary files.  The bytes are a function of the pixels and the table only
+ * (csrc/png_deflate.h, which tools/png_encode_host_check.cpp runs on the host to the same bytes).
+ * Launches, stream-ordered, nothing between them on the host: the filter pass (one 64-lane workgroup per row; PNG
+ * specification sections 9 and 12.8) -> the filtered scanlines in the workspace; the deflate, one 64-lane workgroup per
+ * segment, into per-segment worst-case slots of the workspace (dynamic Huffman blocks over an LZ77 parse, stored blocks where
+ * those would not be smaller); one workgroup per image that sums the segment sizes and writes the offsets and the fixed
+ * chunks; the copy that compacts the segments into the payload; the checksum tile plan, the Adler-32 tiles and fold, the
+ * CRC-32 tiles and fold (csrc/checksum.hip's kernels over csrc/png_checksum.h), written in place.
+ * images: the table, in host memory (validated before any launch) and in device memory (read by the kernels).  Image i's
+ * pixels are pixels_dev[pixel_offset, + H * W * C); its file goes to files_dev[file_offset, ...), a slot of at least
+ * tt_png_encode_bound(&image, 1) bytes, 4-byte aligned, of which the call writes exactly file_sizes_dev[i] bytes (every byte
+ * of the slot beyond them, and everything between slots, stays as it was).  No device-side status: every size is bounded.
+ * workspace: tt_png_encode_workspace_bytes(...) bytes, 256-byte aligned, contents irrelevant.
+ * Returns an error before any launch for: a null pointer; a misaligned table (8 bytes), files_dev or file offset (4),
+ * file_sizes_dev (8) or workspace (256); num_images < 1 or > TT_PNG_MAX_IMAGES; channels not 1 or 3; height or width < 1;
+ * rows_per_segment < 1; an unknown filter mode; pixels outside pixel_bytes; a slot outside files_bytes, smaller than the
+ * bound, or overlapping another; a workspace that is too small; a zlib stream that could pass 2^31 - 8 bytes.  No
+ * allocation, no copy, no synchronisation.
+ * ---------------------------------------------------------------------- */
+enum tt_png_filter {                    /* (a prefix of their own: TT_PNG_* are the decoder's status codes) */
+    TT_PNGE_FILTER_NONE = 0,
+    TT_PNGE_FILTER_SUB = 1,
+    TT_PNGE_FILTER_UP = 2,
+    TT_PNGE_FILTER_AVG = 3,
+    TT_PNGE_FILTER_PAETH = 4,             /* 0..4: that type for every row */
+    TT_PNGE_FILTER_ADAPTIVE = 5           /* per row the type with the smallest sum of |residual as int8|, the lowest on a tie */
+};
+typedef struct tt_png_enc_image {
+    long long pixel_offset;              /* of the image's uint8 [H, W, C] in pixels_dev, bytes */
+    long long file_offset;               /* of the image's slot in files_dev, bytes; a multiple of 4 */
+    long long file_capacity;             /* bytes of the slot, >= tt_png_encode_bound of this image */
+    int width, height;
+    int channels;                        /* 1 (grey) or 3 (RGB) */
+    int rows_per_segment;                /* >= 1 */
+    int filter;                          /* enum tt_png_filter */
+    int reserved;                        /* not read */
+} tt_png_enc_image;                      /* 48 bytes */
+/* Host arithmetic only.  The bound: the sum over the images of the largest file each can become (every segment stored);
+ * both: 0 for a null table, a bad count or an image the entry would refuse for its sizes. */
+long long tt_png_encode_bound(const tt_png_enc_image* images_host, int num_images);
+long long tt_png_encode_workspace_bytes(const tt_png_enc_image* images_host, int num_images);
+int tt_png_encode_u8(const uint8_t* pixels_dev, long long pixel_bytes, const tt_png_enc_image* images_host,
+                     const tt_png_enc_image* images_dev, int num_images, void* workspace, long long workspace_bytes,
+                     uint8_t* files_dev, long long files_bytes, long long* file_sizes_dev, void* stream);
+/* Measurement only (thinktwice_amd/bench_png_encode.py): the same call up to and including the filter pass (phases = 1), the
+ * deflate (2), or all of it (3). */
+int tt_png_encode_u8_phases(const uint8_t* pixels_dev, long long pixel_bytes, const tt_png_enc_image* images_host,
+                            const tt_png_enc_image* images_dev, int num_images, void* workspace, long long workspace_bytes,
+                            uint8_t* files_dev, long long files_bytes, long long* file_sizes_dev, int phases, void* stream);
+
+/* ------------------------------------------------------------------------
  * SURVEY 8f-4 (training step), optimizer half: the reference's `optimizer_config = dict(grad_clip=dict(max_norm=100,
  * norm_type=2))` and `optimizer = dict(type='AdamW', lr=1e-4, weight_decay=1e-7)` (configs/thinktwice.py:282-287:
  * torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW through mmcv's OptimizerHook) over ONE flat f32 parameter /

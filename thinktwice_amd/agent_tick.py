@@ -108,9 +108,22 @@ class AgentTick:
 
     What stays outside is the simulator's side of the tick: BGR -> RGB of the CARLA buffers, the GPS filter, the route planner
     (`pos`, `next_wp`, `next_cmd` are arguments) and carla.VehicleControl.  `run_step` returns (steer, throttle, brake, info);
-    `info["pred"]` holds the forward's output dict (None while the queue fills)."""
+    `info["pred"]` holds the forward's output dict (None while the queue fills).
 
-    def __init__(self, model, lag=10, queue_len=31, use_cache=False, stuck_threshold=800, final_dim=None, undistort=True):
+    recorder: a `png_encode.FrameRecorder`, or None.  With one, every `record_every`-th tick (step % record_every == 0; frame
+    number n = step // record_every, zero-padded as the dataset's, `dataset.frame_name`) submits to it, where the reference
+    agent saves under SAVE_PATH (thinktwice_agent.py:525-539):
+        rgb_front|rgb_left|rgb_right|rgb_back/NNNN.png  the four raw camera frames, encoded on the device from the uint8
+                                                        tensor the tick has uploaded anyway;
+        lidar/NNNN.npy                                  the merged cloud, (n, 4) float32, as `dataset.load_cloud` reads it;
+        meta/NNNN.json                                  the keys of the reference's `pid_metadata` (steer, throttle, brake,
+                                                        the two heads' values, is_stuck, stuck_detector, speed) and the
+                                                        target point.
+    This is a RECORDING of a drive, not a training sample: it holds no labels (depth, segmentation, boxes) and no dataset
+    measurements file.  With recorder=None the tick runs exactly the code it ran before the argument existed."""
+
+    def __init__(self, model, lag=10, queue_len=31, use_cache=False, stuck_threshold=800, final_dim=None, undistort=True,
+                 recorder=None, record_every=10):
         from collections import deque
         from . import calib, preprocess, synth
         from .encoder_decoder import PrevSweepCache
@@ -125,6 +138,8 @@ class AgentTick:
         self.frames = deque(maxlen=lag + 1)                              # preprocessed frames (4, 3, fh, fw) of the last ticks
         self.cache = PrevSweepCache(model, lag=lag) if use_cache else None
         self.step = -1
+        assert int(record_every) >= 1
+        self.recorder, self.record_every = recorder, int(record_every)
 
     def reset(self):
         self.frames.clear()
@@ -137,6 +152,32 @@ class AgentTick:
     def run_step(self, frames_rgb_u8, lidar_half, pos, compass, speed, next_wp, next_cmd):
         """frames_rgb_u8: uint8 (4, 900, 1600, 3) in camera_list order, host or device; lidar_half (n, 4) x y z intensity;
         pos (x, y) filtered GPS position; compass rad; speed m/s; next_wp (x, y) / next_cmd from the route planner."""
+        if self.recorder is None:
+            return self._run_step(frames_rgb_u8, lidar_half, pos, compass, speed, next_wp, next_cmd)
+        raw = torch.as_tensor(frames_rgb_u8)
+        if not raw.is_cuda:
+            raw = raw.to(self.device, non_blocking=True)               # (_run_step then takes the device tensor as it is)
+        steer, throttle, brake, info = self._run_step(raw, lidar_half, pos, compass, speed, next_wp, next_cmd)
+        if self.step % self.record_every == 0:
+            self._record(raw, steer, throttle, brake, info, speed)
+        return steer, throttle, brake, info
+
+    def _record(self, raw, steer, throttle, brake, info, speed):
+        import io
+        import json
+        from . import calib, dataset
+        name = dataset.frame_name(self.step // self.record_every)
+        keys = ("steer_ctrl", "steer_traj", "throttle_ctrl", "throttle_traj", "brake_ctrl", "brake_traj", "is_stuck", "stuck_detector")
+        meta = {k: info[k] for k in keys if k in info}                   # (absent while the queue fills: the control is zero)
+        meta.update(steer=steer, throttle=throttle, brake=brake, speed=float(speed))
+        if "target_point" in info:
+            meta["target_point"] = [float(v) for v in info["target_point"]]
+        cloud = io.BytesIO()
+        np.save(cloud, info["cloud"].detach().cpu().numpy().astype(np.float32, copy=False), allow_pickle=False)
+        self.recorder.submit({f"{cam}/{name}.png": raw[i] for i, cam in enumerate(calib.CAMERA_NAMES)},
+                             {f"lidar/{name}.npy": cloud.getvalue(), f"meta/{name}.json": json.dumps(meta, indent=4).encode()})
+
+    def _run_step(self, frames_rgb_u8, lidar_half, pos, compass, speed, next_wp, next_cmd):
         self.step += 1
         if isinstance(compass, float) and math.isnan(compass):
             compass = 0.0                                                # AGENT:310-313
