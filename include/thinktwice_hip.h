@@ -1024,6 +1024,115 @@ int tt_png_encode_u8_phases(const uint8_t* pixels_dev, long long pixel_bytes, co
                             uint8_t* files_dev, long long files_bytes, long long* file_sizes_dev, int phases, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Debug frames DRAWN on the device (thinktwice_amd/render.py, csrc/render.hip, csrc/render_raster.h): a caller-owned uint8 canvas
+ * [Hc][Wc][3] filled from a display list, so that what the model predicted reaches tt_png_encode_u8 without a copy to the host.
+ * The palette, look-up tables, layout and 5 x 7 font are this project's own (the reference draws nothing).
+ *
+ * The list is a table of tt_render_item, given in host memory (validated before any launch) and in device memory (read by the
+ * kernels), drawn in painter's order by index, later over earlier.  The rasteriser is a GATHER: every canvas pixel starts black,
+ * walks the items that can touch it and keeps the last word, so the picture is a function of the list and its sources only, not
+ * of the launch geometry.  One 256-lane workgroup per tile of 8 rows x 256 columns; the list is staged through LDS in chunks of
+ * TT_RENDER_CHUNK items (polyline points go to fixed point there, once per workgroup) and an item whose bounding box misses the
+ * tile is skipped per workgroup.  EVERY byte of the canvas is written; nothing outside it is.
+ * All arithmetic is integer, or f32 with every operation rounded separately (no contraction); csrc/render_raster.h holds the
+ * per-pixel rules as __host__ __device__ functions, which tools/render_host_check.cpp compiles for the host.
+ * Blend, everywhere: (dst * (256 - a) + src * a + 128) >> 8 per channel, weight a in 0..256.
+ * An item is clipped to the canvas and to its own rectangle [x0, x0 + w) x [y0, y0 + h), which may lie partly or wholly outside
+ * the canvas; w == 0 or h == 0 draws nothing.  `color` is r | g << 8 | b << 16.
+ *
+ *  FILL         the rectangle in `color` at weight `alpha`.
+ *  IMAGE_F32    src: planar f32 [3][sh][sw] (a network input); pixel (x, y) of the rectangle shows source (x / scale, y / scale),
+ *               channel c as clamp(rint(v * m[c] + m[3 + c]), 0, 255) in f32 in that order (m[0..3) = 255 std, m[3..6) = 255 mean: the
+ *               inverse of tt_preprocess_images' normalisation of pixel / 255).  A NaN in any channel: `color`.  Weight `alpha`.
+ *  IMAGE_U8     src: uint8 [sh][sw][channels] (1 or 3), reduced by the box factor `scale` >= 1: per channel
+ *               (sum of scale x scale + scale * scale / 2) / (scale * scale).  Weight `alpha`.
+ *  SEG_OVERLAY  src: f32 logits [sh][sw][stride >= channels] channel-last; the cell of pixel (x, y) is (x / scale, y / scale);
+ *               argmax over [0, channels), ties to the lowest index, padding channels never read (tt_eval_seg_confusion's rule);
+ *               aux: palette, channels x 4 bytes r, g, b, a, blended at weight a + (a >> 7) (0 leaves the pixel alone, 255 is
+ *               opaque).  A NaN among the cell's `channels` logits: `color` at full weight.  channels <= 32.
+ *  DEPTH_MAP    src: f32 logits [sh][sw][stride >= channels]; argmax bin, ties to the lowest (tt_eval_depth_bins' rule); colour
+ *               aux[3 * (bin * 255 / (channels - 1))] of a 256 x 3 byte table (index 0 for one channel); nearest upscale by `scale`;
+ *               a NaN: `color`.  Weight `alpha`.  channels <= 256.
+ *  POINTS_BEV   src: f32 cloud [count][stride >= 3]; m: x, y metres -> 1/16-pixel units of the CANVAS, u = m0 x + m1 y + m2,
+ *               v = m3 x + m4 y + m5.  The point's pixel is (floor(u) >> 4, floor(v) >> 4); its height index
+ *               clamp(floor((z - p[0]) * p[1]), 0, 255).  The highest point of a pixel wins (an integer atomic maximum of
+ *               index + 1 on the item's u32 scratch plane, h x w words at workspace + ws_offset) and is shown as aux[3 * index] of
+ *               a 256 x 3 byte table at weight `alpha`.  Not drawn: a row with x = y = z = 0 (collate padding), a row with a
+ *               non-finite x, y or z, a point beyond +-2^20 units or outside the rectangle or the canvas.
+ *  POLYLINE_DEV src: f32 [count][2] DEVICE points (count <= TT_RENDER_MAX_POINTS), through a matrix m as above, each coordinate
+ *               to fixed point by rint.  A pixel, by its centre (16 px + 8, 16 py + 8), belongs to a point's disc if
+ *               dx^2 + dy^2 <= radius^2 (radius > 0) and to the segment of two consecutive points if its squared distance to
+ *               the segment is <= half_width^2, in exact integer arithmetic (so A->B and B->A cover the same pixels, and a
+ *               segment with equal endpoints is the disc of radius half_width).  Covered pixels take `color` at weight `alpha`.
+ *               A point that is not finite, or beyond +-2^20 units after the matrix, is dropped with its segments, never
+ *               converted to an integer, and adds 1 to status word TT_RENDER_STATUS_DROPPED.
+ *  MARKER       the same from host floats p = (cx, cy, hx, hy) metres: count = TT_RENDER_MARKER_CROSS (the segments
+ *               (cx - hx, cy)-(cx + hx, cy) and (cx, cy - hy)-(cx, cy + hy)) or TT_RENDER_MARKER_BOX (the closed loop of
+ *               the four corners), sums and differences in f32.
+ *  TEXT         src: `count` bytes; aux: the font, 256 bytes (character -> glyph number) then 8 bytes per glyph (7 rows, bit 4 =
+ *               the leftmost of 5 columns); character i fills the cell of 6 x 8 font pixels of `scale` x `scale` canvas pixels
+ *               at x0 + 6 i scale.  Set pixels take `color` at weight `alpha`.
+ *
+ * workspace: tt_render_workspace_bytes(...) bytes, 256-byte aligned: TT_RENDER_STATUS_WORDS int64 status words, then the scratch
+ * planes; an item's ws_offset is that of its plane (a multiple of 256, planes in list order, none overlapping).  The caller zeroes
+ * the workspace ONCE.  The status words are only ever added to; the caller reads and clears them when it wants them.  Every
+ * scratch word the splat sets lies under a canvas pixel of its item, and the compose pass, which reads it exactly once, stores 0
+ * back: the planes are all zero again when the call's last launch ends -- cleared by the pass that reads them, no memset.
+ * Launches, stream-ordered: one splat per POINTS_BEV item with count > 0; one that counts dropped points when the list holds a
+ * POLYLINE_DEV or MARKER; the compose.
+ * Returns an error before any launch for: a null canvas, table or workspace, a null src / aux an item needs; a misaligned
+ * device table (16 bytes) or workspace (256); a canvas side outside 1..16384; num_items < 0 or > TT_RENDER_MAX_ITEMS (no
+ * truncation); an unknown kind; a negative w, h, count or a side above 16384; scale < 1; alpha outside 0..256; a rectangle larger
+ * than its source gives (w > sw * scale, w > sw / scale for IMAGE_U8, w > 6 count scale for TEXT, likewise h); channels or
+ * stride out of range; a negative radius or half_width, or one above 2^15; a non-finite m or p; a plane outside the workspace,
+ * misplaced or overlapping.  No allocation, no copy, no synchronisation.
+ * ---------------------------------------------------------------------- */
+#define TT_RENDER_MAX_ITEMS 1024
+#define TT_RENDER_CHUNK 32                 /* items per LDS stage */
+#define TT_RENDER_MAX_POINTS 16            /* of one POLYLINE_DEV */
+#define TT_RENDER_STATUS_WORDS 4           /* int64 each, at the start of the workspace */
+#define TT_RENDER_STATUS_DROPPED 0
+enum tt_render_kind {
+    TT_RENDER_FILL = 0,
+    TT_RENDER_IMAGE_F32 = 1,
+    TT_RENDER_IMAGE_U8 = 2,
+    TT_RENDER_SEG_OVERLAY = 3,
+    TT_RENDER_DEPTH_MAP = 4,
+    TT_RENDER_POINTS_BEV = 5,
+    TT_RENDER_POLYLINE_DEV = 6,
+    TT_RENDER_MARKER = 7,
+    TT_RENDER_TEXT = 8,
+    TT_RENDER_NUM_KINDS = 9
+};
+enum tt_render_marker {
+    TT_RENDER_MARKER_CROSS = 0,
+    TT_RENDER_MARKER_BOX = 1
+};
+typedef struct tt_render_item {
+    int kind;                            /* enum tt_render_kind */
+    int x0, y0, w, h;                    /* the item's own rectangle on the canvas, pixels */
+    int sw, sh;                          /* the source's width and height: pixels or cells */
+    int scale;                           /* upscale k, box factor s, seg factor f or text scale; >= 1 */
+    int channels;                        /* IMAGE_U8: 1 or 3; SEG_OVERLAY: classes; DEPTH_MAP: bins */
+    int stride;                          /* SEG_OVERLAY / DEPTH_MAP: floats per cell; POINTS_BEV: floats per row */
+    int count;                           /* points, characters, or enum tt_render_marker */
+    int alpha;                           /* 0..256 */
+    unsigned color;                      /* r | g << 8 | b << 16 */
+    int half_width, radius;              /* 1/16 pixel */
+    int reserved;                        /* not read */
+    float m[6];                          /* 2 x 3 matrix, or std[3] then mean[3] */
+    float p[4];                          /* MARKER: cx, cy, hx, hy; POINTS_BEV: z_lo, inv_step */
+    long long ws_offset;                 /* POINTS_BEV: bytes from the workspace to the item's scratch plane */
+    const void* src;                     /* device */
+    const void* aux;                     /* device */
+} tt_render_item;                        /* 128 bytes */
+/* Host arithmetic only: the status words plus, per POINTS_BEV item in list order, its plane rounded up to 256 bytes; 0 for a
+ * null table with num_items > 0, a bad count or a rectangle the entry would refuse. */
+long long tt_render_workspace_bytes(const tt_render_item* items_host, int num_items);
+int tt_render_u8(uint8_t* canvas_dev, int Hc, int Wc, const tt_render_item* items_host, const tt_render_item* items_dev,
+                 int num_items, void* workspace, long long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * SURVEY 8f-4 (training step), optimizer half: the reference's `optimizer_config = dict(grad_clip=dict(max_norm=100,
  * norm_type=2))` and `optimizer = dict(type='AdamW', lr=1e-4, weight_decay=1e-7)` (configs/thinktwice.py:282-287:
  * torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW through mmcv's OptimizerHook) over ONE flat f32 parameter /

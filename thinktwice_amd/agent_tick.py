@@ -120,12 +120,22 @@ class AgentTick:
                                                         the two heads' values, is_stuck, stuck_detector, speed) and the
                                                         target point.
     This is a RECORDING of a drive, not a training sample: it holds no labels (depth, segmentation, boxes) and no dataset
-    measurements file.  With recorder=None the tick runs exactly the code it ran before the argument existed."""
+    measurements file.  With recorder=None the tick runs exactly the code it ran before the argument existed.
+
+    render: None, True or a `render.DebugRenderer`; needs a recorder.  A recorded tick then also submits
+        debug/NNNN.png                                  the debug frame (render.py: the network inputs under the seg overlay, the
+                                                        depth maps, the cloud and the six stages' waypoints top-down, the HUD),
+                                                        drawn on the device and handed to the same `submit` as the camera
+                                                        frames: one encoder call and one write per tick.  While the queue fills
+                                                        (`pred` is None) it shows the cameras and the cloud only.
+    A tick that is not recorded does nothing for it, and with render=None `_record` submits exactly the files above."""
 
     def __init__(self, model, lag=10, queue_len=31, use_cache=False, stuck_threshold=800, final_dim=None, undistort=True,
-                 recorder=None, record_every=10):
+                 recorder=None, record_every=10, render=None):
         from collections import deque
         from . import calib, preprocess, synth
+        if render is not None and render is not False and recorder is None:
+            raise ValueError("AgentTick(render=...) draws into the recording: it needs a recorder")
         from .encoder_decoder import PrevSweepCache
         assert queue_len > lag >= 1
         self.model, self.device = model, model.device
@@ -140,6 +150,10 @@ class AgentTick:
         self.step = -1
         assert int(record_every) >= 1
         self.recorder, self.record_every = recorder, int(record_every)
+        if render is True:
+            from . import config, render as rendering
+            render = rendering.DebugRenderer(config.model_config(final_dim=fd), device=self.device)
+        self.renderer = render or None
 
     def reset(self):
         self.frames.clear()
@@ -174,7 +188,11 @@ class AgentTick:
             meta["target_point"] = [float(v) for v in info["target_point"]]
         cloud = io.BytesIO()
         np.save(cloud, info["cloud"].detach().cpu().numpy().astype(np.float32, copy=False), allow_pickle=False)
-        self.recorder.submit({f"{cam}/{name}.png": raw[i] for i, cam in enumerate(calib.CAMERA_NAMES)},
+        images = {f"{cam}/{name}.png": raw[i] for i, cam in enumerate(calib.CAMERA_NAMES)}
+        if self.renderer is not None:
+            images[f"debug/{name}.png"] = self.renderer.frame(info["img"], info["pred"], info["cloud"], controls=dict(meta, step=self.step),
+                                                              target=info.get("target_point"))
+        self.recorder.submit(images,
                              {f"lidar/{name}.npy": cloud.getvalue(), f"meta/{name}.json": json.dumps(meta, indent=4).encode()})
 
     def _run_step(self, frames_rgb_u8, lidar_half, pos, compass, speed, next_wp, next_cmd):

@@ -285,17 +285,65 @@ def window_for(model, class_names=None):
     return MetricWindow(model.device, num_classes=12, stages=stages, class_names=class_names, model=model)
 
 
-def evaluate(model, loader, dist=None, window=None, raw=False):
+class FrameDump:
+    """Every `every`-th sample of a pass as a debug frame `root/NNNNNN.png`, numbered by the sample's ordinal in this process's
+    pass: drawn by render.DebugRenderer from the forward the metrics read, with the batch's expert waypoints in white and its target
+    point as a red disc (both read on the device), written through a png_encode.FrameRecorder.  Nothing here waits for the device
+    but the recorder's own writer thread."""
+
+    def __init__(self, model, root, every, renderer=None, recorder=None):
+        from . import png_encode
+        if int(every) < 1:
+            raise ValueError(f"render_every {every} must be at least 1")
+        self.every, self.ordinal, self.frames = int(every), 0, 0
+        self.device, self.renderer = model.device, renderer            # (made at the first batch, for the size of its images)
+        self.recorder = recorder or png_encode.FrameRecorder(root, png_encode.PngEncoder(device=model.device))
+
+    def add(self, batch, pred):
+        if self.renderer is None:
+            from . import config, render
+            self.renderer = render.DebugRenderer(config.model_config(final_dim=tuple(batch["img"].shape[-2:])), device=self.device)
+        B = pred["pred_wp"].shape[0]
+        for b in range(B):
+            if self.ordinal % self.every == 0:
+                dl = self.display_list(batch, pred, b)
+                self.recorder.submit({f"{self.ordinal:06d}.png": self.renderer.raster.draw(dl)})
+                self.frames += 1
+            self.ordinal += 1
+
+    def display_list(self, batch, pred, b):
+        r = self.renderer
+        points = batch.get("points")
+        dl = r.display_list(batch["img"], pred, None if points is None else points[b, 0], b=b, gt_wp=batch.get("waypoints"),
+                            controls={"step": self.ordinal})
+        if batch.get("target_point") is not None:
+            dl.polyline(batch["target_point"][b:b + 1], r.matrices["target"], (255, 64, 64), half_width=0, radius=72, clip=r.layout["bev"])
+        return dl
+
+    def close(self):
+        self.recorder.close()
+
+
+def evaluate(model, loader, dist=None, window=None, raw=False, render_dir=None, render_every=0):
     """`model.forward_inference(batch)` under no_grad on every batch of `loader` (a DeviceBatchLoader(train=False)): the inference
     path, no teacher pass, in whatever `dtype` mode the model was built.  -> the summary (merged over the ranks of `dist`);
-    `raw=True`: (summary, raw accumulators)."""
+    `raw=True`: (summary, raw accumulators).  render_dir with render_every = N > 0: every N-th sample also becomes a debug frame
+    (`FrameDump`), from the same forward; the metrics are the bits they are without it."""
     import torch
     window = window or window_for(model)
+    dump = FrameDump(model, render_dir, render_every) if render_dir is not None and int(render_every) > 0 else None
     iters = 0
-    with torch.no_grad():
-        for batch in loader:
-            window.add(batch, model.forward_inference(batch))
-            iters += 1
+    try:
+        with torch.no_grad():
+            for batch in loader:
+                pred = model.forward_inference(batch)
+                window.add(batch, pred)
+                if dump is not None:
+                    dump.add(batch, pred)
+                iters += 1
+    finally:
+        if dump is not None:
+            dump.close()
     if iters == 0:
         raise ValueError("evaluate: the loader gave no batch")
     acc = window.merge_ranks(window.close().result(), dist)
@@ -402,9 +450,15 @@ def parse_args(argv=None):
     ap.add_argument("--dev", action="store_true", help="the reference's is_dev split")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="write the result here as JSON (rank 0)")
+    ap.add_argument("--render", default=None, metavar="DIR", help="write debug frames DIR/NNNNNN.png (DIR/rankK with several ranks)")
+    ap.add_argument("--render-every", type=int, default=0, metavar="N", help="every N-th sample of the pass gets a frame")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be >= 1")
+    if (args.render is None) != (args.render_every <= 0):
+        ap.error("--render DIR and --render-every N (>= 1) go together")
+    if args.render is not None and args.against is not None:
+        ap.error("--render draws the frames of one mode: not with --against")
     if args.against is not None and args.against == args.dtype:
         ap.error("--against names the mode of --dtype")
     return args
@@ -466,7 +520,8 @@ def main(argv=None):
             model = build(args.dtype)
             result = OrderedDict(dtype=args.dtype, towns=towns, world=world)
             if args.against is None:
-                result["metrics"] = evaluate(model, loader)
+                render_dir = args.render if args.render is None or world == 1 else os.path.join(args.render, f"rank{rank}")
+                result["metrics"] = evaluate(model, loader, render_dir=render_dir, render_every=args.render_every)
             else:
                 if world > 1:
                     raise SystemExit("--against compares two modes on one rank's frames: run it without torch.distributed.run")
