@@ -566,8 +566,8 @@ int tt_lidar_voxelize_capped(const float* points, int B, int Np, int nfeat, cons
 /* dense index volume of one resolution level: vol int32 [batch, D, H, W] = feature row or -1 */
 int tt_sp_volume_build(const int* coords, const int* num_rows, long long max_rows, int batch,
                        const int* dims_zyx, int* vol, void* stream);
-/* spconv SparseConv3d output-site generation (mark + scan + compact, no atomics; rows come out in cell
- * order); kernel_stride_pad = {kz,ky,kx,sz,sy,sx,pz,py,px} (host).  Also fills the OUTPUT level's volume. */
+/* spconv SparseConv3d output-site generation (bitmap of the output cells: mark + popcount + compact; rows come
+ * out in cell order); kernel_stride_pad = {kz,ky,kx,sz,sy,sx,pz,py,px} (host).  Also fills the OUTPUT level's volume. */
 long long tt_sp_strided_outputs_workspace_bytes(long long out_cells);
 int tt_sp_strided_outputs(const int* in_coords, const int* in_rows, long long max_in, int batch,
                           const int* kernel_stride_pad, const int* out_dims_zyx, void* workspace,

@@ -162,8 +162,8 @@ __global__ void vfe_mean_capped_kernel(const float* __restrict__ pts, const unsi
 // ----------------------------------------------------------------------------- dense index volumes
 // Each resolution level keeps vol[b][z][y][x] = feature row or -1.  The synthetic / real LiDAR grids of this
 // model are small enough (<= 148 M cells at the input level for B = 8) that a dense volume beats a hash
-// table: neighbour look-ups of spatially ordered rows coalesce, output-site generation needs no atomics
-// (mark + scan + compact), and row ids come out in cell order (deterministic).
+// table: neighbour look-ups of spatially ordered rows coalesce, output-site generation is a bitmap of the output
+// cells (atomicOr marks, popcount + compact), and row ids come out in cell order (deterministic).
 struct ConvGeom { int kz, ky, kx, sz, sy, sx, pz, py, px; };
 
 __device__ __forceinline__ long long lin_cell(int b, int z, int y, int x, Dims3 d) {
@@ -177,66 +177,293 @@ __global__ void volume_scatter_kernel(const int* __restrict__ coords, const int*
     vol[lin_cell(coords[i * 4], coords[i * 4 + 1], coords[i * 4 + 2], coords[i * 4 + 3], d)] = (int)i;
 }
 
-// SparseConv3d active outputs: o is active iff some input i and tap k satisfy i = o*s - p + k
-__global__ void mark_outputs_kernel(const int* __restrict__ in_coords, const int* __restrict__ in_rows,
-                                    long long max_in, ConvGeom g, Dims3 od, int* __restrict__ flags) {
-    const int KV = g.kz * g.ky * g.kx;
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long i = t / KV;
-    const int k = (int)(t % KV);
-    if (i >= *in_rows || i >= max_in) return;
-    const int kz = k / (g.ky * g.kx), ky = (k / g.kx) % g.ky, kx = k % g.kx;
-    const int nz = in_coords[i * 4 + 1] + g.pz - kz;
-    const int ny = in_coords[i * 4 + 2] + g.py - ky;
-    const int nx = in_coords[i * 4 + 3] + g.px - kx;
-    if (nz < 0 || ny < 0 || nx < 0 || nz % g.sz || ny % g.sy || nx % g.sx) return;
-    const int oz = nz / g.sz, oy = ny / g.sy, ox = nx / g.sx;
-    if (oz >= od.z || oy >= od.y || ox >= od.x) return;
-    flags[lin_cell(in_coords[i * 4], oz, oy, ox, od)] = 1;     // duplicates write the same value
+// The index kernels below size their grids by the chip (kIndexBlocks workgroups of 256 threads fill every CU) and walk the
+// live rows / the cells in a grid-stride or a block-contiguous loop: the row counts stay on the device.
+constexpr int kIndexThreads = 256;
+constexpr int kIndexBlocks = kNumCU * 8;
+constexpr int kDirectCountTiles = 64;     // bitmaps of up to this many 8192-cell tiles are counted inside the compaction
+
+// one row's (b, z, y, x); `vec`: the array is 16-byte aligned
+__device__ __forceinline__ int4 load_coord(const int* __restrict__ coords, long long row, bool vec) {
+    if (vec) return reinterpret_cast<const int4*>(coords)[row];
+    return make_int4(coords[row * 4], coords[row * 4 + 1], coords[row * 4 + 2], coords[row * 4 + 3]);
 }
 
-__global__ void compact_outputs_kernel(const int* __restrict__ flags, const int* __restrict__ scan, long long cells,
-                                       Dims3 od, long long max_out, int* __restrict__ vol,
-                                       int* __restrict__ out_coords, int* __restrict__ out_rows) {
-    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cells) return;
-    const int f = flags[c];
-    const int row = scan[c];
-    int v = -1;
-    if (f && row < max_out) {
-        v = row;
-        long long r = c;
-        const int x = (int)(r % od.x); r /= od.x;
-        const int y = (int)(r % od.y); r /= od.y;
-        const int z = (int)(r % od.z); r /= od.z;
-        out_coords[(long long)row * 4 + 0] = (int)r;
-        out_coords[(long long)row * 4 + 1] = z;
-        out_coords[(long long)row * 4 + 2] = y;
-        out_coords[(long long)row * 4 + 3] = x;
-    }
-    vol[c] = v;
-    if (c == cells - 1) {
-        const long long n = (long long)row + f;
-        *out_rows = (int)(n < max_out ? n : max_out);
+__device__ __forceinline__ void store_int4(int* __restrict__ p, int4 v, bool vec) {
+    if (vec) {
+        *reinterpret_cast<int4*>(p) = v;
+    } else {
+        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
     }
 }
 
-// rulebook: nbr[o][k] = input row at (o*s - p + k) or -1
-__global__ void rulebook_kernel(const int* __restrict__ out_coords, const int* __restrict__ out_rows, long long max_out,
-                                ConvGeom g, Dims3 id, const int* __restrict__ vol, int* __restrict__ nbr) {
-    const int KV = g.kz * g.ky * g.kx;
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long o = t / KV;
-    const int k = (int)(t % KV);
-    if (o >= *out_rows || o >= max_out) return;
-    const int kz = k / (g.ky * g.kx), ky = (k / g.kx) % g.ky, kx = k % g.kx;
-    const int z = out_coords[o * 4 + 1] * g.sz - g.pz + kz;
-    const int y = out_coords[o * 4 + 2] * g.sy - g.py + ky;
-    const int x = out_coords[o * 4 + 3] * g.sx - g.px + kx;
-    int r = -1;
-    if (z >= 0 && z < id.z && y >= 0 && y < id.y && x >= 0 && x < id.x)
-        r = vol[lin_cell(out_coords[o * 4], z, y, x, id)];
-    nbr[o * KV + k] = r;
+// sum over the workgroup's 256 threads, returned to every thread (red: 4 ints of LDS, reusable after the call)
+__device__ __forceinline__ int block_sum(int v, int* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// SparseConv3d active outputs: o is active iff some input i and tap k satisfy i = o*s - p + k.  Per dimension those o are
+// the consecutive values ceil((i + p - K + 1) / s) .. floor((i + p) / s), clipped to the output grid: one thread per input
+// row sets their bits in a bitmap of the output cells (bit c & 31 of word c >> 5).  The rows come in cell order, so the
+// lanes of a wave mostly aim at the same few words: wave_or merges them and issues one atomicOr per run of lanes.
+
+// bits[w] |= m of every lane (w = ~0u with m = 0: nothing).  Lanes next to each other with the same w are merged into the
+// first lane of their run (OR is idempotent, so any lanes with equal w may be merged); that lane issues the atomic.
+// All 64 lanes call it together.
+__device__ __forceinline__ void wave_or(unsigned* __restrict__ bits, unsigned w, unsigned m) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned ow = __shfl_down(w, off), om = __shfl_down(m, off);     // past lane 63: the lane's own values
+        m |= ow == w ? om : 0u;
+    }
+    const unsigned pw = __shfl_up(w, 1);
+    if (((threadIdx.x & 63) == 0 || pw != w) && m) atomicOr(bits + w, m);
+}
+
+// nz, ny: ceil(kz / sz), ceil(ky / sy) = the most oz / oy one input reaches (wave-uniform trip counts around wave_or)
+__global__ __launch_bounds__(kIndexThreads) void mark_output_bits_kernel(
+    const int* __restrict__ in_coords, const int* __restrict__ in_rows, long long max_in, ConvGeom g, Dims3 od, int nz, int ny,
+    unsigned* __restrict__ bits, bool vec) {
+    const long long n = min((long long)*in_rows, max_in);
+    for (long long base = (long long)blockIdx.x * kIndexThreads; base < n; base += (long long)gridDim.x * kIndexThreads) {
+        const long long i = base + threadIdx.x;
+        const bool live = i < n;
+        const int4 c = live ? load_coord(in_coords, i, vec) : make_int4(0, 0, 0, 0);
+        const int az = c.y + g.pz, ay = c.z + g.py, ax = c.w + g.px;
+        const int z0 = az - g.kz + 1 > 0 ? (az - g.kz + g.sz) / g.sz : 0, z1 = min(az / g.sz, od.z - 1);
+        const int y0 = ay - g.ky + 1 > 0 ? (ay - g.ky + g.sy) / g.sy : 0, y1 = min(ay / g.sy, od.y - 1);
+        const int x0 = ax - g.kx + 1 > 0 ? (ax - g.kx + g.sx) / g.sx : 0, x1 = min(ax / g.sx, od.x - 1);
+        for (int dz = 0; dz < nz; ++dz)
+            for (int dy = 0; dy < ny; ++dy) {
+                const int oz = z0 + dz, oy = y0 + dy;
+                unsigned w0 = ~0u, m0 = 0, w1 = ~0u, m1 = 0;             // the x run's first word and its last, if another
+                if (live && oz <= z1 && oy <= y1 && x0 <= x1) {
+                    const unsigned line = ((unsigned)(c.x * od.z + oz) * od.y + oy) * od.x;    // cells < 2^31 (host check)
+                    const unsigned first = line + x0, last = line + x1;
+                    w0 = first >> 5;
+                    const unsigned wl = last >> 5;
+                    m0 = ~((1u << (first & 31)) - 1u);
+                    const unsigned upto = (2u << (last & 31)) - 1u;      // bits 0 .. last & 31
+                    if (wl == w0) {
+                        m0 &= upto;
+                    } else {
+                        w1 = wl;
+                        m1 = upto;
+                        for (unsigned w = w0 + 1; w < wl; ++w) atomicOr(bits + w, ~0u);    // a run over three or more words
+                    }
+                }
+                wave_or(bits, w0, m0);
+                wave_or(bits, w1, m1);
+            }
+    }
+}
+
+// The bitmap is cut into tiles of 256 words (8192 cells); workgroup g owns the tiles [g * tiles_per_block, ...) of it.
+// totals[g] = set bits of workgroup g's tiles.
+__global__ __launch_bounds__(kIndexThreads) void count_output_bits_kernel(const unsigned* __restrict__ bits, int tiles_per_block,
+                                                                          int ntiles, int* __restrict__ totals) {
+    __shared__ int red[4];
+    const int t0 = min((int)blockIdx.x * tiles_per_block, ntiles), t1 = min(t0 + tiles_per_block, ntiles);
+    int cnt = 0;
+    for (int t = t0; t < t1; ++t) cnt += __popc(bits[(long long)t * kIndexThreads + threadIdx.x]);
+    cnt = block_sum(cnt, red);
+    if (threadIdx.x == 0) totals[blockIdx.x] = cnt;
+}
+
+// Row id of an active cell = number of active cells before it in cell order (b, z, y, x) = totals of the workgroups before
+// this one + set bits before it in this workgroup's tiles.  One pass writes vol for EVERY cell (row, or -1 for an empty
+// cell and for rows at or beyond max_out), out_coords of the rows below max_out and the clamped live count.
+__global__ __launch_bounds__(kIndexThreads) void compact_output_bits_kernel(
+    const unsigned* __restrict__ bits, const int* __restrict__ totals, int tiles_per_block, int ntiles, unsigned cells, Dims3 od,
+    int max_out, int* __restrict__ vol, int* __restrict__ out_coords, int* __restrict__ out_rows, bool vec_vol, bool vec_coords) {
+    __shared__ int red[4];
+    __shared__ unsigned s_word[kIndexThreads];
+    __shared__ int s_rank[kIndexThreads];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t0 = min((int)blockIdx.x * tiles_per_block, ntiles), t1 = min(t0 + tiles_per_block, ntiles);
+    int before = 0, all = 0;
+    if (totals) {
+        for (int i = tid; i < (int)gridDim.x; i += kIndexThreads) {
+            const int v = totals[i];
+            all += v;
+            before += i < (int)blockIdx.x ? v : 0;
+        }
+    } else {      // a small bitmap (kDirectCountTiles): every workgroup counts the words before its own, no count launch
+        const uint4* bits4 = reinterpret_cast<const uint4*>(bits);            // the workspace is 16-byte aligned (host check)
+        const int n4 = (blockIdx.x == 0 ? ntiles : t0) * (kIndexThreads / 4), before4 = t0 * (kIndexThreads / 4);
+#pragma unroll 4
+        for (int i = tid; i < n4; i += kIndexThreads) {
+            const uint4 w = bits4[i];
+            const int v = __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w);
+            all += v;
+            before += i < before4 ? v : 0;
+        }
+    }
+    before = block_sum(before, red);
+    if (blockIdx.x == 0) {
+        all = block_sum(all, red);
+        if (tid == 0) *out_rows = min(all, max_out);
+    }
+    for (int t = t0; t < t1; ++t) {
+        const unsigned word = bits[(long long)t * kIndexThreads + tid];
+        int incl = __popc(word);
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(incl, off);
+            if (lane >= off) incl += up;
+        }
+        __syncthreads();                     // the previous tile's readers of s_word / s_rank / red are done
+        if (lane == 63) red[wave] = incl;
+        __syncthreads();
+        int wave_base = 0;
+        for (int w = 0; w < wave; ++w) wave_base += red[w];
+        s_word[tid] = word;
+        s_rank[tid] = before + wave_base + incl - __popc(word);
+        before += red[0] + red[1] + red[2] + red[3];
+        __syncthreads();
+        // four cells per thread and step: a wave stores 1 KB of vol in one piece
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int q = k * kIndexThreads + tid;                 // group of four cells within the tile
+            const unsigned cell = (unsigned)t * (kIndexThreads * 32) + (unsigned)q * 4;
+            if (cell >= cells) continue;
+            const unsigned ww = s_word[q >> 3];
+            const int sh = (q & 7) * 4;
+            int row = s_rank[q >> 3] + __popc(ww & ((1u << sh) - 1u));
+            const unsigned four = (ww >> sh) & 15u;
+            int v[4] = {-1, -1, -1, -1};
+            if (four && row < max_out) {
+                const unsigned ry = cell / (unsigned)od.x, rz = ry / (unsigned)od.y, rb = rz / (unsigned)od.z;
+                int4 c = make_int4((int)rb, (int)(rz - rb * od.z), (int)(ry - rz * od.y), (int)(cell - ry * od.x));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (((four >> j) & 1u) && row < max_out) {
+                        v[j] = row;
+                        store_int4(out_coords + (long long)row * 4, c, vec_coords);
+                        ++row;
+                    }
+                    if (++c.w == od.x) {                                   // the next cell in (b, z, y, x) order
+                        c.w = 0;
+                        if (++c.z == od.y) {
+                            c.z = 0;
+                            if (++c.y == od.z) { c.y = 0; ++c.x; }
+                        }
+                    }
+                }
+            }
+            if (vec_vol && cell + 3 < cells) {
+                *reinterpret_cast<int4*>(vol + cell) = make_int4(v[0], v[1], v[2], v[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (cell + j < cells) vol[cell + j] = v[j];
+            }
+        }
+    }
+}
+
+// rulebook: nbr[o][k] = input row at (o*s - p + k) or -1, tap k = (kz * KY + ky) * KX + kx.
+// A workgroup takes 256 output rows at a time: their coordinates go through LDS (one 16-byte load per row), and the work
+// item is one (row, kz, ky) with its KX taps -- adjacent words of the volume in, adjacent words of nbr out, and item it of
+// the block lands at nbr + (base * KV + it * KX), so a wave's stores cover one contiguous piece of nbr.  Every look-up is
+// issued unconditionally (an absent or out-of-grid tap reads vol[0] and keeps -1) before the first store, so the loads of
+// a thread's items are in flight together.  KX = 3 (host: the input has at least 3 cells in x) fetches an item's three
+// words with ONE 12-byte load, from the x window shifted into the row at the grid's edge, three items to a pass.
+// KZ = KY = KX = 0 is the generic form with run-time extents.  Measurements: profiles/sp_index.txt.
+struct __attribute__((aligned(4))) VolWords3 { int w[3]; };
+
+template <int KZ, int KY, int KX>
+__global__ __launch_bounds__(kIndexThreads) void rulebook_rows_kernel(
+    const int* __restrict__ out_coords, const int* __restrict__ out_rows, long long max_out, ConvGeom g, Dims3 id,
+    const int* __restrict__ vol, int* __restrict__ nbr, bool vec) {
+    __shared__ int4 s_coord[kIndexThreads];
+    constexpr bool kFixed = KZ > 0;
+    const int ky_n = kFixed ? KY : g.ky, kx_n = kFixed ? KX : g.kx;
+    const int per_row = (kFixed ? KZ : g.kz) * ky_n;           // items per row
+    const int KV = per_row * kx_n;
+    const int tid = threadIdx.x;
+    const long long n = min((long long)*out_rows, max_out);
+    for (long long base = (long long)blockIdx.x * kIndexThreads; base < n; base += (long long)gridDim.x * kIndexThreads) {
+        const int rows = (int)min((long long)kIndexThreads, n - base);
+        __syncthreads();
+        if (tid < rows) s_coord[tid] = load_coord(out_coords, base + tid, vec);
+        __syncthreads();
+        const int items = rows * per_row;
+        int* __restrict__ dst = nbr + base * KV;
+        auto look_up = [&](int it, int kx) -> int {          // tap kx of item it, it < items
+            const int r = it / per_row, j = it - r * per_row;
+            const int kz = j / ky_n, ky = j - kz * ky_n;
+            const int4 c = s_coord[r];
+            const int z = c.y * g.sz - g.pz + kz, y = c.z * g.sy - g.py + ky, x = c.w * g.sx - g.px + kx;
+            const bool ok = (unsigned)z < (unsigned)id.z && (unsigned)y < (unsigned)id.y && (unsigned)x < (unsigned)id.x;
+            const int r_in = vol[ok ? lin_cell(c.x, z, y, x, id) : 0];
+            return ok ? r_in : -1;
+        };
+        if constexpr (kFixed && KX == 3) {
+            // kPass items of a thread at a time: their loads in flight together, and few enough registers for 8 waves a SIMD
+            constexpr int kPass = 3;
+            static_assert(KZ * KY % kPass == 0, "whole passes");
+#pragma unroll 1
+            for (int u0 = 0; u0 < KZ * KY; u0 += kPass) {
+                VolWords3 win[kPass];
+                unsigned taps[kPass];      // bits 0 .. 2: tap kx lies in the grid; bits 4 .. 7: 8 + (x of tap 0 - window start)
+#pragma unroll
+                for (int u = 0; u < kPass; ++u) {
+                    const int it = min((u0 + u) * kIndexThreads + tid, items - 1);
+                    const int r = it / per_row, j = it - r * per_row;
+                    const int kz = j / KY, ky = j - kz * KY;
+                    const int4 c = s_coord[r];
+                    const int z = c.y * g.sz - g.pz + kz, y = c.z * g.sy - g.py + ky, x0 = c.w * g.sx - g.px;
+                    const bool zy_ok = (unsigned)z < (unsigned)id.z && (unsigned)y < (unsigned)id.y;
+                    const int xs = min(max(x0, 0), id.x - 3);                         // window [xs, xs + 3) lies in the row
+                    win[u] = *reinterpret_cast<const VolWords3*>(vol + (zy_ok ? lin_cell(c.x, z, y, xs, id) : 0));
+                    unsigned t = (unsigned)(min(max(x0 - xs, -8), 7) + 8) << 4;       // beyond +-2 no tap lies in the row
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx) t |= (zy_ok && (unsigned)(x0 + kx) < (unsigned)id.x ? 1u : 0u) << kx;
+                    taps[u] = t;
+                }
+#pragma unroll
+                for (int u = 0; u < kPass; ++u) {
+                    const int it = (u0 + u) * kIndexThreads + tid;
+                    if (it < items) {
+                        const int shift = (int)(taps[u] >> 4) - 8;
+                        VolWords3 out;
+#pragma unroll
+                        for (int kx = 0; kx < 3; ++kx) {
+                            const int d = kx + shift;                                 // a tap inside the row has d in 0 .. 2
+                            const int r_in = d == 0 ? win[u].w[0] : d == 1 ? win[u].w[1] : win[u].w[2];
+                            out.w[kx] = (taps[u] >> kx) & 1u ? r_in : -1;
+                        }
+                        *reinterpret_cast<VolWords3*>(dst + (long long)it * 3) = out;
+                    }
+                }
+            }
+        } else if constexpr (kFixed) {
+            int v[KZ * KY][KX];
+#pragma unroll
+            for (int u = 0; u < KZ * KY; ++u) {
+                const int it = min(u * kIndexThreads + tid, items - 1);
+#pragma unroll
+                for (int kx = 0; kx < KX; ++kx) v[u][kx] = look_up(it, kx);
+            }
+#pragma unroll
+            for (int u = 0; u < KZ * KY; ++u) {
+                const int it = u * kIndexThreads + tid;
+                if (it < items) {
+#pragma unroll
+                    for (int kx = 0; kx < KX; ++kx) dst[(long long)it * KX + kx] = v[u][kx];
+                }
+            }
+        } else {
+            for (int it = tid; it < items; it += kIndexThreads)
+                for (int kx = 0; kx < kx_n; ++kx) dst[(long long)it * kx_n + kx] = look_up(it, kx);
+        }
+    }
 }
 
 // Tap-occupancy mask of every output row of a rulebook (bit t = tap t has an input row), 0xFFFFFFFF for rows beyond
@@ -427,10 +654,20 @@ extern "C" int tt_sp_volume_build(const int* coords, const int* num_rows, long l
     return check_launch("tt_sp_volume_build");
 }
 
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// workgroups of a grid-stride index kernel over at most `rows` rows: one per 256 rows, no more than fill the chip
+static unsigned index_blocks(long long rows) {
+    const long long b = (rows + kIndexThreads - 1) / kIndexThreads;
+    return (unsigned)(b < 1 ? 1 : b < kIndexBlocks ? b : kIndexBlocks);
+}
+
+// workspace of tt_sp_strided_outputs: the bitmap of the output cells in whole tiles of 256 words, then one total per workgroup
+static long long sp_bitmap_tiles(long long out_cells) { return (out_cells + kIndexThreads * 32 - 1) / (kIndexThreads * 32); }
+
 extern "C" long long tt_sp_strided_outputs_workspace_bytes(long long out_cells) {
-    size_t scan_bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int*)nullptr, (int*)nullptr, (int)out_cells);
-    return (long long)(2 * align256(sizeof(int) * out_cells) + align256(scan_bytes));
+    return (long long)(align256(sizeof(unsigned) * kIndexThreads * sp_bitmap_tiles(out_cells)) +
+                       align256(sizeof(int) * kIndexBlocks));
 }
 
 extern "C" int tt_sp_strided_outputs(const int* in_coords, const int* in_rows, long long max_in, int batch,
@@ -443,23 +680,29 @@ extern "C" int tt_sp_strided_outputs(const int* in_coords, const int* in_rows, l
     ConvGeom g = geom_of(kernel_stride_pad);
     Dims3 od{out_dims_zyx[0], out_dims_zyx[1], out_dims_zyx[2]};
     const long long cells = (long long)batch * od.z * od.y * od.x;
-    TT_REQUIRE(cells < (1ll << 31), "tt_sp_strided_outputs: grid too large");
-    TT_REQUIRE(workspace_bytes >= tt_sp_strided_outputs_workspace_bytes(cells), "tt_sp_strided_outputs: workspace");
-    char* w = (char*)workspace;
-    int* flags = (int*)w;
-    int* scan = (int*)(w + align256(sizeof(int) * cells));
-    void* tmp = w + 2 * align256(sizeof(int) * cells);
-    size_t tmp_bytes = (size_t)(workspace_bytes - 2 * (long long)align256(sizeof(int) * cells));
-    (void)hipMemsetAsync(flags, 0, sizeof(int) * cells, st);
-    const long long t = max_in * g.kz * g.ky * g.kx;
-    hipLaunchKernelGGL(mark_outputs_kernel, dim3((unsigned)div_up(t, 256)), dim3(256), 0, st, in_coords, in_rows,
-                       max_in, g, od, flags);
-    if (hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, flags, scan, (int)cells, st) != hipSuccess) {
-        set_error("tt_sp_strided_outputs: scan failed");
-        return -2;
-    }
-    hipLaunchKernelGGL(compact_outputs_kernel, dim3((unsigned)div_up(cells, 256)), dim3(256), 0, st, flags, scan,
-                       cells, od, max_out, out_vol, out_coords, out_rows);
+    TT_REQUIRE(cells > 0 && cells < (1ll << 31), "tt_sp_strided_outputs: bad grid (%lld cells)", cells);
+    TT_REQUIRE(g.kz > 0 && g.ky > 0 && g.kx > 0 && g.sz > 0 && g.sy > 0 && g.sx > 0 && g.pz >= 0 && g.py >= 0 && g.px >= 0,
+               "tt_sp_strided_outputs: bad geometry");
+    TT_REQUIRE(workspace_bytes >= tt_sp_strided_outputs_workspace_bytes(cells) && aligned16(workspace),
+               "tt_sp_strided_outputs: workspace");
+    const int ntiles = (int)sp_bitmap_tiles(cells);
+    const size_t bitmap_bytes = sizeof(unsigned) * kIndexThreads * (size_t)ntiles;
+    unsigned* bits = (unsigned*)workspace;
+    int* totals = (int*)((char*)workspace + align256(bitmap_bytes));
+    const int blocks = ntiles < kIndexBlocks ? ntiles : kIndexBlocks;
+    const int tiles_per_block = div_up(ntiles, blocks);
+    (void)hipMemsetAsync(bits, 0, bitmap_bytes, st);
+    hipLaunchKernelGGL(mark_output_bits_kernel, dim3(index_blocks(max_in)), dim3(kIndexThreads), 0, st, in_coords, in_rows,
+                       max_in, g, od, (g.kz + g.sz - 1) / g.sz, (g.ky + g.sy - 1) / g.sy, bits, aligned16(in_coords));
+    if (ntiles > kDirectCountTiles)
+        hipLaunchKernelGGL(count_output_bits_kernel, dim3(blocks), dim3(kIndexThreads), 0, st, bits, tiles_per_block, ntiles,
+                           totals);
+    else
+        totals = nullptr;
+    const int clamp = (int)(max_out < 0 ? 0 : max_out < 0x7fffffffll ? max_out : 0x7fffffffll);
+    hipLaunchKernelGGL(compact_output_bits_kernel, dim3(blocks), dim3(kIndexThreads), 0, st, bits, totals, tiles_per_block,
+                       ntiles, (unsigned)cells, od, clamp, out_vol, out_coords, out_rows, aligned16(out_vol),
+                       aligned16(out_coords));
     return check_launch("tt_sp_strided_outputs");
 }
 
@@ -469,9 +712,21 @@ extern "C" int tt_sp_rulebook(const int* out_coords, const int* out_rows, long l
     TT_REQUIRE(out_coords && out_rows && kernel_stride_pad && in_dims_zyx && in_vol && nbr, "tt_sp_rulebook: null");
     ConvGeom g = geom_of(kernel_stride_pad);
     Dims3 id{in_dims_zyx[0], in_dims_zyx[1], in_dims_zyx[2]};
-    const long long t = max_out * g.kz * g.ky * g.kx;
-    hipLaunchKernelGGL(rulebook_kernel, dim3((unsigned)div_up(t, 256)), dim3(256), 0, (hipStream_t)stream, out_coords,
-                       out_rows, max_out, g, id, in_vol, nbr);
+    TT_REQUIRE(g.kz > 0 && g.ky > 0 && g.kx > 0 && (long long)g.kz * g.ky * g.kx < (1 << 20),
+               "tt_sp_rulebook: bad kernel extents");
+    const dim3 grid(index_blocks(max_out)), block(kIndexThreads);
+    const bool vec = aligned16(out_coords);
+    hipStream_t st = (hipStream_t)stream;
+    // the model's two geometries with compile-time tap loops; anything else with run-time extents
+    if (g.kz == 3 && g.ky == 3 && g.kx == 3 && id.x >= 3)
+        hipLaunchKernelGGL((rulebook_rows_kernel<3, 3, 3>), grid, block, 0, st, out_coords, out_rows, max_out, g, id, in_vol, nbr,
+                           vec);
+    else if (g.kz == 3 && g.ky == 1 && g.kx == 1)
+        hipLaunchKernelGGL((rulebook_rows_kernel<3, 1, 1>), grid, block, 0, st, out_coords, out_rows, max_out, g, id, in_vol, nbr,
+                           vec);
+    else
+        hipLaunchKernelGGL((rulebook_rows_kernel<0, 0, 0>), grid, block, 0, st, out_coords, out_rows, max_out, g, id, in_vol, nbr,
+                           vec);
     return check_launch("tt_sp_rulebook");
 }
 
