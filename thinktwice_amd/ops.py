@@ -337,6 +337,23 @@ def sp_inverse_rulebook(nbr, m_dev, rows_in):
     return inv
 
 
+def gather_conv_dgrad(dconv, nbr, m_dev, w, gx, in_rows=None, x3=False):
+    """Input gradient of gather_conv, ADDED to gx [R_in, Cin]: dconv [M, Cout] f32 (rows beyond the live count uninitialised),
+    nbr / m_dev / w [Cout,1,taps,Cin] the forward layer's.  The same gathered GEMM on the transposed rulebook with gx as its
+    residual and its output -- in bf16x3 like the dense input gradients when `x3` (a submanifold layer's transposed rulebook
+    is a submanifold rulebook again: the run-staged kernel takes it).  `in_rows`: None for a submanifold layer, else
+    (device row count, allocated rows) of the INPUT level of a strided layer."""
+    from . import weights
+    if in_rows is None:     # submanifold: nbr[m][t] = j  <=>  nbr[j][taps - 1 - t] = m
+        wt = w.flip(2).permute(3, 1, 2, 0).contiguous()
+        return gather_conv(dconv, nbr, m_dev, wt, res=gx, out=gx, _no_tape=True, w_x3=weights.split_pairs_x3(wt) if x3 else None)
+    rows_dev, rows_max = in_rows
+    inv = sp_inverse_rulebook(nbr, m_dev, rows_max)
+    wt = w.permute(3, 1, 2, 0).contiguous()
+    return gather_conv(dconv, inv, rows_dev, wt, res=gx, out=gx, _no_tape=True, stride=2,
+                       w_x3=weights.split_pairs_x3(wt) if x3 else None)
+
+
 def sp_to_dense(x, coords, rows, max_rows, dims, batch_size):
     """rows [R, C] at coords (b, z, y, x) -> dense channel-last (B, H, W, C*D) (== spatial_features.view(N, C*D, H, W))."""
     D, H, W = dims
