@@ -155,6 +155,9 @@ __global__ __launch_bounds__(kChainWaves * 64) void mlp_chain_kernel(const Chain
                 if (!live[q]) continue;
                 const int n = (nb0 + q * kChainWaves) * 32 + r;
                 const bool n_ok = n < S.N;
+                // the kept row is N rounded up to 16 columns wide (the consumer's Kp), the block to 32: with N % 32 in 1 .. 16 the
+                // block's last 16 columns lie behind the row -- in the next row's first group (and, for row 31, behind the buffer)
+                const bool n_kept = S.lds_off >= 0 && n < ((S.N + 15) & ~15);
                 const float bias = (S.bias && n_ok) ? S.bias[n] : 0.f;
                 float sw[8];
 #pragma unroll
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(kChainWaves * 64) void mlp_chain_kernel(const Chain
                     v = apply_act(v, S.act);
                     if (!ok) v = 0.f;
                     if (S.out && ok) S.out[mr * S.out_stride + S.out_coff + n] = v;
-                    if (S.lds_off >= 0) pair_store(smem + S.lds_off + (size_t)rr * S.lds_stride, n, v);
+                    if (n_kept) pair_store(smem + S.lds_off + (size_t)rr * S.lds_stride, n, v);
                 }
             }
         }
