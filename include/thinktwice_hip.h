@@ -1024,6 +1024,60 @@ int tt_png_encode_u8_phases(const uint8_t* pixels_dev, long long pixel_bytes, co
                             uint8_t* files_dev, long long files_bytes, long long* file_sizes_dev, int phases, void* stream);
 
 /* ------------------------------------------------------------------------
+ * JPEG files WRITTEN on the device: uint8 [H, W, C] images (C = 1 grey, 3 RGB) -> complete baseline sequential DCT files
+ * (ITU-T T.81, SOF0, 8-bit) in a JFIF wrapper, for any reader: SOI, APP0 "JFIF" 1.01 density 1:1, DQT, SOF0, DHT, DRI, SOS,
+ * the scan, EOI.  Quantisation tables: Annex K scaled by `quality` (s = 5000 / q below 50, else 200 - 2 q; entry =
+ * clamp((base * s + 50) / 100, 1, 255)).  Huffman tables: the four typical tables of Annex K.3, fixed: one pass over the image.
+ * The arithmetic is integer and this project's own (csrc/jpeg_core.h states it): the files are NOT byte-equal to another
+ * encoder's, they are a function of the pixels and the table only, and tools/jpeg_encode_host_check.cpp runs the same text on
+ * the host to the same bytes.  A restart interval is restart_rows MCU rows (an MCU is 8 x 8 pixels, 16 x 16 at 4:2:0), so the
+ * DRI value is restart_rows * ceil(W / MCU width); an interval's scan bytes depend on its own blocks only.
+ * Launches, stream-ordered, nothing between them on the host: the transform (one lane per 8 x 8 block: colour conversion,
+ * chroma mean, DCT, quantisation -> int16 coefficients in zig-zag order, blocks in scan order, in the workspace); the entropy
+ * pass, one 64-lane workgroup per restart interval, into per-interval worst-case slots of the workspace; one lane per image
+ * that sums the interval sizes and writes the headers and file_sizes_dev[i]; the copy that compacts the intervals into the file.
+ * images: the table, in host memory (validated before any launch) and in device memory (read by the kernels).  Image i's
+ * pixels are pixels_dev[pixel_offset, + H * W * C); its file goes to files_dev[file_offset, ...), a slot of at least
+ * tt_jpeg_encode_bound(&image, 1) bytes, 4-byte aligned, of which the call writes exactly file_sizes_dev[i] bytes (every byte
+ * of the slot beyond them, and everything between slots, stays as it was).  No device-side status: every size is bounded
+ * (a coefficient is at most 16 + 11 bits, 64 per block, every byte may be stuffed, a marker per interval, the fixed header).
+ * workspace: tt_jpeg_encode_workspace_bytes(...) bytes, 256-byte aligned, contents irrelevant.
+ * Returns an error before any launch for: a null pointer; a misaligned table (8 bytes), files_dev or file offset (4),
+ * file_sizes_dev (8) or workspace (256); num_images < 1 or > TT_PNG_MAX_IMAGES; channels not 1 or 3; height or width outside
+ * 1..65535; quality outside 1..100; an unknown subsampling; restart_rows < 1 or a DRI value above 65535; pixels outside
+ * pixel_bytes; a slot outside files_bytes, smaller than the bound, or overlapping another; a workspace that is too small.  No
+ * allocation, no copy, no synchronisation.
+ * ---------------------------------------------------------------------- */
+enum tt_jpeg_subsampling {
+    TT_JPEG_444 = 0,                     /* every component at full size */
+    TT_JPEG_420 = 1                      /* Cb and Cr at half size in both directions; grey images ignore it */
+};
+typedef struct tt_jpeg_enc_image {
+    long long pixel_offset;              /* of the image's uint8 [H, W, C] in pixels_dev, bytes */
+    long long file_offset;               /* of the image's slot in files_dev, bytes; a multiple of 4 */
+    long long file_capacity;             /* bytes of the slot, >= tt_jpeg_encode_bound of this image */
+    int width, height;                   /* 1..65535 */
+    int channels;                        /* 1 (grey) or 3 (RGB) */
+    int quality;                         /* 1..100 */
+    int subsampling;                     /* enum tt_jpeg_subsampling */
+    int restart_rows;                    /* >= 1: MCU rows per restart interval */
+    int reserved;                        /* not read */
+    int reserved2;                       /* not read */
+} tt_jpeg_enc_image;                     /* 56 bytes */
+/* Host arithmetic only.  The bound: the sum over the images of the largest file each can become; both: 0 for a null table, a
+ * bad count or an image the entry would refuse for its sizes or parameters. */
+long long tt_jpeg_encode_bound(const tt_jpeg_enc_image* images_host, int num_images);
+long long tt_jpeg_encode_workspace_bytes(const tt_jpeg_enc_image* images_host, int num_images);
+int tt_jpeg_encode_u8(const uint8_t* pixels_dev, long long pixel_bytes, const tt_jpeg_enc_image* images_host,
+                      const tt_jpeg_enc_image* images_dev, int num_images, void* workspace, long long workspace_bytes,
+                      uint8_t* files_dev, long long files_bytes, long long* file_sizes_dev, void* stream);
+/* Measurement only (thinktwice_amd/bench_jpeg_encode.py): the same call up to and including the transform (phases = 1), the
+ * entropy pass (2), or all of it (3). */
+int tt_jpeg_encode_u8_phases(const uint8_t* pixels_dev, long long pixel_bytes, const tt_jpeg_enc_image* images_host,
+                             const tt_jpeg_enc_image* images_dev, int num_images, void* workspace, long long workspace_bytes,
+                             uint8_t* files_dev, long long files_bytes, long long* file_sizes_dev, int phases, void* stream);
+
+/* ------------------------------------------------------------------------
  * Debug frames DRAWN on the device (thinktwice_amd/render.py, csrc/render.hip, csrc/render_raster.h): a caller-owned uint8 canvas
  * [Hc][Wc][3] filled from a display list, so that what the model predicted reaches tt_png_encode_u8 without a copy to the host.
  * The palette, look-up tables, layout and 5 x 7 font are this project's own (the reference draws nothing).

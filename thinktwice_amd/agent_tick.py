@@ -128,14 +128,26 @@ class AgentTick:
                                                         drawn on the device and handed to the same `submit` as the camera
                                                         frames: one encoder call and one write per tick.  While the queue fills
                                                         (`pred` is None) it shows the cameras and the cloud only.
-    A tick that is not recorded does nothing for it, and with render=None `_record` submits exactly the files above."""
+    A tick that is not recorded does nothing for it, and with render=None `_record` submits exactly the files above.
+
+    image_format: "png" or "jpg".  "jpg" writes rgb_*/NNNN.jpg in place of the .png files: baseline JPEG, encoded on the device
+        by the recorder's `jpeg_encode.JpegEncoder` (lossy, a fraction of the size and of the encoding time; the recording is no
+        training sample).
+    debug_video: needs `render`.  True appends the debug frame to ONE Motion JPEG file debug.avi (jpeg_encode.MjpegWriter) in
+        place of debug/NNNN.png, at 20 / record_every frames a second (the simulator ticks at 20 Hz; the recorder's `video_fps` is
+        set to that), finished by the recorder's close().
+    The defaults reproduce the files above byte for byte: `_record` then makes the call it made before the arguments existed."""
 
     def __init__(self, model, lag=10, queue_len=31, use_cache=False, stuck_threshold=800, final_dim=None, undistort=True,
-                 recorder=None, record_every=10, render=None):
+                 recorder=None, record_every=10, render=None, image_format="png", debug_video=False):
         from collections import deque
         from . import calib, preprocess, synth
         if render is not None and render is not False and recorder is None:
             raise ValueError("AgentTick(render=...) draws into the recording: it needs a recorder")
+        if image_format not in ("png", "jpg"):
+            raise ValueError(f"image_format: {image_format!r} not in ('png', 'jpg')")
+        if debug_video and (render is None or render is False):
+            raise ValueError("AgentTick(debug_video=True) is a video of the debug frames: it needs render")
         from .encoder_decoder import PrevSweepCache
         assert queue_len > lag >= 1
         self.model, self.device = model, model.device
@@ -154,6 +166,9 @@ class AgentTick:
             from . import config, render as rendering
             render = rendering.DebugRenderer(config.model_config(final_dim=fd), device=self.device)
         self.renderer = render or None
+        self.image_format, self.debug_video = image_format, bool(debug_video)
+        if self.debug_video:
+            recorder.video_fps = 20.0 / self.record_every
 
     def reset(self):
         self.frames.clear()
@@ -188,12 +203,20 @@ class AgentTick:
             meta["target_point"] = [float(v) for v in info["target_point"]]
         cloud = io.BytesIO()
         np.save(cloud, info["cloud"].detach().cpu().numpy().astype(np.float32, copy=False), allow_pickle=False)
-        images = {f"{cam}/{name}.png": raw[i] for i, cam in enumerate(calib.CAMERA_NAMES)}
+        images = {f"{cam}/{name}.{self.image_format}": raw[i] for i, cam in enumerate(calib.CAMERA_NAMES)}
+        video = {}
         if self.renderer is not None:
-            images[f"debug/{name}.png"] = self.renderer.frame(info["img"], info["pred"], info["cloud"], controls=dict(meta, step=self.step),
-                                                              target=info.get("target_point"))
-        self.recorder.submit(images,
-                             {f"lidar/{name}.npy": cloud.getvalue(), f"meta/{name}.json": json.dumps(meta, indent=4).encode()})
+            frame = self.renderer.frame(info["img"], info["pred"], info["cloud"], controls=dict(meta, step=self.step),
+                                        target=info.get("target_point"))
+            if self.debug_video:
+                video["debug.avi"] = frame
+            else:
+                images[f"debug/{name}.png"] = frame
+        files = {f"lidar/{name}.npy": cloud.getvalue(), f"meta/{name}.json": json.dumps(meta, indent=4).encode()}
+        if video:
+            self.recorder.submit(images, files, video=video)
+        else:
+            self.recorder.submit(images, files)
 
     def _run_step(self, frames_rgb_u8, lidar_half, pos, compass, speed, next_wp, next_cmd):
         self.step += 1

@@ -289,12 +289,19 @@ class FrameDump:
     """Every `every`-th sample of a pass as a debug frame `root/NNNNNN.png`, numbered by the sample's ordinal in this process's
     pass: drawn by render.DebugRenderer from the forward the metrics read, with the batch's expert waypoints in white and its target
     point as a red disc (both read on the device), written through a png_encode.FrameRecorder.  Nothing here waits for the device
-    but the recorder's own writer thread."""
+    but the recorder's own writer thread.  render_format: "png"; "jpg": `root/NNNNNN.jpg`, baseline JPEG written on the device
+    (jpeg_encode.JpegEncoder); "avi": ONE Motion JPEG file `root/frames.avi` of all the frames in the pass's order
+    (jpeg_encode.MjpegWriter; with several ranks every rank's directory holds its own)."""
 
-    def __init__(self, model, root, every, renderer=None, recorder=None):
+    FORMATS = ("png", "jpg", "avi")
+
+    def __init__(self, model, root, every, renderer=None, recorder=None, render_format="png"):
         from . import png_encode
         if int(every) < 1:
             raise ValueError(f"render_every {every} must be at least 1")
+        if render_format not in self.FORMATS:
+            raise ValueError(f"render_format: {render_format!r} not in {self.FORMATS}")
+        self.render_format = render_format
         self.every, self.ordinal, self.frames = int(every), 0, 0
         self.device, self.renderer = model.device, renderer            # (made at the first batch, for the size of its images)
         self.recorder = recorder or png_encode.FrameRecorder(root, png_encode.PngEncoder(device=model.device))
@@ -307,7 +314,11 @@ class FrameDump:
         for b in range(B):
             if self.ordinal % self.every == 0:
                 dl = self.display_list(batch, pred, b)
-                self.recorder.submit({f"{self.ordinal:06d}.png": self.renderer.raster.draw(dl)})
+                frame = self.renderer.raster.draw(dl)
+                if self.render_format == "avi":
+                    self.recorder.submit({}, video={"frames.avi": frame})
+                else:
+                    self.recorder.submit({f"{self.ordinal:06d}.{self.render_format}": frame})
                 self.frames += 1
             self.ordinal += 1
 
@@ -324,14 +335,15 @@ class FrameDump:
         self.recorder.close()
 
 
-def evaluate(model, loader, dist=None, window=None, raw=False, render_dir=None, render_every=0):
+def evaluate(model, loader, dist=None, window=None, raw=False, render_dir=None, render_every=0, render_format="png"):
     """`model.forward_inference(batch)` under no_grad on every batch of `loader` (a DeviceBatchLoader(train=False)): the inference
     path, no teacher pass, in whatever `dtype` mode the model was built.  -> the summary (merged over the ranks of `dist`);
     `raw=True`: (summary, raw accumulators).  render_dir with render_every = N > 0: every N-th sample also becomes a debug frame
-    (`FrameDump`), from the same forward; the metrics are the bits they are without it."""
+    (`FrameDump`; render_format "png", "jpg" or "avi"), from the same forward; the metrics are the bits they are without it."""
     import torch
     window = window or window_for(model)
-    dump = FrameDump(model, render_dir, render_every) if render_dir is not None and int(render_every) > 0 else None
+    dump = (FrameDump(model, render_dir, render_every, render_format=render_format)
+            if render_dir is not None and int(render_every) > 0 else None)
     iters = 0
     try:
         with torch.no_grad():
@@ -452,6 +464,8 @@ def parse_args(argv=None):
     ap.add_argument("--out", default=None, help="write the result here as JSON (rank 0)")
     ap.add_argument("--render", default=None, metavar="DIR", help="write debug frames DIR/NNNNNN.png (DIR/rankK with several ranks)")
     ap.add_argument("--render-every", type=int, default=0, metavar="N", help="every N-th sample of the pass gets a frame")
+    ap.add_argument("--render-format", default="png", choices=FrameDump.FORMATS,
+                    help="png or jpg: one file a frame; avi: one Motion JPEG video DIR/frames.avi")
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be >= 1")
@@ -521,7 +535,8 @@ def main(argv=None):
             result = OrderedDict(dtype=args.dtype, towns=towns, world=world)
             if args.against is None:
                 render_dir = args.render if args.render is None or world == 1 else os.path.join(args.render, f"rank{rank}")
-                result["metrics"] = evaluate(model, loader, render_dir=render_dir, render_every=args.render_every)
+                result["metrics"] = evaluate(model, loader, render_dir=render_dir, render_every=args.render_every,
+                                             render_format=args.render_format)
             else:
                 if world > 1:
                     raise SystemExit("--against compares two modes on one rank's frames: run it without torch.distributed.run")
