@@ -13,20 +13,18 @@ import functools
 import io
 import os
 import re
-import shutil
 import subprocess
 import sys
 import tempfile
 
 import numpy as np
-import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import host_tool  # noqa: E402
 import jpeg_encode_cases as E  # noqa: E402
 import jpeg_ref  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = {1: 330, 3: 613}
 GUARDED = ("camera_64x96x3_q90_420_r1", "camera_64x96x3_q90_444_r2", "hud_48x80x3_q90_420_r1", "hud_48x80x3_q90_444_r1",
            "quality_24x40x3_q1_420_r1", "quality_24x40x3_q50_420_r1", "quality_24x40x3_q90_420_r1", "quality_24x40x3_q100_420_r1",
@@ -42,21 +40,13 @@ SIZE_RATIO = {"camera_64x96x3_q90_420_r1": 0.9799, "camera_64x96x3_q90_444_r2": 
               "image_17x33x1_q90_420_r1": 0.9917}
 
 
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    pytest.fail("no C++ compiler found for the host checker")
-
-
 def run_checker(sanitize, extra=()):
     """Builds the checker, runs it over every case (and `extra`) -> ([file bytes], {name: (bytes, intervals, bound, header)},
     the run)."""
     with tempfile.TemporaryDirectory() as tmp:
-        exe, cases, out = os.path.join(tmp, "jpeg_encode_host_check"), os.path.join(tmp, "cases.bin"), os.path.join(tmp, "out")
+        cases, out = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "out")
         os.mkdir(out)
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
-        subprocess.run([_compiler(), "-std=c++17", *flags, os.path.join(ROOT, "tools", "jpeg_encode_host_check.cpp"), "-o", exe], check=True)
+        exe = host_tool.build("jpeg_encode_host_check", tmp, sanitize)
         count = E.write_case_file(cases, extra)
         run = subprocess.run([exe, cases, out], capture_output=True, text=True)
         files = [open(os.path.join(out, f"{i}.jpg"), "rb").read() for i in range(count)] if run.returncode == 0 else []
@@ -103,6 +93,22 @@ def test_the_bound_counts_the_format():
         blocks = mx * my * (1 if c == 1 else 6 if m == 16 else 3)
         n_int = -(-my // rr)
         assert stats[name][1:] == (n_int, HEADER[c] + 432 * blocks + 2 * n_int, HEADER[c]), (name, stats[name])
+
+
+def test_the_cases_as_one_table_walk_the_shared_slot_arithmetic():
+    """The tool's batch pass (csrc/file_slots.h under the sanitizers): all cases in one workspace and one file buffer, every file
+    equal to the case's own.  A unit is a group of 64 blocks, a part a restart interval."""
+    _, _, run = _checked()
+    m = re.fullmatch(r"batch: (\d+) images, (\d+) units, (\d+) parts, (\d+) workspace bytes: ok", run.stdout.splitlines()[-2])
+    assert m, run.stdout.splitlines()[-2:]
+    units = parts = 0
+    for name, img, quality, sub, rr in E.cases():
+        h, w, c = img.shape
+        mcu = 16 if (c == 3 and sub == "420") else 8
+        mx, my = -(-w // mcu), -(-h // mcu)
+        units += -(-(mx * my * (1 if c == 1 else 6 if mcu == 16 else 3)) // 64)
+        parts += -(-my // rr)
+    assert (int(m.group(1)), int(m.group(2)), int(m.group(3))) == (len(E.cases()), units, parts)
 
 
 def _psnr(a, b):

@@ -129,12 +129,10 @@ def test_the_tile_table_covers_every_range_exactly_once(tmp_path):
     each is at most T bytes and only a range's last one is shorter, that together they are exactly the range, that a
     zero-length range keeps its first_tile entry and owns no tile, and that 256 planners build the same table as one.  Here
     (without sanitizers, which test_png_checksum_host.py adds): every ranges case passes it, the 201-range one among them."""
-    from test_png_host import _compiler
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import host_tool
     cases = str(tmp_path / "cases.bin")
     K.write_case_file(cases)
-    exe = str(tmp_path / "check")
-    subprocess.run([_compiler(), "-std=c++17", "-O1", os.path.join(root, "tools", "png_checksum_host_check.cpp"), "-o", exe], check=True)
+    exe = host_tool.build("png_checksum_host_check", tmp_path, sanitize=False, extra_flags=("-O1",))    # (as before: the last -O wins)
     run = subprocess.run([exe, cases], capture_output=True, text=True)
     assert run.returncode == 0 and ", 0 failed" in run.stdout.splitlines()[-1]
     ok = [l for l in run.stdout.splitlines() if l.startswith("ok  ") and " ranges, 0 wrong" in l]

@@ -11,16 +11,12 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import host_tool  # noqa: E402
 import png_checksum_cases as K  # noqa: E402
-from test_png_host import _compiler  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_checksum_source_under_sanitizers_over_every_case(tmp_path):
-    exe, cases = str(tmp_path / "png_checksum_host_check"), str(tmp_path / "cases.bin")
-    subprocess.run([_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    os.path.join(ROOT, "tools", "png_checksum_host_check.cpp"), "-o", exe], check=True)
+    exe, cases = host_tool.build("png_checksum_host_check", tmp_path, sanitize=True), str(tmp_path / "cases.bin")
     count = K.write_case_file(cases)
     assert count > 250
     run = subprocess.run([exe, cases], capture_output=True, text=True)

@@ -13,7 +13,6 @@ import functools
 import io
 import os
 import re
-import shutil
 import struct
 import subprocess
 import sys
@@ -21,33 +20,24 @@ import tempfile
 import zlib
 
 import numpy as np
-import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import host_tool  # noqa: E402
 import png_cases as P  # noqa: E402
 import png_encode_cases as E  # noqa: E402
 import png_ref  # noqa: E402
 from thinktwice_amd import png  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEVEL1_RATIO = {"camera_16x1600x3_R16_adaptive": 0.8688, "ramp_16x1600x3_R16_adaptive": 1.1458, "tags_16x1600x1_R16_adaptive": 1.2495}
-
-
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    pytest.fail("no C++ compiler found for the host checker")
 
 
 def run_checker(sanitize):
     """Builds the checker, runs it over every case -> ([file bytes], {name: (bytes, dynamic, stored, limited)}, the run)."""
     with tempfile.TemporaryDirectory() as tmp:
-        exe, cases, out = os.path.join(tmp, "png_encode_host_check"), os.path.join(tmp, "cases.bin"), os.path.join(tmp, "out")
+        cases, out = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "out")
         os.mkdir(out)
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
-        subprocess.run([_compiler(), "-std=c++17", *flags, os.path.join(ROOT, "tools", "png_encode_host_check.cpp"), "-o", exe], check=True)
+        exe = host_tool.build("png_encode_host_check", tmp, sanitize)
         count = E.write_case_file(cases)
         run = subprocess.run([exe, cases, out], capture_output=True, text=True)
         files = [open(os.path.join(out, f"{i}.png"), "rb").read() for i in range(count)] if run.returncode == 0 else []
@@ -73,6 +63,16 @@ def test_encoder_core_under_sanitizers_round_trips_every_case():
     assert len(stats) == count and len(files) == count
     for (name, *_), f in zip(E.cases(), files):
         assert stats[name][0] == len(f), name
+
+
+def test_the_cases_as_one_table_walk_the_shared_slot_arithmetic():
+    """The tool's batch pass (csrc/file_slots.h under the sanitizers): all cases in one workspace and one file buffer, every file
+    equal to the case's own.  A unit is a row, a part a segment of R rows."""
+    _, _, run = _checked()
+    m = re.fullmatch(r"batch: (\d+) images, (\d+) units, (\d+) parts, (\d+) workspace bytes: ok", run.stdout.splitlines()[-2])
+    assert m, run.stdout.splitlines()[-2:]
+    shapes = [(img.shape[0], rows) for _, img, rows, _ in E.cases()]
+    assert (int(m.group(1)), int(m.group(2)), int(m.group(3))) == (len(shapes), sum(h for h, _ in shapes), sum(-(-h // r) for h, r in shapes))
 
 
 def test_every_file_reads_back_with_zlib_pil_and_the_package_parser():

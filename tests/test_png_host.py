@@ -4,30 +4,17 @@ file of tests/png_cases.py.  This is where the malformed streams meet the code f
 block of the exact size, so an access outside the stream, the scanlines or the image is a sanitizer report, and any report
 fails the run.  The device test of the malformed list (test_png_decode.py) uses the identical cases."""
 import os
-import shutil
 import subprocess
 import sys
 
-import pytest
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import host_tool  # noqa: E402
 import png_cases as P  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    pytest.fail("no C++ compiler found for the host checker")
 
 
 def test_inflate_core_under_sanitizers_over_every_case(tmp_path):
-    exe, cases = str(tmp_path / "png_host_check"), str(tmp_path / "cases.bin")
-    subprocess.run([_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    os.path.join(ROOT, "tools", "png_host_check.cpp"), "-o", exe], check=True)
+    exe, cases = host_tool.build("png_host_check", tmp_path, sanitize=True), str(tmp_path / "cases.bin")
     count = P.write_case_file(cases)
     assert count == len(P.good_cases()) + len(P.malformed_cases())
     run = subprocess.run([exe, cases], capture_output=True, text=True)

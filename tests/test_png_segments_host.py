@@ -5,30 +5,17 @@ malformed indices and segments meet the code first: every segment's input and ev
 exact size, so an access outside them is a sanitizer report, and the checker itself fails a case in which a segment changed
 a byte outside its own rows.  The device tests (test_png_segments.py) use the identical cases."""
 import os
-import shutil
 import subprocess
 import sys
 
-import pytest
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import host_tool  # noqa: E402
 import png_segment_cases as S  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    pytest.fail("no C++ compiler found for the host checker")
 
 
 def test_segment_inflate_under_sanitizers_over_every_case(tmp_path):
-    exe, cases = str(tmp_path / "png_segment_host_check"), str(tmp_path / "cases.bin")
-    subprocess.run([_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    os.path.join(ROOT, "tools", "png_segment_host_check.cpp"), "-o", exe], check=True)
+    exe, cases = host_tool.build("png_segment_host_check", tmp_path, sanitize=True), str(tmp_path / "cases.bin")
     count = S.write_case_file(cases)
     assert count == len(S.good_cases()) + len(S.malformed_cases())
     run = subprocess.run([exe, cases], capture_output=True, text=True)

@@ -4,7 +4,6 @@ child process over the case file of tests/render_cases.py.  Its canvases and dro
 restatement's (tests/render_ref.py) byte for byte, the lists the entry must refuse must be refused, and the run must be clean."""
 import functools
 import os
-import shutil
 import struct
 import subprocess
 import sys
@@ -15,26 +14,17 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import host_tool  # noqa: E402
 import render_cases as R  # noqa: E402
 import render_ref  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    pytest.fail("no C++ compiler found for the host checker")
 
 
 @functools.lru_cache(maxsize=None)
 def _checked():
     """Builds the checker, runs it over every case -> ({name: (rc, dropped, canvas or None)}, the run)."""
     with tempfile.TemporaryDirectory() as tmp:
-        exe, cases, out = os.path.join(tmp, "render_host_check"), os.path.join(tmp, "cases.bin"), os.path.join(tmp, "out.bin")
-        flags = ["-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-        subprocess.run([_compiler(), "-std=c++17", *flags, os.path.join(ROOT, "tools", "render_host_check.cpp"), "-o", exe], check=True)
+        cases, out = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "out.bin")
+        exe = host_tool.build("render_host_check", tmp, sanitize=True, extra_flags=("-ffp-contract=off",))
         R.write_case_file(cases)
         run = subprocess.run([exe, cases, out], capture_output=True, text=True)
         data = open(out, "rb").read() if os.path.exists(out) else b""

@@ -125,27 +125,33 @@ def takes_stream(name, params):
             and name not in ("tt_encoder_fwd", "tt_decoder_fwd"))
 
 
+def load(path):
+    """A build of the C-ABI library at `path`, every declared entry typed; raise loudly if it is missing or stale.  The package
+    uses lib(); a tool that sets two builds side by side (tools/file_encode_ab.py) loads the other one here."""
+    if not os.path.exists(path):
+        raise TTError(
+            f"{path} is missing: run `python -m thinktwice_amd.build` "
+            "(hipcc --offload-arch=gfx950). There is no fallback path.")
+    so = ctypes.CDLL(path)
+    missing = []
+    for name, p in prototypes().items():
+        try:
+            f = getattr(so, name)
+        except AttributeError:
+            missing.append(name)
+            continue
+        f.restype, f.argtypes = p.restype, p.argtypes
+    if missing:
+        raise TTError(f"{path} does not export {', '.join(missing)} declared in include/thinktwice_hip.h: "
+                      "rebuild it (`python -m thinktwice_amd.build`)")
+    return so
+
+
 def lib():
-    """Load (once) and return the C-ABI library, every declared entry typed; raise loudly if it is missing or stale."""
+    """Load (once) and return the C-ABI library, every declared entry typed."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise TTError(
-                f"{LIB_PATH} is missing: run `python -m thinktwice_amd.build` "
-                "(hipcc --offload-arch=gfx950). There is no fallback path.")
-        so = ctypes.CDLL(LIB_PATH)
-        missing = []
-        for name, p in prototypes().items():
-            try:
-                f = getattr(so, name)
-            except AttributeError:
-                missing.append(name)
-                continue
-            f.restype, f.argtypes = p.restype, p.argtypes
-        if missing:
-            raise TTError(f"{LIB_PATH} does not export {', '.join(missing)} declared in include/thinktwice_hip.h: "
-                          "rebuild it (`python -m thinktwice_amd.build`)")
-        _lib = so
+        _lib = load(LIB_PATH)
     return _lib
 
 

@@ -3,7 +3,7 @@
 // signature.  csrc/jpeg_encode.hip compiles them as device code (one lane per 8 x 8 block in the transform, one 64-lane
 // workgroup per restart interval in the entropy pass); tools/jpeg_encode_host_check.cpp compiles the same text as host C++.
 //
-// Execution model: png_deflate.h's.  The entropy pass is written for 64 lanes (`Lanes`, TT_ENC_LANES, PerLane, TT_PNG_SYNC);
+// Execution model: lanes.h's.  The entropy pass is written for 64 lanes (`Lanes`, TT_ENC_LANES, PerLane, TT_PNG_SYNC);
 // the host plays all 64, so its bytes are the device's.  The transform of a block is a function of the pixels and the block's
 // index alone and touches no shared state.
 //
@@ -36,7 +36,8 @@
 #pragma once
 #include <stdint.h>
 
-#include "png_deflate.h"        // the lane convention: Lanes, PerLane, TT_ENC_LANES, exclusive_scan, TT_ENC_OR, TT_PNG_SYNC
+#include "../../include/thinktwice_hip.h"
+#include "lanes.h"              // the lane convention: Lanes, PerLane, TT_ENC_LANES, exclusive_scan, TT_ENC_OR, TT_PNG_SYNC
 
 namespace tt_jpeg {
 
@@ -476,5 +477,27 @@ TT_HD inline int write_header(uint8_t* f, int H, int W, int quality, const Geom&
     *p++ = 0;
     return (int)(p - f);
 }
+
+// ------------------------------------------------------------------------------------------------- the slot table's format
+// What file_slots.h asks of a format: a unit is a workgroup of the transform (64 blocks of 128 bytes), a part a restart interval.
+struct SlotFormat {
+    typedef tt_jpeg_enc_image Image;
+    typedef tt_jpeg::Geom Geom;
+    TT_HD static Geom geom(const Image& im) { return tt_jpeg::geom(im.height, im.width, im.channels, im.subsampling, im.restart_rows); }
+    TT_HD static long long units(const Image&, const Geom& g) { return (g.blocks + kLanes - 1) / kLanes; }
+    TT_HD static int parts(const Geom& g) { return g.nint; }
+    TT_HD static long long first_bytes(const Geom& g) { return g.blocks * 128; }
+    TT_HD static long long slot_bytes(const Image& im, const Geom& g, bool last) {
+        return interval_slot_bytes(interval_blocks(g, im.restart_rows, last ? g.nint - 1 : 0));
+    }
+    // 0 where the table is refused for its sizes or parameters
+    static long long bound(const Image& im) {
+        if ((im.channels != 1 && im.channels != 3) || im.height < 1 || im.width < 1 || im.height > kMaxDim || im.width > kMaxDim) return 0;
+        if (im.quality < 1 || im.quality > 100 || (im.subsampling != TT_JPEG_444 && im.subsampling != TT_JPEG_420) || im.restart_rows < 1) return 0;
+        const Geom g = geom(im);
+        if (g.dri > 65535) return 0;
+        return file_bound(g);
+    }
+};
 
 }  // namespace tt_jpeg

@@ -23,13 +23,7 @@
 
 #include "../../include/thinktwice_hip.h"
 
-#ifndef TT_HD
-#if defined(__HIPCC__)
-#define TT_HD __host__ __device__
-#else
-#define TT_HD
-#endif
-#endif
+#include "lanes.h"          // TT_HD
 
 namespace tt_cksum {
 

@@ -2,14 +2,7 @@
 // 12.8) and a deflate compressor (RFC 1951) that writes SEGMENTS -- whole non-final blocks that end in the empty stored block
 // 00 00 FF FF and inflate alone, what png_inflate.h's inflate_segment reads.  Plain functions over byte spans, no HIP type in
 // any signature.  csrc/png_encode.hip compiles them as device code, one 64-lane workgroup per row (filter) or per segment
-// (deflate); tools/png_encode_host_check.cpp compiles the same text as host C++.
-//
-// Execution model.  The text is written for kLanes = 64 lanes.  `Lanes` names the lanes the caller runs: {l, l + 1} on the
-// device, where every lane of the wave calls with its own l, and {0, 64} on the host, where one thread plays all 64 in turn.
-// TT_ENC_LANES(l) { ... } is one phase of per-lane work; a value a lane keeps from one phase to the next is a PerLane<T> (a
-// register on the device, an array of 64 on the host).  Everything outside a phase is the same in every lane.  Between two
-// phases that touch the same shared state stands TT_PNG_SYNC().  So the host runs 64 lanes, not "lane 0 of 1", and the bytes
-// are the device's.
+// (deflate); tools/png_encode_host_check.cpp compiles the same text as host C++.  Execution model: lanes.h's.
 //
 // Determinism.  The bytes are a function of the input and the parameters.  No result depends on which lane's LDS update
 // lands first: the three shared updates of a phase are commutative and associative (integer add into a histogram, or into the
@@ -48,22 +41,11 @@
 #pragma once
 #include <stdint.h>
 
+#include "lanes.h"
 #include "png_inflate.h"
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define TT_ENC_ADD(p, v) atomicAdd((p), (v))
-#define TT_ENC_OR(p, v) atomicOr((p), (v))
-#define TT_ENC_MAX(p, v) atomicMax((p), (v))
-#else
-#define TT_ENC_ADD(p, v) (*(p) += (v))
-#define TT_ENC_OR(p, v) (*(p) |= (v))
-#define TT_ENC_MAX(p, v) (*(p) = *(p) > (v) ? *(p) : (v))
-#endif
-#define TT_ENC_LANES(l) for (int l = L.lo; l < L.hi; ++l)
 
 namespace tt_pngenc {
 
-constexpr int kLanes = 64;
 constexpr int kWindow = 32768;
 constexpr int kMinMatch = 4, kMaxMatch = 258;       // what the parse takes; the format's lengths start at kLenBase
 constexpr int kLenBase = 3;
@@ -74,59 +56,6 @@ constexpr int kOutWords = 512;
 constexpr int kStoredMax = 65535;
 constexpr uint32_t kEob = 256u;                 // token values: 0..255 a literal, 256 end of block, bit 31 a match
 enum FilterMode { kNone = 0, kSub = 1, kUp = 2, kAvg = 3, kPaeth = 4, kAdaptive = 5 };
-
-struct Lanes {
-    int lo, hi;
-};
-
-template <typename T>
-struct PerLane {
-#if defined(__HIP_DEVICE_COMPILE__)
-    T v;
-    TT_HD T& operator[](int) { return v; }
-#else
-    T v[kLanes];
-    TT_HD T& operator[](int l) { return v[l]; }
-#endif
-};
-
-// pred != 0, lane by lane, as a mask
-TT_HD inline uint64_t ballot(PerLane<int>& pred, Lanes L) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    (void)L;
-    return __ballot(pred.v != 0);
-#else
-    uint64_t m = 0;
-    TT_ENC_LANES(l) m |= (uint64_t)(pred[l] != 0) << l;
-    return m;
-#endif
-}
-
-// v[l] becomes the sum of the lanes below l; returns the sum of all
-TT_HD inline uint32_t exclusive_scan(PerLane<uint32_t>& v, Lanes L) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t own = v.v;
-    uint32_t inc = own;
-#pragma unroll
-    for (int o = 1; o < kLanes; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, kLanes);
-        if (L.lo >= o) inc += t;
-    }
-    v.v = inc - own;
-    return __shfl(inc, kLanes - 1, kLanes);
-#else
-    uint32_t run = 0;
-    TT_ENC_LANES(l) {
-        const uint32_t t = v[l];
-        v[l] = run;
-        run += t;
-    }
-    return run;
-#endif
-}
-
-TT_HD inline int popcount64(uint64_t x) { return __builtin_popcountll(x); }
-TT_HD inline uint64_t bits_below(int b) { return b >= 64 ? ~0ull : ((1ull << b) - 1); }      // b >= 0
 
 // ---------------------------------------------------------------------------------------------------------------- sizes
 // A segment of n >= 1 bytes as stored blocks only: 5 bytes a piece (3 header bits padded to a byte, LEN, NLEN), then the
@@ -738,6 +667,7 @@ struct FileGeom {
     long long stride, expect;           // bytes of a filtered row, of all rows
     int rows, nseg;                     // rows of a full segment (R, at most H), segments
     long long idat_at;                  // of the IDAT chunk's length field
+    long long n_full, n_last;           // filtered bytes of a full segment, of the last
 };
 
 TT_HD inline FileGeom file_geom(int H, int W, int C, int R) {
@@ -747,6 +677,8 @@ TT_HD inline FileGeom file_geom(int H, int W, int C, int R) {
     g.rows = R < H ? R : H;
     g.nseg = (H + g.rows - 1) / g.rows;
     g.idat_at = kTtsgAt + 12 + 9 + 4 * ((long long)g.nseg + 1);
+    g.n_full = g.rows * g.stride;
+    g.n_last = (H - (g.nseg - 1) * g.rows) * g.stride;
     return g;
 }
 
@@ -797,5 +729,27 @@ TT_HD inline long long write_container(uint8_t* file, int H, int W, int C, int R
     for (int i = 0; i < 12; ++i) e[i] = iend[i];
     return file_bytes(g, at - 2);
 }
+
+// ------------------------------------------------------------------------------------------------- the slot table's format
+// What file_slots.h asks of a format: the first pass is the filter, a row per unit; the parts are the segments.
+struct SlotFormat {
+    typedef tt_png_enc_image Image;
+    typedef FileGeom Geom;
+    TT_HD static Geom geom(const Image& im) { return file_geom(im.height, im.width, im.channels, im.rows_per_segment); }
+    TT_HD static int units(const Image& im, const Geom&) { return im.height; }
+    TT_HD static int parts(const Geom& g) { return g.nseg; }
+    TT_HD static long long first_bytes(const Geom& g) { return g.expect; }
+    TT_HD static long long slot_bytes(const Image&, const Geom& g, bool last) { return segment_slot_bytes(last ? g.n_last : g.n_full); }
+    // 0 where the table is refused for its sizes
+    static long long bound(const Image& im) {
+        if ((im.channels != 1 && im.channels != 3) || im.height < 1 || im.width < 1 || im.rows_per_segment < 1) return 0;
+        if (im.filter < TT_PNGE_FILTER_NONE || im.filter > TT_PNGE_FILTER_ADAPTIVE) return 0;
+        const Geom g = geom(im);
+        if (g.rows * g.stride > 2147483647LL - 64) return 0;
+        const long long most = file_bound(g, im.height);
+        if (most - g.idat_at - 24 > 2147483640LL) return 0;                        // the zlib stream: at most 2^31 - 8 bytes
+        return most;
+    }
+};
 
 }  // namespace tt_pngenc

@@ -27,32 +27,9 @@
 #include <stdint.h>
 
 #include "../../include/thinktwice_hip.h"
-
-#if defined(__HIPCC__)
-#define TT_HD __host__ __device__
-#else
-#define TT_HD
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-#define TT_PNG_SYNC() __syncthreads()
-#else
-#define TT_PNG_SYNC() ((void)0)
-#endif
-// TT_PNG_UNIFORM(x): a 32-bit value every lane holds alike, read from LDS or memory.  On the device it is taken from the
-// first lane, which tells the compiler what the execution model guarantees: the reader state and every branch on it then
-// live in scalar registers and scalar branches.  It changes no value.
-#define TT_PNG_UNIFORM(x) ::tt_png::uniform(x)
+#include "lanes.h"          // TT_HD, TT_PNG_SYNC, TT_PNG_UNIFORM / uniform
 
 namespace tt_png {
-
-template <typename T>
-TT_HD inline T uniform(T x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (T)__builtin_amdgcn_readfirstlane((int)x);
-#else
-    return x;
-#endif
-}
 
 constexpr int kWindow = 32768;          // the ring: deflate's largest window
 constexpr int kFlush = 8192;            // bytes per flush of the ring to the output; divides kWindow, a multiple of 16
